@@ -2,6 +2,7 @@
 """Benchmark of the GP-posterior + safe-set sweep (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+                    [--dump-outputs DIR]
 
 A "step" is one ``SafeOpt.optimize()`` = ``update_confidence_intervals`` +
 ``compute_sets`` + ``get_new_query_point`` over the whole resident candidate
@@ -744,6 +745,51 @@ def nrank_selfcheck(opt, comm):
             "ok": bool(np.array_equal(xa, xb) and np.array_equal(ca, cb))}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all files together, headers included
+DUMP_SEED = 12345                   # the rows of the sample when the outputs are larger
+
+
+def last_step_outputs(config, opt, last):
+    """What a caller of the timed path holds after its last step: the chosen point and
+    the per-row intervals and sets of ``SafeOpt.optimize()`` (config 5: the fitness
+    values and safety flags ``_compute_particle_fitness`` returns).  Returns
+    ``(per_row, whole)``: arrays whose first axis is the candidate row, and the rest.
+    N ranks: reading the host mirrors gathers them over the ranks, every rank calls this."""
+    if config == 5:
+        values, safe = last["fitness"]
+        return {"values": np.array(values, dtype=np.float64),
+                "safe": np.asarray(safe, dtype=np.float32)}, {}
+    per_row = {"Q": np.array(opt.Q, dtype=np.float64)}
+    for name in ("S", "M", "G"):
+        per_row[name] = np.asarray(getattr(opt, name), dtype=np.float32)
+    return per_row, {"x": np.array(np.atleast_1d(last["x"]), dtype=np.float64)}
+
+
+def dump_outputs(out_dir, per_row, whole):
+    """Write every array as ``out_dir/<name>.npy``, at most DUMP_LIMIT_BYTES in all.  When
+    the per-row arrays do not fit whole, each is cut to the same fixed, seeded sample of
+    rows (ascending), whose indices go to ``rows.npy``."""
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                   # (np.save's header of these arrays)
+    n = next(iter(per_row.values())).shape[0]
+    fixed = sum(a.nbytes + header for a in whole.values()) + header * len(per_row)
+    row_bytes = sum(a[:1].nbytes for a in per_row.values())
+    out = dict(whole)
+    sampled = None
+    if fixed + n * row_bytes <= DUMP_LIMIT_BYTES:
+        out.update(per_row)
+    else:
+        k = (DUMP_LIMIT_BYTES - fixed - header) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+        out.update({name: a[rows] for name, a in per_row.items()})
+        out["rows"] = rows.astype(np.float64)
+        sampled = int(k)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "rows": int(n), "sampled_rows": sampled,
+            "files": {name + ".npy": [str(a.dtype)] + list(a.shape) for name, a in out.items()}}
+
+
 def spawn_ranks(n, argv):
     """``python bench.py --gpus N`` from a bare shell: start the N ranks (one
     process per GPU, torchrun-style environment) and pass rank 0's line on."""
@@ -796,6 +842,10 @@ def main():
                          "GPs (profiles: every k_sweep launch of the run is then the headline path)")
     ap.add_argument("--profile-steps", type=int, default=10,
                     help="steps of the separate (untimed) per-launch hipEvent pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: a fixed, seeded sample of the rows "
+                         "of a larger grid, indices in rows.npy)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous the ranks (no device): launcher self-test")
     ap.add_argument("--probe-transport", default=None, help=argparse.SUPPRESS)
@@ -807,6 +857,8 @@ def main():
         args.config = 3
     if args.steps is None:
         args.steps = {2: 500, 3: 40, 4: 6, 5: 40}[args.config]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.check_chosen is None:
         args.check_chosen = args.config in (2, 3) and args.side is None
 
@@ -864,7 +916,7 @@ def main():
 
         # P / t of ONE _compute_particle_fitness call over all G GPs
         def step():
-            opt._compute_particle_fitness("maximizers", parts)
+            last["fitness"] = opt._compute_particle_fitness("maximizers", parts)
 
         def step3():
             for st in ("greedy", "maximizers", "expanders"):
@@ -925,6 +977,13 @@ def main():
     dt = time.perf_counter() - t0
     ev_ms = ctx.timer_stop()
     dt = float(comm.allreduce_max(np.array([dt]))[0])       # MAX over ranks
+    # ---- the outputs of the last timed step, read before any later pass touches them
+    dumped = None
+    if args.dump_outputs:
+        per_row, whole = last_step_outputs(args.config, opt, last)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, per_row, whole)
+        del per_row, whole
 
     # ---- separate, untimed pass: a hipEvent pair around every sweep launch on
     # the library's stream (roofline.achieved); rocprofv3 --kernel-trace of the
@@ -1066,6 +1125,8 @@ def main():
         "hip_event_ms_per_step": ev_ms / args.steps,
         "timed_region_s": dt,
     }
+    if dumped:
+        res["dumped_outputs"] = dumped
     # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc
     # passes (FETCH_SIZE / WRITE_SIZE cannot be read from inside the process)
     try:

@@ -2,6 +2,7 @@
 SafeOpt host logic (shard ranges, phase driver, top-k / arg-max merges) with the
 NumPy oracle standing in for the per-rank HIP kernels.  Result must equal the
 reference's golden vectors, i.e. the unsharded run."""
+import importlib.util
 import json
 import os
 import socket
@@ -12,6 +13,14 @@ import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _needs_torch():
+    """Skip without torch -- looked up, not imported: the ranks import it in their own
+    processes.  Imported here it would bring its bundled HIP runtime and RCCL into the
+    test process, and every GPU test after this module would run on those."""
+    if importlib.util.find_spec("torch") is None:
+        pytest.skip("torch is not installed")
 
 
 def _free_port():
@@ -102,7 +111,7 @@ def _worker(rank, world, port, names, q):
 
 @pytest.mark.timeout(600)
 def test_two_ranks_reproduce_unsharded_golden():
-    pytest.importorskip("torch")
+    _needs_torch()
     import multiprocessing as mp
     ctx = mp.get_context("spawn")
     names = ["safeopt_2d_rbf", "safeopt_1d_multi", "safeopt_1d_lipschitz", "safeopt_context",
@@ -170,7 +179,7 @@ def test_two_ranks_big_passes_of_the_expander_loop():
     three calls of a pass (histograms summed, candidates gathered, flags or-ed): a converged
     state -- every candidate visited in passes of 8 and 16, none marked -- with GP and with
     Lipschitz certificates, equal to the unsharded oracle."""
-    pytest.importorskip("torch")
+    _needs_torch()
     import multiprocessing as mp
     ctx = mp.get_context("spawn")
     port = _free_port()
