@@ -184,14 +184,12 @@ int sgp_reserve(sgp_ctx* ctx, DevBuf* b, size_t bytes) {
   return 0;
 }
 
-void* sgp_scratch(sgp_ctx* ctx, int slot, size_t bytes) {
+void* scratch_slot(sgp_ctx* ctx, ScratchSlot slot, size_t bytes) {
   if (sgp_reserve(ctx, &ctx->scratch[slot], bytes) != 0) return nullptr;
   // SGP_POISON=2: ... and a scratch slot every time it is asked for (what a call finds there
-  // from the call before is as good as unwritten), except the slots that are asked for again
-  // with their contents in place: the candidate staged in front of enqueue_expander (7), the
-  // selection carried from one call of a pass to the next (8), the operand blocks (9-11)
+  // from the call before is as good as unwritten), except the kept slots (common.h)
   static const bool every = getenv("SGP_POISON") && atoi(getenv("SGP_POISON")) == 2;
-  if (every && (slot < 7 || slot > 11) &&
+  if (every && !scratch_kept(slot) &&
       hipMemsetAsync(ctx->scratch[slot].p, 0xFF, bytes, ctx->stream) != hipSuccess)
     return nullptr;
   return ctx->scratch[slot].p;
@@ -332,7 +330,7 @@ int sgp_gp_set_data(sgp_gp* gp, const double* X, const double* Y, int64_t n,
                     int* chol_info, double* jitter_used) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, n >= 1 && n <= 16384, "n = %lld training points unsupported",
+  SGP_CHECK(ctx, n >= 1 && n <= kMaxObservations, "n = %lld training points unsupported",
             (long long)n);
   const int d = gp->kern.d;
   ++gp->data_version;
@@ -426,13 +424,12 @@ int sgp_gp_predict(sgp_gp* gp, const double* Xnew, int64_t N,
   if (N <= 0) return 0;
   const int d = gp->kern.d;
   // stage the rows through a dense row-major device copy
-  double* stage = static_cast<double*>(
-      sgp_scratch(ctx, 3, size_t(N) * d * sizeof(double)));
-  double* pts = static_cast<double*>(
-      sgp_scratch(ctx, 4, size_t(N) * (d + 2) * sizeof(double)));
-  GpDev* gdev = static_cast<GpDev*>(sgp_scratch(ctx, 5, sizeof(GpDev)));
-  SGP_CHECK(ctx, stage && pts && gdev, "device allocation failed: %s",
-            ctx->err.c_str());
+  double* stage;
+  double* pts;
+  GpDev* gdev;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, size_t(N) * d * sizeof(double), &stage));
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, size_t(N) * (d + 2) * sizeof(double), &pts));
+  SGP_TRY(sgp_scratch(ctx, kSlotGpDev, sizeof(GpDev), &gdev));
   if (small_path_pays(gp, N)) {
     // a few points: triangular multi-RHS products instead of one sweep tile
     std::vector<double> tmp(size_t(N) * d);
@@ -443,8 +440,7 @@ int sgp_gp_predict(sgp_gp* gp, const double* Xnew, int64_t N,
     double* mvs = pts;                        // [mean N | var N]
     SGP_TRY(sgp_h2d(ctx, gdev, &gp->dev, sizeof(GpDev)));
     SmallBufs sb;
-    SGP_CHECK(ctx, small_reserve(ctx, &gp->dev, 1, int(N), &sb) == 0,
-              "device allocation failed: %s", ctx->err.c_str());
+    SGP_TRY(small_reserve(ctx, &gp->dev, 1, int(N), &sb));
     SGP_TRY(posterior_small_all(ctx, gdev, &gp->dev, 1, stage, int(N), sb, mvs, mvs + N));
     SGP_TRY(sgp_d2h(ctx, mean, mvs, size_t(N) * sizeof(double)));
     return sgp_d2h(ctx, var, mvs + N, size_t(N) * sizeof(double));
@@ -504,9 +500,10 @@ int sgp_kern_K(sgp_ctx* ctx, int d, int n_parts, const int* kinds,
   const size_t b1 = size_t(n1) * d * sizeof(double);
   const size_t b2 = size_t(n2) * d * sizeof(double);
   const size_t bo = size_t(n1) * n2 * sizeof(double);
-  double* x1 = static_cast<double*>(sgp_scratch(ctx, 3, b1 + b2));
-  double* o = static_cast<double*>(sgp_scratch(ctx, 4, bo));
-  SGP_CHECK(ctx, x1 && o, "device allocation failed: %s", ctx->err.c_str());
+  double* x1;
+  double* o;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, b1 + b2, &x1));
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, bo, &o));
   double* x2 = x1 + size_t(n1) * d;
   SGP_TRY(sgp_h2d(ctx, x1, X1, b1));
   SGP_TRY(sgp_h2d(ctx, x2, X2, b2));
@@ -573,8 +570,8 @@ int sgp_grid_create(sgp_ctx* ctx, const double* base, int64_t N, int d,
   if (sr == 1 && sc == N) {
     SGP_TRY(sgp_h2d(ctx, g->pts, base, nd * d));
   } else if (sc == 1 && sr == d) {
-    double* stage = static_cast<double*>(sgp_scratch(ctx, 3, nd * d));
-    SGP_CHECK(ctx, stage, "device allocation failed: %s", ctx->err.c_str());
+    double* stage;
+    SGP_TRY(sgp_scratch(ctx, kSlotStage, nd * d, &stage));
     SGP_TRY(sgp_h2d(ctx, stage, base, nd * d));
     SGP_TRY(launch_import_points(ctx, stage, N, d, d, 1, g->pts));
     SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -659,8 +656,8 @@ int sgp_grid_set_axes(sgp_grid* g, int d, const int64_t* count, const int64_t* s
   }
   SGP_TRY(sgp_reserve(ctx, &g->ax_vals, size_t(nvals) * sizeof(double)));
   SGP_TRY(sgp_h2d(ctx, g->ax_vals.p, g->ax_host.data(), size_t(nvals) * sizeof(double)));
-  int* mism = static_cast<int*>(sgp_scratch(ctx, 2, 256));
-  SGP_CHECK(ctx, mism, "device allocation failed: %s", ctx->err.c_str());
+  int* mism;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, 256, &mism));
   SGP_HIP(ctx, hipMemsetAsync(mism, 0, sizeof(int), ctx->stream));
   SGP_TRY(launch_verify_axes(g, mism));
   int bad = 0;
@@ -811,14 +808,34 @@ static int stage_gpdev(sgp_grid* g, const GpDev* host, int G) {
   return 0;
 }
 
-int sgp_grid_confidence(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
-                        const double* fmin, double* out2) {
+// The preamble of the grid entry points that take GPs: the device, the G the grid was made
+// for, the GPs' descriptors in `host` and, staged, in g->gpdev.
+static int grid_gps(sgp_grid* g, sgp_gp* const* gps, int G, GpDev* host) {
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  GpDev host[SGP_MAX_GPS];
   SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
-  SGP_TRY(stage_gpdev(g, host, G));
+  return stage_gpdev(g, host, G);
+}
+
+// `words` doubles of zeroed host memory the device writes directly (pinned, mapped,
+// coherent): *host, and *dev as the device sees it
+static int mapped_block(sgp_ctx* ctx, size_t words, double** host, double** dev) {
+  void* h = nullptr;
+  SGP_HIP(ctx, hipHostMalloc(&h, words * 8, hipHostMallocMapped | hipHostMallocCoherent));
+  memset(h, 0, words * 8);
+  void* dv = nullptr;
+  SGP_HIP(ctx, hipHostGetDevicePointer(&dv, h, 0));
+  *host = static_cast<double*>(h);
+  *dev = static_cast<double*>(dv);
+  return 0;
+}
+
+int sgp_grid_confidence(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
+                        const double* fmin, double* out2) {
+  sgp_ctx* ctx = g->ctx;
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
   SweepPoints sp{g->pts, g->N, 1, g->N};
   ConfOut co{};
   co.Q = g->Q;
@@ -836,11 +853,8 @@ int sgp_grid_confidence(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
 
 int sgp_grid_posterior(sgp_grid* g, sgp_gp* const* gps, int G) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
   GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
-  SGP_TRY(stage_gpdev(g, host, G));
+  SGP_TRY(grid_gps(g, gps, G, host));
   SweepPoints sp{g->pts, g->N, 1, g->N};
   ConfOut co{};            // Q, S, partial stay null: mean / var only
   co.mean = g->mean;
@@ -856,10 +870,8 @@ int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
                           const int* which, double beta, const double* fmin,
                           double* out2) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
   GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
+  SGP_TRY(grid_gps(g, gps, G, host));
   Rank1Args ra{};
   for (int i = 0; i < SGP_MAX_GPS; ++i) {
     ra.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
@@ -868,7 +880,6 @@ int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
       SGP_CHECK(ctx, gps[i]->upd_valid,
                 "GP %d has no append record for a rank-1 update", i);
   }
-  SGP_TRY(stage_gpdev(g, host, G));
   ra.Q = g->Q;
   ra.mean = g->mean;
   ra.var = g->var;
@@ -893,8 +904,8 @@ int sgp_grid_maximizers(sgp_grid* g, double max_l, double* out) {
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_TRY(launch_maximizers(g, max_l));
-  double* red = static_cast<double*>(sgp_scratch(ctx, 1, 64));
-  SGP_CHECK(ctx, red, "device allocation failed: %s", ctx->err.c_str());
+  double* red;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, 64, &red));
   SGP_TRY(launch_reduce_max(ctx, g->partial, (g->N + 255) / 256, red));
   return sgp_d2h(ctx, out, red, sizeof(double));
 }
@@ -904,9 +915,8 @@ int sgp_grid_candidates(sgp_grid* g, double max_var, const double* scaling,
                         int64_t* counts) {
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
-  unsigned long long* cd =
-      static_cast<unsigned long long*>(sgp_scratch(ctx, 1, 64));
-  SGP_CHECK(ctx, cd, "device allocation failed: %s", ctx->err.c_str());
+  unsigned long long* cd;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, 64, &cd));
   SGP_TRY(launch_candidates(g, max_var, nullptr, scaling, thr_beta, full_sets,
                             cd));
   return sgp_d2h(ctx, counts, cd, 2 * sizeof(int64_t));
@@ -917,8 +927,8 @@ int sgp_grid_topk(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, int k,
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, k >= 1 && k <= 64, "k = %d not in 1..64", k);
-  char* res = static_cast<char*>(sgp_scratch(ctx, 1, 2048));
-  SGP_CHECK(ctx, res, "device allocation failed: %s", ctx->err.c_str());
+  char* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, 2048, &res));
   double* wd = reinterpret_cast<double*>(res);
   int64_t* id = reinterpret_cast<int64_t*>(res + 512);
   int* nd = reinterpret_cast<int*>(res + 1024);
@@ -943,8 +953,8 @@ static int upload_local_idx(sgp_grid* g, const int64_t* gidx, int m,
               "global index %lld is not owned by this shard",
               (long long)gidx[j]);
   }
-  int64_t* d = static_cast<int64_t*>(sgp_scratch(ctx, 6, size_t(m) * 8));
-  SGP_CHECK(ctx, d, "device allocation failed: %s", ctx->err.c_str());
+  int64_t* d;
+  SGP_TRY(sgp_scratch(ctx, kSlotSmall, size_t(m) * 8, &d));
   SGP_TRY(sgp_h2d(ctx, d, li.data(), size_t(m) * 8));
   *dev = d;
   return 0;
@@ -958,8 +968,8 @@ int sgp_grid_gather_rows(sgp_grid* g, const int64_t* gidx, int m, double* x,
   SGP_TRY(upload_local_idx(g, gidx, m, &li));
   const int d = g->d, G = g->G;
   const size_t per = size_t(d) + 4 * size_t(G);
-  double* o = static_cast<double*>(sgp_scratch(ctx, 7, size_t(m) * per * 8));
-  SGP_CHECK(ctx, o, "device allocation failed: %s", ctx->err.c_str());
+  double* o;
+  SGP_TRY(sgp_scratch(ctx, kSlotOperands, size_t(m) * per * 8, &o));
   double* ox = o;
   double* om = ox + size_t(m) * d;
   double* ov = om + size_t(m) * G;
@@ -1002,8 +1012,8 @@ int sgp_grid_lipschitz_check(sgp_grid* g, int G, const double* fmin,
   const int d = g->d;
   const size_t bx = size_t(m) * d * 8, bu = size_t(m) * G * 8,
                bf = size_t(m) * G * 4;
-  char* buf = static_cast<char*>(sgp_scratch(ctx, 7, bx + bu + bf + 64));
-  SGP_CHECK(ctx, buf, "device allocation failed: %s", ctx->err.c_str());
+  char* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotOperands, bx + bu + bf + 64, &buf));
   double* dx = reinterpret_cast<double*>(buf);
   double* du = reinterpret_cast<double*>(buf + bx);
   int32_t* df = reinterpret_cast<int32_t*>(buf + bx + bu);
@@ -1018,8 +1028,8 @@ int sgp_grid_argmax(sgp_grid* g, int mode, const double* scaling, double* value,
                     int64_t* gidx) {
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
-  char* res = static_cast<char*>(sgp_scratch(ctx, 1, 64));
-  SGP_CHECK(ctx, res, "device allocation failed: %s", ctx->err.c_str());
+  char* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, 64, &res));
   SGP_TRY(launch_argmax(g, mode, scaling, reinterpret_cast<double*>(res),
                         reinterpret_cast<int64_t*>(res + 8)));
   char host[16];
@@ -1055,9 +1065,8 @@ int sgp_grid_download(sgp_grid* g, int what, void* out) {
   return -2;
 }
 
-// Enqueue the expander test (operands + scan); flags stay on the device.
-// `top` != nullptr: the single candidate is already on the device (result
-// block of the front half: x | mean | q) and xc / mu_c / u_c are ignored.
+// The operands of an expander test of up to SGP_TOPK candidates (kept slot: staged by the
+// caller, on the device or from the host, then built by enqueue_expander).
 struct ExpanderBufs {   // device layout: xc | resid[G][16] | delta | inv_s2 | tn2 | flags | W
   double *xc, *resid, *delta, *inv_s2, *tn2, *W;
   int32_t* flags;
@@ -1065,17 +1074,21 @@ struct ExpanderBufs {   // device layout: xc | resid[G][16] | delta | inv_s2 | t
   int64_t wstride;
 };
 
-static int expander_bufs(sgp_grid* g, const GpDev* host, int G, ExpanderBufs* b) {
-  sgp_ctx* ctx = g->ctx;
+// doubles between consecutive GPs of a W operand block: the largest factor's n_pad / 4 k-steps
+static int64_t w_stride(const GpDev* host, int G) {
   int np_max = 0;
   for (int i = 0; i < G; ++i) np_max = host[i].n_pad > np_max ? host[i].n_pad : np_max;
-  b->wstride = int64_t(np_max / 4) * 64;
+  return int64_t(np_max / 4) * 64;
+}
+
+static int expander_bufs(sgp_grid* g, const GpDev* host, int G, ExpanderBufs* b) {
+  b->wstride = w_stride(host, G);
   b->bx = size_t(SGP_TOPK) * g->d * 8;
   b->bv = size_t(G) * 16 * 8;
   b->bf = size_t(SGP_TOPK) * G * 4 + 64;
   const size_t total = b->bx + 4 * b->bv + b->bf + size_t(G) * b->wstride * 8;
-  char* buf = static_cast<char*>(sgp_scratch(ctx, 7, total));
-  SGP_CHECK(ctx, buf, "device allocation failed: %s", ctx->err.c_str());
+  char* buf;
+  SGP_TRY(sgp_scratch(g->ctx, kSlotOperands, total, &buf));
   b->xc = reinterpret_cast<double*>(buf);
   b->resid = reinterpret_cast<double*>(buf + b->bx);
   b->delta = reinterpret_cast<double*>(buf + b->bx + b->bv);
@@ -1086,90 +1099,74 @@ static int expander_bufs(sgp_grid* g, const GpDev* host, int G, ExpanderBufs* b)
   return 0;
 }
 
-// `staged`: xc / resid already hold the (single) candidate and the flags are
-// zeroed (k_front_final did both on the device); xc / mu_c / u_c are ignored.
-static int enqueue_expander(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
-                            const double* fmin, int m, const double* xc,
-                            const double* mu_c, const double* u_c,
-                            double near_frac, int32_t** flags_dev,
-                            const double* top = nullptr, bool staged = false,
+// fmin of every GP slot and the GPs with a constraint, for the operands and the scan
+static void fill_fmin_active(const double* fmin, int G, ExpanderArgs* ea, ExpanderOps* ops) {
+  for (int i = 0; i < SGP_MAX_GPS; ++i) {
+    ea->fmin[i] = (i < G) ? fmin[i] : -INFINITY;
+    ea->active[i] = (i < G) && (fmin[i] != -INFINITY);
+    ops->active[i] = ea->active[i];
+  }
+}
+
+// Enqueue the expander test of m <= SGP_TOPK candidates (operands + scan) on the GPs `host`,
+// staged in g->gpdev; the flags stay on the device (eb.flags).  xc == nullptr: eb already
+// holds the candidates and zeroed flags (launch_stage_batch, the front fold, k_merge_front);
+// else they come from the host arrays xc / mu_c / u_c.
+static int enqueue_expander(sgp_grid* g, const GpDev* host, const ExpanderBufs& eb,
+                            double beta, const double* fmin, int m, const double* xc,
+                            const double* mu_c, const double* u_c, double near_frac,
                             const FrontArgs* fold = nullptr) {
   sgp_ctx* ctx = g->ctx;
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
+  const int d = g->d, G = g->G;
   SGP_CHECK(ctx, m >= 1 && m <= SGP_TOPK, "m = %d not in 1..%d", m, SGP_TOPK);
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
-  const int d = g->d;
-  ExpanderBufs eb;
-  SGP_TRY(expander_bufs(g, host, G, &eb));
-  const size_t bx = eb.bx, bv = eb.bv, bf = eb.bf;
-  const int64_t wstride = eb.wstride;
-  double *dxc = eb.xc, *dres = eb.resid, *ddel = eb.delta, *dis2 = eb.inv_s2,
-         *dtn2 = eb.tn2, *dW = eb.W;
-  int32_t* dfl = eb.flags;
-  // pinned staging block: xc | resid (descriptors have their own slot)
-  const size_t hb = bx + bv + sizeof(GpDev) * SGP_MAX_GPS;
-  SGP_CHECK(ctx, hb <= ctx->pinned_cap / 2, "staging buffer too small");
-  char* stage = static_cast<char*>(ctx->pinned) + ctx->pinned_cap / 2;
-  // previous users of this block have completed (every call that writes it
-  // syncs before returning)
-  if (staged) {
-    // nothing to stage
-  } else if (top) {
-    SGP_HIP(ctx, hipMemsetAsync(dxc, 0, bx + bv, ctx->stream));
-    SGP_TRY(launch_stage_top(g, top, top + d, top + d + G, dxc, dres));
-  } else {
-    memset(stage, 0, bx + bv);
+  if (xc) {
+    // pinned staging block: xc | resid (descriptors have their own slot); previous users of
+    // this block have completed (every call that writes it syncs before returning)
+    const size_t hb = eb.bx + eb.bv + sizeof(GpDev) * SGP_MAX_GPS;
+    SGP_CHECK(ctx, hb <= ctx->pinned_cap / 2, "staging buffer too small");
+    char* stage = static_cast<char*>(ctx->pinned) + ctx->pinned_cap / 2;
+    memset(stage, 0, eb.bx + eb.bv);
     memcpy(stage, xc, size_t(m) * d * 8);
-    double* resid = reinterpret_cast<double*>(stage + bx);
+    double* resid = reinterpret_cast<double*>(stage + eb.bx);
     for (int c = 0; c < m; ++c)
       for (int i = 0; i < G; ++i)
         resid[size_t(i) * 16 + c] = u_c[c * G + i] - mu_c[c * G + i];
-    SGP_HIP(ctx, hipMemcpyAsync(dxc, stage, bx + bv, hipMemcpyHostToDevice,
+    SGP_HIP(ctx, hipMemcpyAsync(eb.xc, stage, eb.bx + eb.bv, hipMemcpyHostToDevice,
                                 ctx->stream));
+    SGP_HIP(ctx, hipMemsetAsync(eb.flags, 0, eb.bf, ctx->stream));
   }
-  SGP_TRY(stage_gpdev(g, host, G));
-  if (!staged) SGP_HIP(ctx, hipMemsetAsync(dfl, 0, bf, ctx->stream));
   ExpanderArgs ea{};
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    ea.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
-    ea.active[i] = (i < G) && (fmin[i] != -INFINITY);
-  }
   ExpanderOps ops{};
-  ops.xc = dxc;
-  ops.resid = dres;
-  ops.Wpack = dW;
-  ops.delta = ddel;
-  ops.inv_s2 = dis2;
-  ops.tn2 = dtn2;
-  ops.wstride = wstride;
+  fill_fmin_active(fmin, G, &ea, &ops);
+  ops.xc = eb.xc;
+  ops.resid = eb.resid;
+  ops.Wpack = eb.W;
+  ops.delta = eb.delta;
+  ops.inv_s2 = eb.inv_s2;
+  ops.tn2 = eb.tn2;
+  ops.wstride = eb.wstride;
   ops.m = m;
-  for (int i = 0; i < SGP_MAX_GPS; ++i) ops.active[i] = ea.active[i];
   SGP_TRY(expander_operands_all(ctx, g->gpdev, host, G, d, ops, fold));
-  ea.Wpack = dW;
-  ea.xc = dxc;
-  ea.delta = ddel;
-  ea.inv_s2 = dis2;
-  ea.tn2 = dtn2;
+  ea.Wpack = eb.W;
+  ea.xc = eb.xc;
+  ea.delta = eb.delta;
+  ea.inv_s2 = eb.inv_s2;
+  ea.tn2 = eb.tn2;
   ea.m = m;
   ea.beta = beta;
   ea.S = g->S;
   ea.mean = g->mean;
   ea.var = g->var;
-  ea.flags = dfl;
-  ea.wstride = wstride;
+  ea.flags = eb.flags;
+  ea.wstride = eb.wstride;
   ea.near_frac = near_frac;
   // single candidate: pre-filter + listed contraction; the group counter sits
   // in the slack behind the flags (zeroed with them), the list in scratch
-  ea.count = reinterpret_cast<int*>(reinterpret_cast<char*>(dfl) +
+  ea.count = reinterpret_cast<int*>(reinterpret_cast<char*>(eb.flags) +
                                     size_t(SGP_TOPK) * G * 4 + 32);
-  ea.list = (m == 1) ? static_cast<int*>(sgp_scratch(
-                           ctx, 0, (size_t(g->N) + 64) * sizeof(int)))
-                     : nullptr;
+  if (m == 1) SGP_TRY(sgp_scratch(ctx, kSlotList, (size_t(g->N) + 64) * sizeof(int), &ea.list));
   SweepPoints sp{g->pts, g->N, 1, g->N};
-  SGP_TRY(launch_expander_check(ctx, g->gpdev, host, G, d, sp, ea));
-  *flags_dev = dfl;
-  return 0;
+  return launch_expander_check(ctx, g->gpdev, host, G, d, sp, ea);
 }
 
 int sgp_grid_expander_check(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
@@ -1177,12 +1174,13 @@ int sgp_grid_expander_check(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
                             const double* mu_c, const double* u_c,
                             double near_frac, int32_t* flags) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  int32_t* dfl = nullptr;
-  SGP_TRY(enqueue_expander(g, gps, G, beta, fmin, m, xc, mu_c, u_c, near_frac,
-                           &dfl));
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
+  ExpanderBufs eb;
+  SGP_TRY(expander_bufs(g, host, G, &eb));
+  SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, m, xc, mu_c, u_c, near_frac));
   std::vector<int32_t> fl(size_t(SGP_TOPK) * G);
-  SGP_TRY(sgp_d2h(ctx, fl.data(), dfl, fl.size() * 4));
+  SGP_TRY(sgp_d2h(ctx, fl.data(), eb.flags, fl.size() * 4));
   memcpy(flags, fl.data(), size_t(m) * G * 4);
   return 0;
 }
@@ -1199,36 +1197,143 @@ int sgp_grid_expander_batch(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
                             int k, double* w_out, int64_t* gidx_out, int* n_out,
                             int32_t* flags) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
   SGP_CHECK(ctx, k >= 1 && k <= SGP_TOPK, "k = %d not in 1..%d", k, SGP_TOPK);
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  char* res = static_cast<char*>(sgp_scratch(ctx, 1, 2048));
-  SGP_CHECK(ctx, res, "device allocation failed: %s", ctx->err.c_str());
+  char* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, 2048, &res));
   double* wd = reinterpret_cast<double*>(res);
   int64_t* id = reinterpret_cast<int64_t*>(res + 512);
   int* nd = reinterpret_cast<int*>(res + 1024);
   if (mode == 1) cut_w = (cut_idx < 0) ? INFINITY : -double(cut_idx);
   SGP_TRY(launch_topk(g, mode, cut_w, cut_idx, k, wd, id, nd));
-  GpDev ghost[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, ghost));
   ExpanderBufs eb;
-  SGP_TRY(expander_bufs(g, ghost, G, &eb));
+  SGP_TRY(expander_bufs(g, host, G, &eb));
   SGP_TRY(launch_stage_batch(g, id, nd, k, eb.xc, int((eb.bx + eb.bv) / 8), eb.flags,
                              int(eb.bf / 4)));
-  int32_t* dfl = nullptr;
-  SGP_TRY(enqueue_expander(g, gps, G, beta, fmin, k, nullptr, nullptr, nullptr, 0.0, &dfl,
-                           nullptr, true));
+  SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, k, nullptr, nullptr, nullptr, 0.0));
   // flags behind the top-k block of the scratch: one read-back for both
-  SGP_HIP(ctx, hipMemcpyAsync(res + 1032, dfl, size_t(SGP_TOPK) * G * 4,
+  SGP_HIP(ctx, hipMemcpyAsync(res + 1032, eb.flags, size_t(SGP_TOPK) * G * 4,
                               hipMemcpyDeviceToDevice, ctx->stream));
-  char host[2048];
+  char hbuf[2048];
   const size_t span = 1032 + size_t(SGP_TOPK) * G * 4;
-  SGP_TRY(sgp_d2h(ctx, host, res, span));
-  memcpy(w_out, host, size_t(k) * sizeof(double));
-  memcpy(gidx_out, host + 512, size_t(k) * sizeof(int64_t));
-  memcpy(n_out, host + 1024, sizeof(int));
-  memcpy(flags, host + 1032, size_t(k) * G * 4);
+  SGP_TRY(sgp_d2h(ctx, hbuf, res, span));
+  memcpy(w_out, hbuf, size_t(k) * sizeof(double));
+  memcpy(gidx_out, hbuf + 512, size_t(k) * sizeof(int64_t));
+  memcpy(n_out, hbuf + 1024, sizeof(int));
+  memcpy(flags, hbuf + 1032, size_t(k) * G * 4);
   return 0;
+}
+
+// The scratch of a big pass (kept slot): the listed candidates (local rows) | the key
+// histogram | the selection | per-chunk counts of the listing
+struct PassScratch {
+  int* list;        // [N]
+  unsigned* hist;   // [kPassBins]
+  PassSel* sel;
+  int* counts;      // [N / 256 + 2]
+};
+
+static int pass_scratch(sgp_grid* g, PassScratch* ps) {
+  const size_t nl = (size_t(g->N) * 4 + 63) & ~size_t(63);
+  const size_t nh = kPassBins * sizeof(unsigned);
+  static_assert(sizeof(PassSel) <= 256, "PassSel has 256 bytes");
+  char* sb;
+  SGP_TRY(sgp_scratch(g->ctx, kSlotPass, nl + nh + 256 + (size_t(g->N) / 256 + 2) * 4, &sb));
+  ps->list = reinterpret_cast<int*>(sb);
+  ps->hist = reinterpret_cast<unsigned*>(sb + nl);
+  ps->sel = reinterpret_cast<PassSel*>(sb + nl + nh);
+  ps->counts = reinterpret_cast<int*>(sb + nl + nh + 256);
+  return 0;
+}
+
+// The expander test of m listed candidates in one scan of the unsafe rows (k_expander_many):
+// the operand / W / flag blocks of the kept slots, the operands of every active GP (staged
+// GPs `host`), the scan.  The candidates are the first m of the device list of a pass
+// (list) or come from the host: xc [m][d], resid [m][G] = u_g - mu_g at the candidate.
+// *flags_dev: [m][G] flags, then 64 bytes of slack.
+static int expander_many_test(sgp_grid* g, const GpDev* host, double beta, const double* fmin,
+                              int m, const int* list, const double* xc, const double* resid,
+                              int32_t** flags_dev) {
+  sgp_ctx* ctx = g->ctx;
+  const int d = g->d, G = g->G;
+  const int64_t wstride = w_stride(host, G);
+  const size_t ngroups = (size_t(m) + 15) / 16;
+  const size_t nxc = ngroups * 16 * d, nv = ngroups * G * 16;
+  // xc | resid[group][g][16] | delta | inv_s2 | tn2 | stn | svc | agg | box | sagg | sbox
+  double* ob;
+  double* Wp;
+  int32_t* dfl;
+  SGP_TRY(sgp_scratch(ctx, kSlotManyOps,
+                      (nxc + 7 * nv + ngroups * 2 * d + 8 + (ngroups / 8 + 1) * (4 * G + 2 * d)) * 8,
+                      &ob));
+  SGP_TRY(sgp_scratch(ctx, kSlotManyW, ngroups * G * size_t(wstride) * 8, &Wp));
+  SGP_TRY(sgp_scratch(ctx, kSlotManyFlags, ngroups * 16 * G * 4 + 64, &dfl));
+  double *dxc = ob, *dres = ob + nxc, *ddel = dres + nv, *dis2 = ddel + nv, *dtn2 = dis2 + nv;
+  if (list) {
+    SGP_HIP(ctx, hipMemsetAsync(ob, 0, (nxc + nv) * 8, ctx->stream));
+    SGP_TRY(launch_pass_stage(g, list, m, dxc, dres));
+  } else {
+    std::vector<double> st(nxc + nv, 0.0);
+    memcpy(st.data(), xc, size_t(m) * d * 8);
+    for (int c = 0; c < m; ++c)
+      for (int i = 0; i < G; ++i)
+        st[nxc + (size_t(c >> 4) * G + i) * 16 + (c & 15)] = resid[size_t(c) * G + i];
+    SGP_TRY(sgp_h2d(ctx, ob, st.data(), st.size() * 8));
+  }
+  SGP_HIP(ctx, hipMemsetAsync(dfl, 0, ngroups * 16 * G * 4, ctx->stream));
+  ExpanderArgs ea{};
+  ExpanderOps ops{};
+  fill_fmin_active(fmin, G, &ea, &ops);
+  ops.xc = dxc;
+  ops.resid = dres;
+  ops.Wpack = Wp;
+  ops.delta = ddel;
+  ops.inv_s2 = dis2;
+  ops.tn2 = dtn2;
+  ops.wstride = wstride;
+  ops.m = m;
+  ops.Gs = G;
+  SGP_TRY(expander_operands_all(ctx, g->gpdev, host, G, d, ops, nullptr));
+  ea.Wpack = Wp;
+  ea.xc = dxc;
+  ea.delta = ddel;
+  ea.inv_s2 = dis2;
+  ea.tn2 = dtn2;
+  ea.stn = dtn2 + nv;
+  ea.svc = dtn2 + 2 * nv;
+  ea.agg = dtn2 + 3 * nv;          // (ngroups G 4 <= nv)
+  ea.box = dtn2 + 4 * nv;
+  ea.sagg = ea.box + ngroups * 2 * d + 8;
+  ea.sbox = ea.sagg + (ngroups / 8 + 1) * 4 * G;
+  ea.m = m;
+  ea.beta = beta;
+  ea.S = g->S;
+  ea.mean = g->mean;
+  ea.var = g->var;
+  ea.flags = dfl;
+  ea.wstride = wstride;
+  ea.near_frac = 0.0;
+  SweepPoints sp{g->pts, g->N, 1, g->N};
+  SGP_TRY(launch_expander_many(ctx, g->gpdev, G, d, sp, ea));
+  *flags_dev = dfl;
+  return 0;
+}
+
+// The work and flag blocks of the Lipschitz test of m candidates (launch_lipschitz_many);
+// *flags: [m][G], then 64 bytes of slack.
+static int lipschitz_bufs(sgp_grid* g, int m, double** work, int32_t** flags) {
+  const int d = g->d, G = g->G;
+  const size_t ngroups = (size_t(m) + 15) / 16;
+  SGP_TRY(sgp_scratch(g->ctx, kSlotManyOps, (size_t(m) * (d + G) + ngroups * (2 * d + 1) + 8) * 8,
+                      work));
+  return sgp_scratch(g->ctx, kSlotManyFlags, size_t(m) * G * 4 + 64, flags);
+}
+
+// the 8-byte aligned slack behind `bytes` of flags
+static double* behind_flags(int32_t* flags, size_t bytes) {
+  const uintptr_t p = reinterpret_cast<uintptr_t>(flags) + bytes;
+  return reinterpret_cast<double*>((p + 7) & ~uintptr_t(7));
 }
 
 // A pass of the expander loop over MANY candidates (gp_opt.py:557-612 where the loop has to
@@ -1245,12 +1350,33 @@ int sgp_grid_expander_batch(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
 //   mode 1: every expander of the pass is marked in G; out6[2..3] unused.
 // key_lo / key_hi: range of the keys still behind the cut (histogram range; mode 0:
 // 0 .. the width of the cut).  One rank.
+//
+// The selection of such a pass: *count candidates listed in ps, out6[0] / out6[4] set.
+static int pass_select(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, double key_lo,
+                       double key_hi, int want, double* out6, PassScratch* ps, int* count) {
+  sgp_ctx* ctx = g->ctx;
+  SGP_CHECK(ctx, want >= 1, "want = %d", want);
+  SGP_CHECK(ctx, key_hi > key_lo, "empty key range %g .. %g", key_lo, key_hi);
+  SGP_CHECK(ctx, g->N < (int64_t(1) << 31), "%lld rows", (long long)g->N);
+  for (int i = 0; i < 6; ++i) out6[i] = 0.0;
+  SGP_TRY(pass_scratch(g, ps));
+  SGP_TRY(launch_pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, ps->sel, ps->list,
+                             ps->hist, ps->counts));
+  PassSel hs;
+  SGP_TRY(sgp_d2h(ctx, &hs, ps->sel, sizeof(hs)));
+  *count = hs.count;
+  out6[0] = double(hs.count);
+  out6[4] = hs.count == 0 ? -INFINITY : hs.thr;
+  return 0;
+}
+
 // the result of a pass and, behind it in the same read-back, the arg-max of the step
 // (gp_opt.py:631-641 over M | G) for the case that the pass ends the loop without a hit
-static int pass_result_and_argmax(sgp_grid* g, const int* list, int count, const int32_t* dfl,
-                                  const double* fmin, int mode, const double* scaling,
-                                  double* res, double* out6) {
+static int pass_result_and_argmax(sgp_grid* g, const int* list, int count, int32_t* dfl,
+                                  size_t flag_bytes, const double* fmin, int mode,
+                                  const double* scaling, double* out6) {
   sgp_ctx* ctx = g->ctx;
+  double* res = behind_flags(dfl, flag_bytes);
   SGP_TRY(launch_pass_result(g, list, count, dfl, fmin, mode, res));
   const bool spec = scaling != nullptr && mode == 0;
   if (spec)
@@ -1273,93 +1399,16 @@ int sgp_grid_expander_pass(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
                            const double* fmin, int mode, double cut_w, int64_t cut_idx,
                            double key_lo, double key_hi, int want, const double* scaling,
                            double* out6) {
-  sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  SGP_CHECK(ctx, want >= 1, "want = %d", want);
-  SGP_CHECK(ctx, key_hi > key_lo, "empty key range %g .. %g", key_lo, key_hi);
-  SGP_CHECK(ctx, g->N < (int64_t(1) << 31), "%lld rows", (long long)g->N);
-  for (int i = 0; i < 6; ++i) out6[i] = 0.0;
-  // selection
-  const size_t nl = (size_t(g->N) * 4 + 63) & ~size_t(63);      // list | histogram | sel | counts
-  char* sb = static_cast<char*>(sgp_scratch(ctx, 8, nl + 16384 + 256 + (size_t(g->N) / 256 + 2) * 4));
-  SGP_CHECK(ctx, sb, "device allocation failed: %s", ctx->err.c_str());
-  int* list = reinterpret_cast<int*>(sb);
-  unsigned* hist = reinterpret_cast<unsigned*>(sb + nl);
-  char* sel = sb + nl + 16384;
-  int* counts = reinterpret_cast<int*>(sb + nl + 16384 + 256);
-  SGP_TRY(launch_pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, sel, list, hist, counts));
-  struct { double thr; int count, est; } hs;
-  SGP_TRY(sgp_d2h(ctx, &hs, sel, sizeof(hs)));
-  const int count = hs.count;
-  out6[0] = double(count);
-  out6[4] = hs.thr;
-  if (count == 0) {
-    out6[4] = -INFINITY;
-    return 0;
-  }
-  // operands
   GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
-  const int d = g->d;
-  int np_max = 0;
-  for (int i = 0; i < G; ++i) np_max = host[i].n_pad > np_max ? host[i].n_pad : np_max;
-  const int64_t wstride = int64_t(np_max / 4) * 64;
-  const size_t ngroups = (size_t(count) + 15) / 16;
-  const size_t nxc = ngroups * 16 * d, nv = ngroups * G * 16;
-  double* ob = static_cast<double*>(sgp_scratch(
-      ctx, 9, (nxc + 7 * nv + ngroups * 2 * d + 8 + (ngroups / 8 + 1) * (4 * G + 2 * d)) * 8));
-  SGP_CHECK(ctx, ob, "device allocation failed: %s", ctx->err.c_str());
-  double* Wp = static_cast<double*>(sgp_scratch(ctx, 10, ngroups * G * size_t(wstride) * 8));
-  SGP_CHECK(ctx, Wp, "device allocation failed: %s", ctx->err.c_str());
-  int32_t* dfl = static_cast<int32_t*>(sgp_scratch(ctx, 11, ngroups * 16 * G * 4 + 64));
-  SGP_CHECK(ctx, dfl, "device allocation failed: %s", ctx->err.c_str());
-  double* res = reinterpret_cast<double*>(reinterpret_cast<char*>(dfl) + ngroups * 16 * G * 4);
-  res = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(res) + 7) & ~uintptr_t(7));
-  double *dxc = ob, *dres = ob + nxc, *ddel = dres + nv, *dis2 = ddel + nv, *dtn2 = dis2 + nv;
-  SGP_HIP(ctx, hipMemsetAsync(ob, 0, (nxc + nv) * 8, ctx->stream));
-  SGP_HIP(ctx, hipMemsetAsync(dfl, 0, ngroups * 16 * G * 4, ctx->stream));
-  SGP_TRY(launch_pass_stage(g, list, count, dxc, dres));
-  SGP_TRY(stage_gpdev(g, host, G));
-  ExpanderOps ops{};
-  ops.xc = dxc;
-  ops.resid = dres;
-  ops.Wpack = Wp;
-  ops.delta = ddel;
-  ops.inv_s2 = dis2;
-  ops.tn2 = dtn2;
-  ops.wstride = wstride;
-  ops.m = count;
-  ops.Gs = G;
-  ExpanderArgs ea{};
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    ea.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
-    ea.active[i] = (i < G) && (fmin[i] != -INFINITY);
-    ops.active[i] = ea.active[i];
-  }
-  SGP_TRY(expander_operands_all(ctx, g->gpdev, host, G, d, ops, nullptr));
-  ea.Wpack = Wp;
-  ea.xc = dxc;
-  ea.delta = ddel;
-  ea.inv_s2 = dis2;
-  ea.tn2 = dtn2;
-  ea.stn = dtn2 + nv;
-  ea.svc = dtn2 + 2 * nv;
-  ea.agg = dtn2 + 3 * nv;          // (ngroups G 4 <= nv)
-  ea.box = dtn2 + 4 * nv;
-  ea.sagg = ea.box + ngroups * 2 * d + 8;
-  ea.sbox = ea.sagg + (ngroups / 8 + 1) * 4 * G;
-  ea.m = count;
-  ea.beta = beta;
-  ea.S = g->S;
-  ea.mean = g->mean;
-  ea.var = g->var;
-  ea.flags = dfl;
-  ea.wstride = wstride;
-  ea.near_frac = 0.0;
-  SweepPoints sp{g->pts, g->N, 1, g->N};
-  SGP_TRY(launch_expander_many(ctx, g->gpdev, G, d, sp, ea));
-  return pass_result_and_argmax(g, list, count, dfl, fmin, mode, scaling, res, out6);
+  SGP_TRY(grid_gps(g, gps, G, host));
+  PassScratch ps;
+  int count = 0;
+  SGP_TRY(pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, out6, &ps, &count));
+  if (count == 0) return 0;
+  int32_t* dfl;
+  SGP_TRY(expander_many_test(g, host, beta, fmin, count, ps.list, nullptr, nullptr, &dfl));
+  return pass_result_and_argmax(g, ps.list, count, dfl, (size_t(count) + 15) / 16 * 16 * G * 4,
+                                fmin, mode, scaling, out6);
 }
 
 // The same pass with Lipschitz certificates (gp_opt.py:558-576 instead of :577-606): selection
@@ -1371,38 +1420,16 @@ int sgp_grid_lipschitz_pass(sgp_grid* g, int G, const double* fmin, const double
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  SGP_CHECK(ctx, want >= 1, "want = %d", want);
-  SGP_CHECK(ctx, key_hi > key_lo, "empty key range %g .. %g", key_lo, key_hi);
-  SGP_CHECK(ctx, g->N < (int64_t(1) << 31), "%lld rows", (long long)g->N);
-  for (int i = 0; i < 6; ++i) out6[i] = 0.0;
-  const size_t nl = (size_t(g->N) * 4 + 63) & ~size_t(63);      // list | histogram | sel | counts
-  char* sb = static_cast<char*>(sgp_scratch(ctx, 8, nl + 16384 + 256 + (size_t(g->N) / 256 + 2) * 4));
-  SGP_CHECK(ctx, sb, "device allocation failed: %s", ctx->err.c_str());
-  int* list = reinterpret_cast<int*>(sb);
-  unsigned* hist = reinterpret_cast<unsigned*>(sb + nl);
-  char* sel = sb + nl + 16384;
-  int* counts = reinterpret_cast<int*>(sb + nl + 16384 + 256);
-  SGP_TRY(launch_pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, sel, list, hist, counts));
-  struct { double thr; int count, est; } hs;
-  SGP_TRY(sgp_d2h(ctx, &hs, sel, sizeof(hs)));
-  const int count = hs.count;
-  out6[0] = double(count);
-  out6[4] = hs.thr;
-  if (count == 0) {
-    out6[4] = -INFINITY;
-    return 0;
-  }
-  const int d = g->d;
-  const size_t ngroups = (size_t(count) + 15) / 16;
-  double* work = static_cast<double*>(
-      sgp_scratch(ctx, 9, (size_t(count) * (d + G) + ngroups * (2 * d + 1) + 8) * 8));
-  SGP_CHECK(ctx, work, "device allocation failed: %s", ctx->err.c_str());
-  int32_t* dfl = static_cast<int32_t*>(sgp_scratch(ctx, 11, size_t(count) * G * 4 + 64));
-  SGP_CHECK(ctx, dfl, "device allocation failed: %s", ctx->err.c_str());
-  double* res = reinterpret_cast<double*>(reinterpret_cast<char*>(dfl) + size_t(count) * G * 4);
-  res = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(res) + 7) & ~uintptr_t(7));
-  SGP_TRY(launch_lipschitz_many(g, G, fmin, lipschitz, list, count, nullptr, nullptr, work, dfl));
-  return pass_result_and_argmax(g, list, count, dfl, fmin, mode, scaling, res, out6);
+  PassScratch ps;
+  int count = 0;
+  SGP_TRY(pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, out6, &ps, &count));
+  if (count == 0) return 0;
+  double* work;
+  int32_t* dfl;
+  SGP_TRY(lipschitz_bufs(g, count, &work, &dfl));
+  SGP_TRY(launch_lipschitz_many(g, G, fmin, lipschitz, ps.list, count, nullptr, nullptr, work, dfl));
+  return pass_result_and_argmax(g, ps.list, count, dfl, size_t(count) * G * 4, fmin, mode,
+                                scaling, out6);
 }
 
 // ---- the same pass on N ranks, in three calls with the ranks' agreement in between ----------
@@ -1415,12 +1442,10 @@ int sgp_grid_pass_hist(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, dou
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, key_hi > key_lo, "empty key range %g .. %g", key_lo, key_hi);
-  const size_t nl = (size_t(g->N) * 4 + 63) & ~size_t(63);      // list | histogram | sel | counts
-  char* sb = static_cast<char*>(sgp_scratch(ctx, 8, nl + 16384 + 256 + (size_t(g->N) / 256 + 2) * 4));
-  SGP_CHECK(ctx, sb, "device allocation failed: %s", ctx->err.c_str());
-  unsigned* dh = reinterpret_cast<unsigned*>(sb + nl);
-  SGP_TRY(launch_pass_hist(g, mode, cut_w, cut_idx, key_lo, key_hi, dh));
-  return sgp_d2h(ctx, hist, dh, 4096 * sizeof(uint32_t));
+  PassScratch ps;
+  SGP_TRY(pass_scratch(g, &ps));
+  SGP_TRY(launch_pass_hist(g, mode, cut_w, cut_idx, key_lo, key_hi, ps.hist));
+  return sgp_d2h(ctx, hist, ps.hist, kPassBins * sizeof(uint32_t));
 }
 
 int sgp_grid_pass_list(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, double thr, int cap,
@@ -1428,28 +1453,24 @@ int sgp_grid_pass_list(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, dou
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, g->N < (int64_t(1) << 31), "%lld rows", (long long)g->N);
-  const size_t nl = (size_t(g->N) * 4 + 63) & ~size_t(63);      // list | histogram | sel | counts
-  char* sb = static_cast<char*>(sgp_scratch(ctx, 8, nl + 16384 + 256 + (size_t(g->N) / 256 + 2) * 4));
-  SGP_CHECK(ctx, sb, "device allocation failed: %s", ctx->err.c_str());
-  int* list = reinterpret_cast<int*>(sb);
-  char* sel = sb + nl + 16384;
-  struct { double thr; int count, est; } hs = {thr, 0, 0};
-  SGP_TRY(sgp_h2d(ctx, sel, &hs, sizeof(hs)));
-  int* counts = reinterpret_cast<int*>(sb + nl + 16384 + 256);
+  PassScratch ps;
+  SGP_TRY(pass_scratch(g, &ps));
+  PassSel hs = {thr, 0, 0};
+  SGP_TRY(sgp_h2d(ctx, ps.sel, &hs, sizeof(hs)));
   const int upper = mode & 2;            // resid = u_i (Lipschitz certificates) instead of u_i - mu_i
   mode &= 1;
-  SGP_TRY(launch_pass_list(g, mode, cut_w, cut_idx, sel, list, counts));
-  SGP_TRY(sgp_d2h(ctx, &hs, sel, sizeof(hs)));
+  SGP_TRY(launch_pass_list(g, mode, cut_w, cut_idx, ps.sel, ps.list, ps.counts));
+  SGP_TRY(sgp_d2h(ctx, &hs, ps.sel, sizeof(hs)));
   *count = hs.count;
   if (hs.count == 0) return 0;
   SGP_CHECK(ctx, hs.count <= cap, "%d candidates above the threshold, room for %d", hs.count, cap);
   const int d = g->d, G = g->G;
   const size_t per = 2 + size_t(d) + size_t(G);
-  double* ob = static_cast<double*>(sgp_scratch(ctx, 9, size_t(hs.count) * per * 8));
-  SGP_CHECK(ctx, ob, "device allocation failed: %s", ctx->err.c_str());
+  double* ob;
+  SGP_TRY(sgp_scratch(ctx, kSlotManyOps, size_t(hs.count) * per * 8, &ob));
   int64_t* dg = reinterpret_cast<int64_t*>(ob);
   double *dk = ob + hs.count, *dx = dk + hs.count, *dr = dx + size_t(hs.count) * d;
-  SGP_TRY(launch_pass_gather(g, list, hs.count, mode | upper, dg, dk, dx, dr));
+  SGP_TRY(launch_pass_gather(g, ps.list, hs.count, mode | upper, dg, dk, dx, dr));
   std::vector<double> host(size_t(hs.count) * per);
   SGP_TRY(sgp_d2h(ctx, host.data(), ob, host.size() * 8));
   memcpy(gidx, host.data(), size_t(hs.count) * 8);
@@ -1463,74 +1484,12 @@ int sgp_grid_pass_list(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, dou
 // lifts one of THIS shard's unsafe rows above fmin_i.
 int sgp_grid_pass_test(sgp_grid* g, sgp_gp* const* gps, int G, double beta, const double* fmin,
                        int K, const double* xc, const double* resid, int32_t* flags) {
-  sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  if (K <= 0) return 0;
   GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
-  const int d = g->d;
-  int np_max = 0;
-  for (int i = 0; i < G; ++i) np_max = host[i].n_pad > np_max ? host[i].n_pad : np_max;
-  const int64_t wstride = int64_t(np_max / 4) * 64;
-  const size_t ngroups = (size_t(K) + 15) / 16;
-  const size_t nxc = ngroups * 16 * d, nv = ngroups * G * 16;
-  double* ob = static_cast<double*>(sgp_scratch(
-      ctx, 9, (nxc + 7 * nv + ngroups * 2 * d + 8 + (ngroups / 8 + 1) * (4 * G + 2 * d)) * 8));
-  SGP_CHECK(ctx, ob, "device allocation failed: %s", ctx->err.c_str());
-  double* Wp = static_cast<double*>(sgp_scratch(ctx, 10, ngroups * G * size_t(wstride) * 8));
-  SGP_CHECK(ctx, Wp, "device allocation failed: %s", ctx->err.c_str());
-  int32_t* dfl = static_cast<int32_t*>(sgp_scratch(ctx, 11, ngroups * 16 * G * 4 + 64));
-  SGP_CHECK(ctx, dfl, "device allocation failed: %s", ctx->err.c_str());
-  double *dxc = ob, *dres = ob + nxc, *ddel = dres + nv, *dis2 = ddel + nv, *dtn2 = dis2 + nv;
-  // operand block on the host: xc | resid[group][g][16]
-  std::vector<double> st(nxc + nv, 0.0);
-  memcpy(st.data(), xc, size_t(K) * d * 8);
-  for (int c = 0; c < K; ++c)
-    for (int i = 0; i < G; ++i)
-      st[nxc + (size_t(c >> 4) * G + i) * 16 + (c & 15)] = resid[size_t(c) * G + i];
-  SGP_TRY(sgp_h2d(ctx, ob, st.data(), st.size() * 8));
-  SGP_HIP(ctx, hipMemsetAsync(dfl, 0, ngroups * 16 * G * 4, ctx->stream));
-  SGP_TRY(stage_gpdev(g, host, G));
-  ExpanderOps ops{};
-  ops.xc = dxc;
-  ops.resid = dres;
-  ops.Wpack = Wp;
-  ops.delta = ddel;
-  ops.inv_s2 = dis2;
-  ops.tn2 = dtn2;
-  ops.wstride = wstride;
-  ops.m = K;
-  ops.Gs = G;
-  ExpanderArgs ea{};
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    ea.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
-    ea.active[i] = (i < G) && (fmin[i] != -INFINITY);
-    ops.active[i] = ea.active[i];
-  }
-  SGP_TRY(expander_operands_all(ctx, g->gpdev, host, G, d, ops, nullptr));
-  ea.Wpack = Wp;
-  ea.xc = dxc;
-  ea.delta = ddel;
-  ea.inv_s2 = dis2;
-  ea.tn2 = dtn2;
-  ea.stn = dtn2 + nv;
-  ea.svc = dtn2 + 2 * nv;
-  ea.agg = dtn2 + 3 * nv;          // (ngroups G 4 <= nv)
-  ea.box = dtn2 + 4 * nv;
-  ea.sagg = ea.box + ngroups * 2 * d + 8;
-  ea.sbox = ea.sagg + (ngroups / 8 + 1) * 4 * G;
-  ea.m = K;
-  ea.beta = beta;
-  ea.S = g->S;
-  ea.mean = g->mean;
-  ea.var = g->var;
-  ea.flags = dfl;
-  ea.wstride = wstride;
-  ea.near_frac = 0.0;
-  SweepPoints sp{g->pts, g->N, 1, g->N};
-  SGP_TRY(launch_expander_many(ctx, g->gpdev, G, d, sp, ea));
-  return sgp_d2h(ctx, flags, dfl, size_t(K) * G * 4);
+  SGP_TRY(grid_gps(g, gps, G, host));
+  if (K <= 0) return 0;
+  int32_t* dfl;
+  SGP_TRY(expander_many_test(g, host, beta, fmin, K, nullptr, xc, resid, &dfl));
+  return sgp_d2h(g->ctx, flags, dfl, size_t(K) * G * 4);
 }
 
 // ... and with Lipschitz certificates: the distance test of ALL K gathered candidates (rows xc
@@ -1543,39 +1502,73 @@ int sgp_grid_pass_lipschitz_test(sgp_grid* g, int G, const double* fmin, const d
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
   if (K <= 0) return 0;
-  const int d = g->d;
-  const size_t ngroups = (size_t(K) + 15) / 16;
-  double* work = static_cast<double*>(
-      sgp_scratch(ctx, 9, (size_t(K) * (d + G) + ngroups * (2 * d + 1) + 8) * 8));
-  SGP_CHECK(ctx, work, "device allocation failed: %s", ctx->err.c_str());
-  int32_t* dfl = static_cast<int32_t*>(sgp_scratch(ctx, 11, size_t(K) * G * 4 + 64));
-  SGP_CHECK(ctx, dfl, "device allocation failed: %s", ctx->err.c_str());
+  double* work;
+  int32_t* dfl;
+  SGP_TRY(lipschitz_bufs(g, K, &work, &dfl));
   SGP_TRY(launch_lipschitz_many(g, G, fmin, lipschitz, nullptr, K, xc, uc, work, dfl));
   return sgp_d2h(ctx, flags, dfl, size_t(K) * G * 4);
 }
 
-// Host copy of a front block ([0] max width | [1..2] counts (u64) | [3] w_top | [4]
-// idx_top (i64) | [5] n_found, n_tied (int) | x[d] | mean[G] | q[2G]) -> the caller's
-// arrays; out5[4] = -1 when the shard / grid has no candidate, out5[5] = number of
-// candidates that share the first one's width.
-static void unpack_front(const double* host, int d, int G, double* out5, double* x_top,
-                         double* mean_top, double* q_top) {
+// The ABI's outputs of a step (null: not asked for) ...
+struct StepOut {
+  double* out5;
+  double* x_top;
+  double* mean_top;
+  double* q_top;
+  int32_t* flags;
+  double* value;
+  int64_t* gidx;
+  double* max_l;
+};
+
+// ... from a host copy of its result block (sets_front.h): out5 = { max width, candidates,
+// unsafe rows, w_top, global index of the first candidate (-1: the shard / grid has none),
+// the candidates that share its width }.
+static void unpack_result(const double* h, int d, int G, const StepOut& o) {
   unsigned long long cnt[2];
   int64_t idx;
   int nfound, ntied;
-  memcpy(cnt, &host[1], 16);
-  memcpy(&idx, &host[4], 8);
-  memcpy(&nfound, &host[5], 4);
-  memcpy(&ntied, reinterpret_cast<const char*>(&host[5]) + 4, 4);
-  out5[0] = host[0];
-  out5[1] = double(cnt[0]);
-  out5[2] = double(cnt[1]);
-  out5[3] = host[3];
-  out5[4] = (nfound > 0) ? double(idx) : -1.0;
-  out5[5] = double(ntied);
-  memcpy(x_top, &host[6], size_t(d) * 8);
-  memcpy(mean_top, &host[6 + d], size_t(G) * 8);
-  memcpy(q_top, &host[6 + d + G], size_t(2 * G) * 8);
+  memcpy(cnt, &h[kResCounts], 16);
+  memcpy(&idx, &h[kResTopIdx], 8);
+  memcpy(&nfound, &h[kResFound], 4);
+  memcpy(&ntied, reinterpret_cast<const char*>(&h[kResFound]) + 4, 4);
+  o.out5[0] = h[kResMaxWidth];
+  o.out5[1] = double(cnt[0]);
+  o.out5[2] = double(cnt[1]);
+  o.out5[3] = h[kResTopW];
+  o.out5[4] = (nfound > 0) ? double(idx) : -1.0;
+  o.out5[5] = double(ntied);
+  memcpy(o.x_top, &h[kResX], size_t(d) * 8);
+  memcpy(o.mean_top, &h[res_mean(d)], size_t(G) * 8);
+  memcpy(o.q_top, &h[res_q(d, G)], size_t(2 * G) * 8);
+  if (o.flags) memcpy(o.flags, &h[res_flags(d, G)], size_t(G) * 4);
+  if (o.value) *o.value = h[res_value(d, G)];
+  if (o.gidx) memcpy(o.gidx, &h[res_index(d, G)], 8);
+  if (o.max_l) *o.max_l = h[res_max_l(d, G)];
+}
+static_assert(res_words(SGP_MAX_D, SGP_MAX_GPS) < kStepResWords, "result block too large");
+
+// ... read back from the device (the first `words` words)
+static int read_result(sgp_grid* g, const double* res_dev, int words, const StepOut& o) {
+  double h[kStepResWords];
+  SGP_TRY(sgp_d2h(g->ctx, h, res_dev, size_t(words) * 8));
+  unpack_result(h, g->d, g->G, o);
+  return 0;
+}
+
+// The first candidate in visiting order behind the max width and counts of a front block:
+// w_top, its index, n_found, the ties and its rows
+static int front_first(sgp_grid* g, double* res) {
+  const int d = g->d, G = g->G;
+  SGP_TRY(launch_topk(g, 0, INFINITY, INT64_MAX, 1, res + kResTopW,
+                      reinterpret_cast<int64_t*>(res + kResTopIdx),
+                      reinterpret_cast<int*>(res + kResFound)));
+  // (the fused single-rank pass counts the ties in k_front_final; here nothing
+  // else writes that word)
+  SGP_TRY(launch_count_ties(g, res + kResTopW, reinterpret_cast<const int*>(res + kResFound),
+                            reinterpret_cast<int*>(res + kResFound) + 1));
+  return launch_gather_top(g, reinterpret_cast<int64_t*>(res + kResTopIdx), res + kResX,
+                           res + res_mean(d), res + res_q(d, G));
 }
 
 // Single-rank fast path, front half of compute_sets (gp_opt.py:511-552) with
@@ -1588,36 +1581,21 @@ int sgp_grid_sets_front(sgp_grid* g, double max_l, int have_max_var,
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   const int d = g->d, G = g->G;
-  // result block: [0] max width | [1..2] counts (u64) | [3] w_top | [4] idx_top
-  //               (i64) | [5] n_found (int) | x[d] | mean[G] | q[2G]
-  const size_t nres = 6 + size_t(d) + 3 * size_t(G);
-  double* res = static_cast<double*>(sgp_scratch(ctx, 1, (nres + 8) * 8));
-  SGP_CHECK(ctx, res, "device allocation failed: %s", ctx->err.c_str());
+  double* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, size_t(res_words(d, G) + 8) * 8, &res));
+  unsigned long long* counts = reinterpret_cast<unsigned long long*>(res + kResCounts);
   if (have_max_var) {
     // multi-rank: M is already set (sgp_grid_maximizers) and max_var is the
     // all-reduced value
-    SGP_HIP(ctx, hipMemsetAsync(res, 0, 8, ctx->stream));
-    SGP_TRY(launch_candidates(g, max_var, nullptr, scaling, thr_beta, 0,
-                              reinterpret_cast<unsigned long long*>(res + 1)));
+    SGP_HIP(ctx, hipMemsetAsync(res + kResMaxWidth, 0, 8, ctx->stream));
+    SGP_TRY(launch_candidates(g, max_var, nullptr, scaling, thr_beta, 0, counts));
   } else {
     SGP_TRY(launch_maximizers(g, max_l));
-    SGP_TRY(launch_reduce_max(ctx, g->partial, (g->N + 255) / 256, res));
-    SGP_TRY(launch_candidates(g, 0.0, res, scaling, thr_beta, 0,
-                              reinterpret_cast<unsigned long long*>(res + 1)));
+    SGP_TRY(launch_reduce_max(ctx, g->partial, (g->N + 255) / 256, res + kResMaxWidth));
+    SGP_TRY(launch_candidates(g, 0.0, res + kResMaxWidth, scaling, thr_beta, 0, counts));
   }
-  SGP_TRY(launch_topk(g, 0, INFINITY, INT64_MAX, 1, res + 3,
-                      reinterpret_cast<int64_t*>(res + 4),
-                      reinterpret_cast<int*>(res + 5)));
-  // (the fused single-rank pass counts the ties in k_front_final; here nothing
-  // else writes that word)
-  SGP_TRY(launch_count_ties(g, res + 3, reinterpret_cast<const int*>(res + 5),
-                            reinterpret_cast<int*>(res + 5) + 1));
-  SGP_TRY(launch_gather_top(g, reinterpret_cast<int64_t*>(res + 4), res + 6,
-                            res + 6 + d, res + 6 + d + G));
-  std::vector<double> host(nres);
-  SGP_TRY(sgp_d2h(ctx, host.data(), res, nres * 8));
-  unpack_front(host.data(), d, G, out5, x_top, mean_top, q_top);
-  return 0;
+  SGP_TRY(front_first(g, res));
+  return read_result(g, res, res_front(d, G), {out5, x_top, mean_top, q_top});
 }
 
 // ---- the collectives of the N-rank step on DEVICE operands -------------------------
@@ -1676,37 +1654,34 @@ static int coll_allgather(sgp_ctx* ctx, const void* send, void* recv, size_t nby
   return sgp_h2d(ctx, recv, hr.data(), hr.size());
 }
 
-// Front half of compute_sets on this rank's shard with the cross-rank scalars kept
-// on the device: max l0[S] (left in g->scal[0] by a confidence pass without
-// read-back) and the maximiser width are all-reduced IN STREAM, the kernels read
-// them from device memory; `res` (device) receives the front block of
-// unpack_front.  Without a communicator (one rank) the all-reduces are skipped.
-static int front_half_in_stream(sgp_grid* g, const double* scaling, const double* thr_beta,
-                                double* res) {
-  sgp_ctx* ctx = g->ctx;
-  const int d = g->d, G = g->G;
-  SGP_TRY(settle_max_l(g));
-  const bool comm = have_comm(ctx);
-  SGP_CHECK(ctx, comm || ctx->world <= 1,
+// have_comm(ctx) -- or the error of a rank of several without a communicator
+static int comm_or_single(sgp_ctx* ctx, bool* comm) {
+  *comm = have_comm(ctx);
+  SGP_CHECK(ctx, *comm || ctx->world <= 1,
             "rank %d of %d has no communicator in the grid's context: the "
             "in-stream collectives cannot run (sgp_comm_init on THIS context)",
             ctx->rank, ctx->world);
+  return 0;
+}
+
+// Front half of compute_sets on this rank's shard with the cross-rank scalars kept
+// on the device: max l0[S] (left in g->scal[0] by a confidence pass without
+// read-back) and the maximiser width are all-reduced IN STREAM, the kernels read
+// them from device memory; `res` (device) receives the front block.  Without a
+// communicator (one rank) the all-reduces are skipped.
+static int front_half_in_stream(sgp_grid* g, const double* scaling, const double* thr_beta,
+                                double* res) {
+  sgp_ctx* ctx = g->ctx;
+  SGP_TRY(settle_max_l(g));
+  bool comm;
+  SGP_TRY(comm_or_single(ctx, &comm));
   if (comm) SGP_TRY(coll_allreduce_max_f64(ctx, g->scal, 1));
   SGP_TRY(launch_maximizers(g, 0.0, g->scal));
-  SGP_TRY(launch_reduce_max(ctx, g->partial, (g->N + 255) / 256, res));
-  if (comm) SGP_TRY(coll_allreduce_max_f64(ctx, res, 1));
-  SGP_TRY(launch_candidates(g, 0.0, res, scaling, thr_beta, 0,
-                            reinterpret_cast<unsigned long long*>(res + 1)));
-  SGP_TRY(launch_topk(g, 0, INFINITY, INT64_MAX, 1, res + 3,
-                      reinterpret_cast<int64_t*>(res + 4),
-                      reinterpret_cast<int*>(res + 5)));
-  // (the fused single-rank pass counts the ties in k_front_final; here nothing
-  // else writes that word)
-  SGP_TRY(launch_count_ties(g, res + 3, reinterpret_cast<const int*>(res + 5),
-                            reinterpret_cast<int*>(res + 5) + 1));
-  SGP_TRY(launch_gather_top(g, reinterpret_cast<int64_t*>(res + 4), res + 6,
-                            res + 6 + d, res + 6 + d + G));
-  return 0;
+  SGP_TRY(launch_reduce_max(ctx, g->partial, (g->N + 255) / 256, res + kResMaxWidth));
+  if (comm) SGP_TRY(coll_allreduce_max_f64(ctx, res + kResMaxWidth, 1));
+  SGP_TRY(launch_candidates(g, 0.0, res + kResMaxWidth, scaling, thr_beta, 0,
+                            reinterpret_cast<unsigned long long*>(res + kResCounts)));
+  return front_first(g, res);
 }
 
 // N-rank front half with the cross-rank scalars kept on the device: max l0[S]
@@ -1721,17 +1696,14 @@ int sgp_grid_sets_front_comm(sgp_grid* g, const double* scaling,
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   const int d = g->d, G = g->G;
-  const size_t nres = 7 + size_t(d) + 3 * size_t(G);   // front block + max_l
-  double* res = static_cast<double*>(sgp_scratch(ctx, 1, (nres + 8) * 8));
-  SGP_CHECK(ctx, res, "device allocation failed: %s", ctx->err.c_str());
+  double* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, size_t(res_words(d, G) + 8) * 8, &res));
   SGP_TRY(front_half_in_stream(g, scaling, thr_beta, res));
-  SGP_HIP(ctx, hipMemcpyAsync(res + nres - 1, g->scal, 8,
+  SGP_HIP(ctx, hipMemcpyAsync(res + res_max_l(d, G), g->scal, 8,
                               hipMemcpyDeviceToDevice, ctx->stream));
-  std::vector<double> host(nres);
-  SGP_TRY(sgp_d2h(ctx, host.data(), res, nres * 8));
-  unpack_front(host.data(), d, G, out5, x_top, mean_top, q_top);
-  *max_l_out = host[nres - 1];
-  return 0;
+  StepOut o{out5, x_top, mean_top, q_top};
+  o.max_l = max_l_out;
+  return read_result(g, res, res_words(d, G), o);
 }
 
 // Back half for ONE candidate (the common case: the first candidate is the
@@ -1742,26 +1714,26 @@ int sgp_grid_sets_back(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
                        int mark, const double* scaling, int32_t* flags,
                        double* value, int64_t* gidx) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
   const int64_t li = gidx_c - g->goff;
   SGP_CHECK(ctx, !mark || (li >= 0 && li < g->N),
             "candidate %lld is not owned by this shard", (long long)gidx_c);
-  int32_t* dfl = nullptr;
-  SGP_TRY(enqueue_expander(g, gps, G, beta, fmin, 1, xc, mu_c, u_c, near_frac,
-                           &dfl));
-  if (mark) SGP_TRY(launch_mark_if(g, li, dfl, fmin));
+  ExpanderBufs eb;
+  SGP_TRY(expander_bufs(g, host, G, &eb));
+  SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, 1, xc, mu_c, u_c, near_frac));
+  if (mark) SGP_TRY(launch_mark_if(g, li, eb.flags, fmin));
   // results right behind the flags block: value (f64) | index (i64)
-  char* res = reinterpret_cast<char*>(dfl) + size_t(SGP_TOPK) * G * 4;
-  res += (8 - (reinterpret_cast<uintptr_t>(res) & 7)) & 7;
-  SGP_TRY(launch_argmax(g, SGP_ARGMAX_MG_WIDTH, scaling,
-                        reinterpret_cast<double*>(res),
-                        reinterpret_cast<int64_t*>(res + 8)));
-  const size_t span = size_t(res + 16 - reinterpret_cast<char*>(dfl));
-  std::vector<char> host(span);
-  SGP_TRY(sgp_d2h(ctx, host.data(), dfl, span));
-  memcpy(flags, host.data(), size_t(G) * 4);
-  memcpy(value, host.data() + (span - 16), 8);
-  memcpy(gidx, host.data() + (span - 8), 8);
+  double* res = behind_flags(eb.flags, size_t(SGP_TOPK) * G * 4);
+  SGP_TRY(launch_argmax(g, SGP_ARGMAX_MG_WIDTH, scaling, res,
+                        reinterpret_cast<int64_t*>(res + 1)));
+  const size_t span = size_t(reinterpret_cast<char*>(res + 2) -
+                             reinterpret_cast<char*>(eb.flags));
+  std::vector<char> hb(span);
+  SGP_TRY(sgp_d2h(ctx, hb.data(), eb.flags, span));
+  memcpy(flags, hb.data(), size_t(G) * 4);
+  memcpy(value, hb.data() + (span - 16), 8);
+  memcpy(gidx, hb.data() + (span - 8), 8);
   return 0;
 }
 
@@ -1778,96 +1750,64 @@ int sgp_grid_sets_fused(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
                         int32_t* flags, double* value, int64_t* gidx,
                         double* max_l_out) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  const int d = g->d;
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  // result block: [0] max width | [1..2] counts (u64) | [3] w_top | [4] idx_top
-  //   (i64) | [5] n_found (int) | x[d] | mean[G] | q[2G] | flags[G] (i32, padded
-  //   to 8 B) | value | index (i64) | max_l (when it was resident)
-  const size_t nfront = 6 + size_t(d) + 3 * size_t(G);
-  const size_t nfl = (size_t(G) + 1) / 2;
-  const size_t nres = nfront + nfl + 3;
-  double* res = static_cast<double*>(sgp_scratch(ctx, 1, (nres + 8) * 8));
-  SGP_CHECK(ctx, res, "device allocation failed: %s", ctx->err.c_str());
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
+  const int d = g->d, nres = res_words(d, G);
+  double* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, size_t(nres + 8) * 8, &res));
   // max_l = NaN: the confidence pass was issued without read-back; the value
   // is in g->scal[0] or still spread over the sweep's per-wave partials
   const bool resident = max_l != max_l;
   const bool pending = resident && g->l0_pending > 0;
-  GpDev ghost[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, d, ghost));
   ExpanderBufs eb;
-  SGP_TRY(expander_bufs(g, ghost, G, &eb));
+  SGP_TRY(expander_bufs(g, host, G, &eb));
   // Seven launches and one stream synchronisation: maximisers -> candidates (+ the first
   // one per workgroup) -> [k_expkt: first candidate of the shard, staged as the operand of
   // the expander test, AND L^-1 k_c] -> k_expw1 -> pre-filter -> listed rows -> conditional
   // G mark + M|G arg-max per workgroup.  The reductions in between are folded into the
   // consumers; the result block and the arg-max partials land in mapped host memory, where
   // the last level of the arg-max is taken (no final launch, no read-back copy).
+  // Grids beyond ~2.5e8 rows (or SGP_SETS_COPY set) keep the block in scratch: the front
+  // and the arg-max end in launches of their own (k_front_final, k_argmax_final_f), and one
+  // read-back copy returns the block.
   const int nbp = argmax_marked_blocks(g->N);
-  const size_t need = nres + 8 + 2 * size_t(nbp);
-  const bool zero_copy = need * 8 <= (size_t(4) << 20) && !getenv("SGP_SETS_COPY");
-  if (zero_copy && ctx->sets_cap < need) {
+  const size_t part_at = size_t(nres) + 8 - (nres & 1);      // (16-byte aligned pairs)
+  const size_t need = size_t(nres) + 8 + 2 * size_t(nbp);
+  static const bool copy = getenv("SGP_SETS_COPY") != nullptr;
+  const bool mapped = !copy && need * 8 <= (size_t(4) << 20);
+  if (mapped && ctx->sets_cap < need) {
     if (ctx->sets_host) (void)hipHostFree(ctx->sets_host);
     ctx->sets_host = nullptr;
     ctx->sets_cap = 0;
-    void* h = nullptr;
     const size_t cap = std::max<size_t>(need, 4096);
-    SGP_HIP(ctx, hipHostMalloc(&h, cap * 8, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h, 0, cap * 8);
-    void* dv = nullptr;
-    SGP_HIP(ctx, hipHostGetDevicePointer(&dv, h, 0));
-    ctx->sets_host = static_cast<double*>(h);
-    ctx->sets_dev = static_cast<double*>(dv);
+    SGP_TRY(mapped_block(ctx, cap, &ctx->sets_host, &ctx->sets_dev));
     ctx->sets_cap = cap;
   }
-  if (!zero_copy) {
-    // (grids beyond ~2.5e8 rows, or SGP_SETS_COPY=1: the round-4 chain -- final launches
-    // and one read-back copy)
-    SGP_TRY(launch_sets_front_fused(
-        g, max_l, pending ? g->partial : nullptr, g->l0_pending,
-        (resident && !pending) ? g->scal : nullptr, scaling, thr_beta, res,
-        res + nfront + nfl + 2, eb.xc, int((eb.bx + eb.bv) / 8), eb.flags,
-        int(eb.bf / 4)));
-    g->l0_pending = 0;
-    int32_t* dfl = nullptr;
-    SGP_TRY(enqueue_expander(g, gps, G, beta, fmin, 1, nullptr, nullptr, nullptr,
-                             near_frac, &dfl, nullptr, true));
-    SGP_TRY(launch_argmax_marked(
-        g, scaling, fmin, dfl, reinterpret_cast<int64_t*>(res + 4),
-        reinterpret_cast<int*>(res + 5), reinterpret_cast<int32_t*>(res + nfront),
-        res + nfront + nfl, reinterpret_cast<int64_t*>(res + nfront + nfl + 1)));
-    std::vector<double> host(nres);
-    SGP_TRY(sgp_d2h(ctx, host.data(), res, nres * 8));
-    unpack_front(host.data(), d, G, out5, x_top, mean_top, q_top);
-    memcpy(flags, &host[nfront], size_t(G) * 4);
-    *value = host[nfront + nfl];
-    memcpy(gidx, &host[nfront + nfl + 1], 8);
-    if (max_l_out) *max_l_out = resident ? host[nfront + nfl + 2] : max_l;
-    return 0;
-  }
-  double* hres = ctx->sets_host;
-  double* dres = ctx->sets_dev;
-  double* hpart = hres + nres + 8 - (nres & 1);      // (16-byte aligned pairs)
-  double* dpart = dres + (hpart - hres);
+  double* dres = mapped ? ctx->sets_dev : res;     // the block the host reads
   FrontArgs fold{};
   SGP_TRY(launch_sets_front_fused(
       g, max_l, pending ? g->partial : nullptr, g->l0_pending,
       (resident && !pending) ? g->scal : nullptr, scaling, thr_beta, res,
-      dres + nfront + nfl + 2, eb.xc, int((eb.bx + eb.bv) / 8), eb.flags,
-      int(eb.bf / 4), &fold));
+      dres + res_max_l(d, G), eb.xc, int((eb.bx + eb.bv) / 8), eb.flags, int(eb.bf / 4),
+      mapped ? &fold : nullptr));
   fold.res_host = dres;
   g->l0_pending = 0;
-  int32_t* dfl = nullptr;
-  SGP_TRY(enqueue_expander(g, gps, G, beta, fmin, 1, nullptr, nullptr, nullptr,
-                           near_frac, &dfl, nullptr, true, &fold));
+  SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, 1, nullptr, nullptr, nullptr, near_frac,
+                           mapped ? &fold : nullptr));
   SGP_TRY(launch_argmax_marked(
-      g, scaling, fmin, dfl, reinterpret_cast<int64_t*>(res + 4),
-      reinterpret_cast<int*>(res + 5), reinterpret_cast<int32_t*>(dres + nfront),
-      nullptr, nullptr, dpart));
-  SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  unpack_front(hres, d, G, out5, x_top, mean_top, q_top);
-  memcpy(flags, &hres[nfront], size_t(G) * 4);
-  {   // np.argmax over the workgroups' results: largest value, first index among equals
+      g, scaling, fmin, eb.flags, reinterpret_cast<int64_t*>(res + kResTopIdx),
+      reinterpret_cast<int*>(res + kResFound), reinterpret_cast<int32_t*>(dres + res_flags(d, G)),
+      mapped ? nullptr : dres + res_value(d, G),
+      mapped ? nullptr : reinterpret_cast<int64_t*>(dres + res_index(d, G)),
+      mapped ? ctx->sets_dev + part_at : nullptr));
+  const StepOut o{out5, x_top, mean_top, q_top, flags, value, gidx, max_l_out};
+  if (!mapped) {
+    SGP_TRY(read_result(g, res, nres, o));
+  } else {
+    SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    unpack_result(ctx->sets_host, d, G, o);
+    // np.argmax over the workgroups' results: largest value, first index among equals
+    const double* hpart = ctx->sets_host + part_at;
     const int64_t* hidx = reinterpret_cast<const int64_t*>(hpart + nbp);
     double bv = -INFINITY;
     int64_t bi = -1;
@@ -1883,7 +1823,7 @@ int sgp_grid_sets_fused(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
     *value = bv;
     *gidx = bi;
   }
-  if (max_l_out) *max_l_out = resident ? hres[nfront + nfl + 2] : max_l;
+  if (max_l_out && !resident) *max_l_out = max_l;
   return 0;
 }
 
@@ -1895,32 +1835,16 @@ int sgp_grid_step_small(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
                         double* out5, double* x_top, double* mean_top, double* q_top,
                         int32_t* flags, double* value, int64_t* gidx, double* max_l_out) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  const int d = g->d;
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
   GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, d, host));
+  SGP_TRY(grid_gps(g, gps, G, host));
   SGP_CHECK(ctx, step_small_eligible(ctx, host, G, g->N),
             "sgp_grid_step_small: %lld rows / a GP with more than 48 observations "
             "(sgp_grid_step_small_ok)", (long long)g->N);
-  SGP_TRY(stage_gpdev(g, host, G));
-  const size_t nfront = 6 + size_t(d) + 3 * size_t(G);
-  const size_t nfl = (size_t(G) + 1) / 2;
-  const size_t nres = nfront + nfl + 3;
-  SGP_CHECK(ctx, nres < size_t(kStepResWords), "result block of %zu words", nres);
-  if (!ctx->step_host) {
-    void* h = nullptr;
-    SGP_HIP(ctx, hipHostMalloc(&h, kStepResWords * 8, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h, 0, kStepResWords * 8);
-    void* dv = nullptr;
-    SGP_HIP(ctx, hipHostGetDevicePointer(&dv, h, 0));
-    ctx->step_host = static_cast<double*>(h);
-    ctx->step_dev = static_cast<double*>(dv);
-  }
+  if (!ctx->step_host) SGP_TRY(mapped_block(ctx, kStepResWords, &ctx->step_host, &ctx->step_dev));
   g->l0_pending = 0;
   const uint64_t seq = ++ctx->step_seq;
   SGP_TRY(launch_step_small(g, g->gpdev, host, G, beta, fmin, scaling, thr_beta, ctx->step_dev,
-                            int(nfront), int(nfl), seq));
+                            seq));
   // No read-back copy, no stream synchronisation: the kernel writes its result block into
   // host memory and a completion word behind it; spin on that word (a launch of 20-40 us),
   // fall back to the stream when it does not turn up.
@@ -1940,8 +1864,9 @@ int sgp_grid_step_small(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
     std::atomic_thread_fence(std::memory_order_acquire);
   }
   double hostres[kStepResWords];
-  memcpy(hostres, ctx->step_host, nres * 8);
-  if (getenv("SGP_STEP_STAMPS")) {      // (-DSTEP_STAMPS builds of step_small.hip)
+  memcpy(hostres, ctx->step_host, size_t(res_words(g->d, G)) * 8);
+  static const bool stamps = getenv("SGP_STEP_STAMPS") != nullptr;
+  if (stamps) {      // (-DSTEP_STAMPS builds of step_small.hip)
     const uint64_t* st = reinterpret_cast<const uint64_t*>(ctx->step_host) + 40;
     static int shown = 0;
     if (++shown % 500 == 0) {
@@ -1950,37 +1875,30 @@ int sgp_grid_step_small(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
       fprintf(stderr, "\n");
     }
   }
-  unpack_front(hostres, d, G, out5, x_top, mean_top, q_top);
-  memcpy(flags, &hostres[nfront], size_t(G) * 4);
-  *value = hostres[nfront + nfl];
-  memcpy(gidx, &hostres[nfront + nfl + 1], 8);
-  *max_l_out = hostres[nfront + nfl + 2];
+  unpack_result(hostres, g->d, G, {out5, x_top, mean_top, q_top, flags, value, gidx, max_l_out});
   return 0;
 }
 
 // Every candidate of a small grid at once (step_small.hip: k_cand_ops, k_cand_scan):
 // flags[c * G + i] != 0 when candidate gidx[c] lifts an unsafe row above fmin_i after the
 // rank-1 update by (x_c, u_i(x_c)) -- the test of gp_opt.py:579-606 for m candidates in
-// two launches and one round trip.  Grids of at most 16384 rows, GPs with at most 48
+// two launches and one round trip.  Grids of at most kStepSmallRows rows, GPs with at most 48
 // observations (sgp_grid_step_small_ok).
 int sgp_grid_expanders_small(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
                              const double* fmin, const int64_t* gidx, int m, int32_t* flags) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  if (m <= 0) return 0;
   GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
+  SGP_TRY(grid_gps(g, gps, G, host));
+  if (m <= 0) return 0;
   SGP_CHECK(ctx, step_small_eligible(ctx, host, G, g->N),
             "sgp_grid_expanders_small: %lld rows / a GP with more than 48 observations",
             (long long)g->N);
   for (int c = 0; c < m; ++c)
     SGP_CHECK(ctx, gidx[c] >= g->goff && gidx[c] < g->goff + g->N,
               "candidate %lld is not a row of this grid", (long long)gidx[c]);
-  SGP_TRY(stage_gpdev(g, host, G));
   const size_t nops = cand_ops_doubles(m, G);
-  char* buf = static_cast<char*>(sgp_scratch(ctx, 7, nops * 8 + size_t(m) * 8 + size_t(m) * G * 4));
-  SGP_CHECK(ctx, buf, "device allocation failed: %s", ctx->err.c_str());
+  char* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotOperands, nops * 8 + size_t(m) * 8 + size_t(m) * G * 4, &buf));
   double* ops = reinterpret_cast<double*>(buf);
   int64_t* cl = reinterpret_cast<int64_t*>(buf + nops * 8);
   int32_t* dfl = reinterpret_cast<int32_t*>(buf + nops * 8 + size_t(m) * 8);
@@ -1997,40 +1915,33 @@ int sgp_grid_expanders_small_all(sgp_grid* g, sgp_gp* const* gps, int G, double 
                                  const double* fmin, int cap, int* count, int64_t* gidx,
                                  double* width, int32_t* flags) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  SGP_CHECK(ctx, cap >= 1, "cap = %d", cap);
   *count = 0;
   GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, g->d, host));
+  SGP_TRY(grid_gps(g, gps, G, host));
+  SGP_CHECK(ctx, cap >= 1, "cap = %d", cap);
   SGP_CHECK(ctx, step_small_eligible(ctx, host, G, g->N),
             "sgp_grid_expanders_small_all: %lld rows / a GP with more than 48 observations",
             (long long)g->N);
-  SGP_TRY(stage_gpdev(g, host, G));
   if (cap > g->N) cap = int(g->N);
   // the list: every candidate, row order (the selection of the big passes with no threshold)
-  const size_t nl = (size_t(g->N) * 4 + 63) & ~size_t(63);
-  char* sb = static_cast<char*>(sgp_scratch(ctx, 8, nl + 16384 + 256 + (size_t(g->N) / 256 + 2) * 4));
-  SGP_CHECK(ctx, sb, "device allocation failed: %s", ctx->err.c_str());
-  int* list = reinterpret_cast<int*>(sb);
-  char* sel = sb + nl + 16384;
-  int* counts = reinterpret_cast<int*>(sb + nl + 16384 + 256);
-  struct { double thr; int count, est; } hs = {-INFINITY, 0, 0};
-  SGP_TRY(sgp_h2d(ctx, sel, &hs, sizeof(hs)));
-  SGP_TRY(launch_pass_list(g, 0, INFINITY, -1, sel, list, counts));
-  const int* count_dev = reinterpret_cast<const int*>(sel + 8);
+  PassScratch ps;
+  SGP_TRY(pass_scratch(g, &ps));
+  PassSel hs = {-INFINITY, 0, 0};
+  SGP_TRY(sgp_h2d(ctx, ps.sel, &hs, sizeof(hs)));
+  SGP_TRY(launch_pass_list(g, 0, INFINITY, -1, ps.sel, ps.list, ps.counts));
+  const int* count_dev = &ps.sel->count;
   // [count | rows | widths | flags] for the read-back, the operands behind them
   const size_t bh = 8, bc = size_t(cap) * 8, bw = size_t(cap) * 8,
                bf = (size_t(cap) * G * 4 + 7) & ~size_t(7);
   const size_t nops = cand_ops_doubles(cap, G);
-  char* buf = static_cast<char*>(sgp_scratch(ctx, 7, bh + bc + bw + bf + nops * 8));
-  SGP_CHECK(ctx, buf, "device allocation failed: %s", ctx->err.c_str());
+  char* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotOperands, bh + bc + bw + bf + nops * 8, &buf));
   int64_t* hdr = reinterpret_cast<int64_t*>(buf);
   int64_t* cl = reinterpret_cast<int64_t*>(buf + bh);
   double* dw = reinterpret_cast<double*>(buf + bh + bc);
   int32_t* dfl = reinterpret_cast<int32_t*>(buf + bh + bc + bw);
   double* ops = reinterpret_cast<double*>(buf + bh + bc + bw + bf);
-  SGP_TRY(launch_small_pack(g, list, count_dev, cap, hdr, cl, dw, dfl));
+  SGP_TRY(launch_small_pack(g, ps.list, count_dev, cap, hdr, cl, dw, dfl));
   SGP_TRY(launch_cand_all(g, g->gpdev, host, G, beta, fmin, cl, cap, ops, dfl, count_dev));
   std::vector<char> hb(bh + bc + bw + bf);
   SGP_TRY(sgp_d2h(ctx, hb.data(), buf, hb.size()));
@@ -2044,7 +1955,7 @@ int sgp_grid_expanders_small_all(sgp_grid* g, sgp_gp* const* gps, int G, double 
   return 0;
 }
 
-// 1 when sgp_grid_step_small serves this grid with these GPs (at most 16384 rows, every GP
+// 1 when sgp_grid_step_small serves this grid with these GPs (at most kStepSmallRows rows, every GP
 // with at most 48 observations, sweep kernel not forced), else 0
 int sgp_grid_step_small_ok(sgp_grid* g, sgp_gp* const* gps, int G) {
   if (!g || G != g->G || G < 1 || G > SGP_MAX_GPS) return 0;
@@ -2075,31 +1986,24 @@ int sgp_grid_sets_fused_comm(sgp_grid* g, sgp_gp* const* gps, int G, double beta
                              int32_t* flags, double* value, int64_t* gidx,
                              double* max_l_out) {
   sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  const int d = g->d;
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  const bool comm = have_comm(ctx);
-  SGP_CHECK(ctx, comm || ctx->world <= 1,
-            "rank %d of %d has no communicator in the grid's context: the "
-            "in-stream collectives cannot run (sgp_comm_init on THIS context)",
-            ctx->rank, ctx->world);
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
+  bool comm;
+  SGP_TRY(comm_or_single(ctx, &comm));
   const int world = comm ? ctx->world : 1;
-  // device block: merged result (layout of sgp_grid_sets_fused) | this rank's front
-  // block | gathered front blocks | this rank's (value, index) | gathered pairs
-  const size_t nfront = 6 + size_t(d) + 3 * size_t(G);
-  const size_t nfl = (size_t(G) + 1) / 2;
-  const size_t nres = nfront + nfl + 3;
+  // device block: merged result | this rank's front block | gathered front blocks | this
+  // rank's (value, index) | gathered pairs
+  const int d = g->d, nres = res_words(d, G);
+  const size_t nfront = size_t(res_front(d, G));
   const size_t total = nres + 1 + nfront * (1 + size_t(world)) + 2 * (1 + size_t(world));
-  double* res = static_cast<double*>(sgp_scratch(ctx, 1, (total + 8) * 8));
-  SGP_CHECK(ctx, res, "device allocation failed: %s", ctx->err.c_str());
+  double* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, (total + 8) * 8, &res));
   double* mine = res + nres + 1;
   double* all = mine + nfront;
   double* pair = all + nfront * size_t(world);
   double* pairs = pair + 2;
-  GpDev ghost[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, d, ghost));
   ExpanderBufs eb;
-  SGP_TRY(expander_bufs(g, ghost, G, &eb));
+  SGP_TRY(expander_bufs(g, host, G, &eb));
 
   // ---- front half on this shard
   SGP_TRY(front_half_in_stream(g, scaling, thr_beta, mine));
@@ -2113,33 +2017,23 @@ int sgp_grid_sets_fused_comm(sgp_grid* g, sgp_gp* const* gps, int G, double beta
   SGP_TRY(launch_merge_front(g, blocks, world, int(nfront), res, eb.xc,
                              int((eb.bx + eb.bv) / 8), eb.flags, int(eb.bf / 4)));
   // ---- probe scan over this shard, flags over all shards
-  int32_t* dfl = nullptr;
-  SGP_TRY(enqueue_expander(g, gps, G, beta, fmin, 1, nullptr, nullptr, nullptr,
-                           near_frac, &dfl, nullptr, true));
-  if (comm) SGP_TRY(coll_allreduce_max_i32(ctx, dfl, size_t(G)));
+  SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, 1, nullptr, nullptr, nullptr, near_frac));
+  if (comm) SGP_TRY(coll_allreduce_max_i32(ctx, eb.flags, size_t(G)));
   // ---- conditional G mark (owner of the candidate) + arg-max over the whole grid
   SGP_TRY(launch_argmax_marked(
-      g, scaling, fmin, dfl, reinterpret_cast<int64_t*>(res + 4),
-      reinterpret_cast<int*>(res + 5), reinterpret_cast<int32_t*>(res + nfront),
+      g, scaling, fmin, eb.flags, reinterpret_cast<int64_t*>(res + kResTopIdx),
+      reinterpret_cast<int*>(res + kResFound), reinterpret_cast<int32_t*>(res + res_flags(d, G)),
       pair, reinterpret_cast<int64_t*>(pair + 1)));
   const double* prs = pair;
   if (comm) {
     SGP_TRY(coll_allgather(ctx, pair, pairs, 16));
     prs = pairs;
   }
-  SGP_TRY(launch_merge_argmax(ctx, prs, world, res + nfront + nfl,
-                              reinterpret_cast<int64_t*>(res + nfront + nfl + 1)));
-  SGP_HIP(ctx, hipMemcpyAsync(res + nfront + nfl + 2, g->scal, 8,
+  SGP_TRY(launch_merge_argmax(ctx, prs, world, res + res_value(d, G),
+                              reinterpret_cast<int64_t*>(res + res_index(d, G))));
+  SGP_HIP(ctx, hipMemcpyAsync(res + res_max_l(d, G), g->scal, 8,
                               hipMemcpyDeviceToDevice, ctx->stream));
-
-  std::vector<double> host(nres);
-  SGP_TRY(sgp_d2h(ctx, host.data(), res, nres * 8));
-  unpack_front(host.data(), d, G, out5, x_top, mean_top, q_top);
-  memcpy(flags, &host[nfront], size_t(G) * 4);
-  *value = host[nfront + nfl];
-  memcpy(gidx, &host[nfront + nfl + 1], 8);
-  *max_l_out = host[nfront + nfl + 2];
-  return 0;
+  return read_result(g, res, nres, {out5, x_top, mean_top, q_top, flags, value, gidx, max_l_out});
 }
 
 // Fitness of P <= kSmallPoints particles (row-major, device) through the
@@ -2148,11 +2042,11 @@ static int fitness_small(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_ho
                          int G, const double* pts_rowmajor, int64_t P,
                          const FitnessArgs& fa) {
   const int Geff = (fa.swarm_type == SGP_SWARM_GREEDY) ? 1 : G;
-  double* mv = static_cast<double*>(
-      sgp_scratch(ctx, 2, size_t(2) * SGP_MAX_GPS * kSmallPoints * sizeof(double)));
+  double* mv;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(2) * SGP_MAX_GPS * kSmallPoints * sizeof(double),
+                      &mv));
   SmallBufs sb;
-  SGP_CHECK(ctx, mv && small_reserve(ctx, gps_host, Geff, int(P), &sb) == 0,
-            "device allocation failed: %s", ctx->err.c_str());
+  SGP_TRY(small_reserve(ctx, gps_host, Geff, int(P), &sb));
   double* mean = mv;
   double* var = mv + size_t(SGP_MAX_GPS) * kSmallPoints;
   SGP_TRY(posterior_small_all(ctx, gps_dev, gps_host, Geff, pts_rowmajor, int(P), sb,
@@ -2180,10 +2074,11 @@ int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   GpDev host[SGP_MAX_GPS];
   SGP_TRY(collect_gps(ctx, gps, G, d, host));
   const size_t nd = size_t(P) * 8;
-  double* stage = static_cast<double*>(sgp_scratch(ctx, 3, nd * d));
-  char* work = static_cast<char*>(
-      sgp_scratch(ctx, 4, nd * d + nd + size_t(P) + sizeof(GpDev) * SGP_MAX_GPS + 64));
-  SGP_CHECK(ctx, stage && work, "device allocation failed: %s", ctx->err.c_str());
+  double* stage;
+  char* work;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, nd * d, &stage));
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, nd * d + nd + size_t(P) + sizeof(GpDev) * SGP_MAX_GPS + 64,
+                      &work));
   double* pts = reinterpret_cast<double*>(work);
   double* dval = reinterpret_cast<double*>(work + nd * d);
   GpDev* gdev = reinterpret_cast<GpDev*>(work + nd * d + nd);
@@ -2234,10 +2129,10 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   const size_t nrand = rand ? (size_t(init ? 1 : 0) + 2 * size_t(iters)) * nd : 0;
   // pos | vel | best | best_values | values | gbest | vscale | bounds | gpdev | safe
   const size_t small = size_t(d) * 8 * 4 + sizeof(GpDev) * SGP_MAX_GPS + 64;
-  char* buf = static_cast<char*>(sgp_scratch(ctx, 4, 3 * nd + 2 * nv + small + size_t(P)));
-  double* drand = rand ? static_cast<double*>(sgp_scratch(ctx, 3, nrand)) : nullptr;
-  SGP_CHECK(ctx, buf && (!rand || drand), "device allocation failed: %s",
-            ctx->err.c_str());
+  char* buf;
+  double* drand = nullptr;
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, 3 * nd + 2 * nv + small + size_t(P), &buf));
+  if (rand) SGP_TRY(sgp_scratch(ctx, kSlotStage, nrand, &drand));
   double* dpos = reinterpret_cast<double*>(buf);
   double* dvel = reinterpret_cast<double*>(buf + nd);
   double* dbest = reinterpret_cast<double*>(buf + 2 * nd);
@@ -2286,8 +2181,7 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
     SmallBufs sb{};
     ConfOut post{};
     if (few) {
-      SGP_CHECK(ctx, small_reserve(ctx, host, Geff, int(P), &sb) == 0,
-                "device allocation failed: %s", ctx->err.c_str());
+      SGP_TRY(small_reserve(ctx, host, Geff, int(P), &sb));
     } else {
       const size_t np = size_t(Geff) * size_t(P);
       SGP_TRY(sgp_reserve(ctx, &ctx->pair_post, 2 * np * sizeof(double)));
@@ -2381,9 +2275,8 @@ int sgp_swarm_grow(sgp_ctx* ctx, sgp_gp* gp0, const double* S, int64_t m,
   const size_t bs = size_t(m) * d * 8, bb = size_t(n) * d * 8;
   const size_t bp = size_t(n) * size_t(nchunks > 0 ? nchunks : 1) * 8;
   const size_t bl = size_t(n) * 4, ba = size_t(n);
-  char* buf = static_cast<char*>(
-      sgp_scratch(ctx, 4, bs + bb + bp + bl + ba + 64));
-  SGP_CHECK(ctx, buf, "device allocation failed: %s", ctx->err.c_str());
+  char* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, bs + bb + bp + bl + ba + 64, &buf));
   double* dS = reinterpret_cast<double*>(buf);
   double* dB = reinterpret_cast<double*>(buf + bs);
   double* part = reinterpret_cast<double*>(buf + bs + bb);
@@ -2525,8 +2418,8 @@ int sgp_comm_allreduce_max(sgp_ctx* ctx, double* buf, int n) {
   }
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, ctx->comm, "sgp_comm_init was not called");
-  double* d = static_cast<double*>(sgp_scratch(ctx, 6, size_t(n) * 8));
-  SGP_CHECK(ctx, d, "device allocation failed: %s", ctx->err.c_str());
+  double* d;
+  SGP_TRY(sgp_scratch(ctx, kSlotSmall, size_t(n) * 8, &d));
   SGP_TRY(stage_h2d(ctx, d, buf, size_t(n) * 8));
   SGP_NCCL(ctx, g_rccl.AllReduce(d, d, size_t(n), ncclFloat64, ncclMax,
                                  static_cast<ncclComm_t>(ctx->comm),
@@ -2548,9 +2441,8 @@ int sgp_comm_allgather(sgp_ctx* ctx, const void* send, void* recv,
   }
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, ctx->comm, "sgp_comm_init was not called");
-  char* d = static_cast<char*>(
-      sgp_scratch(ctx, 6, size_t(nbytes) * (size_t(ctx->world) + 1)));
-  SGP_CHECK(ctx, d, "device allocation failed: %s", ctx->err.c_str());
+  char* d;
+  SGP_TRY(sgp_scratch(ctx, kSlotSmall, size_t(nbytes) * (size_t(ctx->world) + 1), &d));
   char* r = d + nbytes;
   SGP_TRY(stage_h2d(ctx, d, send, size_t(nbytes)));
   SGP_NCCL(ctx, g_rccl.AllGather(d, r, size_t(nbytes), ncclInt8,

@@ -119,6 +119,42 @@ struct SepLaunch {
   const double* tab[SGP_MAX_GPS][4];
 };
 
+// ---- device scratch (sgp_ctx::scratch) --------------------------------------
+// One buffer per slot, grown on demand.  Asking for a slot may reallocate it (and under
+// SGP_POISON=2 fills it with 0xFF), which voids every pointer into it that is still held.
+// Hence the rule every call chain keeps: a slot is never asked for below (in a callee of)
+// a caller that still holds a pointer into it.  The one exception are the KEPT slots: an
+// entry point sizes and fills them, and a callee asks for them again with the same size
+// to find the contents in place (SGP_POISON=2 leaves them alone).
+enum ScratchSlot : int {
+  kSlotList = 0,        // the rows the pre-filter of ONE candidate lists (enqueue_expander)
+  kSlotResult = 1,      // small result blocks the entry points read back: maximizers,
+                        // candidates, topk, argmax, expander_batch, sets_front[_comm],
+                        // sets_fused[_comm]
+  kSlotPartials = 2,    // per-workgroup partials of the sets.hip launchers (candidates, topk,
+                        // argmax[_marked], the fused front, read by its fold); set_axes'
+                        // mismatch count; fitness_small's mean | var
+  kSlotStage = 3,       // host rows staged for a launch: gp_predict, kern_K, grid_create,
+                        // swarm_fitness, swarm_run's random numbers; factor.hip: append_gp,
+                        // expander_operands_all
+  kSlotWork = 4,        // gp_predict's points, kern_K's matrix, the swarm entry points' state
+  kSlotGpDev = 5,       // gp_predict's GP descriptor
+  kSlotSmall = 6,       // small_reserve (few-points path), upload_local_idx,
+                        // comm_allreduce_max, comm_allgather
+  kSlotOperands = 7,    // kept: operands of <= SGP_TOPK candidates (expander_bufs: staged by
+                        // expander_batch / sets_fused[_comm], asked for again by
+                        // enqueue_expander); gather_rows, lipschitz_check, expanders_small[_all]
+  kSlotPass = 8,        // kept: the scratch of a big pass (PassScratch: list | histogram |
+                        // PassSel | counts), the selection carried from pass_list on
+  kSlotManyOps = 9,     // kept: operands of m listed candidates (expander_many_test), the
+                        // Lipschitz work block, pass_list's gathered rows
+  kSlotManyW = 10,      // kept: their W operands
+  kSlotManyFlags = 11,  // kept: their flags, the pass result behind them
+  kSlotHot = 12,        // launch_expander_many / launch_lipschitz_many: the hot waves and rows
+  kScratchSlots
+};
+inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }
+
 // ---- host-side objects ------------------------------------------------------
 struct DevBuf {
   void* p = nullptr;
@@ -133,7 +169,7 @@ struct sgp_ctx {
   void* pinned = nullptr;
   size_t pinned_cap = 0;
   // device scratch (grown on demand)
-  DevBuf scratch[13];
+  DevBuf scratch[kScratchSlots];
   int64_t n_allocs = 0;       // hipMalloc calls so far (sgp_ctx_alloc_count)
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -184,6 +220,7 @@ struct sgp_ctx {
   int num_cu = 256;
 };
 
+constexpr int64_t kMaxObservations = 16384;    // training points of a GP, at most
 struct sgp_gp {
   sgp_ctx* ctx = nullptr;
   KernDesc kern;
@@ -243,7 +280,14 @@ struct sgp_grid {
 
 // ---- helpers (api.hip) ------------------------------------------------------
 int sgp_reserve(sgp_ctx* ctx, DevBuf* b, size_t bytes);
-void* sgp_scratch(sgp_ctx* ctx, int slot, size_t bytes);  // nullptr on failure
+void* scratch_slot(sgp_ctx* ctx, ScratchSlot slot, size_t bytes);  // nullptr on failure
+// *out = `bytes` of the slot, or the usual error (through SGP_TRY)
+template <class T>
+inline int sgp_scratch(sgp_ctx* ctx, ScratchSlot slot, size_t bytes, T** out) {
+  *out = static_cast<T*>(scratch_slot(ctx, slot, bytes));
+  SGP_CHECK(ctx, *out, "device allocation failed: %s", ctx->err.c_str());
+  return 0;
+}
 int sgp_poison(sgp_ctx* ctx, void* p, size_t bytes);       // SGP_POISON=1: fill a fresh allocation with 0xFF
 int sgp_h2d(sgp_ctx* ctx, void* dst, const void* src, size_t bytes);
 int sgp_d2h(sgp_ctx* ctx, void* dst, const void* src, size_t bytes);  // syncs
@@ -394,7 +438,7 @@ constexpr int64_t kStepSmallRows = 16384;
 bool step_small_eligible(const sgp_ctx* ctx, const GpDev* gh, int G, int64_t N);
 int launch_step_small(sgp_grid* g, const GpDev* gps_dev, const GpDev* gh, int G, double beta,
                       const double* fmin, const double* scaling, const double* thr_beta,
-                      double* res, int nfront, int nfl, uint64_t seq);
+                      double* res, uint64_t seq);
 // count_dev != nullptr: the list was formed on the device, m is its room and *count_dev its length
 int launch_cand_all(sgp_grid* g, const GpDev* gps_dev, const GpDev* gh, int G, double beta,
                     const double* fmin, const int64_t* clist_dev, int m, double* ops,
@@ -402,7 +446,8 @@ int launch_cand_all(sgp_grid* g, const GpDev* gps_dev, const GpDev* gh, int G, d
 int launch_small_pack(sgp_grid* g, const int* list_dev, const int* count_dev, int cap,
                       int64_t* hdr, int64_t* clist, double* wout, int32_t* flags);
 size_t cand_ops_doubles(int m, int G);
-constexpr int kStepResWords = 64;     // doubles of the result block (6 + d + 3 G + ... <= 50)
+constexpr int kStepResWords = 64;     // doubles of the block: res_words(d, G) <= 50 (sets_front.h),
+                                      // the last one the completion word
 
 // sets.hip
 int launch_reduce_max(sgp_ctx* ctx, const double* in, int64_t n, double* out);
@@ -422,8 +467,18 @@ int launch_mark_top_if(sgp_grid* g, const int64_t* gidx_dev, const int* nfound_d
                        const int32_t* flags_dev, const double* fmin);
 int launch_mark_if(sgp_grid* g, int64_t li, const int32_t* flags_dev,
                    const double* fmin);
-// a pass of the expander loop over many candidates (sets.hip): selection by a key
-// histogram (sel_dev: { double thr; int count; int est }), operand staging, hits
+// a pass of the expander loop over many candidates (sets.hip): selection by a histogram of
+// kPassBins keys into a PassSel, operand staging, hits
+constexpr int kPassBins = 4096;
+// (internal linkage, like the pass kernels of sets.hip whose symbols name it: the launchers
+// take it as void*)
+namespace {
+struct PassSel {
+  double thr;      // the pass = candidates behind the cut with key >= thr
+  int count;       // ... as k_pass_list counted them
+  int est;         // ... as the histogram promised
+};
+}  // namespace
 int launch_pass_select(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, double lo,
                        double hi, int want, void* sel_dev, int* list_dev, unsigned* hist_dev,
                        int* counts_dev);

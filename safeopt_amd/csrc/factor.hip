@@ -541,8 +541,8 @@ int append_gp(sgp_gp* gp, double y, int* info) {
   const int n = int(gp->n), ld = gp->ld, d = gp->kern.d;
   double* Li = static_cast<double*>(gp->Linv.p);
   double* X = static_cast<double*>(gp->X.p);
-  double* buf = static_cast<double*>(sgp_scratch(ctx, 3, size_t(3) * ld * 8 + 64));
-  if (!buf) return -1;
+  double* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, size_t(3) * ld * 8 + 64, &buf));
   double* Kc = buf;
   double* Tt = buf + ld;
   double* Wt = buf + 2 * size_t(ld);
@@ -999,9 +999,9 @@ int expander_operands_all(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_h
   const int64_t ldk = (np_max + 31) / 32 * 32;
   const int ngroups = (ops.m + kMaxRhs - 1) / kMaxRhs;
   SGP_CHECK(ctx, ngroups == 1 || ops.Gs == G, "ExpanderOps::Gs = %d for %d GPs", ops.Gs, G);
-  double* buf = static_cast<double*>(
-      sgp_scratch(ctx, 3, size_t(2) * ngroups * G * kMaxRhs * ldk * sizeof(double)));
-  SGP_CHECK(ctx, buf, "device allocation failed: %s", ctx->err.c_str());
+  double* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, size_t(2) * ngroups * G * kMaxRhs * ldk * sizeof(double),
+                      &buf));
   double* Kc = buf;
   double* Tt = buf + size_t(ngroups) * G * kMaxRhs * ldk;
   if (ops.m == 1) {
@@ -1064,9 +1064,10 @@ int small_reserve(sgp_ctx* ctx, const GpDev* gps_host, int G, int P, SmallBufs* 
   sb->nblk_max = np_max / 16;
   sb->kb_stride = int64_t(sb->passes) * sb->nsteps_max * 64;
   sb->part_stride = int64_t(sb->passes) * sb->nblk_max * 16;
-  double* buf = static_cast<double*>(sgp_scratch(
-      ctx, 6, size_t(G) * (sb->kb_stride + sb->part_stride + sb->passes * 16) * sizeof(double)));
-  if (!buf) return -1;
+  double* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotSmall,
+                      size_t(G) * (sb->kb_stride + sb->part_stride + sb->passes * 16) * sizeof(double),
+                      &buf));
   sb->Kb = buf;
   sb->part = buf + size_t(G) * sb->kb_stride;
   sb->mtmp = sb->part + size_t(G) * sb->part_stride;

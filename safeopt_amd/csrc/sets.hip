@@ -613,8 +613,7 @@ __global__ __launch_bounds__(T) void k_argmax_final_f(
 }
 
 // ---- N ranks: merges behind in-stream all-gathers ------------------------------------
-// Every rank's front block ([0] max width | [1..2] counts (u64) | [3] w_top | [4]
-// idx_top (i64) | [5] n_found, n_tied (int) | x[d] | mean[G] | q[2G]) gathered into
+// Every rank's front block (sets_front.h: res_front(d, G) = nfront doubles) gathered into
 // `all` [world][nfront]: the first candidate of the WHOLE grid in visiting order
 // (gp_opt.py:542-552: width descending, among equal widths the larger index first),
 // total counts, the number of candidates tied with it over all shards -> `res` in the
@@ -634,10 +633,10 @@ __global__ __launch_bounds__(64) void k_merge_front(
     int wr = -1;
     for (int r = 0; r < world; ++r) {
       const double* b = all + size_t(r) * nfront;
-      ta += reinterpret_cast<const unsigned long long*>(b)[1];
-      tb += reinterpret_cast<const unsigned long long*>(b)[2];
-      const int found = reinterpret_cast<const int*>(b + 5)[0];
-      const Pair p{b[3], reinterpret_cast<const int64_t*>(b)[4]};
+      ta += reinterpret_cast<const unsigned long long*>(b)[kResCounts];
+      tb += reinterpret_cast<const unsigned long long*>(b)[kResCounts + 1];
+      const int found = reinterpret_cast<const int*>(b + kResFound)[0];
+      const Pair p{b[kResTopW], reinterpret_cast<const int64_t*>(b)[kResTopIdx]};
       if (found > 0 && p.i >= 0 && (best.i < 0 || before_desc(p, best))) {
         best = p;
         wr = r;
@@ -646,16 +645,16 @@ __global__ __launch_bounds__(64) void k_merge_front(
     int ties = 0;
     for (int r = 0; r < world; ++r) {
       const double* b = all + size_t(r) * nfront;
-      if (reinterpret_cast<const int*>(b + 5)[0] > 0 && b[3] == best.v)
-        ties += reinterpret_cast<const int*>(b + 5)[1];
+      if (reinterpret_cast<const int*>(b + kResFound)[0] > 0 && b[kResTopW] == best.v)
+        ties += reinterpret_cast<const int*>(b + kResFound)[1];
     }
-    res[0] = all[0];                      // (all-reduced before: the same everywhere)
-    reinterpret_cast<unsigned long long*>(res)[1] = ta;
-    reinterpret_cast<unsigned long long*>(res)[2] = tb;
-    res[3] = best.v;
-    reinterpret_cast<int64_t*>(res)[4] = best.i;
-    reinterpret_cast<int*>(res + 5)[0] = wr >= 0 ? 1 : 0;
-    reinterpret_cast<int*>(res + 5)[1] = wr >= 0 ? ties : 0;
+    res[kResMaxWidth] = all[kResMaxWidth];   // (all-reduced before: the same everywhere)
+    reinterpret_cast<unsigned long long*>(res)[kResCounts] = ta;
+    reinterpret_cast<unsigned long long*>(res)[kResCounts + 1] = tb;
+    res[kResTopW] = best.v;
+    reinterpret_cast<int64_t*>(res)[kResTopIdx] = best.i;
+    reinterpret_cast<int*>(res + kResFound)[0] = wr >= 0 ? 1 : 0;
+    reinterpret_cast<int*>(res + kResFound)[1] = wr >= 0 ? ties : 0;
     win_rank = wr;
   }
   __syncthreads();
@@ -664,15 +663,15 @@ __global__ __launch_bounds__(64) void k_merge_front(
   const double* b = all + size_t(wr) * nfront;
   double* resid = xc + (n_xc_resid - G * 16);
   for (int k = lane; k < d; k += 64) {
-    res[6 + k] = b[6 + k];
-    xc[k] = b[6 + k];
+    res[kResX + k] = b[kResX + k];
+    xc[k] = b[kResX + k];
   }
   for (int g = lane; g < G; g += 64) {
-    const double mu = b[6 + d + g];
-    res[6 + d + g] = mu;
-    resid[g * 16] = b[6 + d + G + 2 * g + 1] - mu;
+    const double mu = b[res_mean(d) + g];
+    res[res_mean(d) + g] = mu;
+    resid[g * 16] = b[res_q(d, G) + 2 * g + 1] - mu;
   }
-  for (int q = lane; q < 2 * G; q += 64) res[6 + d + G + q] = b[6 + d + G + q];
+  for (int q = lane; q < 2 * G; q += 64) res[res_q(d, G) + q] = b[res_q(d, G) + q];
 }
 
 // Every rank's (value, global index) of the M | G arg-max gathered into `all`
@@ -723,9 +722,9 @@ int launch_candidates(sgp_grid* g, double max_var, const double* max_width_dev,
                       int full_sets, unsigned long long* counts) {
   sgp_ctx* ctx = g->ctx;
   const unsigned nb = nblk(g->N, T);
-  unsigned* bc = static_cast<unsigned*>(
-      sgp_scratch(ctx, 2, size_t(nb) * 2 * sizeof(unsigned)));
-  if (!counts || !bc) return -1;
+  if (!counts) return -1;
+  unsigned* bc;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(nb) * 2 * sizeof(unsigned), &bc));
   hipLaunchKernelGGL(k_candidates, dim3(nb), dim3(T), 0, ctx->stream, g->Q,
                      g->S, g->M, g->N, g->G, max_var, max_width_dev,
                      vec8(scaling, g->G, 1.0), vec8(thr_beta, g->G, 0.0),
@@ -740,9 +739,8 @@ int launch_topk(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, int k,
                 double* w_out_dev, int64_t* idx_out_dev, int* n_out_dev) {
   sgp_ctx* ctx = g->ctx;
   const unsigned nb = nblk(g->N, TK_CHUNK);
-  double* pw = static_cast<double*>(
-      sgp_scratch(ctx, 2, size_t(nb) * k * (sizeof(double) + sizeof(int64_t))));
-  if (!pw) return -1;
+  double* pw;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(nb) * k * (sizeof(double) + sizeof(int64_t)), &pw));
   int64_t* pi = reinterpret_cast<int64_t*>(pw + size_t(nb) * k);
   hipLaunchKernelGGL(k_topk, dim3(nb), dim3(T), 0, ctx->stream, g->cand, g->w,
                      static_cast<const int64_t*>(nullptr), g->N, g->goff, mode,
@@ -800,9 +798,8 @@ int launch_argmax(sgp_grid* g, int mode, const double* scaling,
                   double* value_dev, int64_t* idx_dev) {
   sgp_ctx* ctx = g->ctx;
   const unsigned nb = nblk(g->N, T * 4);
-  double* pv = static_cast<double*>(
-      sgp_scratch(ctx, 2, size_t(nb) * (sizeof(double) + sizeof(int64_t))));
-  if (!pv) return -1;
+  double* pv;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(nb) * (sizeof(double) + sizeof(int64_t)), &pv));
   int64_t* pi = reinterpret_cast<int64_t*>(pv + nb);
   hipLaunchKernelGGL(k_argmax, dim3(nb), dim3(T), 0, ctx->stream, g->Q, g->S,
                      g->M, g->Gm, g->N, g->G, g->goff, mode,
@@ -889,14 +886,6 @@ int launch_mark_top_if(sgp_grid* g, const int64_t* gidx_dev, const int* nfound_d
 // VISITING order is the listed hit with the largest (key, index) -- everything in front of it
 // was tested in this pass or an earlier one.
 namespace {
-constexpr int kPassBins = 4096;
-
-struct PassSel {
-  double thr;      // the pass = candidates behind the cut with key >= thr
-  int count;       // ... as k_pass_list counted them
-  int est;         // ... as the histogram promised
-};
-
 __device__ __forceinline__ bool pass_key(const uint8_t* cand, const double* w, int64_t e,
                                          int64_t goff, int index_key, double cut_w,
                                          int64_t cut_idx, double* key) {
@@ -1367,8 +1356,8 @@ int launch_lipschitz_many(sgp_grid* g, int G, const double* fmin, const double* 
     SGP_HIP(ctx, hipMemcpyAsync(uc, uc_in, size_t(count) * G * 8, hipMemcpyHostToDevice, ctx->stream));
   }
   const size_t nw = size_t((g->N + 15) >> 4);
-  int* hot = static_cast<int*>(sgp_scratch(ctx, 12, (64 + nw) * sizeof(int)));
-  SGP_CHECK(ctx, hot, "device allocation failed: %s", ctx->err.c_str());
+  int* hot;
+  SGP_TRY(sgp_scratch(ctx, kSlotHot, (64 + nw) * sizeof(int), &hot));
   SGP_HIP(ctx, hipMemsetAsync(hot, 0, 64 * sizeof(int), ctx->stream));
   SGP_HIP(ctx, hipMemsetAsync(flags_dev, 0, size_t(count) * G * 4, ctx->stream));
   LipPass a{};
@@ -1429,9 +1418,8 @@ int launch_sets_front_fused(sgp_grid* g, double max_l, const double* l0_part,
   sgp_ctx* ctx = g->ctx;
   const unsigned nb = front_blocks(g->N);
   // scratch: width partials | block counts | block bests
-  char* sc = static_cast<char*>(sgp_scratch(
-      ctx, 2, size_t(kFrontBlocks) * (8 + 8 + 8 + 8 + 8)));
-  if (!sc) return -1;
+  char* sc;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(kFrontBlocks) * (8 + 8 + 8 + 8 + 8), &sc));
   double* wpart = reinterpret_cast<double*>(sc);
   unsigned* bc = reinterpret_cast<unsigned*>(sc + size_t(kFrontBlocks) * 8);
   double* bw = reinterpret_cast<double*>(sc + size_t(kFrontBlocks) * 16);
@@ -1497,9 +1485,8 @@ int launch_argmax_marked(sgp_grid* g, const double* scaling, const double* fmin,
     SGP_HIP(ctx, hipGetLastError());
     return 0;
   }
-  double* pv = static_cast<double*>(
-      sgp_scratch(ctx, 2, size_t(nb) * (sizeof(double) + sizeof(int64_t))));
-  if (!pv) return -1;
+  double* pv;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(nb) * (sizeof(double) + sizeof(int64_t)), &pv));
   int64_t* pi = reinterpret_cast<int64_t*>(pv + nb);
   hipLaunchKernelGGL(k_argmax_marked, dim3(nb), dim3(T), 0, ctx->stream, g->Q,
                      g->M, g->Gm, g->N, g->G, g->goff, vec8(scaling, g->G, 1.0),

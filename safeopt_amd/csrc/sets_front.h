@@ -11,6 +11,24 @@
 
 #include "set_order.h"
 
+// The result block of a step, in doubles.  The FRONT block (sgp_grid_sets_front[_comm];
+// what the N ranks gather) is
+//   [0] max width | [1..2] counts (u64: candidates, unsafe rows) | [3] w_top |
+//   [4] idx_top (i64) | [5] n_found, n_tied (two ints) | x[d] | mean[G] | q[2G]
+// and the whole step (sgp_grid_sets_fused[_comm], sgp_grid_step_small) appends
+//   flags[G] (i32, padded to 8 B) | value | index (i64) | max_l
+constexpr int kResMaxWidth = 0, kResCounts = 1, kResTopW = 3, kResTopIdx = 4,
+              kResFound = 5,      // (int) n_found; the int behind it: n_tied
+              kResX = 6;
+__host__ __device__ constexpr int res_mean(int d) { return kResX + d; }
+__host__ __device__ constexpr int res_q(int d, int G) { return kResX + d + G; }
+__host__ __device__ constexpr int res_front(int d, int G) { return kResX + d + 3 * G; }
+__host__ __device__ constexpr int res_flags(int d, int G) { return res_front(d, G); }
+__host__ __device__ constexpr int res_value(int d, int G) { return res_flags(d, G) + (G + 1) / 2; }
+__host__ __device__ constexpr int res_index(int d, int G) { return res_value(d, G) + 1; }
+__host__ __device__ constexpr int res_max_l(int d, int G) { return res_value(d, G) + 2; }
+__host__ __device__ constexpr int res_words(int d, int G) { return res_value(d, G) + 3; }
+
 struct FrontArgs {
   const unsigned* block_counts;   // [nb][2] candidates, unsafe rows
   const double* best_w;           // [nb] width of the workgroup's first candidate
@@ -22,7 +40,7 @@ struct FrontArgs {
   const double* Q;                // [N][2 G]
   int64_t N, goff;
   int d, G;
-  double* res;                    // result block (device), layout: sgp_grid_sets_fused
+  double* res;                    // result block (device), layout above
   double* res_host;               // the same block in mapped host memory, or null
   double* xc;                     // xc | resid[G][16]: n_xc_resid doubles
   int n_xc_resid;
@@ -71,18 +89,18 @@ __device__ __forceinline__ int64_t front_final_fold(const FrontArgs& a, bool wri
       ta += shc[0][wv];
       tb += shc[1][wv];
     }
-    reinterpret_cast<unsigned long long*>(a.res)[1] = ta;
-    reinterpret_cast<unsigned long long*>(a.res)[2] = tb;
-    a.res[3] = win.v;
-    reinterpret_cast<int64_t*>(a.res)[4] = win.i;
-    reinterpret_cast<int*>(a.res + 5)[0] = win.i >= 0 ? 1 : 0;
+    reinterpret_cast<unsigned long long*>(a.res)[kResCounts] = ta;
+    reinterpret_cast<unsigned long long*>(a.res)[kResCounts + 1] = tb;
+    a.res[kResTopW] = win.v;
+    reinterpret_cast<int64_t*>(a.res)[kResTopIdx] = win.i;
+    reinterpret_cast<int*>(a.res + kResFound)[0] = win.i >= 0 ? 1 : 0;
     if (rh) {
-      rh[0] = a.res[0];           // max width (k_candidates_f)
-      reinterpret_cast<unsigned long long*>(rh)[1] = ta;
-      reinterpret_cast<unsigned long long*>(rh)[2] = tb;
-      rh[3] = win.v;
-      reinterpret_cast<int64_t*>(rh)[4] = win.i;
-      reinterpret_cast<int*>(rh + 5)[0] = win.i >= 0 ? 1 : 0;
+      rh[kResMaxWidth] = a.res[kResMaxWidth];     // (k_candidates_f)
+      reinterpret_cast<unsigned long long*>(rh)[kResCounts] = ta;
+      reinterpret_cast<unsigned long long*>(rh)[kResCounts + 1] = tb;
+      rh[kResTopW] = win.v;
+      reinterpret_cast<int64_t*>(rh)[kResTopIdx] = win.i;
+      reinterpret_cast<int*>(rh + kResFound)[0] = win.i >= 0 ? 1 : 0;
     }
     top = win.i;
     topw = win.v;
@@ -90,8 +108,8 @@ __device__ __forceinline__ int64_t front_final_fold(const FrontArgs& a, bool wri
   __syncthreads();
   if (top < 0) {
     if (threadIdx.x == 0) {
-      reinterpret_cast<int*>(a.res + 5)[1] = 0;
-      if (rh) reinterpret_cast<int*>(rh + 5)[1] = 0;
+      reinterpret_cast<int*>(a.res + kResFound)[1] = 0;
+      if (rh) reinterpret_cast<int*>(rh + kResFound)[1] = 0;
     }
     return -1;
   }
@@ -106,8 +124,8 @@ __device__ __forceinline__ int64_t front_final_fold(const FrontArgs& a, bool wri
     if (threadIdx.x == 0) {
       unsigned t = 0;
       for (int wv = 0; wv < kT / 64; ++wv) t += unsigned(shc[0][wv]);
-      reinterpret_cast<int*>(a.res + 5)[1] = int(t);
-      if (rh) reinterpret_cast<int*>(rh + 5)[1] = int(t);
+      reinterpret_cast<int*>(a.res + kResFound)[1] = int(t);
+      if (rh) reinterpret_cast<int*>(rh + kResFound)[1] = int(t);
     }
   }
   const int64_t li = top - a.goff;
@@ -115,21 +133,21 @@ __device__ __forceinline__ int64_t front_final_fold(const FrontArgs& a, bool wri
   double* resid = a.xc + (a.n_xc_resid - G * 16);   // the block is xc | resid[G][16]
   for (int k = threadIdx.x; k < d; k += kT) {
     const double v = a.pts[int64_t(k) * a.N + li];
-    a.res[6 + k] = v;
-    if (rh) rh[6 + k] = v;
+    a.res[kResX + k] = v;
+    if (rh) rh[kResX + k] = v;
     a.xc[k] = v;
   }
   for (int g = threadIdx.x; g < G; g += kT) {
     const double mu = a.mean[int64_t(g) * a.N + li];
     const double up = a.Q[li * 2 * G + 2 * g + 1];
-    a.res[6 + d + g] = mu;
-    if (rh) rh[6 + d + g] = mu;
+    a.res[res_mean(d) + g] = mu;
+    if (rh) rh[res_mean(d) + g] = mu;
     resid[g * 16] = up - mu;
   }
   for (int q = threadIdx.x; q < 2 * G; q += kT) {
     const double v = a.Q[li * 2 * G + q];
-    a.res[6 + d + G + q] = v;
-    if (rh) rh[6 + d + G + q] = v;
+    a.res[res_q(d, G) + q] = v;
+    if (rh) rh[res_q(d, G) + q] = v;
   }
   return top;
 }

@@ -20,13 +20,14 @@
 //      (sweep.hip:k_expander_list, factor.hip:k_expkt / k_expw1 -- the same summation
 //      orders, so the flags are those of the large-grid path)      gp_opt.py:579-606
 //   F  G mark when every active GP certified it, arg-max over M | G   gp_opt.py:611-649
-// and one result block in the layout of sgp_grid_sets_fused comes back.  Everything the
+// and one result block (sets_front.h) comes back.  Everything the
 // uncommon branches of the host driver read afterwards (Q, mean, var, S, M, G, the
 // candidate mask and widths, max l0[S]) is resident exactly as the large-grid path
 // leaves it.
 #include <algorithm>
 
 #include "set_order.h"
+#include "sets_front.h"
 #include "tiny_row.h"
 
 namespace {
@@ -49,9 +50,9 @@ struct StepParams {
   double* w;
   int64_t goff;
   Vec8 scaling, thr_beta;
-  double* res;             // result block (layout of sgp_grid_sets_fused)
+  double* res;             // result block (sets_front.h)
   double* scal;            // [0] = max l0[S]
-  int nfront, nfl;
+  int nfront, nfl;         // res_flags(d, G), res_value(d, G) - res_flags(d, G)
   unsigned long long seq;  // written behind the results (system scope): the host spins on it
 };
 
@@ -261,24 +262,24 @@ __global__ __launch_bounds__(TH) void k_step_small(StepParams p) {
   const int64_t li = win.i - p.goff;
   if (tid == 0) {
     p.scal[0] = max_l;
-    p.res[0] = mw;
-    reinterpret_cast<unsigned long long*>(p.res)[1] = ncand;
-    reinterpret_cast<unsigned long long*>(p.res)[2] = nunsafe;
-    p.res[3] = win.v;
-    reinterpret_cast<int64_t*>(p.res)[4] = win.i;
-    reinterpret_cast<int*>(p.res + 5)[0] = win.i >= 0 ? 1 : 0;
-    reinterpret_cast<int*>(p.res + 5)[1] = win.i >= 0 ? int(ntied) : 0;
+    p.res[kResMaxWidth] = mw;
+    reinterpret_cast<unsigned long long*>(p.res)[kResCounts] = ncand;
+    reinterpret_cast<unsigned long long*>(p.res)[kResCounts + 1] = nunsafe;
+    p.res[kResTopW] = win.v;
+    reinterpret_cast<int64_t*>(p.res)[kResTopIdx] = win.i;
+    reinterpret_cast<int*>(p.res + kResFound)[0] = win.i >= 0 ? 1 : 0;
+    reinterpret_cast<int*>(p.res + kResFound)[1] = win.i >= 0 ? int(ntied) : 0;
     p.res[p.nfront + p.nfl + 2] = max_l;
   }
   if (win.i >= 0) {
     if (tid < d) {
       const double xv = p.pts.base[li * p.pts.stride_row + tid * p.pts.stride_col];
-      p.res[6 + tid] = xv;
+      p.res[kResX + tid] = xv;
       xcs[tid] = xv;
     }
-    if (tid >= 64 && tid < 64 + G) p.res[6 + d + (tid - 64)] = p.conf.mean[int64_t(tid - 64) * N + li];
+    if (tid >= 64 && tid < 64 + G) p.res[res_mean(d) + (tid - 64)] = p.conf.mean[int64_t(tid - 64) * N + li];
     if (tid >= 128 && tid < 128 + 2 * G)
-      p.res[6 + d + G + (tid - 128)] = p.conf.Q[li * 2 * G + (tid - 128)];
+      p.res[res_q(d, G) + (tid - 128)] = p.conf.Q[li * 2 * G + (tid - 128)];
   }
   __syncthreads();
 
@@ -711,7 +712,7 @@ bool step_small_eligible(const sgp_ctx* ctx, const GpDev* gh, int G, int64_t N) 
 
 int launch_step_small(sgp_grid* g, const GpDev* gps_dev, const GpDev* gh, int G, double beta,
                       const double* fmin, const double* scaling, const double* thr_beta,
-                      double* res, int nfront, int nfl, uint64_t seq) {
+                      double* res, uint64_t seq) {
   sgp_ctx* ctx = g->ctx;
   StepParams p{};
   p.gps = gps_dev;
@@ -735,8 +736,8 @@ int launch_step_small(sgp_grid* g, const GpDev* gps_dev, const GpDev* gh, int G,
   p.goff = g->goff;
   p.res = res;
   p.scal = g->scal;
-  p.nfront = nfront;
-  p.nfl = nfl;
+  p.nfront = res_flags(g->d, G);
+  p.nfl = res_value(g->d, G) - res_flags(g->d, G);
   p.seq = seq;
   int np = 1;
   bool single = true;

@@ -2106,8 +2106,8 @@ int launch_expander_many(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d, Sweep
   // GP: counts | [G][N / 16] waves | [G][N / 16] masks of their listed rows | [G][N] rows
   {
     const size_t nw = size_t((pts.N + 15) >> 4);
-    int* hot = static_cast<int*>(sgp_scratch(ctx, 12, (64 + size_t(G) * (2 * nw + size_t(pts.N))) * sizeof(int)));
-    SGP_CHECK(ctx, hot, "device allocation failed: %s", ctx->err.c_str());
+    int* hot;
+    SGP_TRY(sgp_scratch(ctx, kSlotHot, (64 + size_t(G) * (2 * nw + size_t(pts.N))) * sizeof(int), &hot));
     ea.count = hot;
     ea.wcount = hot + 32;
     ea.wlist = hot + 64;

@@ -539,3 +539,23 @@ def test_mask_edits_are_dropped_by_the_one_launch_step(mods):
         for f in ("S", "M", "G"):
             assert_array_equal(getattr(opt, f), getattr(fresh, f))
         assert_array_equal(opt.get_new_query_point(), x_ref)
+
+
+@pytest.mark.timeout(1800)
+def test_sets_fused_copy_branch():
+    """SGP_SETS_COPY=1 takes ``sgp_grid_sets_fused`` down the branch of grids beyond ~2.5e8 rows:
+    the result block stays in device scratch, the front half and the arg-max end in launches of
+    their own (k_front_final, k_argmax_final_f) and one read-back copy returns the block.  The
+    golden replays, expander loops and tied widths of this module (with the one-launch step of
+    small grids off, so that ``optimize()`` goes through ``sgp_grid_sets_fused``) and the big
+    passes of test_gpu_expander_passes.py give the same results through it."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, SGP_SETS_COPY="1", SGP_NO_STEP_SMALL="1")
+    sel = ("replay_reference_golden or expander_loop_golden or tied_widths_golden "
+           "or test_gpu_expander_passes")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_sets.py"),
+                        os.path.join(root, "tests", "test_gpu_expander_passes.py"),
+                        "-q", "-m", "gpu", "-x", "--tb=line", "-k", sel],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=1700)
+    assert r.returncode == 0, r.stdout[-3000:]
