@@ -403,6 +403,27 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
                   const double* bounds, int init, int iters, double inertia0,
                   double step, const double* rand, uint64_t seed);
 
+/* sgp_swarm_run on a rank's contiguous block of particles [p0, p0 + P) of a swarm
+ * of P_total (shard_range): the state arrays hold the block's P rows.  After the
+ * personal bests of init and of every iteration each rank's best (value, global
+ * index, x) is all-gathered over the context's communicator (in stream on RCCL,
+ * or the host transport of sgp_comm_init_host) and the global best is the largest
+ * value, the lowest global index on ties -- on every rank, as for the whole swarm.
+ * Philox mode draws the numbers of the block's global elements (p0*d + e; r2:
+ * P_total*d + p0*d + e), so a block draws what the whole run draws for it; with
+ * rand != NULL the caller passes the block's rows of every draw (P*d for init,
+ * then per iteration its P r1 rows and its P r2 rows).  The posterior kernel and
+ * the few-points / small-swarm choices follow P_total.  p0 = 0, P = P_total is
+ * sgp_swarm_run; P < P_total needs a communicator on ctx.                     */
+int sgp_swarm_run_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                        double beta, const double* fmin, const double* scaling,
+                        double best_lower_bound, int64_t P, double* positions,
+                        double* velocities, double* best_positions, double* best_values,
+                        double* global_best, const double* velocity_scale,
+                        const double* bounds, int init, int iters, double inertia0,
+                        double step, const double* rand, uint64_t seed, int64_t p0,
+                        int64_t P_total);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------
  * The only cross-rank traffic of the path is a handful of scalars per
  * iteration (max / any / arg-max / top-k merge).                             */

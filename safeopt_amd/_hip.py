@@ -145,6 +145,12 @@ PROTOTYPES = {
                                 c_double_p, c_double_p, c_double_p, C.c_int,
                                 C.c_int, C.c_double, C.c_double, c_double_p,
                                 C.c_uint64]),
+    "sgp_swarm_run_shard": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
+                                      c_double_p, c_double_p, C.c_double, C.c_int64,
+                                      c_double_p, c_double_p, c_double_p, c_double_p,
+                                      c_double_p, c_double_p, c_double_p, C.c_int,
+                                      C.c_int, C.c_double, C.c_double, c_double_p,
+                                      C.c_uint64, C.c_int64, C.c_int64]),
     "sgp_comm_unique_id": (C.c_int, [vp]),
     "sgp_comm_init": (C.c_int, [vp, vp, C.c_int, C.c_int]),
     "sgp_comm_init_host": (C.c_int, [vp, C.c_int, C.c_int, HOST_ALLREDUCE_F64,
@@ -1001,21 +1007,29 @@ def swarm_grow(ctx, gp, S, B, scale2, thr=0.95):
 
 def swarm_run(ctx, gps, swarm_type, beta, fmin, scaling, best_lower_bound,
               positions, velocities, best_positions, best_values, global_best,
-              velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0):
-    """Whole PSO run on the device; the state arrays are updated in place."""
+              velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0,
+              shard=None):
+    """Whole PSO run on the device; the state arrays are updated in place.
+
+    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
+    ``P_total`` sharded over the ranks of ``ctx``'s communicator
+    (``sgp_swarm_run_shard``); ``global_best`` comes back as the whole swarm's."""
     P = positions.shape[0]
     for a in (positions, velocities, best_positions, best_values, global_best):
         assert a.dtype == np.float64 and a.flags.c_contiguous
     bnd = None if bounds is None else f64(bounds)
     rnd = None if rand is None else f64(rand).ravel()
-    ctx.check(lib().sgp_swarm_run(
-        ctx.h, _gp_array(gps), len(gps), SWARM_TYPES[swarm_type], float(beta),
-        dptr(f64(fmin)), dptr(f64(scaling)), float(best_lower_bound), P,
-        dptr(positions), dptr(velocities), dptr(best_positions),
-        dptr(best_values), dptr(global_best), dptr(f64(velocity_scale)),
-        None if bnd is None else dptr(bnd), int(bool(init)), int(iters),
-        float(inertia0), float(step), None if rnd is None else dptr(rnd),
-        int(seed)))
+    args = (ctx.h, _gp_array(gps), len(gps), SWARM_TYPES[swarm_type], float(beta),
+            dptr(f64(fmin)), dptr(f64(scaling)), float(best_lower_bound), P,
+            dptr(positions), dptr(velocities), dptr(best_positions),
+            dptr(best_values), dptr(global_best), dptr(f64(velocity_scale)),
+            None if bnd is None else dptr(bnd), int(bool(init)), int(iters),
+            float(inertia0), float(step), None if rnd is None else dptr(rnd),
+            int(seed))
+    if shard is None:
+        ctx.check(lib().sgp_swarm_run(*args))
+    else:
+        ctx.check(lib().sgp_swarm_run_shard(*(args + (int(shard[0]), int(shard[1])))))
 
 
 def swarm_fitness(ctx, gps, swarm_type, particles, beta, fmin, scaling,

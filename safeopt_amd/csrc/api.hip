@@ -2109,26 +2109,40 @@ int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
 
 // SwarmOptimization.init_swarm / run_swarm (swarm.py:61-146) with the state in
 // HBM and the fitness fused in: one call = the whole run, one host round trip.
-int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
-                  double beta, const double* fmin, const double* scaling,
-                  double best_lower_bound, int64_t P, double* positions,
-                  double* velocities, double* best_positions, double* best_values,
-                  double* global_best, const double* velocity_scale,
-                  const double* bounds, int init, int iters, double inertia0,
-                  double step_size, const double* rand, uint64_t seed) {
+// The particles [p0, p0 + P) of a swarm of Pt; P < Pt: a rank's block of a sharded
+// swarm (sgp_swarm_run_shard) -- the global best goes through the record all-gather.
+static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                     double beta, const double* fmin, const double* scaling,
+                     double best_lower_bound, int64_t P, double* positions,
+                     double* velocities, double* best_positions, double* best_values,
+                     double* global_best, const double* velocity_scale,
+                     const double* bounds, int init, int iters, double inertia0,
+                     double step_size, const double* rand, uint64_t seed, int64_t p0,
+                     int64_t Pt) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, swarm_type >= SGP_SWARM_GREEDY && swarm_type <= SGP_SWARM_SAFE_SET,
             "Invalid swarm type %d", swarm_type);
   SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
   SGP_CHECK(ctx, P >= 1 && iters >= 0, "bad swarm size %lld / iterations %d",
             (long long)P, iters);
+  SGP_CHECK(ctx, p0 >= 0 && p0 + P <= Pt, "bad block [%lld, %lld) of a swarm of %lld",
+            (long long)p0, (long long)(p0 + P), (long long)Pt);
+  const bool shard = P < Pt;
+  const bool comm = have_comm(ctx);
+  SGP_CHECK(ctx, comm || !shard,
+            "a block of %lld of a swarm of %lld particles needs a communicator in the "
+            "context (sgp_comm_init / sgp_comm_init_host)", (long long)P, (long long)Pt);
+  const int world = comm ? ctx->world : 1;
   const int d = gps[0]->kern.d;
   GpDev host[SGP_MAX_GPS];
   SGP_TRY(collect_gps(ctx, gps, G, d, host));
   const size_t nd = size_t(P) * d * 8, nv = size_t(P) * 8;
   const size_t nrand = rand ? (size_t(init ? 1 : 0) + 2 * size_t(iters)) * nd : 0;
-  // pos | vel | best | best_values | values | gbest | vscale | bounds | gpdev | safe
-  const size_t small = size_t(d) * 8 * 4 + sizeof(GpDev) * SGP_MAX_GPS + 64;
+  // pos | vel | best | best_values | values | gbest | vscale | bounds | gpdev |
+  // this rank's record | the gathered records (shard: value | index | x[d] each) | safe
+  const size_t nrec = size_t(2 + d);
+  const size_t recs = shard ? (1 + size_t(world)) * nrec * 8 : 0;
+  const size_t small = size_t(d) * 8 * 4 + sizeof(GpDev) * SGP_MAX_GPS + recs + 64;
   char* buf;
   double* drand = nullptr;
   SGP_TRY(sgp_scratch(ctx, kSlotWork, 3 * nd + 2 * nv + small + size_t(P), &buf));
@@ -2142,7 +2156,9 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   double* dvs = dgb + d;
   double* dbd = dvs + d;                       // 2 d entries
   GpDev* gdev = reinterpret_cast<GpDev*>(dbd + 2 * d);
-  uint8_t* dsafe = reinterpret_cast<uint8_t*>(gdev + SGP_MAX_GPS);
+  double* drec = reinterpret_cast<double*>(gdev + SGP_MAX_GPS);
+  double* drecs = drec + nrec;
+  uint8_t* dsafe = reinterpret_cast<uint8_t*>(drec) + recs;
   SGP_TRY(sgp_h2d(ctx, dpos, positions, nd));
   if (!init) {
     SGP_TRY(sgp_h2d(ctx, dvel, velocities, nd));
@@ -2165,15 +2181,16 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   fa.values = dval;
   fa.safe = dsafe;
   const SweepPoints sp{dpos, P, d, 1};          // row-major (P, d) in place
-  const bool few = P <= kSmallSwarm && small_path_pays_all(gps, G, P);
+  // (the paths and the posterior kernel follow the whole swarm: same bits on every rank)
+  const bool few = Pt <= kSmallSwarm && small_path_pays_all(gps, G, Pt);
   // a small swarm against GPs with few observations (SafeOptSwarm's defaults on the
   // reference's own examples: 20 particles, n <= 20): the posterior is one sweep launch
   // (sweep_tiny.hip up to 48 observations), everything else of the iteration the same ONE
   // workgroup as on the few-points path -- two launches per iteration instead of five
-  const bool few_swept = P <= kSmallSwarm && !few;
+  const bool few_swept = Pt <= kSmallSwarm && !few;
   const double* r = drand;
   double inertia = inertia0;
-  if (few || few_swept) {
+  if ((few || few_swept) && !shard) {
     // small swarm: three launches per iteration -- k(X, particles), the block
     // products on the matrix cores, and ONE workgroup for everything else
     // (fitness, bests, and the move that opens the next iteration)
@@ -2232,26 +2249,37 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
     for (int it = 0; it < iters; ++it)
       SGP_TRY(step(0, it + 1 < iters ? it + 1 : -1));
   } else {
-    // (up to kSmallPoints particles still take the few-points posterior)
-    const bool few_points = small_path_pays_all(gps, G, P);
+    // (up to kSmallPoints particles still take the few-points posterior; a block of a
+    // small swarm takes these launches, the arithmetic of k_pso_small_step)
+    const bool few_points = small_path_pays_all(gps, G, Pt);
     auto fitness = [&]() -> int {
       return few_points ? fitness_small(ctx, gdev, host, G, dpos, P, fa)
-                        : launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa);
+                        : launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa, Pt);
     };
+    // personal bests, then the global best: of the block, or merged over the ranks
+    auto bests = [&](int is_init) -> int {
+      if (!shard)
+        return launch_pso_best(ctx, P, d, dval, dsafe, dpos, dbest, dbv, dgb, is_init);
+      SGP_TRY(launch_pso_best(ctx, P, d, dval, dsafe, dpos, dbest, dbv, dgb, is_init, drec,
+                              p0));
+      SGP_TRY(coll_allgather(ctx, drec, drecs, nrec * 8));
+      return launch_pso_gbest_merge(ctx, drecs, world, d, dgb);
+    };
+    const int64_t e0 = p0 * d, e2 = Pt * d + p0 * d;
     if (init) {
-      SGP_TRY(launch_pso_init_vel(ctx, P, d, dvel, dvs, r, seed));
+      SGP_TRY(launch_pso_init_vel(ctx, P, d, dvel, dvs, r, seed, e0));
       if (r) r += size_t(P) * d;
       SGP_TRY(fitness());
-      SGP_TRY(launch_pso_best(ctx, P, d, dval, dsafe, dpos, dbest, dbv, dgb, 1));
+      SGP_TRY(bests(1));
     }
     for (int it = 0; it < iters; ++it) {
       SGP_TRY(launch_pso_move(ctx, P, d, dpos, dvel, dbest, dgb, dvs,
                               bounds ? dbd : nullptr, inertia, r, seed,
-                              uint32_t(it + 1)));
+                              uint32_t(it + 1), e0, e2));
       if (r) r += 2 * size_t(P) * d;
       inertia += step_size;
       SGP_TRY(fitness());
-      SGP_TRY(launch_pso_best(ctx, P, d, dval, dsafe, dpos, dbest, dbv, dgb, 0));
+      SGP_TRY(bests(0));
     }
   }
   SGP_TRY(sgp_d2h(ctx, positions, dpos, nd));
@@ -2259,6 +2287,32 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   SGP_TRY(sgp_d2h(ctx, best_positions, dbest, nd));
   SGP_TRY(sgp_d2h(ctx, best_values, dbv, nv));
   return sgp_d2h(ctx, global_best, dgb, size_t(d) * 8);
+}
+
+int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                  double beta, const double* fmin, const double* scaling,
+                  double best_lower_bound, int64_t P, double* positions,
+                  double* velocities, double* best_positions, double* best_values,
+                  double* global_best, const double* velocity_scale,
+                  const double* bounds, int init, int iters, double inertia0,
+                  double step_size, const double* rand, uint64_t seed) {
+  return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
+                   positions, velocities, best_positions, best_values, global_best,
+                   velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, 0, P);
+}
+
+int sgp_swarm_run_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                        double beta, const double* fmin, const double* scaling,
+                        double best_lower_bound, int64_t P, double* positions,
+                        double* velocities, double* best_positions, double* best_values,
+                        double* global_best, const double* velocity_scale,
+                        const double* bounds, int init, int iters, double inertia0,
+                        double step_size, const double* rand, uint64_t seed, int64_t p0,
+                        int64_t P_total) {
+  return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
+                   positions, velocities, best_positions, best_values, global_best,
+                   velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, p0,
+                   P_total);
 }
 
 // SafeOptSwarm safe-set growth, gp_opt.py:1089-1111 (kernels in swarm.hip).
@@ -2271,22 +2325,14 @@ int sgp_swarm_grow(sgp_ctx* ctx, sgp_gp* gp0, const double* S, int64_t m,
             (long long)m, (long long)n);
   if (n == 0) return 0;
   const int d = gp0->kern.d;
-  const int nchunks = swarm_grow_chunks(m);
-  const size_t bs = size_t(m) * d * 8, bb = size_t(n) * d * 8;
-  const size_t bp = size_t(n) * size_t(nchunks > 0 ? nchunks : 1) * 8;
-  const size_t bl = size_t(n) * 4, ba = size_t(n);
+  const GrowLayout l = grow_layout(m, n, d);          // (common.h)
   char* buf;
-  SGP_TRY(sgp_scratch(ctx, kSlotWork, bs + bb + bp + bl + ba + 64, &buf));
-  double* dS = reinterpret_cast<double*>(buf);
-  double* dB = reinterpret_cast<double*>(buf + bs);
-  double* part = reinterpret_cast<double*>(buf + bs + bb);
-  int* list = reinterpret_cast<int*>(buf + bs + bb + bp);
-  uint8_t* dacc = reinterpret_cast<uint8_t*>(buf + bs + bb + bp + bl);
-  SGP_TRY(sgp_h2d(ctx, dS, S, bs));
-  SGP_TRY(sgp_h2d(ctx, dB, B, bb));
-  SGP_TRY(launch_swarm_grow(ctx, gp0->kern, dS, m, dB, int(n), scale2, thr, part,
-                            list, dacc));
-  return sgp_d2h(ctx, accept, dacc, ba);
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, l.bytes + 64, &buf));
+  const GrowBufs gb = grow_bufs(buf, l);
+  SGP_TRY(sgp_h2d(ctx, gb.S, S, size_t(m) * d * 8));
+  SGP_TRY(sgp_h2d(ctx, gb.B, B, size_t(n) * d * 8));
+  SGP_TRY(launch_swarm_grow(ctx, gp0->kern, gb.S, m, gb.B, int(n), scale2, thr, gb));
+  return sgp_d2h(ctx, accept, gb.accept, size_t(n));
 }
 
 // ---- timing ---------------------------------------------------------------------

@@ -366,7 +366,7 @@ constexpr int kSepMinBlocks = 8;
 int launch_verify_axes(sgp_grid* g, int* mismatch_dev);
 int launch_sweep_fitness(sgp_ctx* ctx, const GpDev* gps_dev,
                          const GpDev* gps_host, int G, int d, SweepPoints pts,
-                         FitnessArgs fa);
+                         FitnessArgs fa, int64_t sel_rows = -1);
 // few-points posterior / small-swarm step: small_path.h
 constexpr int kSmallPoints = 4096;   // few-points posterior path (factor.hip)
 constexpr int kSmallSwarm = 64;     // ... with the whole PSO step in one workgroup (swarm.hip)
@@ -526,18 +526,59 @@ int launch_fill_cols(sgp_grid* g, const double* c, int nc);
 int launch_gather_rows(sgp_grid* g, const int64_t* lidx_dev, int m, double* x,
                        double* mean, double* var, double* Q);
 int launch_mark(sgp_grid* g, const int64_t* lidx_dev, int m, int value = 1);
+// sgp_swarm_grow's block in kSlotWork, sized from m, n and d (kGrowBlock fixes the serial
+// step, not the size):
+//   S[m][d] f64 | B[n][d] f64 | list[n] i32 (accepted candidates, in order) |
+//   count (i32, padded to 8 B) | flag[n] u8 (1: rejected by S or by a candidate accepted
+//   in an earlier block) | accept[n] u8 (the result, read back)
+constexpr int kGrowBlock = 512;   // candidates whose order one workgroup resolves (swarm.hip)
+struct GrowBufs {
+  double* S;
+  double* B;
+  int* list;
+  int* count;
+  uint8_t* flag;
+  uint8_t* accept;
+};
+struct GrowLayout {
+  size_t S, B, list, count, flag, accept, bytes;
+};
+inline GrowLayout grow_layout(int64_t m, int64_t n, int d) {
+  GrowLayout l;
+  l.S = 0;
+  l.B = l.S + size_t(m) * d * 8;
+  l.list = l.B + size_t(n) * d * 8;
+  l.count = l.list + (size_t(n) * 4 + 7) / 8 * 8;
+  l.flag = l.count + 8;
+  l.accept = l.flag + size_t(n);
+  l.bytes = l.accept + size_t(n);
+  return l;
+}
+inline GrowBufs grow_bufs(char* base, const GrowLayout& l) {
+  return GrowBufs{reinterpret_cast<double*>(base + l.S), reinterpret_cast<double*>(base + l.B),
+                  reinterpret_cast<int*>(base + l.list), reinterpret_cast<int*>(base + l.count),
+                  reinterpret_cast<uint8_t*>(base + l.flag),
+                  reinterpret_cast<uint8_t*>(base + l.accept)};
+}
 int launch_swarm_grow(sgp_ctx* ctx, const KernDesc& kd, const double* S, int64_t m,
-                      const double* B, int n, double scale2, double thr,
-                      double* part, int* list, uint8_t* accept);
-int swarm_grow_chunks(int64_t m);
+                      const double* B, int n, double scale2, double thr, const GrowBufs& gb);
+// The swarm kernels take the rank's block of particles [p0, p0 + P) of a swarm of P_total:
+// e0 / e2 are the global element indices of the block's first r1 / r2 number on the
+// device generator (0 / P d for a whole swarm).
 int launch_pso_init_vel(sgp_ctx* ctx, int64_t P, int d, double* vel,
-                        const double* vscale, const double* rand, uint64_t seed);
+                        const double* vscale, const double* rand, uint64_t seed,
+                        int64_t e0 = 0);
 int launch_pso_move(sgp_ctx* ctx, int64_t P, int d, double* pos, double* vel,
                     const double* best, const double* gbest, const double* vscale,
                     const double* bounds, double inertia, const double* rand,
-                    uint64_t seed, uint32_t draw);
+                    uint64_t seed, uint32_t draw, int64_t e0 = 0, int64_t e2 = -1);
+// rec != nullptr: the global best of the block goes to the record
+//   value | global index (i64) | x[d]
+// (what the ranks gather; k_pso_gbest_merge picks the swarm's) instead of to gbest
 int launch_pso_best(sgp_ctx* ctx, int64_t P, int d, const double* values,
                     const uint8_t* safe, const double* pos, double* best,
-                    double* best_values, double* gbest, int init);
+                    double* best_values, double* gbest, int init, double* rec = nullptr,
+                    int64_t p0 = 0);
+int launch_pso_gbest_merge(sgp_ctx* ctx, const double* recs, int world, int d, double* gbest);
 int launch_import_points(sgp_ctx* ctx, const double* src, int64_t N, int d,
                          int64_t stride_row, int64_t stride_col, double* dst);

@@ -5,104 +5,185 @@
 // swarm's best positions B (n x d) against the current safe set S (m x d),
 // candidate j is appended iff C[j, p] <= 0.95 for every point p of S and for
 // every candidate accepted before it.  The reference materialises the
-// n x (m + n) matrix on the host and loops over j; here
-//   k_grow_old : max_p C[j, p] over S, tiled over (candidate, chunk of S)
-//   k_grow_new : the order-dependent part -- one workgroup walks over the
-//                candidates in order and tests each one against the accepted
-//                list in parallel.
-// The covariance matrix is never stored.
+// n x (m + n) matrix on the host and loops over j; here the covariance matrix is
+// never stored and the order is resolved in ceil(n / kGrowBlock) serial steps:
+//   k_grow_vs_set      : every candidate against S -- a 1-D grid over (tile of 256
+//                        candidates x chunk of S staged in LDS), one flag per candidate
+//   per block of kGrowBlock candidates, in order:
+//     k_grow_vs_accepted : the block against the candidates accepted in EARLIER blocks,
+//                          over the chip (tile x chunk of the accepted list in LDS)
+//     k_grow_block       : one workgroup: the block's strictly lower triangular conflict
+//                          matrix as bitmasks, the order resolved by one wave over those
+//                          bitmasks, the accepted candidates appended to the list in order
+// Every covariance is kern_eval<D>(kd, candidate, other) / scale2 with the candidate
+// first, as the reference's row j of C.  Against S the values fold with fmax (a NaN
+// value drops out) and the candidate is rejected iff !(max <= thr); against accepted
+// candidates any value with !(c <= thr) rejects (NaN rejects).  Scratch: GrowLayout
+// (common.h).
 #include "kern_eval.h"
 #include "fitness.h"
 #include "small_path.h"
 
 namespace {
 
-constexpr int kGrowChunk = 4096;   // safe-set points per workgroup of k_grow_old
+constexpr int kGrowTile = 256;    // candidates per workgroup of the chip-wide kernels
+constexpr int kGrowChunk = 512;   // safe-set points / accepted candidates staged in LDS
+constexpr int kGrowWords = kGrowBlock / 64;
 
 template <int D>
-__global__ __launch_bounds__(256) void k_grow_old(KernDesc kd, const double* S,
-                                                  int64_t m, const double* B,
-                                                  double scale2, double* part,
-                                                  int nchunks) {
-  __shared__ double sh[4];
-  const int j = blockIdx.y;
-  const int64_t p0 = int64_t(blockIdx.x) * kGrowChunk;
+__global__ __launch_bounds__(kGrowTile) void k_grow_vs_set(KernDesc kd, const double* S,
+                                                           int64_t m, const double* B, int n,
+                                                           int ntile, double scale2,
+                                                           double thr, uint8_t* flag) {
+  __shared__ double sh[kGrowChunk * D];
+  const int tile = int(blockIdx.x % unsigned(ntile));
+  const int64_t p0 = int64_t(blockIdx.x / unsigned(ntile)) * kGrowChunk;
+  const int np = int(min(int64_t(kGrowChunk), m - p0));
+  for (int e = threadIdx.x; e < np * D; e += kGrowTile) sh[e] = S[p0 * D + e];
+  __syncthreads();
+  const int j = tile * kGrowTile + int(threadIdx.x);
+  if (j >= n || flag[j]) return;       // (a flag set by another chunk: nothing to add)
   double b[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) b[k] = B[int64_t(j) * D + k];
   double mx = -INFINITY;
-  for (int64_t p = p0 + threadIdx.x; p < min(p0 + kGrowChunk, m); p += 256) {
-    double s[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) s[k] = S[p * D + k];
-    mx = fmax(mx, kern_eval<D>(kd, b, s) / scale2);
+  for (int p = 0; p < np; ++p) {
+    mx = fmax(mx, kern_eval<D>(kd, b, sh + p * D) / scale2);
+    if (!(mx <= thr)) break;           // (mx is never NaN: fmax drops NaN values)
   }
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    part[int64_t(j) * nchunks + blockIdx.x] =
-        fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+  if (!(mx <= thr)) flag[j] = 1;
 }
 
 template <int D>
-__global__ __launch_bounds__(1024) void k_grow_new(KernDesc kd, const double* B,
-                                                   int n, const double* part,
-                                                   int nchunks, double scale2,
-                                                   double thr, int* list,
-                                                   uint8_t* accept) {
-  __shared__ int clash[1024 / 64];
-  __shared__ int count;
-  const int tid = threadIdx.x;
-  if (tid == 0) count = 0;
-  __syncthreads();
-  for (int j = 0; j < n; ++j) {
-    // against the old safe set (all threads evaluate the same few partials)
-    double mx = -INFINITY;
-    for (int c = 0; c < nchunks; ++c) mx = fmax(mx, part[int64_t(j) * nchunks + c]);
-    bool bad = !(mx <= thr);             // NaN rejects, as `<=` does in NumPy
-    const int na = count;
-    if (!bad) {
-      double b[D];
-#pragma unroll
-      for (int k = 0; k < D; ++k) b[k] = B[int64_t(j) * D + k];
-      for (int a = tid; a < na; a += 1024) {
-        const int i = list[a];
-        double o[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) o[k] = B[int64_t(i) * D + k];
-        bad = bad || !(kern_eval<D>(kd, b, o) / scale2 <= thr);
-      }
-    }
-    const unsigned long long any = __ballot(bad);
-    if ((tid & 63) == 0) clash[tid >> 6] = any != 0ULL;
-    __syncthreads();
-    bool rej = false;
-    for (int w = 0; w < 1024 / 64; ++w) rej = rej || clash[w];
-    if (tid == 0) {
-      accept[j] = rej ? 0 : 1;
-      if (!rej) {
-        list[na] = j;
-        count = na + 1;
-      }
-    }
-    __syncthreads();
+__global__ __launch_bounds__(kGrowTile) void k_grow_vs_accepted(KernDesc kd, const double* B,
+                                                                int j0, int nb, int ntile,
+                                                                const int* list,
+                                                                const int* count, double scale2,
+                                                                double thr, uint8_t* flag) {
+  __shared__ double sh[kGrowChunk * D];
+  const int na = *count;
+  const int tile = int(blockIdx.x % unsigned(ntile));
+  const int a0 = int(blockIdx.x / unsigned(ntile)) * kGrowChunk;
+  if (a0 >= na) return;                // (uniform: fewer accepted than the grid allows)
+  const int np = min(kGrowChunk, na - a0);
+  for (int e = threadIdx.x; e < np * D; e += kGrowTile) {
+    const int a = e / D;
+    sh[e] = B[int64_t(list[a0 + a]) * D + (e - a * D)];
   }
+  __syncthreads();
+  const int r = tile * kGrowTile + int(threadIdx.x);
+  if (r >= nb) return;
+  const int j = j0 + r;
+  if (flag[j]) return;
+  double b[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) b[k] = B[int64_t(j) * D + k];
+  for (int p = 0; p < np; ++p)
+    if (!(kern_eval<D>(kd, b, sh + p * D) / scale2 <= thr)) {
+      flag[j] = 1;
+      break;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(1024) void k_grow_block(KernDesc kd, const double* B, int j0,
+                                                     int nb, double scale2, double thr,
+                                                     const uint8_t* flag, int* list,
+                                                     int* count, uint8_t* accept) {
+  __shared__ double sb[kGrowBlock * D];
+  __shared__ unsigned long long conf[kGrowBlock][kGrowWords];   // bit k of row i: k < i clashes
+  __shared__ unsigned long long alive[kGrowWords], acc[kGrowWords];
+  const int t = threadIdx.x;
+  const int na = *count;               // (thread 0 writes it back after the last barrier)
+  for (int e = t; e < nb * D; e += 1024) sb[e] = B[int64_t(j0) * D + e];
+  {
+    const bool ok = t < nb && !flag[j0 + t];
+    const unsigned long long w = __ballot(ok);
+    if ((t & 63) == 0 && (t >> 6) < kGrowWords) alive[t >> 6] = w;
+  }
+  __syncthreads();
+  // conflict words: item (i, w) = row i against the candidates 64 w .. 64 w + 63 before it
+  for (int it = t; it < kGrowBlock * kGrowWords; it += 1024) {
+    const int i = it / kGrowWords, w = it % kGrowWords;
+    unsigned long long word = 0;
+    if (i < nb && w <= (i >> 6) && ((alive[i >> 6] >> (i & 63)) & 1ULL)) {
+      const unsigned long long live = alive[w];
+      const int kend = min(64, i - 64 * w);
+      for (int q = 0; q < kend; ++q)
+        if ((live >> q) & 1ULL)
+          if (!(kern_eval<D>(kd, sb + i * D, sb + (64 * w + q) * D) / scale2 <= thr))
+            word |= 1ULL << q;
+    }
+    conf[i][w] = word;
+  }
+  __syncthreads();
+  // the order: lane l holds word l of the accepted bits; candidate i is accepted iff it is
+  // alive and clashes with none of the accepted candidates before it
+  if (t < 64) {
+    unsigned long long a = 0;
+    for (int i = 0; i < nb; ++i) {
+      if (!((alive[i >> 6] >> (i & 63)) & 1ULL)) continue;    // (wave-uniform)
+      const unsigned long long c = t < kGrowWords ? conf[i][t] : 0ULL;
+      const unsigned long long hit = __ballot((c & a) != 0ULL);
+      if (hit == 0ULL && t == (i >> 6)) a |= 1ULL << (i & 63);
+    }
+    if (t < kGrowWords) acc[t] = a;
+  }
+  __syncthreads();
+  // accept[] of the block and the accepted candidates appended in order
+  if (t < nb) {
+    const int w = t >> 6;
+    const unsigned long long bit = 1ULL << (t & 63);
+    const bool ok = (acc[w] & bit) != 0ULL;
+    accept[j0 + t] = ok ? 1 : 0;
+    if (ok) {
+      int pos = na + __popcll(acc[w] & (bit - 1ULL));
+      for (int v = 0; v < w; ++v) pos += __popcll(acc[v]);
+      list[pos] = j0 + t;
+    }
+  }
+  if (t == 0) {
+    int tot = na;
+    for (int v = 0; v < kGrowWords; ++v) tot += __popcll(acc[v]);
+    *count = tot;
+  }
+}
+
+template <int D>
+int grow_launches(sgp_ctx* ctx, const KernDesc& kd, const double* S, int64_t m,
+                  const double* B, int n, double scale2, double thr, const GrowBufs& gb) {
+  const int ntile = (n + kGrowTile - 1) / kGrowTile;
+  const int64_t nchunk = (m + kGrowChunk - 1) / kGrowChunk;
+  SGP_CHECK(ctx, int64_t(ntile) * nchunk <= INT32_MAX, "safe set too large (m=%lld, n=%d)",
+            (long long)m, n);
+  if (nchunk > 0)
+    hipLaunchKernelGGL(k_grow_vs_set<D>, dim3(unsigned(ntile * nchunk)), dim3(kGrowTile), 0,
+                       ctx->stream, kd, S, m, B, n, ntile, scale2, thr, gb.flag);
+  for (int j0 = 0; j0 < n; j0 += kGrowBlock) {
+    const int nb = min(kGrowBlock, n - j0);
+    if (j0 > 0) {
+      // as many chunks as the earlier blocks could have accepted; the surplus returns at once
+      const int bt = (nb + kGrowTile - 1) / kGrowTile;
+      const int nc = (j0 + kGrowChunk - 1) / kGrowChunk;
+      hipLaunchKernelGGL(k_grow_vs_accepted<D>, dim3(unsigned(bt * nc)), dim3(kGrowTile), 0,
+                         ctx->stream, kd, B, j0, nb, bt, gb.list, gb.count, scale2, thr,
+                         gb.flag);
+    }
+    hipLaunchKernelGGL(k_grow_block<D>, dim3(1), dim3(1024), 0, ctx->stream, kd, B, j0, nb,
+                       scale2, thr, gb.flag, gb.list, gb.count, gb.accept);
+  }
+  return 0;
 }
 
 }  // namespace
 
 int launch_swarm_grow(sgp_ctx* ctx, const KernDesc& kd, const double* S, int64_t m,
-                      const double* B, int n, double scale2, double thr,
-                      double* part, int* list, uint8_t* accept) {
-  const int nchunks = int((m + kGrowChunk - 1) / kGrowChunk);
-#define GROW_CASE(DD)                                                           \
-  case DD:                                                                      \
-    if (nchunks > 0)                                                            \
-      hipLaunchKernelGGL(k_grow_old<DD>, dim3(nchunks, n), dim3(256), 0,        \
-                         ctx->stream, kd, S, m, B, scale2, part, nchunks);      \
-    hipLaunchKernelGGL(k_grow_new<DD>, dim3(1), dim3(1024), 0, ctx->stream, kd, \
-                       B, n, part, nchunks, scale2, thr, list, accept);         \
+                      const double* B, int n, double scale2, double thr, const GrowBufs& gb) {
+  SGP_HIP(ctx, hipMemsetAsync(gb.flag, 0, size_t(n), ctx->stream));
+  SGP_HIP(ctx, hipMemsetAsync(gb.count, 0, sizeof(int), ctx->stream));
+#define GROW_CASE(DD) \
+  case DD:            \
+    SGP_TRY(grow_launches<DD>(ctx, kd, S, m, B, n, scale2, thr, gb)); \
     break;
   switch (kd.d) {
     GROW_CASE(1) GROW_CASE(2) GROW_CASE(3) GROW_CASE(4)
@@ -115,8 +196,6 @@ int launch_swarm_grow(sgp_ctx* ctx, const KernDesc& kd, const double* S, int64_t
   SGP_HIP(ctx, hipGetLastError());
   return 0;
 }
-
-int swarm_grow_chunks(int64_t m) { return int((m + kGrowChunk - 1) / kGrowChunk); }
 
 // ---- particle swarm on the device ---------------------------------------------------
 // SwarmOptimization.init_swarm / run_swarm (safeopt/swarm.py:61-146) with the
@@ -160,10 +239,10 @@ __device__ __forceinline__ double philox_uniform(uint64_t seed, uint32_t draw,
 // velocities = rand(P, d) * velocity_scale          (swarm.py:75-76)
 __global__ void k_pso_init_vel(int64_t P, int d, double* vel,
                                const double* vscale, const double* rand,
-                               uint64_t seed) {
+                               uint64_t seed, int64_t e0) {
   const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (e >= P * d) return;
-  const double r = rand ? rand[e] : philox_uniform(seed, 0u, uint64_t(e));
+  const double r = rand ? rand[e] : philox_uniform(seed, 0u, uint64_t(e0 + e));
   vel[e] = r * vscale[e % d];
 }
 
@@ -172,17 +251,17 @@ __global__ void k_pso_move(int64_t P, int d, double* pos, double* vel,
                            const double* best, const double* gbest,
                            const double* vscale, const double* bounds,
                            double inertia, const double* rand, uint64_t seed,
-                           uint32_t draw) {
+                           uint32_t draw, int64_t e0, int64_t e2) {
   const int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (e >= P * d) return;
   const int k = int(e % d);
   const double x = pos[e];
   const double to_global = gbest[k] - x;
   const double to_own = best[e] - x;
-  // r = rand(2 P, d); r1 = r[:P], r2 = r[P:]
-  const double r1 = rand ? rand[e] : philox_uniform(seed, draw, uint64_t(e));
+  // r = rand(2 P, d); r1 = r[:P], r2 = r[P:] (of the whole swarm: element e0 + e, e2 + e)
+  const double r1 = rand ? rand[e] : philox_uniform(seed, draw, uint64_t(e0 + e));
   const double r2 = rand ? rand[P * d + e]
-                         : philox_uniform(seed, draw, uint64_t(P * d + e));
+                         : philox_uniform(seed, draw, uint64_t(e2 + e));
   double v = vel[e] * inertia;
   v = v + (r1 * to_own + r2 * to_global) / vscale[k];
   const double vmax = 10.0 * vscale[k];
@@ -206,11 +285,13 @@ __global__ void k_pso_best(int64_t P, int d, const double* values,
   }
 }
 
-// global_best = best_positions[argmax(best_values)], first index on ties
+// global_best = best_positions[argmax(best_values)], first index on ties; rec: the
+// record of a rank's block instead (value | p0 + index | x[d])
 __global__ __launch_bounds__(1024) void k_pso_gbest(int64_t P, int d,
                                                     const double* best_values,
                                                     const double* best,
-                                                    double* gbest) {
+                                                    double* gbest, double* rec,
+                                                    int64_t p0) {
   __shared__ double sv[1024 / 64];
   __shared__ long long si[1024 / 64];
   double v = -INFINITY;
@@ -242,8 +323,28 @@ __global__ __launch_bounds__(1024) void k_pso_gbest(int64_t P, int d,
         v = sv[w];
         idx = si[w];
       }
-    for (int k = 0; k < d; ++k) gbest[k] = best[idx * d + k];
+    if (rec) {
+      rec[0] = v;
+      rec[1] = __longlong_as_double(p0 + idx);
+      for (int k = 0; k < d; ++k) rec[2 + k] = best[idx * d + k];
+    } else {
+      for (int k = 0; k < d; ++k) gbest[k] = best[idx * d + k];
+    }
   }
+}
+
+// the swarm's global best from the records of the ranks (rank order = order of the
+// blocks): the largest value, the lowest global index on ties -- the rule of k_pso_gbest
+__global__ void k_pso_gbest_merge(const double* recs, int world, int d, double* gbest) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int best = 0;
+  for (int r = 1; r < world; ++r) {
+    const double* a = recs + size_t(r) * (2 + d);
+    const double* b = recs + size_t(best) * (2 + d);
+    const long long ia = __double_as_longlong(a[1]), ib = __double_as_longlong(b[1]);
+    if (a[0] > b[0] || (a[0] == b[0] && ia < ib)) best = r;
+  }
+  for (int k = 0; k < d; ++k) gbest[k] = recs[size_t(best) * (2 + d) + 2 + k];
 }
 
 // Fitness of a few particles from resident mean / var ([G][P]): the path of
@@ -364,9 +465,10 @@ __global__ __launch_bounds__(1024) void k_pso_small_step(const GpDev* gps, int G
 }  // namespace
 
 int launch_pso_init_vel(sgp_ctx* ctx, int64_t P, int d, double* vel,
-                        const double* vscale, const double* rand, uint64_t seed) {
+                        const double* vscale, const double* rand, uint64_t seed,
+                        int64_t e0) {
   hipLaunchKernelGGL(k_pso_init_vel, dim3(unsigned((P * d + 255) / 256)),
-                     dim3(256), 0, ctx->stream, P, d, vel, vscale, rand, seed);
+                     dim3(256), 0, ctx->stream, P, d, vel, vscale, rand, seed, e0);
   SGP_HIP(ctx, hipGetLastError());
   return 0;
 }
@@ -374,21 +476,29 @@ int launch_pso_init_vel(sgp_ctx* ctx, int64_t P, int d, double* vel,
 int launch_pso_move(sgp_ctx* ctx, int64_t P, int d, double* pos, double* vel,
                     const double* best, const double* gbest, const double* vscale,
                     const double* bounds, double inertia, const double* rand,
-                    uint64_t seed, uint32_t draw) {
+                    uint64_t seed, uint32_t draw, int64_t e0, int64_t e2) {
   hipLaunchKernelGGL(k_pso_move, dim3(unsigned((P * d + 255) / 256)), dim3(256), 0,
                      ctx->stream, P, d, pos, vel, best, gbest, vscale, bounds,
-                     inertia, rand, seed, draw);
+                     inertia, rand, seed, draw, e0, e2 < 0 ? P * d : e2);
   SGP_HIP(ctx, hipGetLastError());
   return 0;
 }
 
 int launch_pso_best(sgp_ctx* ctx, int64_t P, int d, const double* values,
                     const uint8_t* safe, const double* pos, double* best,
-                    double* best_values, double* gbest, int init) {
+                    double* best_values, double* gbest, int init, double* rec,
+                    int64_t p0) {
   hipLaunchKernelGGL(k_pso_best, dim3(unsigned((P + 255) / 256)), dim3(256), 0,
                      ctx->stream, P, d, values, safe, pos, best, best_values, init);
   hipLaunchKernelGGL(k_pso_gbest, dim3(1), dim3(1024), 0, ctx->stream, P, d,
-                     best_values, best, gbest);
+                     best_values, best, gbest, rec, p0);
+  SGP_HIP(ctx, hipGetLastError());
+  return 0;
+}
+
+int launch_pso_gbest_merge(sgp_ctx* ctx, const double* recs, int world, int d, double* gbest) {
+  hipLaunchKernelGGL(k_pso_gbest_merge, dim3(1), dim3(64), 0, ctx->stream, recs, world, d,
+                     gbest);
   SGP_HIP(ctx, hipGetLastError());
   return 0;
 }

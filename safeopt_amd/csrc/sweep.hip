@@ -1881,12 +1881,15 @@ int launch_sweep_sep(sgp_ctx* ctx, const SweepParams& p, double flops) {
 }
 
 int launch_posterior(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d, int Geff,
-                     double flops, const SepLaunch* sep, bool rows_sharded);
+                     double flops, const SepLaunch* sep, bool rows_sharded, int64_t sel_rows);
 
 // rows_sharded: the rows are a rank's shard of a grid (sgp_grid_*) -- the kernel is then
-// chosen by the GPs alone, never by the number of rows (same kernel on every rank)
+// chosen by the GPs alone, never by the number of rows (same kernel on every rank).
+// sel_rows >= 0: the kernel is chosen as for that many rows (a rank's block of a sharded
+// swarm: the kernel of the whole swarm, sgp_swarm_run_shard)
 int launch_sweep(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d,
-                 const SepLaunch* sep = nullptr, bool rows_sharded = false) {
+                 const SepLaunch* sep = nullptr, bool rows_sharded = false,
+                 int64_t sel_rows = -1) {
   // algorithmic flops: G * (n^2 + 2n) per row
   double flops = 0.0;
   const int Geff =
@@ -1912,7 +1915,7 @@ int launch_sweep(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d,
     q.G = Geff;
     for (int i = 0; i < SGP_MAX_GPS; ++i) q.conf.fmin[i] = -INFINITY;
   }
-  int rc = launch_posterior(ctx, q, gh, d, Geff, flops, sep, rows_sharded);
+  int rc = launch_posterior(ctx, q, gh, d, Geff, flops, sep, rows_sharded, sel_rows);
   if (rc != 0 || !fitness) return rc;
   return launch_fitness_small(ctx, p.G, p.pts.N, q.conf.mean, q.conf.var, p.fit);
 }
@@ -1921,8 +1924,8 @@ int launch_sweep(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d,
 // kernel below, the resident-factor kernel (sweep_mid.hip) for 49 .. 128 observations of
 // single-part kernels, the VALU kernel (sweep_tiny.hip) up to 48 observations.
 int launch_posterior(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d, int Geff,
-                     double flops, const SepLaunch* sep, bool rows_sharded) {
-  if (tiny_sweep_wanted(ctx, gh, Geff, p.pts.N, rows_sharded)) {
+                     double flops, const SepLaunch* sep, bool rows_sharded, int64_t sel_rows) {
+  if (tiny_sweep_wanted(ctx, gh, Geff, sel_rows >= 0 ? sel_rows : p.pts.N, rows_sharded)) {
     ctx->last_sweep = 3;
     SweepArgs a{p.gps, p.G, p.mode, p.pts, p.conf, p.fit};
     return launch_sweep_tiny(ctx, a, gh, d, Geff, flops);    // (sets ctx->sweep_partials)
@@ -2013,7 +2016,7 @@ int launch_sweep_conf(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_host,
 
 int launch_sweep_fitness(sgp_ctx* ctx, const GpDev* gps_dev,
                          const GpDev* gps_host, int G, int d, SweepPoints pts,
-                         FitnessArgs fa) {
+                         FitnessArgs fa, int64_t sel_rows) {
   SweepParams p{};
   p.gps = gps_dev;
   p.G = G;
@@ -2021,7 +2024,7 @@ int launch_sweep_fitness(sgp_ctx* ctx, const GpDev* gps_dev,
   p.pts = pts;
   p.conf = ConfOut{};
   p.fit = fa;
-  return launch_sweep(ctx, p, gps_host, d);
+  return launch_sweep(ctx, p, gps_host, d, nullptr, false, sel_rows);
 }
 
 

@@ -1402,12 +1402,37 @@ class SafeOptSwarm(GaussianProcessOptimization):
     -- is one fused HIP kernel per swarm iteration; the swarm bookkeeping and
     its NumPy global RNG stay on the host so runs are reproducible against the
     reference.
+
+    ``comm`` (as for :class:`SafeOpt`; SPMD: same data, seeds and calls on every
+    rank): every swarm run is split over the ranks by particle
+    (``sgp_swarm_run_shard``), the global best merged on the device after every
+    iteration; growth of the safe set, its recheck and the point predictions stay
+    replicated, so every rank holds the same ``S`` and returns the same point as
+    one rank would.  ``pso='host'`` runs on one rank only.
     """
 
     def __init__(self, gp, fmin, bounds, beta=2, scaling='auto', threshold=0,
-                 swarm_size=20, pso='device'):
+                 swarm_size=20, pso='device', comm=None):
         if pso not in ('device', 'device-rng', 'host'):
             raise ValueError("pso must be 'device', 'device-rng' or 'host'")
+        self._comm = comm if comm is not None else LocalComm()
+        world = self._comm.world
+        if world > 1:
+            # checked on every rank before any collective
+            if pso == 'host':
+                raise ValueError("pso='host' runs on one rank; %d ranks need pso='device' "
+                                 "or 'device-rng'" % world)
+            if swarm_size < world:
+                raise ValueError("swarm_size %d for %d ranks" % (swarm_size, world))
+            ctx = getattr(self._comm, 'ctx', None)
+            if ctx is None:
+                raise ValueError("the communicator has no device context: the swarm's "
+                                 "global best is merged in its stream")
+            for g in (gp if isinstance(gp, list) else [gp]):
+                g_ctx = getattr(g, '_ctx', None)
+                if g_ctx is not None and g_ctx is not ctx:
+                    raise ValueError("the GPs live on HIP device %d but the communicator"
+                                     " context is device %d" % (g_ctx.device, ctx.device))
         GaussianProcessOptimization.__init__(self, gp, fmin=fmin, beta=beta, num_contexts=0,
                                              threshold=threshold, scaling=scaling)
         # the safe set starts as the observed inputs; one (min, max) pair may
@@ -1435,7 +1460,7 @@ class SafeOptSwarm(GaussianProcessOptimization):
                 swarm_type: DeviceSwarmOptimization(
                     swarm_size, self.optimal_velocities, self, swarm_type,
                     bounds=self.bounds,
-                    rng='numpy' if pso == 'device' else 'device')
+                    rng='numpy' if pso == 'device' else 'device', comm=self._comm)
                 for swarm_type in ['greedy', 'maximizers', 'expanders']}
 
     def optimize_particle_velocity(self):

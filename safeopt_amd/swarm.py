@@ -128,14 +128,25 @@ class DeviceSwarmOptimization(SwarmOptimization):
 
     ``owner`` is the :class:`SafeOptSwarm` whose GPs / beta / fmin / scaling /
     best lower bound define the fitness of ``swarm_type``.
+
+    ``comm`` with ``world > 1``: every rank runs its contiguous block of the
+    particles (``shard_range``, ``sgp_swarm_run_shard``) and the global best is
+    merged over the ranks on the device.  Every rank draws the initial particles
+    and NumPy's numbers as the one-rank run does and uses its own rows; Philox
+    draws the numbers of the block's global elements.  After a run
+    ``best_positions`` / ``best_values`` are gathered over the ranks (the whole
+    swarm on every rank); ``positions`` / ``velocities`` stay the rank's block.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
-                 rng='numpy', seed=None):
+                 rng='numpy', seed=None, comm=None):
         super(DeviceSwarmOptimization, self).__init__(
             swarm_size, velocity, None, bounds=bounds)
         if rng not in ('numpy', 'device'):
             raise ValueError("rng must be 'numpy' or 'device'")
+        from .dist import LocalComm, shard_range
+        self._comm = comm if comm is not None else LocalComm()
+        self._rows = shard_range(swarm_size, self._comm.rank, self._comm.world)
         self._owner = owner
         self._type = swarm_type
         self._rng = rng
@@ -157,26 +168,71 @@ class DeviceSwarmOptimization(SwarmOptimization):
         o = self._owner
         devs = [g._fitted() for g in o.gps]
         P, d = self.positions.shape
+        rand = None
+        self._calls += 1
+        if self._comm.world == 1:
+            if self._rng == 'numpy':
+                rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
+            _hip.swarm_run(
+                devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
+                o.best_lower_bound, self.positions, self.velocities,
+                self.best_positions, self.best_values, self.global_best,
+                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init,
+                iters, inertia0, step, rand,
+                seed=(self._seed << 20) + self._calls)
+            return
+        lo, hi = self._rows
+        P = self.swarm_size
         if self._rng == 'numpy':
             rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
-        else:
-            rand = None
-        self._calls += 1
+            # this rank's rows of every draw: init's (P, d), then per iteration the r1 and
+            # r2 rows of (2 P, d)
+            parts, at = [], 0
+            if init:
+                parts.append(rand[lo * d:hi * d])
+                at = P * d
+            for _ in range(iters):
+                it = rand[at:at + 2 * P * d]
+                parts += [it[lo * d:hi * d], it[(P + lo) * d:(P + hi) * d]]
+                at += 2 * P * d
+            rand = np.concatenate(parts) if parts else None
+        loc = self._local
         _hip.swarm_run(
             devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
             o.best_lower_bound, self.positions, self.velocities,
-            self.best_positions, self.best_values, self.global_best,
+            loc['best_positions'], loc['best_values'], self.global_best,
             np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init,
             iters, inertia0, step, rand,
-            seed=(self._seed << 20) + self._calls)
+            seed=(self._seed << 20) + self._calls, shard=(lo, self.swarm_size))
+        self.best_positions, self.best_values = self._gather(
+            loc['best_positions'], loc['best_values'])
+
+    def _gather(self, best_positions, best_values):
+        """The whole swarm's personal bests on every rank (blocks padded to one size)."""
+        from .dist import shard_range
+        world, P = self._comm.world, self.swarm_size
+        n = best_values.shape[0]
+        buf = np.zeros((-(-P // world), best_positions.shape[1] + 1))
+        buf[:n, :-1] = best_positions
+        buf[:n, -1] = best_values
+        allp = self._comm.allgather(buf)
+        sizes = [hi - lo for lo, hi in (shard_range(P, r, world) for r in range(world))]
+        full = np.concatenate([allp[r, :sizes[r]] for r in range(world)])
+        return np.ascontiguousarray(full[:, :-1]), np.ascontiguousarray(full[:, -1])
 
     def init_swarm(self, positions):
-        self.positions = np.ascontiguousarray(positions, dtype=float)
+        positions = np.ascontiguousarray(positions, dtype=float)
+        if self._comm.world > 1:
+            lo, hi = self._rows
+            positions = np.ascontiguousarray(positions[lo:hi])
+        self.positions = positions
         shape = self.positions.shape
         self.velocities = np.empty(shape)
         self.best_positions = np.empty(shape)
         self.best_values = np.empty(shape[0])
         self.global_best = np.empty(shape[1])
+        # the rank's block of the personal bests (the run's state between calls)
+        self._local = dict(best_positions=self.best_positions, best_values=self.best_values)
         self._device_run(True, 0, self.initial_inertia, 0.0)
 
     def run_swarm(self, max_iter):
