@@ -2,7 +2,16 @@
 """Benchmark of the GP-posterior + safe-set sweep (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last
+one if asked to and prints the headline line: nothing else.  ``--full`` adds
+everything else the benchmark measures or checks, after the timed region: the
+per-launch hipEvent pass and its roofline, the shared-factor pass, the extra
+keys (set-pass and rank-1 rooflines, a user's BO iteration, config 1, the
+reference's regime, the converged state, config 4 at this number of ranks,
+config 5's three-call step), the CPU baseline with its parity and whole-grid
+checks, and at N ranks the self-check of both variants of the N-rank step.
 
 A "step" is one ``SafeOpt.optimize()`` = ``update_confidence_intervals`` +
 ``compute_sets`` + ``get_new_query_point`` over the whole resident candidate
@@ -790,6 +799,159 @@ def dump_outputs(out_dir, per_row, whole):
             "files": {name + ".npy": [str(a.dtype)] + list(a.shape) for name, a in out.items()}}
 
 
+def full_passes(args, cfg, opt, step, step3, gpy, safeopt_amd, dist, ctx, comm, rank, world,
+                units, rows_rank, default_run):
+    """``--full``: what the benchmark measures besides its headline, after the timed region
+    and on every rank (the steps are collectives at N ranks) -- the per-launch hipEvent pass
+    and its roofline, the shared-factor pass, config 5's three-call step, the extra keys and
+    the per-rank figures.  Returns these keys of the line."""
+    G, d = cfg["G"], cfg["d"]
+    # ---- separate, untimed pass: a hipEvent pair around every sweep launch on
+    # the library's stream (roofline.achieved); rocprofv3 --kernel-trace of the
+    # same command must agree (profiles/)
+    ctx.profile_enable(True)
+    for _ in range(max(1, args.profile_steps)):
+        step()
+    ctx.sync()
+    prof_ms, launches, flops = ctx.profile_read()
+    ctx.profile_enable(False)
+    sweep_kernel = {"pair": "k_sweep_pair (posterior sweep, paired waves: n > 256)",
+                    "classic": "k_sweep (posterior sweep, 4 waves)",
+                    "mid": "k_sweep_mid (posterior sweep with the factor resident in LDS: 49 .. 128 "
+                           "observations; on tensor grids with factor tables up to 256, in passes "
+                           "of row blocks -- one timed launch = all passes of all GPs)",
+                    "tiny": "k_sweep_tiny (one thread per row, fp64 VALU: up to 48 observations)",
+                    }.get(ctx.last_sweep(), str(ctx.last_sweep()))
+
+    # ---- the product's default: consecutive GPs with identical (X, kernel, noise)
+    # share the variance contraction -- own timing, own flop count
+    shared = None
+    if cfg["G"] > 1 and not args.no_shared_pass:
+        ctx.set_share(True)
+        for _ in range(args.warmup):
+            step()
+        comm.barrier()
+        ctx.sync()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        ctx.sync()
+        comm.barrier()
+        dts = float(comm.allreduce_max(np.array([time.perf_counter() - t1]))[0])
+        ctx.profile_enable(True)
+        for _ in range(max(1, args.profile_steps)):
+            step()
+        ctx.sync()
+        s_ms, s_launches, _ = ctx.profile_read()
+        ctx.profile_enable(False)
+        ctx.set_share(False)
+        shared = (dts, s_ms, s_launches)
+
+    # ---- config 5: the step of three calls a swarm iteration makes (extra key)
+    three = None
+    if args.config == 5:
+        for _ in range(2):
+            step3()
+        ctx.sync(); t3 = time.perf_counter()
+        for _ in range(max(4, args.steps // 4)):
+            step3()
+        ctx.sync()
+        three = (time.perf_counter() - t3) / max(4, args.steps // 4)
+
+    # ---- extra keys
+    extras = {}
+    if not args.no_extras and args.config != 5 and args.side is None:
+        if world == 1:
+            try:
+                extras["sets_roofline"] = sets_roofline(opt, ctx, cfg, rows_rank)
+                extras["bo_iteration"] = bo_iteration(cfg, gpy, safeopt_amd, ctx)
+                # (also at the top level, next to sets_roofline)
+                if "rank1_roofline" in extras["bo_iteration"]:
+                    extras["rank1_roofline"] = extras["bo_iteration"]["rank1_roofline"]
+            except Exception as e:      # noqa -- an extra must never break the line
+                extras["extras_error"] = repr(e)
+        if default_run and world == 1:
+            try:
+                extras["reference_regime"] = reference_regime(gpy, safeopt_amd, ctx)
+            except Exception as e:      # noqa
+                extras["reference_regime"] = {"error": repr(e)}
+            try:
+                extras["config1"] = config1(gpy, safeopt_amd, ctx)
+            except Exception as e:      # noqa
+                extras["config1"] = {"error": repr(e)}
+            try:
+                extras["no_expander_state"] = no_expander_state(gpy, safeopt_amd, ctx)
+            except Exception as e:      # noqa
+                extras["no_expander_state"] = {"error": repr(e)}
+        if default_run:
+            try:
+                extras["config4_strong"] = config4_strong(gpy, safeopt_amd, dist, ctx, comm,
+                                                          rank, world)
+            except Exception as e:      # noqa
+                extras["config4_strong"] = {"error": repr(e)}
+
+    # ---- what the ranks did, for the N-rank line
+    per_rank_ms = comm.allgather(np.array([prof_ms / max(launches, 1)]))[:, 0]
+    t2 = time.perf_counter()
+    for _ in range(50):
+        comm.allreduce_max(np.zeros(2))
+    coll_us = (time.perf_counter() - t2) / 50 * 1e6
+    achieved = flops / (prof_ms * 1e-3) / 1e12 if prof_ms > 0 else 0.0
+    out = {
+        "per_rank_sweep_ms": [float(v) for v in per_rank_ms],
+        "scalar_allreduce_us": coll_us if world > 1 else None,
+        "roofline": {
+            "bound": "mfma",
+            "kernel": sweep_kernel,
+            "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS,
+            "unit": "TFLOP/s", "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
+            "traffic": None,
+            "kernel_ms_avg": prof_ms / max(launches, 1),
+            "launches": int(launches),
+            "algorithmic_flops_per_launch": flops / max(launches, 1),
+            "algorithmic_hbm_bytes_per_launch": (8 * d + 16 * G + 3) * rows_rank,
+            "algorithmic_hbm_frac": ((8 * d + 16 * G + 3) * rows_rank /
+                                     (prof_ms / max(launches, 1) * 1e-3) /
+                                     1e9 / HBM_PEAK_GBS) if prof_ms > 0 else 0.0,
+        },
+    }
+    # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc
+    # passes (FETCH_SIZE / WRITE_SIZE cannot be read from inside the process)
+    try:
+        with open(os.path.join(REPO, "profiles", "traffic.json")) as f:
+            tr = json.load(f).get("config%d" % args.config)
+        if tr and args.side is None and world == 1:
+            out["roofline"]["traffic"] = tr["hbm_bytes_per_launch"]
+            out["roofline"]["traffic_source"] = tr["note"]
+            if "mfma_pipe_busy" in tr:       # SQ_VALU_MFMA_BUSY_CYCLES, same PMC passes
+                out["roofline"]["mfma_pipe_busy"] = tr["mfma_pipe_busy"]
+                out["roofline"]["clock_ghz_under_profiler"] = tr["clock_ghz_under_profiler"]
+    except (OSError, ValueError):
+        pass
+    if shared:
+        dts, s_ms, s_launches = shared
+        sfl = (cfg["n"] ** 2 + 2.0 * G * cfg["n"]) * rows_rank
+        out["shared_factor"] = {
+            "note": "the product default (sgp_ctx_set_share): the GPs of this config have "
+                    "identical inputs, kernel and noise, so |L^-1 k|^2 is formed once and "
+                    "alpha . k per GP -- the followers ride in their leader's stages; same "
+                    "bits (tests/test_gpu_posterior.py)",
+            "value": units / (dts / args.steps), "unit": "candidates/s",
+            "ms_per_step": dts * 1e3 / args.steps,
+            "kernel_ms_avg": s_ms / max(s_launches, 1),
+            "algorithmic_flops_per_launch": sfl,
+            "achieved": sfl / (s_ms / max(s_launches, 1) * 1e-3) / 1e12 if s_ms > 0 else 0.0,
+        }
+        out["shared_factor"]["frac"] = out["shared_factor"]["achieved"] / FP64_MFMA_PEAK_TFLOPS
+    out.update(extras)
+    if three is not None:
+        out["three_call_step"] = {
+            "note": "greedy + maximizers + expanders: the three fitness calls of one swarm "
+                    "iteration of SafeOptSwarm.optimize (gp_opt.py:1136-1177)",
+            "ms": three * 1e3, "value": units / three, "unit": "particles/s"}
+    return out
+
+
 def spawn_ranks(n, argv):
     """``python bench.py --gpus N`` from a bare shell: start the N ranks (one
     process per GPU, torchrun-style environment) and pass rank 0's line on."""
@@ -823,24 +985,29 @@ def main():
                          "40 at configs 3 and 5, 500 at config 2, 6 at config 4)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=None, choices=[2, 3, 4, 5],
-                    help="BASELINE.json config (default: 3, the north-star config, plus "
-                         "the key config4_strong: the 8-GPU config at this number of ranks)")
-    ap.add_argument("--no-extras", action="store_true",
-                    help="skip bo_iteration / sets_roofline / config4_strong")
+                    help="BASELINE.json config (default: 3, the north-star config; with --full "
+                         "plus the key config4_strong: the 8-GPU config at this number of ranks)")
     ap.add_argument("--side", type=int, default=None,
                     help="grid points per dimension (default: the config's)")
-    ap.add_argument("--cpu-rows", type=int, default=None,
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything besides "
+                         "the headline (rooflines, shared factor, extra keys, CPU baseline, "
+                         "parity; N ranks: the self-check of the N-rank step)")
+    fo = ap.add_argument_group("with --full", "(no effect on a plain run)")
+    fo.add_argument("--no-extras", action="store_true",
+                    help="skip bo_iteration / sets_roofline / config4_strong")
+    fo.add_argument("--cpu-rows", type=int, default=None,
                     help="rows of the CPU-baseline sample (default: ~2.5 s per run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--check-chosen", dest="check_chosen", action="store_true", default=None,
+    fo.add_argument("--no-cpu-baseline", action="store_true")
+    fo.add_argument("--check-chosen", dest="check_chosen", action="store_true", default=None,
                     help="after the timed region, run the oracle ONCE on the whole grid and "
                          "report whether S / M / G and the chosen index are identical "
                          "(default: on at configs 2 and 3 -- 7 s / 28 s of host work)")
-    ap.add_argument("--no-check-chosen", dest="check_chosen", action="store_false")
-    ap.add_argument("--no-shared-pass", action="store_true",
+    fo.add_argument("--no-check-chosen", dest="check_chosen", action="store_false")
+    fo.add_argument("--no-shared-pass", action="store_true",
                     help="skip the second timing pass with the factor shared between identical "
                          "GPs (profiles: every k_sweep launch of the run is then the headline path)")
-    ap.add_argument("--profile-steps", type=int, default=10,
+    fo.add_argument("--profile-steps", type=int, default=10,
                     help="steps of the separate (untimed) per-launch hipEvent pass")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last step as DIR/<name>.npy "
@@ -907,6 +1074,7 @@ def main():
     ctx.set_share(False)
 
     last = {}
+    step3 = None
     if args.config == 5:
         parts = cfg["particles"]
         opt = safeopt_amd.SafeOptSwarm(gps, cfg["fmin"], bounds=[(-5., 5.)] * cfg["d"],
@@ -944,7 +1112,7 @@ def main():
                      units, rows_rank))
 
     selfcheck = None
-    if world > 1 and args.config != 5:
+    if args.full and world > 1 and args.config != 5:
         try:
             selfcheck = nrank_selfcheck(opt, comm)
         except Exception as e:      # noqa -- reported, never fatal
@@ -985,102 +1153,16 @@ def main():
             dumped = dump_outputs(args.dump_outputs, per_row, whole)
         del per_row, whole
 
-    # ---- separate, untimed pass: a hipEvent pair around every sweep launch on
-    # the library's stream (roofline.achieved); rocprofv3 --kernel-trace of the
-    # same command must agree (profiles/)
-    ctx.profile_enable(True)
-    for _ in range(max(1, args.profile_steps)):
-        step()
-    ctx.sync()
-    prof_ms, launches, flops = ctx.profile_read()
-    ctx.profile_enable(False)
-    sweep_kernel = {"pair": "k_sweep_pair (posterior sweep, paired waves: n > 256)",
-                    "classic": "k_sweep (posterior sweep, 4 waves)",
-                    "mid": "k_sweep_mid (posterior sweep with the factor resident in LDS: 49 .. 128 "
-                           "observations; on tensor grids with factor tables up to 256, in passes "
-                           "of row blocks -- one timed launch = all passes of all GPs)",
-                    "tiny": "k_sweep_tiny (one thread per row, fp64 VALU: up to 48 observations)",
-                    }.get(ctx.last_sweep(), str(ctx.last_sweep()))
-
-    # ---- the product's default: consecutive GPs with identical (X, kernel, noise)
-    # share the variance contraction -- own timing, own flop count
-    shared = None
-    if cfg["G"] > 1 and not args.no_shared_pass:
-        ctx.set_share(True)
-        for _ in range(args.warmup):
-            step()
-        comm.barrier()
-        ctx.sync()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        ctx.sync()
-        comm.barrier()
-        dts = float(comm.allreduce_max(np.array([time.perf_counter() - t1]))[0])
-        ctx.profile_enable(True)
-        for _ in range(max(1, args.profile_steps)):
-            step()
-        ctx.sync()
-        s_ms, s_launches, _ = ctx.profile_read()
-        ctx.profile_enable(False)
-        ctx.set_share(False)
-        shared = (dts, s_ms, s_launches)
-
-    # ---- config 5: the step of three calls a swarm iteration makes (extra key)
-    three = None
-    if args.config == 5:
-        for _ in range(2):
-            step3()
-        ctx.sync(); t3 = time.perf_counter()
-        for _ in range(max(4, args.steps // 4)):
-            step3()
-        ctx.sync()
-        three = (time.perf_counter() - t3) / max(4, args.steps // 4)
-
-    # ---- extra keys (never inside the timed region above)
-    extras = {}
-    if not args.no_extras and args.config != 5 and args.side is None:
-        if world == 1:
-            try:
-                extras["sets_roofline"] = sets_roofline(opt, ctx, cfg, rows_rank)
-                extras["bo_iteration"] = bo_iteration(cfg, gpy, safeopt_amd, ctx)
-                # (also at the top level, next to sets_roofline)
-                if "rank1_roofline" in extras["bo_iteration"]:
-                    extras["rank1_roofline"] = extras["bo_iteration"]["rank1_roofline"]
-            except Exception as e:      # noqa -- an extra must never break the line
-                extras["extras_error"] = repr(e)
-        if default_run and world == 1:
-            try:
-                extras["reference_regime"] = reference_regime(gpy, safeopt_amd, ctx)
-            except Exception as e:      # noqa
-                extras["reference_regime"] = {"error": repr(e)}
-            try:
-                extras["config1"] = config1(gpy, safeopt_amd, ctx)
-            except Exception as e:      # noqa
-                extras["config1"] = {"error": repr(e)}
-            try:
-                extras["no_expander_state"] = no_expander_state(gpy, safeopt_amd, ctx)
-            except Exception as e:      # noqa
-                extras["no_expander_state"] = {"error": repr(e)}
-        if default_run:
-            try:
-                extras["config4_strong"] = config4_strong(gpy, safeopt_amd, dist, ctx, comm,
-                                                          rank, world)
-            except Exception as e:      # noqa
-                extras["config4_strong"] = {"error": repr(e)}
-
-    # ---- what the ranks did, for the N-rank line
-    per_rank_ms = comm.allgather(np.array([prof_ms / max(launches, 1)]))[:, 0]
-    t2 = time.perf_counter()
-    for _ in range(50):
-        comm.allreduce_max(np.zeros(2))
-    coll_us = (time.perf_counter() - t2) / 50 * 1e6
+    # ---- --full: everything besides the headline, after the timed region
+    full = None
+    if args.full:
+        full = full_passes(args, cfg, opt, step, step3, gpy, safeopt_amd, dist, ctx, comm,
+                           rank, world, units, rows_rank, default_run)
     rccl_ranks = ctx.comm_count() if world > 1 or os.environ.get("SAFEOPT_FORCE_RCCL") == "1" else 1
 
     if rank != 0:
         return
     ms_per_step = dt * 1e3 / args.steps
-    achieved = flops / (prof_ms * 1e-3) / 1e12 if prof_ms > 0 else 0.0
     G, d = cfg["G"], cfg["d"]
     res = {
         "metric": "candidate-points/s (posterior+safe-set sweep)",
@@ -1101,72 +1183,25 @@ def main():
         # at a glance (N > 1): anything but "rccl-in-stream" here means the RCCL path FAILED
         # its probe and the number below was measured over a fallback transport
         "transport_chosen": None if transport is None else transport["chosen"],
-        "transport": transport, "nrank_selfcheck": selfcheck,
+        "transport": transport,
         "nrank_step": (None if world == 1 else
                        "in stream (sgp_grid_sets_fused_comm: one round trip, merges on the device)"
                        if getattr(comm, "in_stream", False) else
                        "host side (sets_front / sets_back: three round trips)"),
-        "per_rank_sweep_ms": [float(v) for v in per_rank_ms],
-        "scalar_allreduce_us": coll_us if world > 1 else None,
-        "roofline": {
-            "bound": "mfma",
-            "kernel": sweep_kernel,
-            "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS,
-            "unit": "TFLOP/s", "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
-            "traffic": None,
-            "kernel_ms_avg": prof_ms / max(launches, 1),
-            "launches": int(launches),
-            "algorithmic_flops_per_launch": flops / max(launches, 1),
-            "algorithmic_hbm_bytes_per_launch": (8 * d + 16 * G + 3) * rows_rank,
-            "algorithmic_hbm_frac": ((8 * d + 16 * G + 3) * rows_rank /
-                                     (prof_ms / max(launches, 1) * 1e-3) /
-                                     1e9 / HBM_PEAK_GBS) if prof_ms > 0 else 0.0,
-        },
         "hip_event_ms_per_step": ev_ms / args.steps,
         "timed_region_s": dt,
     }
     if dumped:
         res["dumped_outputs"] = dumped
-    # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc
-    # passes (FETCH_SIZE / WRITE_SIZE cannot be read from inside the process)
-    try:
-        with open(os.path.join(REPO, "profiles", "traffic.json")) as f:
-            tr = json.load(f).get("config%d" % args.config)
-        if tr and args.side is None and world == 1:
-            res["roofline"]["traffic"] = tr["hbm_bytes_per_launch"]
-            res["roofline"]["traffic_source"] = tr["note"]
-            if "mfma_pipe_busy" in tr:       # SQ_VALU_MFMA_BUSY_CYCLES, same PMC passes
-                res["roofline"]["mfma_pipe_busy"] = tr["mfma_pipe_busy"]
-                res["roofline"]["clock_ghz_under_profiler"] = tr["clock_ghz_under_profiler"]
-    except (OSError, ValueError):
-        pass
-    if shared:
-        dts, s_ms, s_launches = shared
-        sfl = (cfg["n"] ** 2 + 2.0 * G * cfg["n"]) * rows_rank
-        res["shared_factor"] = {
-            "note": "the product default (sgp_ctx_set_share): the GPs of this config have "
-                    "identical inputs, kernel and noise, so |L^-1 k|^2 is formed once and "
-                    "alpha . k per GP -- the followers ride in their leader's stages; same "
-                    "bits (tests/test_gpu_posterior.py)",
-            "value": units / (dts / args.steps), "unit": "candidates/s",
-            "ms_per_step": dts * 1e3 / args.steps,
-            "kernel_ms_avg": s_ms / max(s_launches, 1),
-            "algorithmic_flops_per_launch": sfl,
-            "achieved": sfl / (s_ms / max(s_launches, 1) * 1e-3) / 1e12 if s_ms > 0 else 0.0,
-        }
-        res["shared_factor"]["frac"] = res["shared_factor"]["achieved"] / FP64_MFMA_PEAK_TFLOPS
-    res.update(extras)
-    if three is not None:
-        res["three_call_step"] = {
-            "note": "greedy + maximizers + expanders: the three fitness calls of one swarm "
-                    "iteration of SafeOptSwarm.optimize (gp_opt.py:1136-1177)",
-            "ms": three * 1e3, "value": units / three, "unit": "particles/s"}
+    if args.full:
+        res["nrank_selfcheck"] = selfcheck
+        res.update(full)
     if args.config != 5:
         x = np.atleast_1d(last["x"])
         res["chosen_x"] = [float(v) for v in x]
         hit = np.flatnonzero(np.all(cfg["grid"] == x, axis=1))
         res["chosen_index"] = int(hit[0]) if hit.size else None
-    if world == 1 and not args.no_cpu_baseline and args.config != 5:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.config != 5:
         rows = None if args.cpu_rows is None else min(args.cpu_rows, units)
         base, parity = cpu_baseline(cfg, rows, dev_Q=opt.Q)
         res["cpu_baseline"] = base

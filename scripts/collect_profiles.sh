@@ -17,22 +17,22 @@ OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd $R
 if [ -z "$ONLY_PMC" ]; then
-  # the driver's command (config 3 + bo_iteration / sets_roofline / rank1_roofline /
-  # config4_strong / shared_factor keys), then every config on its own
-  python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  # the full line of the default config (config 3 + bo_iteration / sets_roofline /
+  # rank1_roofline / config4_strong / shared_factor keys), then every config on its own
+  python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   for c in $CFGS; do
     extra=""; [ $c = 4 ] && extra="--warmup 2 --profile-steps 3"
-    python bench.py --config $c $extra > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err
+    python bench.py --full --config $c $extra > $OUT/bench_cfg$c.json 2> $OUT/bench_cfg$c.err
   done
 fi
 cd /tmp && export TMPDIR=/tmp
-SHORT="--steps 3 --warmup 1 --profile-steps 1 --no-extras --no-cpu-baseline --no-check-chosen --no-shared-pass"
+SHORT="--full --steps 3 --warmup 1 --profile-steps 1 --no-extras --no-cpu-baseline --no-check-chosen --no-shared-pass"
 # (kernel stats: enough steps that the launches of the clock ramp -- the first ~30 ms of
 # load run ~10 % slower, profiles/r04/clock_ramp.txt -- are a small part of the average)
 declare -A STEPS=([2]="--steps 300 --warmup 20 --profile-steps 100" [3]="--steps 40 --warmup 5 --profile-steps 20" [4]="--steps 5 --warmup 2 --profile-steps 3" [5]="--steps 30 --warmup 5 --profile-steps 20")
 for c in $CFGS; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_cfg$c -- \
-    python $R/bench.py --config $c ${STEPS[$c]} --no-extras --no-cpu-baseline --no-check-chosen --no-shared-pass > $OUT/stats_cfg$c.log 2>&1
+    python $R/bench.py --full --config $c ${STEPS[$c]} --no-extras --no-cpu-baseline --no-check-chosen --no-shared-pass > $OUT/stats_cfg$c.log 2>&1
   rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES \
     --output-format csv -d $OUT/pmc_mfma_cfg$c -- python $R/bench.py --config $c $SHORT > $OUT/pmc_mfma_cfg$c.log 2>&1
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_cfg$c -- \

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../../.."
 CFG=${1:-3}
 cp safeopt_amd/libsafeopt_hip.so /tmp/cur.so
-one() { python bench.py --config $1 --no-cpu-baseline | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('cfg', $1, j['ms_per_step'], j['roofline']['kernel_ms_avg'], j['roofline']['frac'])"; }
+one() { python bench.py --full --config $1 --no-cpu-baseline | python -c "import json,sys; j=json.loads(sys.stdin.read()); print('cfg', $1, j['ms_per_step'], j['roofline']['kernel_ms_avg'], j['roofline']['frac'])"; }
 for rep in 1 2; do
   for so in scripts/dev/ab/*.so /tmp/cur.so; do
     cp $so safeopt_amd/libsafeopt_hip.so

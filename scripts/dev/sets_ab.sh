@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2; do
 for v in 0 1; do
   if [ $v = 1 ]; then export SGP_SETS_COPY=1; else unset SGP_SETS_COPY; fi
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-check-chosen --no-shared-pass 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('copy=$v', d['ms_per_step'], d['sets_roofline']['ms'], d.get('bo_iteration',{}).get('optimize_ms'))"
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-check-chosen --no-shared-pass 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('copy=$v', d['ms_per_step'], d['sets_roofline']['ms'], d.get('bo_iteration',{}).get('optimize_ms'))"
 done; done
 unset SGP_SETS_COPY
 cd /tmp && export TMPDIR=/tmp

@@ -85,3 +85,25 @@ def test_bench_dumps_the_same_outputs_twice(hip_device, tmp_path):
     assert np.array_equal(S, (Q[:, 0] > 0.0).astype(np.float32))
     for f in os.listdir(d):
         assert np.array_equal(np.load(os.path.join(d, f)), np.load(os.path.join(d2, f))), f
+
+
+def test_bench_offers_full():
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"],
+                         capture_output=True, text=True, timeout=120, cwd=REPO)
+    assert out.returncode == 0 and "--full" in out.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only(hip_device):
+    """Without --full the run stops at the headline: no per-launch pass, no shared-factor
+    pass, no CPU baseline or oracle check behind the timed steps."""
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", "2",
+                          "--side", "200", "--steps", "3", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = json.loads(out.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in res, key
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["value"] > 0
+    for key in ("roofline", "shared_factor", "per_rank_sweep_ms", "cpu_baseline", "parity"):
+        assert key not in res, key

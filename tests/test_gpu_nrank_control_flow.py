@@ -222,7 +222,8 @@ def test_torchrun_launch_with_rccl(mods, tmp_path):
     env = dict(os.environ, SAFEOPT_FORCE_RCCL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(repo, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--side", "200", "--no-cpu-baseline"]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--side", "200", "--full",
+           "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
