@@ -22,7 +22,7 @@ import time
 
 import numpy as np
 
-__all__ = ["shard_range", "LocalComm", "RcclComm", "SocketComm", "init_from_env",
+__all__ = ["shard_range", "allgather_rows", "LocalComm", "RcclComm", "SocketComm", "init_from_env",
            "merge_topk", "merge_argmax", "launch_check"]
 
 
@@ -36,6 +36,24 @@ def shard_range(N, rank, world):
     lo = rank * base + min(rank, rem)
     hi = lo + base + (1 if rank < rem else 0)
     return lo, hi
+
+
+def allgather_rows(comm, part, counts=None, count_dtype=np.int64):
+    """Every rank's block of rows, concatenated in rank order (a ragged all-gather: the
+    blocks are padded to one size).  ``counts``: the blocks' sizes when every rank knows
+    them (the ``shard_range`` blocks); otherwise they are all-gathered first, as
+    ``count_dtype``.  No rank with a row: nothing more is gathered."""
+    part = np.asarray(part)
+    if counts is None:
+        counts = comm.allgather(np.array([part.shape[0]], dtype=count_dtype))[:, 0]
+    counts = [int(c) for c in counts]
+    pad = max(counts)
+    if pad == 0:
+        return part[:0]
+    buf = np.zeros((pad,) + part.shape[1:], dtype=part.dtype)
+    buf[:part.shape[0]] = part
+    allp = comm.allgather(buf)
+    return np.concatenate([allp[r][:c] for r, c in enumerate(counts)])
 
 
 class LocalComm(object):

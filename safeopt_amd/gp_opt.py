@@ -31,7 +31,7 @@ import weakref
 import numpy as np
 
 from . import _hip
-from .dist import LocalComm, merge_argmax, merge_topk, shard_range
+from .dist import LocalComm, allgather_rows, merge_argmax, merge_topk, shard_range
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
 
 __all__ = ['SafeOpt', 'SafeOptSwarm']
@@ -207,6 +207,11 @@ class _WriteBackView(np.ndarray):
 #: came with it (``fused``), and the number of candidates tied with it (None: unknown)
 _Front = collections.namedtuple(
     '_Front', 'n_cand n_unsafe w_c idx_c x_c mu_c q_c fused n_tied')
+
+#: what one big pass of the expander loop found (``SafeOpt._pass_*``): candidates tested
+#: (0: none left), the key and global row of the first expander in visiting order (row -1:
+#: none), the cut in front of the next pass (-inf: none), the step's arg-max (-1: unknown)
+_Pass = collections.namedtuple('_Pass', 'tested key row left amax')
 
 
 class _HipGridBackend(object):
@@ -523,21 +528,12 @@ class SafeOpt(GaussianProcessOptimization):
         if self._stale[name]:
             arr = getattr(self, '_' + name)
             part = self._backend.download(what)
-            if self._comm.world == 1:
-                np.copyto(arr, part)
-            else:
-                lo, hi = self._shard
-                counts = [np.subtract(*shard_range(arr.shape[0], r,
-                                                   self._comm.world)[::-1])
-                          for r in range(self._comm.world)]
-                pad = max(counts)
-                buf = np.zeros((pad,) + arr.shape[1:], dtype=arr.dtype)
-                buf[:hi - lo] = part
-                allp = self._comm.allgather(buf)
-                off = 0
-                for r, c in enumerate(counts):
-                    arr[off:off + c] = allp[r][:c]
-                    off += c
+            world = self._comm.world
+            if world > 1:
+                part = allgather_rows(self._comm, np.asarray(part, dtype=arr.dtype), [
+                    hi - lo for lo, hi in (shard_range(arr.shape[0], r, world)
+                                           for r in range(world))])
+            np.copyto(arr, part)
             self._stale[name] = False
         # (the properties hand out write-back views of this array)
         return getattr(self, '_' + name)
@@ -849,39 +845,24 @@ class SafeOpt(GaussianProcessOptimization):
         else:
             flags, val, idx = be.sets_back(beta, self.fmin, x_c, mu_c, q_c[1::2], 0.5,
                                            idx_c, self.scaling, world == 1)
-        merged = fused is not None       # (flags and arg-max already global)
-        if world > 1 and not merged:
+        # N ranks without the fused step: flags and arg-max are merged here, and a certified
+        # candidate is marked here (otherwise the device has marked it)
+        host = world > 1 and fused is None
+        if host:
             pk = self._comm.allgather(np.concatenate(
                 [flags.astype(np.float64), [val, float(idx)]]))
             flags = pk[:, :G].max(axis=0)
         if np.all(flags[active] != 0):
-            if world > 1 and not merged:
-                if be.owns(idx_c):
-                    be.mark_expanders(np.array([idx_c], dtype=np.int64))
+            if host:
                 # arg-max over M on every rank + the certified expander
                 v_c = np.max((q_c[1::2] - q_c[::2]) / self.scaling)
                 val, idx = merge_argmax(
                     np.append(pk[:, G], v_c),
                     np.append(pk[:, G + 1].astype(np.int64), idx_c))
             self._argmax_cache = (val, int(idx))
-            if self._settle_ties(beta, active, w_c, idx_c, n_tied) != idx_c:
-                self._argmax_cache = None
+            self._first_expander(beta, active, w_c, idx_c, n_tied, mark=host)
             return
-        # not certified by the probe.  One rank with big passes: the exact test of this candidate
-        # rides in the first pass (the cut in FRONT of it) -- a candidate that lifts no row close
-        # to it rarely lifts a far one, and a pass costs little more than its scan
-        if (not exact and world == 1 and self.big_passes and not self.use_lipschitz
-                and hasattr(be, 'expander_pass') and np.isfinite(w_c)):
-            return self._visit_in_big_passes(beta, active, False, w_c, idx_c + 1)
-        # ... otherwise: exact scan, then the general loop
-        hit = [False] if exact else self._expander_flags(
-            beta, x_c[None, :], mu_c[None, :], q_c[None, 1::2], active, probe=False)
-        if hit[0]:
-            if be.owns(idx_c):
-                be.mark_expanders(np.array([idx_c], dtype=np.int64))
-            self._settle_ties(beta, active, w_c, idx_c, n_tied)
-            return
-        self._visit_candidates(beta, active, False, w_c, idx_c)
+        self._visit_candidates(beta, active, False, w_c, idx_c, None if exact else front)
 
     def _general_sets(self, beta, active, thr_beta, full_sets):
         """Step by step (``full_sets``, Lipschitz certificates, backends without the fused
@@ -901,118 +882,120 @@ class SafeOpt(GaussianProcessOptimization):
         self._visit_candidates(beta, active, full_sets, np.inf,
                                -1 if full_sets else _I64_MAX)
 
-    def _visit_candidates(self, beta, active, full_sets, cut_w, cut_idx):
-        """Expander loop of gp_opt.py:557-612 from the cut onwards."""
-        be = self._backend
-        G = len(self.gps)
-        mode = 1 if full_sets else 0
-        # The first expander in visiting order is very often the very first
-        # candidate, so the first pass fetches and tests only that one; later
-        # passes take SGP_TOPK candidates at a time.
-        K = _hip.TOPK if (full_sets or cut_idx != _I64_MAX) else 1
-        if (self._comm.world == 1 and not self.use_lipschitz and self.small_step
-                and hasattr(be, 'expanders_small') and be.small_grid()):
+    def _visit_candidates(self, beta, active, full_sets, cut_w, cut_idx, first=None):
+        """Expander loop of gp_opt.py:557-612 from the cut onwards; the one place that picks
+        the loop.  ``first``: the candidate at the cut, which the probe did not certify and the
+        exact scan has not tested.  The first matching rule decides:
+
+        =  ==================================  ============================================
+        1  ``first``, one rank, big passes,    big passes from ``(w_c, idx_c + 1)``: its
+           finite width                        exact test rides in the first one
+        2  ``first``                           its exact test; a hit ends the loop
+        3  one rank, GP, ``small_step``,       ``_visit_all_candidates``
+           ``small_grid()``
+        4  big passes, ``full_sets`` or (one   big passes from the cut (``full_sets``:
+           rank, finite cut)                   over every safe row)
+        5  otherwise                           ``_visit_in_batches``, handing over to big
+                                               passes after a batch of SGP_TOPK (one rank,
+                                               Lipschitz: any batch) without an expander
+        =  ==================================  ============================================
+
+        Big passes: ``big_passes`` and ``expander_pass`` / ``lipschitz_pass`` on one rank,
+        ``pass_test`` / ``pass_lipschitz_test`` on N ranks.  Batches: ``expander_batch`` on one
+        rank with GP certificates, ``topk`` otherwise."""
+        be, one, gp = self._backend, self._comm.world == 1, not self.use_lipschitz
+        need = (('expander_pass' if gp else 'lipschitz_pass') if one
+                else ('pass_test' if gp else 'pass_lipschitz_test'))
+        big = ((self._pass_one_rank if one else self._pass_n_ranks)
+               if self.big_passes and hasattr(be, need) else None)
+        if first is not None:
+            if one and big is not None and np.isfinite(cut_w):
+                # a candidate that lifts no row close to it rarely lifts a far one, and a pass
+                # costs little more than its scan
+                return self._visit_in_big_passes(beta, active, False, cut_w, cut_idx + 1, big)
+            if self._expander_flags(beta, first.x_c[None, :], first.mu_c[None, :],
+                                    first.q_c[None, 1::2], active, probe=False)[0]:
+                return self._first_expander(beta, active, cut_w, cut_idx, first.n_tied)
+        if (one and gp and self.small_step and hasattr(be, 'expanders_small')
+                and be.small_grid()):
             return self._visit_all_candidates(beta, active, full_sets, cut_idx)
-        if (self._comm.world == 1 and not self.use_lipschitz
-                and hasattr(be, 'expander_batch')):
-            # one rank: a pass of the loop -- the next K candidates, their rows, the exact
-            # test -- is ONE device round trip
-            big = hasattr(be, 'expander_pass') and self.big_passes
-            if big and full_sets:
-                return self._visit_in_big_passes(beta, active, True, np.inf, -1)
-            if big and np.isfinite(cut_w):
-                # behind a first candidate that is no expander: a pass of 256 candidates costs
-                # less than the 16 of sgp_grid_expander_batch (whose scan knows neither the
-                # block test nor the posterior Cauchy-Schwarz bound)
-                return self._visit_in_big_passes(beta, active, False, cut_w, cut_idx)
-            while True:
-                w_b, i_b, fl = be.expander_batch(beta, self.fmin, mode, cut_w, cut_idx, K)
-                m = i_b.size
-                if m == 0:
-                    break
-                is_exp = np.all(fl[:, active] != 0, axis=1)
-                if full_sets:
-                    be.mark_expanders(i_b[is_exp])
-                elif is_exp.any():
-                    first = int(np.argmax(is_exp))
-                    be.mark_expanders(i_b[first:first + 1])
-                    self._settle_ties(beta, active, float(w_b[first]), int(i_b[first]))
-                    break
-                if m < K:
-                    break
-                cut_w, cut_idx = float(w_b[-1]), int(i_b[-1])
-                if big and K == _hip.TOPK:
-                    # SGP_TOPK candidates in, no expander: from here on hundreds, then
-                    # thousands of candidates per pass
-                    return self._visit_in_big_passes(beta, active, False, cut_w, cut_idx)
-                K = _hip.TOPK
-            return
-        big_n = (self._comm.world > 1 and self.big_passes and
-                 hasattr(be, 'pass_lipschitz_test' if self.use_lipschitz else 'pass_test'))
-        if big_n and full_sets:
-            return self._visit_in_big_passes_nrank(beta, active, True, np.inf, -1)
-        # Lipschitz certificates, one rank: the same big passes (sgp_grid_lipschitz_pass)
-        big_l = (self._comm.world == 1 and self.use_lipschitz and self.big_passes
-                 and hasattr(be, 'lipschitz_pass'))
-        if big_l and full_sets:
-            return self._visit_in_big_passes(beta, active, True, np.inf, -1)
-        if big_l and np.isfinite(cut_w):
-            return self._visit_in_big_passes(beta, active, False, cut_w, cut_idx)
+        if big is not None and (full_sets or one and np.isfinite(cut_w)):
+            # (behind a first candidate that is no expander: a pass of 256 candidates costs less
+            # than the 16 of sgp_grid_expander_batch, whose scan knows neither the block test
+            # nor the posterior Cauchy-Schwarz bound)
+            return self._visit_in_big_passes(beta, active, full_sets, cut_w, cut_idx, big)
+        batch = (self._batch_one_rank if one and gp and hasattr(be, 'expander_batch')
+                 else self._batch_topk)
+        return self._visit_in_batches(beta, active, full_sets, cut_w, cut_idx, batch, big,
+                                      1 if one and not gp else _hip.TOPK)
+
+    def _first_expander(self, beta, active, w, row, n_tied=None, mark=True):
+        """First expander ``row`` of width ``w`` found: its owner marks it (``mark``; False:
+        the device has), exact ties are settled.  Returns the row that ends up in ``G``."""
+        if mark and self._backend.owns(row):
+            self._backend.mark_expanders(np.array([row], dtype=np.int64))
+        return self._settle_ties(beta, active, w, row, n_tied)
+
+    def _visit_in_batches(self, beta, active, full_sets, cut_w, cut_idx, batch, big, big_after):
+        """The loop K candidates in visiting order at a time (``batch``); the first hit ends it
+        (``full_sets``: every hit is marked).  The first expander is very often the very first
+        candidate: without a cut the first batch is that one alone, later ones SGP_TOPK.  A full
+        batch of at least ``big_after`` candidates without a hit hands over to ``big``."""
+        mode = 1 if full_sets else 0
+        K = _hip.TOPK if (full_sets or cut_idx != _I64_MAX) else 1
         while True:
-            w_loc, i_loc = be.topk(mode, cut_w, cut_idx, K)
-            if self._comm.world > 1:
-                wp = np.full(K, -np.inf)
-                ip = np.full(K, -1, dtype=np.int64)
-                wp[:w_loc.size] = w_loc
-                ip[:i_loc.size] = i_loc
-                w_b, i_b = merge_topk(self._comm.allgather(wp),
-                                      self._comm.allgather(ip), K,
-                                      by_index=full_sets)
-            else:
-                w_b, i_b = w_loc, i_loc
-            m = i_b.size
-            if m == 0:
-                break
-
-            # rows of the candidates from their owners
-            own = np.array([be.owns(int(i)) for i in i_b])
-            xc = np.zeros((m, self.inputs.shape[1]))
-            mu_c = np.zeros((m, G))
-            u_c = np.zeros((m, G))
-            if own.any():
-                x_o, mean_o, _var_o, Q_o = be.gather_rows(i_b[own])
-                xc[own], mu_c[own], u_c[own] = x_o, mean_o, Q_o[:, 1::2]
-            if self._comm.world > 1:
-                packed = np.concatenate([xc, mu_c, u_c], axis=1)
-                packed = self._comm.allgather(packed).sum(axis=0)
-                d = self.inputs.shape[1]
-                xc, mu_c, u_c = (packed[:, :d], packed[:, d:d + G],
-                                 packed[:, d + G:])
-
-            is_exp = self._expander_flags(beta, xc, mu_c, u_c, active,
-                                          probe=not full_sets)
-
+            w_b, i_b, is_exp, own = batch(beta, active, mode, cut_w, cut_idx, K)
+            if i_b.size == 0:
+                return
             if full_sets:
-                mine = [int(i) for i, e, o in zip(i_b, is_exp, own) if e and o]
-                be.mark_expanders(np.asarray(mine, dtype=np.int64))
+                self._backend.mark_expanders(i_b[is_exp & own])
             elif is_exp.any():
                 first = int(np.argmax(is_exp))
-                if own[first]:
-                    be.mark_expanders(i_b[first:first + 1])
-                self._settle_ties(beta, active, float(w_b[first]), int(i_b[first]))
-                break
-            if m < K:
-                break
+                return self._first_expander(beta, active, float(w_b[first]), int(i_b[first]))
+            if i_b.size < K:
+                return
             cut_w, cut_idx = float(w_b[-1]), int(i_b[-1])
-            if big_n and K == _hip.TOPK:
-                return self._visit_in_big_passes_nrank(beta, active, False, cut_w, cut_idx)
-            if big_l:
-                # behind a first candidate that is no expander
-                return self._visit_in_big_passes(beta, active, False, cut_w, cut_idx)
+            if big is not None and K >= big_after:
+                return self._visit_in_big_passes(beta, active, False, cut_w, cut_idx, big)
             K = _hip.TOPK
 
-    #: candidates per pass of ``_visit_in_big_passes`` (the last entry repeats); None: by the
-    #: number of observations (``_pass_size``)
+    def _batch_one_rank(self, beta, active, mode, cut_w, cut_idx, K):
+        """Widths, rows, expander flags and ownership of the next K candidates: one rank, GP
+        certificates, ONE device round trip (``sgp_grid_expander_batch``)."""
+        w_b, i_b, fl = self._backend.expander_batch(beta, self.fmin, mode, cut_w, cut_idx, K)
+        return w_b, i_b, np.all(fl[:, active] != 0, axis=1), True
+
+    def _batch_topk(self, beta, active, mode, cut_w, cut_idx, K):
+        """``_batch_one_rank`` step by step: every rank's next K candidates, merged; their rows
+        from their owners; the test (the probe first, unless ``full_sets``)."""
+        w_b, i_b = self._backend.topk(mode, cut_w, cut_idx, K)
+        if self._comm.world > 1:
+            wp = np.full(K, -np.inf)
+            ip = np.full(K, -1, dtype=np.int64)
+            wp[:w_b.size] = w_b
+            ip[:i_b.size] = i_b
+            w_b, i_b = merge_topk(self._comm.allgather(wp), self._comm.allgather(ip), K,
+                                  by_index=mode == 1)
+        if i_b.size == 0:
+            return w_b, i_b, None, None
+        xc, mu_c, u_c, own = self._candidate_rows(i_b)
+        return w_b, i_b, self._expander_flags(beta, xc, mu_c, u_c, active, probe=mode == 0), own
+
+    def _candidate_rows(self, gidx):
+        """Rows, means and upper bounds of the global rows ``gidx`` on every rank: the owners
+        fetch theirs, one all-gather sums them.  Also returns which of them this rank owns."""
+        be, d, G = self._backend, self.inputs.shape[1], len(self.gps)
+        own = np.array([be.owns(int(i)) for i in gidx])
+        packed = np.zeros((gidx.size, d + 2 * G))
+        if own.any():
+            x_o, mean_o, _var_o, Q_o = be.gather_rows(gidx[own])
+            packed[own, :d], packed[own, d:d + G], packed[own, d + G:] = x_o, mean_o, Q_o[:, 1::2]
+        if self._comm.world > 1:
+            packed = self._comm.allgather(packed).sum(axis=0)
+        return packed[:, :d], packed[:, d:d + G], packed[:, d + G:], own
+
+    #: candidates per big pass (the last entry repeats); None: by the number of observations
+    #: (``_pass_size``)
     pass_sizes = None
     #: False: the expander loop of a large grid stays at SGP_TOPK candidates per round trip
     big_passes = True
@@ -1033,110 +1016,91 @@ class SafeOpt(GaussianProcessOptimization):
             first *= 2
         return min(8192, first * 8 ** min(k, 2))
 
-    def _visit_in_big_passes(self, beta, active, full_sets, cut_w, cut_idx):
-        """The expander loop of gp_opt.py:557-612 behind the cut, one rank, where it goes
-        far -- no expander among the first SGP_TOPK candidates (a converged run has none at
-        all), or ``full_sets`` (:553-555: every safe row is visited).  A pass takes the next
-        few hundred to few thousand candidates in visiting order (``pass_sizes``; chosen on
-        the device by a histogram of the widths, not a sort) and tests ALL of them in one
-        scan of the unsafe rows (``sgp_grid_expander_pass``): the first expander in visiting
-        order is the widest hit of the first pass that has one -- every candidate in front of
-        it has been tested -- and exact ties among equal widths are settled as always."""
-        be = self._backend
+    def _visit_in_big_passes(self, beta, active, full_sets, cut_w, cut_idx, step):
+        """The expander loop of gp_opt.py:557-612 behind the cut where it goes far -- no
+        expander among the first candidates (a converged run has none at all), or ``full_sets``
+        (:553-555: every safe row is visited).  A pass (``step``: ``_pass_one_rank`` /
+        ``_pass_n_ranks``) takes the next few hundred to few thousand candidates in visiting
+        order (``pass_sizes``; chosen by a histogram of the keys, not a sort) and tests ALL of
+        them in one scan of the unsafe rows: the first expander in visiting order is the widest
+        hit of the first pass that has one -- every candidate in front of it has been tested --
+        and exact ties among equal widths are settled as always."""
         if full_sets:
-            n_all = float(self.inputs.shape[0])
-            lo, hi, mode = -(n_all + 1.0), 1.0, 1           # keys: minus the row index
+            lo, hi, mode = -(float(self.inputs.shape[0]) + 1.0), 1.0, 1   # keys: minus the row
         else:
-            lo, hi, mode = 0.0, float(cut_w), 0             # keys: the interval widths
+            lo, hi, mode = 0.0, float(cut_w), 0                            # keys: the widths
         for k in range(1 << 30):
-            want = self._pass_size(k)
-            # (the arg-max of the step comes back with the result of the pass: when the pass ends
-            # the loop without an expander G is final and the next query point is known)
-            sc = None if full_sets else self.scaling
-            if self.use_lipschitz:
-                tested, hits, key, row, left, amax = be.lipschitz_pass(
-                    self.fmin, self.liptschitz, mode, cut_w, cut_idx, lo, hi, want, sc)
-            else:
-                tested, hits, key, row, left, amax = be.expander_pass(
-                    beta, self.fmin, mode, cut_w, cut_idx, lo, hi, want, sc)
-            if hits and not full_sets:
-                be.mark_expanders(np.array([row], dtype=np.int64))
-                self._settle_ties(beta, active, key, row)
+            p = step(beta, active, mode, cut_w, cut_idx, lo, hi, self._pass_size(k))
+            if p.row >= 0 and not full_sets:
+                return self._first_expander(beta, active, p.key, p.row)
+            if p.tested == 0 or p.left == -np.inf:
+                if p.amax >= 0 and p.tested > 0:
+                    self._argmax_cache = (None, p.amax)
                 return
-            if tested == 0 or left == -np.inf:
-                if amax >= 0 and tested > 0:
-                    self._argmax_cache = (None, amax)
-                return
-            cut_w, cut_idx = left, -1
+            cut_w, cut_idx = p.left, -1
             if not full_sets:
-                hi = left
+                hi = p.left
 
-    def _visit_in_big_passes_nrank(self, beta, active, full_sets, cut_w, cut_idx):
-        """``_visit_in_big_passes`` on a row-sharded grid.  Per pass: the ranks sum their
-        histograms of the keys behind the cut and pick ONE threshold (every rank computes the
-        same one from the same sum); every rank lists its candidates above it and the lists are
-        gathered -- the same candidates in the same order everywhere; every rank tests ALL of
-        them against its own unsafe rows (the operands of the test are recomputed on every rank:
-        a few MFLOP per candidate against the scan) and the flags are or-ed over the ranks
-        (gp_opt.py:602: ``np.any`` over all unsafe rows).  Three small collectives per pass
-        instead of three per 16 candidates."""
-        be, comm = self._backend, self._comm
-        G, d = len(self.gps), self.inputs.shape[1]
-        if full_sets:
-            n_all = float(self.inputs.shape[0])
-            lo, hi, mode = -(n_all + 1.0), 1.0, 1
+    def _pass_one_rank(self, beta, active, mode, cut_w, cut_idx, lo, hi, want):
+        """One big pass on one rank, one device round trip (``sgp_grid_expander_pass`` /
+        ``sgp_grid_lipschitz_pass``; ``full_sets``: the device marks the hits).  The step's
+        arg-max comes with a pass that ends the loop without an expander."""
+        sc = None if mode else self.scaling
+        if self.use_lipschitz:
+            tested, hits, key, row, left, amax = self._backend.lipschitz_pass(
+                self.fmin, self.liptschitz, mode, cut_w, cut_idx, lo, hi, want, sc)
         else:
-            lo, hi, mode = 0.0, float(cut_w), 0
-        nbins = 4096
-        for k in range(1 << 30):
-            want = self._pass_size(k)
-            hist = comm.allgather(be.pass_hist(mode, cut_w, cut_idx, lo, hi).astype(np.float64))
-            from_top = np.cumsum(hist.sum(axis=0)[::-1])
-            if from_top[-1] == 0:
-                return
-            # the highest bin at which the count from the top reaches `want` (k_pass_pick)
-            b = nbins - 1 - int(np.argmax(from_top >= want)) if from_top[-1] >= want else 0
-            thr = -np.inf if b == 0 else lo + (hi - lo) * (float(b) / nbins)
-            # (rounding at a bin edge can move a few candidates across it: room for the
-            # bin below as well)
-            cap = int(from_top[min(nbins - 1, nbins - b)] if b > 0 else from_top[-1]) + 64
-            # (Lipschitz certificates: the candidates' upper bounds themselves, mode | 2)
-            gi, key, xc, resid = be.pass_list(mode | (2 if self.use_lipschitz else 0), cut_w,
-                                              cut_idx, thr, cap)
-            counts = comm.allgather(np.array([float(gi.size)]))[:, 0].astype(int)
-            pad = int(counts.max())
-            if pad == 0:
-                return
-            buf = np.zeros((pad, 2 + d + G))
-            buf[:gi.size, 0], buf[:gi.size, 1] = gi, key            # (row indices < 2^53)
-            buf[:gi.size, 2:2 + d], buf[:gi.size, 2 + d:] = xc, resid
-            allp = comm.allgather(buf)
-            rows = np.concatenate([allp[r][:c] for r, c in enumerate(counts)])
-            if self.use_lipschitz:
-                flags = be.pass_lipschitz_test(self.fmin, self.liptschitz, rows[:, 2:2 + d],
-                                               rows[:, 2 + d:])
-            else:
-                flags = be.pass_test(beta, self.fmin, rows[:, 2:2 + d], rows[:, 2 + d:])
-            flags = comm.allreduce_max(flags.astype(np.float64)) > 0
-            hits = np.all(flags[:, active], axis=1)
-            gidx_all = rows[:, 0].astype(np.int64)
-            if full_sets:
-                mine = [int(i) for i in gidx_all[hits] if be.owns(int(i))]
-                for a in range(0, len(mine), 4096):
-                    be.mark_expanders(np.asarray(mine[a:a + 4096], dtype=np.int64))
-            elif hits.any():
-                hk, hg = rows[hits, 1], gidx_all[hits]
-                first = np.lexsort((hg, hk))[-1]             # widest, then the larger row
-                row, w_star = int(hg[first]), float(hk[first])
-                if be.owns(row):
-                    be.mark_expanders(np.array([row], dtype=np.int64))
-                self._settle_ties(beta, active, w_star, row)
-                return
-            if thr == -np.inf:
-                return
-            cut_w, cut_idx = thr, -1
-            if not full_sets:
-                hi = thr
+            tested, hits, key, row, left, amax = self._backend.expander_pass(
+                beta, self.fmin, mode, cut_w, cut_idx, lo, hi, want, sc)
+        return _Pass(tested, key, row if hits else -1, left, amax)
+
+    def _pass_n_ranks(self, beta, active, mode, cut_w, cut_idx, lo, hi, want, nbins=4096):
+        """One big pass on a row-sharded grid.  The ranks sum their histograms of the keys
+        behind the cut and pick ONE threshold (every rank computes the same one from the same
+        sum); every rank lists its candidates above it and the lists are gathered -- the same
+        candidates in the same order everywhere; every rank tests ALL of them against its own
+        unsafe rows (the operands of the test are recomputed on every rank: a few MFLOP per
+        candidate against the scan) and the flags are or-ed over the ranks (gp_opt.py:602:
+        ``np.any`` over all unsafe rows).  Three small collectives per pass instead of three
+        per 16 candidates.  ``full_sets``: the owners mark every hit."""
+        be, comm = self._backend, self._comm
+        d, G = self.inputs.shape[1], len(self.gps)
+        hist = comm.allgather(be.pass_hist(mode, cut_w, cut_idx, lo, hi).astype(np.float64))
+        from_top = np.cumsum(hist.sum(axis=0)[::-1])
+        if from_top[-1] == 0:
+            return _Pass(0, None, -1, -np.inf, -1)
+        # the highest bin at which the count from the top reaches `want` (k_pass_pick)
+        b = nbins - 1 - int(np.argmax(from_top >= want)) if from_top[-1] >= want else 0
+        thr = -np.inf if b == 0 else lo + (hi - lo) * (float(b) / nbins)
+        # (rounding at a bin edge can move a few candidates across it: room for the
+        # bin below as well)
+        cap = int(from_top[min(nbins - 1, nbins - b)] if b > 0 else from_top[-1]) + 64
+        # (Lipschitz certificates: the candidates' upper bounds themselves, mode | 2)
+        gi, key, xc, resid = be.pass_list(mode | (2 if self.use_lipschitz else 0), cut_w,
+                                          cut_idx, thr, cap)
+        part = np.empty((gi.size, 2 + d + G))
+        part[:, 0], part[:, 1] = gi, key                        # (row indices < 2^53)
+        part[:, 2:2 + d], part[:, 2 + d:] = xc, resid
+        rows = allgather_rows(comm, part, count_dtype=np.float64)
+        if rows.shape[0] == 0:
+            return _Pass(0, None, -1, -np.inf, -1)
+        if self.use_lipschitz:
+            flags = be.pass_lipschitz_test(self.fmin, self.liptschitz, rows[:, 2:2 + d],
+                                           rows[:, 2 + d:])
+        else:
+            flags = be.pass_test(beta, self.fmin, rows[:, 2:2 + d], rows[:, 2 + d:])
+        flags = comm.allreduce_max(flags.astype(np.float64)) > 0
+        hits = np.all(flags[:, active], axis=1)
+        gidx = rows[:, 0].astype(np.int64)
+        if mode == 1:
+            mine = [int(i) for i in gidx[hits] if be.owns(int(i))]
+            for a in range(0, len(mine), 4096):
+                be.mark_expanders(np.asarray(mine[a:a + 4096], dtype=np.int64))
+        elif hits.any():
+            hk, hg = rows[hits, 1], gidx[hits]
+            first = np.lexsort((hg, hk))[-1]             # widest, then the larger row
+            return _Pass(rows.shape[0], float(hk[first]), int(hg[first]), thr, -1)
+        return _Pass(rows.shape[0], None, -1, thr, -1)
 
     def _visit_all_candidates(self, beta, active, full_sets, cut_idx, chunk=1024):
         """The expander loop of a SMALL grid on one rank: every candidate is tested at once
@@ -1179,17 +1143,6 @@ class SafeOpt(GaussianProcessOptimization):
                 self._argmax_cache = None
                 return
 
-    def _gather_shards(self, part, N):
-        """Concatenate every rank's block of a per-row array."""
-        if self._comm.world == 1:
-            return part
-        counts = [np.subtract(*shard_range(N, r, self._comm.world)[::-1])
-                  for r in range(self._comm.world)]
-        buf = np.zeros((max(counts),) + part.shape[1:], dtype=part.dtype)
-        buf[:part.shape[0]] = part
-        allp = self._comm.allgather(buf)
-        return np.concatenate([allp[r][:c] for r, c in enumerate(counts)])
-
     def _settle_ties(self, beta, active, w_star, idx_star, n_tied=None):
         """Exact ties in the visiting order of the expander loop.
 
@@ -1224,13 +1177,10 @@ class SafeOpt(GaussianProcessOptimization):
         wc_loc = np.asarray(w_loc, dtype=float)[rows_loc]
         rows_loc = rows_loc + self._shard[0]
         if self._comm.world > 1:
-            counts = self._comm.allgather(np.array([rows_loc.size], dtype=np.int64))[:, 0]
-            pad = int(counts.max())
-            buf = np.zeros((pad, 2))
-            buf[:rows_loc.size, 0], buf[:rows_loc.size, 1] = rows_loc, wc_loc   # (idx < 2^53)
-            allp = self._comm.allgather(buf)
-            rows = np.concatenate([allp[r][:c, 0] for r, c in enumerate(counts)]).astype(np.int64)
-            wrows = np.concatenate([allp[r][:c, 1] for r, c in enumerate(counts)])
+            part = np.empty((rows_loc.size, 2))
+            part[:, 0], part[:, 1] = rows_loc, wc_loc              # (idx < 2^53)
+            part = allgather_rows(self._comm, part)
+            rows, wrows = part[:, 0].astype(np.int64), part[:, 1]
         else:
             rows, wrows = rows_loc, wc_loc
         order = wrows.argsort()[::-1]              # the reference's own expression
@@ -1241,19 +1191,7 @@ class SafeOpt(GaussianProcessOptimization):
                 continue                           # other width / rejected before
             if idx == idx_star:
                 break
-            own = be.owns(idx)
-            xc = np.zeros((1, self.inputs.shape[1]))
-            mu_c = np.zeros((1, len(self.gps)))
-            u_c = np.zeros((1, len(self.gps)))
-            if own:
-                x_o, mean_o, _v, Q_o = be.gather_rows(np.array([idx], dtype=np.int64))
-                xc[0], mu_c[0], u_c[0] = x_o[0], mean_o[0], Q_o[0, 1::2]
-            if self._comm.world > 1:
-                packed = self._comm.allgather(
-                    np.concatenate([xc, mu_c, u_c], axis=1)).sum(axis=0)
-                d = self.inputs.shape[1]
-                xc, mu_c, u_c = (packed[:, :d], packed[:, d:d + len(self.gps)],
-                                 packed[:, d + len(self.gps):])
+            xc, mu_c, u_c, _own = self._candidate_rows(np.array([idx], dtype=np.int64))
             if self._expander_flags(beta, xc, mu_c, u_c, active, probe=False)[0]:
                 winner = idx
                 break

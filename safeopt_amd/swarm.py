@@ -209,15 +209,13 @@ class DeviceSwarmOptimization(SwarmOptimization):
 
     def _gather(self, best_positions, best_values):
         """The whole swarm's personal bests on every rank (blocks padded to one size)."""
-        from .dist import shard_range
+        from .dist import allgather_rows, shard_range
         world, P = self._comm.world, self.swarm_size
-        n = best_values.shape[0]
-        buf = np.zeros((-(-P // world), best_positions.shape[1] + 1))
-        buf[:n, :-1] = best_positions
-        buf[:n, -1] = best_values
-        allp = self._comm.allgather(buf)
-        sizes = [hi - lo for lo, hi in (shard_range(P, r, world) for r in range(world))]
-        full = np.concatenate([allp[r, :sizes[r]] for r in range(world)])
+        part = np.empty((best_values.shape[0], best_positions.shape[1] + 1))
+        part[:, :-1] = best_positions
+        part[:, -1] = best_values
+        full = allgather_rows(self._comm, part, [hi - lo for lo, hi in (
+            shard_range(P, r, world) for r in range(world))])
         return np.ascontiguousarray(full[:, :-1]), np.ascontiguousarray(full[:, -1])
 
     def init_swarm(self, positions):

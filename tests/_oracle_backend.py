@@ -120,7 +120,7 @@ class OracleGridBackend(object):
                 flags[:, i] = np.any(u_c[:, [i]] - lipschitz[i] * d >= fmin[i], axis=1)
         return flags
 
-    # -- the big passes of the expander loop on N ranks (SafeOpt._visit_in_big_passes_nrank) --
+    # -- the big passes of the expander loop on N ranks (SafeOpt._pass_n_ranks) --
     def _behind(self, mode, cut_w, cut_idx):
         """Global rows and keys (width; mode & 1: minus the row index) of this shard's
         candidates strictly behind the cut -- pass_key of csrc/sets.hip."""

@@ -175,7 +175,7 @@ def _pass_worker(rank, world, port, q):
 
 @pytest.mark.timeout(600)
 def test_two_ranks_big_passes_of_the_expander_loop():
-    """``SafeOpt._visit_in_big_passes_nrank`` over gloo with the oracle's arithmetic behind the
+    """``SafeOpt._pass_n_ranks`` over gloo with the oracle's arithmetic behind the
     three calls of a pass (histograms summed, candidates gathered, flags or-ed): a converged
     state -- every candidate visited in passes of 8 and 16, none marked -- with GP and with
     Lipschitz certificates, equal to the unsharded oracle."""

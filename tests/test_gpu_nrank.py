@@ -154,7 +154,7 @@ def _big_pass_cases(sa, gpy, comm, report):
     whose first expander sits far down the visiting order, and ``full_sets``, on true shards
     against the SAME product on one rank.  The ranks agree on a threshold from their summed
     histograms, gather the candidates, test all of them against their own unsafe rows and or
-    the flags (``SafeOpt._visit_in_big_passes_nrank``)."""
+    the flags (``SafeOpt._pass_n_ranks``)."""
     import _scenarios as sc
     from safeopt_amd import dist, gp_opt
     calls = {"n": 0}
