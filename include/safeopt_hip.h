@@ -85,6 +85,35 @@ int sgp_gp_pop(sgp_gp* gp);
 int sgp_gp_predict(sgp_gp* gp, const double* Xnew, int64_t N,
                    int64_t stride_row, int64_t stride_col, double* mean,
                    double* var);
+/* An edited hyper-parameter (kern.variance / kern.lengthscale / noise_var written in
+ * place; GPy refits through its parameter observers): the kernel descriptor of the GP is
+ * rewritten in place -- same d, kinds and number of parts; variances[n_parts],
+ * inv_ls[n_parts * d] as in sgp_gp_create -- and the RESIDENT data are factorised again.
+ * No buffer is reallocated and X / Y are not uploaded again.  Jitter retries, chol_info
+ * and jitter_used as sgp_gp_set_data (on failure the GP has no data any more).      */
+int sgp_gp_set_hyper(sgp_gp* gp, const double* variances, const double* inv_ls,
+                     double noise_var, int* chol_info, double* jitter_used);
+/* gp.log_likelihood() and its gradient (GPy: ExactGaussianInference,
+ * Stationary.update_gradients_full) at a full set of hyper-parameters, in one device ->
+ * host copy.  As sgp_gp_set_hyper, but WITHOUT jitter retries (jitter = 0): *info = 0, or
+ * the first non-positive pivot of Ky = K + (noise_var + 1e-8) I -- that theta is
+ * infeasible, `out` is meaningless and the GP stays unfitted (data resident) until the
+ * next sgp_gp_lml / sgp_gp_set_hyper / sgp_gp_set_data succeeds.  With P = n_parts:
+ *   out[0]                log p(y | X, theta) = -1/2 y^T alpha - sum_i log L_ii - n/2 log 2 pi
+ *   out[1]                d/d noise_var
+ *   out[2 .. 2+P)         d/d variance[p]
+ *   out[2+P .. 2+P+P*d)   d/d inv_ls[p*d + a]   (0 for a column the part does not use)
+ * The gradient is 1/2 sum_ij W_ij dKy_ij/dtheta, W = alpha alpha^T - Ky^-1,
+ * Ky^-1 = L^-T L^-1.  With s = inv_ls[p][a], D_a = x_ia - x_ja,
+ * r_p^2 = sum_a (D_a s_pa)^2 and k = prod_p v_p f_p(r_p):
+ *   dk/dv_p = k / v_p,   dKy/dnoise_var = I,   dk/ds_pa = (k / f_p) c_p(r_p) D_a^2 s_pa,
+ *   RBF        f = exp(-r^2/2)                              c = -f
+ *   Matern-3/2 f = (1 + sqrt3 r) exp(-sqrt3 r)              c = -3 exp(-sqrt3 r)
+ *   Matern-5/2 f = (1 + sqrt5 r + 5 r^2/3) exp(-sqrt5 r)    c = -5/3 (1 + sqrt5 r) exp(-sqrt5 r)
+ * (exact at r = 0).  The sums are formed in a fixed order: the same theta on the same
+ * data returns the same bits.  On success the GP is fitted at theta.               */
+int sgp_gp_lml(sgp_gp* gp, const double* variances, const double* inv_ls,
+               double noise_var, double* out, int* info);
 /* test hook: dense L^-1 (n x n, row-major) and alpha (n)                     */
 int sgp_gp_get_factor(sgp_gp* gp, double* Linv, double* alpha);
 /* gp.kern.K(X, X2) (gp_opt.py:847, 1093; utilities.py:89, 135): out is

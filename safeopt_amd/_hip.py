@@ -46,6 +46,10 @@ PROTOTYPES = {
     "sgp_gp_destroy": (None, [vp]),
     "sgp_gp_set_data": (C.c_int, [vp, c_double_p, c_double_p, C.c_int64,
                                   c_int_p, c_double_p]),
+    "sgp_gp_set_hyper": (C.c_int, [vp, c_double_p, c_double_p, C.c_double,
+                                   c_int_p, c_double_p]),
+    "sgp_gp_lml": (C.c_int, [vp, c_double_p, c_double_p, C.c_double, c_double_p,
+                             c_int_p]),
     "sgp_gp_append": (C.c_int, [vp, c_double_p, C.c_double, c_int_p]),
     "sgp_gp_pop": (C.c_int, [vp]),
     "sgp_gp_predict": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
@@ -452,6 +456,7 @@ class DeviceGP(object):
             ctx.h, d, len(kinds), kinds.ctypes.data_as(c_int_p),
             dptr(variances), dptr(inv_ls), float(noise_var), C.byref(h)))
         self.h = h
+        self.n_parts = len(kinds)
         self.n = 0
         self.jitter = 0.0
         # data version: bumped by every change; `appended` = the last change
@@ -482,6 +487,47 @@ class DeviceGP(object):
         self.jitter = jit.value
         self.version += 1
         self.appended = False
+
+    def _hyper(self, variances, inv_ls):
+        variances = f64(variances).reshape(-1)
+        inv_ls = f64(inv_ls).reshape(-1)
+        if variances.size != self.n_parts or inv_ls.size != self.n_parts * self.d:
+            raise ValueError("hyper-parameters of %d parts on %d columns expected"
+                             % (self.n_parts, self.d))
+        return variances, inv_ls
+
+    def set_hyper(self, variances, inv_ls, noise_var):
+        """New hyper-parameters for the resident data: the descriptor is rewritten in
+        place and the data are factorised again (no allocation, no upload); jitter and
+        ``LinAlgError`` as ``set_data``."""
+        variances, inv_ls = self._hyper(variances, inv_ls)
+        info, jit = C.c_int(0), C.c_double(0)
+        rc = lib().sgp_gp_set_hyper(self.h, dptr(variances), dptr(inv_ls),
+                                    float(noise_var), C.byref(info), C.byref(jit))
+        self.version += 1
+        self.appended = False
+        if rc > 0 or info.value != 0:
+            self.n = 0
+            raise np.linalg.LinAlgError(
+                lib().sgp_last_error(self.ctx.h).decode())
+        self.ctx.check(rc)
+        self.jitter = jit.value
+
+    def lml(self, variances, inv_ls, noise_var):
+        """``(log p(y | X, theta), d/d noise_var, d/d variance[P], d/d inv_ls[P, d],
+        info)`` in one round trip; the GP is left fitted at theta when ``info == 0``
+        (no jitter), unfitted -- data resident -- otherwise."""
+        variances, inv_ls = self._hyper(variances, inv_ls)
+        P, d = self.n_parts, self.d
+        out = np.empty(2 + P + P * d)
+        info = C.c_int(0)
+        self.version += 1
+        self.appended = False
+        self.ctx.check(lib().sgp_gp_lml(self.h, dptr(variances), dptr(inv_ls),
+                                        float(noise_var), dptr(out), C.byref(info)))
+        self.jitter = 0.0
+        return (float(out[0]), float(out[1]), out[2:2 + P].copy(),
+                out[2 + P:].reshape(P, d).copy(), int(info.value))
 
     def append(self, x, y):
         """One more observation by a bordered update; False = not possible

@@ -107,6 +107,7 @@ int collect_gps(sgp_ctx* ctx, sgp_gp* const* gps, int G, int d, GpDev* host) {
             SGP_MAX_GPS);
   for (int g = 0; g < G; ++g) {
     SGP_CHECK(ctx, gps[g] && gps[g]->n > 0, "GP %d has no data", g);
+    SGP_CHECK(ctx, gps[g]->factored, "GP %d is not fitted (infeasible hyper-parameters)", g);
     SGP_CHECK(ctx, gps[g]->ctx == ctx,
               "GP %d lives in another context (device %d) than the grid "
               "(device %d): no stream ordering, foreign device pointers",
@@ -326,6 +327,54 @@ void sgp_gp_destroy(sgp_gp* gp) {
   delete gp;
 }
 
+// Factorise the resident data at gp->kern / gp->noise_var as GPy's util.linalg.jitchol does:
+// plain attempt, then jitter = mean(diag)*1e-6, *10 per retry, at most 5 retries.
+static int fit_with_jitter(sgp_gp* gp, int* chol_info, double* jitter_used) {
+  sgp_ctx* ctx = gp->ctx;
+  gp->jitter = 0.0;
+  gp->factored = true;
+  int info = 0;
+  SGP_TRY(factor_gp(gp, &info));
+  if (info != 0) {
+    const double diag_mean = gp->kern.kdiag + gp->noise_var + 1e-8;
+    double jitter = diag_mean * 1e-6;
+    for (int t = 0; t < 5 && info != 0 && std::isfinite(jitter); ++t) {
+      gp->jitter = jitter;
+      SGP_TRY(factor_gp(gp, &info));
+      jitter *= 10.0;
+    }
+  }
+  if (chol_info) *chol_info = info;
+  if (jitter_used) *jitter_used = gp->jitter;
+  if (info != 0) {
+    gp->n = 0;
+    sgp_set_error(ctx, "not positive definite, even with jitter (pivot %d)",
+                  info);
+    return info > 0 ? info : -2;
+  }
+  return 0;
+}
+
+// The hyper-parameters of a GP rewritten in place (same d, kinds and number of parts): the
+// descriptor with its derived fields, nothing else.  The factor no longer belongs to it:
+// the version moves (factor tables, the grid's copy of the descriptor) and the rank-1
+// record of the last append is dropped.
+static int rewrite_hyper(sgp_gp* gp, const double* variances, const double* inv_ls,
+                         double noise_var) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, std::isfinite(noise_var), "noise_var is not finite");
+  KernDesc kd;
+  SGP_TRY(fill_kern(ctx, &kd, gp->kern.d, gp->kern.n_parts, gp->kern.kind, variances, inv_ls));
+  gp->kern = kd;
+  gp->noise_var = noise_var;
+  ++gp->data_version;
+  gp->upd_valid = false;
+  // (a refit at the current n: the history of appends and removals no longer matters)
+  gp->prov = 0x9e3779b97f4a7c15ull ^ uint64_t(gp->n);
+  return 0;
+}
+
 int sgp_gp_set_data(sgp_gp* gp, const double* X, const double* Y, int64_t n,
                     int* chol_info, double* jitter_used) {
   sgp_ctx* ctx = gp->ctx;
@@ -353,28 +402,36 @@ int sgp_gp_set_data(sgp_gp* gp, const double* X, const double* Y, int64_t n,
     }
     gp->prov = 0x9e3779b97f4a7c15ull ^ uint64_t(n);
   }
-  // GPy util.linalg.jitchol: plain attempt, then jitter = mean(diag)*1e-6,
-  // *10 per retry, at most 5 retries.
+  return fit_with_jitter(gp, chol_info, jitter_used);
+}
+
+int sgp_gp_set_hyper(sgp_gp* gp, const double* variances, const double* inv_ls,
+                     double noise_var, int* chol_info, double* jitter_used) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_TRY(rewrite_hyper(gp, variances, inv_ls, noise_var));
+  return fit_with_jitter(gp, chol_info, jitter_used);
+}
+
+int sgp_gp_lml(sgp_gp* gp, const double* variances, const double* inv_ls, double noise_var,
+               double* out, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_TRY(rewrite_hyper(gp, variances, inv_ls, noise_var));
   gp->jitter = 0.0;
-  int info = 0;
-  SGP_TRY(factor_gp(gp, &info));
-  if (info != 0) {
-    const double diag_mean = gp->kern.kdiag + gp->noise_var + 1e-8;
-    double jitter = diag_mean * 1e-6;
-    for (int t = 0; t < 5 && info != 0 && std::isfinite(jitter); ++t) {
-      gp->jitter = jitter;
-      SGP_TRY(factor_gp(gp, &info));
-      jitter *= 10.0;
-    }
-  }
-  if (chol_info) *chol_info = info;
-  if (jitter_used) *jitter_used = gp->jitter;
-  if (info != 0) {
-    gp->n = 0;
-    sgp_set_error(ctx, "not positive definite, even with jitter (pivot %d)",
-                  info);
-    return info > 0 ? info : -2;
-  }
+  gp->factored = false;          // until the pivot word says otherwise
+  const int words = lml_result_words(gp->kern);
+  double* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, size_t(words) * sizeof(double), &res));
+  const int* info_dev = nullptr;
+  int unused = 0;
+  SGP_TRY(factor_gp(gp, &unused, &info_dev));
+  SGP_TRY(launch_lml(gp, info_dev, res));
+  double host[3 + SGP_MAX_PARTS + SGP_MAX_PARTS * SGP_MAX_D];
+  SGP_TRY(sgp_d2h(ctx, host, res, size_t(words) * sizeof(double)));
+  *info = int(host[words - 1]);
+  gp->factored = *info == 0;
+  memcpy(out, host, size_t(words - 1) * sizeof(double));
   return 0;
 }
 
@@ -382,6 +439,7 @@ int sgp_gp_append(sgp_gp* gp, const double* x, double y, int* info) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
   *info = -1;
   if (gp->n + 1 > gp->ld) return 0;  // no room: caller refits with set_data
   const int d = gp->kern.d;
@@ -407,6 +465,7 @@ int sgp_gp_pop(sgp_gp* gp) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, gp->n > 1, "cannot remove the only training point");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
   ++gp->data_version;
   SGP_TRY(pop_gp(gp));
   gp->xhost.resize(size_t(gp->n) * gp->kern.d);
@@ -421,6 +480,7 @@ int sgp_gp_predict(sgp_gp* gp, const double* Xnew, int64_t N,
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
   if (N <= 0) return 0;
   const int d = gp->kern.d;
   // stage the rows through a dense row-major device copy
@@ -478,6 +538,7 @@ int sgp_gp_get_factor(sgp_gp* gp, double* Linv, double* alpha) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
   const int64_t n = gp->n;
   if (Linv) {
     SGP_HIP(ctx, hipMemcpy2DAsync(Linv, n * sizeof(double), gp->Linv.p,

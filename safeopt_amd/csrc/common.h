@@ -239,6 +239,8 @@ struct sgp_gp {
                                  // (fit at n, appends, removals): two GPs with equal
                                  // inputs AND equal history have the same bits in L^-1
   bool upd_valid = false;  // dev.upd* describes the step to the current data
+  bool factored = true;    // false: sgp_gp_lml met a non-positive pivot -- the data are
+                           // resident, the factor is not valid until the next fit
   DevBuf X, Y, Xpad, Xs, XA, alpha, Apack, Linv, Kmat, work, tvec, updw, upd;
   GpDev dev;      // filled by set_data
 };
@@ -298,7 +300,11 @@ int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
                          int64_t n1, const double* X2, int64_t n2, double* out,
                          int64_t ld, int symmetric_diag, double diag_add,
                          int64_t n_valid);
-int factor_gp(sgp_gp* gp, int* info);  // Kmat -> Linv, Apack, alpha
+// Kmat -> Linv, Apack, alpha (info_dev_out: the pivot word stays on the device, factor.hip)
+int factor_gp(sgp_gp* gp, int* info, const int** info_dev_out = nullptr);
+// hyper.hip: log marginal likelihood and gradient of a GP factor_gp has just factorised
+int lml_result_words(const KernDesc& kd);   // 2 + P + P d values and the pivot word
+int launch_lml(sgp_gp* gp, const int* info_dev, double* out_dev);
 int append_gp(sgp_gp* gp, double y, int* info);  // row n already in gp->X
 int pop_gp(sgp_gp* gp);
 int publish_gp(sgp_gp* gp);  // Apack / Xpad / Xs / dev descriptor from Linv

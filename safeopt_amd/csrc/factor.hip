@@ -436,7 +436,10 @@ int publish_gp(sgp_gp* gp) {
 // Build Ky (with gp->jitter), factor, invert, pack, alpha.  *info = 0 or the
 // 1-based index of the first non-positive pivot.  Buffers are sized for
 // gp->ld >= n_f rows so later one-row appends need no reallocation.
-int factor_gp(sgp_gp* gp, int* info) {
+// info_dev_out != nullptr: the pivot word is NOT read back (no stream sync) -- the caller
+// gets its device address and reads it with its own result (hyper.hip); everything behind
+// the factorisation is enqueued regardless, on garbage when a pivot failed.
+int factor_gp(sgp_gp* gp, int* info, const int** info_dev_out) {
   sgp_ctx* ctx = gp->ctx;
   const int n = int(gp->n), nf = gp->n_f, np = gp->n_pad, ld = gp->ld;
   const size_t mat = size_t(ld) * ld * sizeof(double);
@@ -461,8 +464,12 @@ int factor_gp(sgp_gp* gp, int* info) {
   SGP_HIP(ctx, hipMemsetAsync(Li, 0, mat, ctx->stream));
   SGP_HIP(ctx, hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
   SGP_TRY(factor_rec(ctx, K, Li, T, ld, 0, nf, info_dev));
-  SGP_TRY(sgp_d2h(ctx, info, info_dev, sizeof(int)));
-  if (*info != 0) return 0;
+  if (info_dev_out) {
+    *info_dev_out = info_dev;
+  } else {
+    SGP_TRY(sgp_d2h(ctx, info, info_dev, sizeof(int)));
+    if (*info != 0) return 0;
+  }
 
   SGP_TRY(launch_tri_mv(ctx, Li, ld, n, static_cast<double*>(gp->Y.p), 0, 1, tv, 0));
   SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, tv, 0, 1,

@@ -11,8 +11,10 @@ touches (``/root/reference/safeopt/gp_opt.py:83, 121-126, 227, 267, 275, 469,
 
 Every number is produced on the GPU: ``set_XY`` builds the covariance matrix,
 factorises it and inverts the factor on the device; ``predict_noiseless`` and
-``kern.K`` run HIP kernels.  The Python objects only carry hyper-parameters
-and the host copies of ``X`` / ``Y`` that SafeOpt's plumbing reads back.
+``kern.K`` run HIP kernels; ``log_likelihood`` and every evaluation of
+``optimize`` (value and gradient of the marginal likelihood) are one device
+call.  The Python objects only carry hyper-parameters and the host copies of
+``X`` / ``Y`` that SafeOpt's plumbing reads back.
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ import types as _types
 import numpy as np
 
 from . import _hip
+from . import hyper as _hyper
 
 __all__ = ["kern", "models"]
 
@@ -160,8 +163,12 @@ class GPRegression(object):
 
     Mirrors ``GPy.models.GPRegression(X, Y, kernel=None, noise_var=1.)`` as
     SafeOpt uses it.  Hyper-parameters are taken from the kernel object each
-    time the model is (re)fitted; they are never optimised (the reference never
-    calls ``gp.optimize()`` either).
+    time the model is (re)fitted; an edit in place refits the resident data on
+    the device.  ``optimize()`` / ``optimize_restarts()`` fit them by maximum
+    marginal likelihood (L-BFGS-B, softplus-transformed as in GPy) and write the
+    result back into ``kern.variance`` / ``kern.lengthscale`` / ``noise_var``.
+    The reference never calls ``gp.optimize()``: fit first, then build the
+    ``SafeOpt`` object (its ``scaling='auto'`` reads ``kern.Kdiag`` once).
     """
 
     def __init__(self, X, Y, kernel=None, noise_var=1., device=None):
@@ -191,14 +198,22 @@ class GPRegression(object):
     def Gaussian_noise_variance(self):
         return self.noise_var
 
-    def _device_gp(self):
+    def _device_gp(self, in_place=False):
         desc = self.kern._desc(self.input_dim)
         key = (desc[0], desc[1].tobytes(), desc[2].tobytes(),
                desc[3].tobytes(), self.noise_var)
         if self._dev is None or key != self._dev_key:
-            self._dev = _hip.DeviceGP(self._ctx, desc, self.noise_var)
+            if (in_place and self._dev is not None and self._dev_fitted
+                    and key[:2] == self._dev_key[:2]):
+                # only numbers changed: the same device GP, its data resident, refitted
+                self._dev_key = None
+                self._dev_fitted = False
+                self._dev.set_hyper(desc[2], desc[3], self.noise_var)   # may raise LinAlgError
+                self._dev_fitted = True
+            else:
+                self._dev = _hip.DeviceGP(self._ctx, desc, self.noise_var)
+                self._dev_fitted = False
             self._dev_key = key
-            self._dev_fitted = False
         self._sig = (self.kern._signature(), self.noise_var)
         return self._dev
 
@@ -233,11 +248,83 @@ class GPRegression(object):
         if self._dev is not None and self._dev_fitted:
             if (self.kern._signature(), self.noise_var) == self._sig:
                 return self._dev
-        dev = self._device_gp()
+        dev = self._device_gp(in_place=True)
         if not self._dev_fitted:
             dev.set_data(self.X, self.Y[:, 0])
             self._dev_fitted = True
         return dev
+
+    # -- fitting the hyper-parameters
+    def _evaluate(self, variances, inv_ls, noise_var):
+        """One device call: likelihood and gradient at theta; the device GP is left
+        fitted there (or unfitted, data resident, when theta is infeasible)."""
+        dev = self._dev
+        if dev is None or dev.n != self.X.shape[0]:
+            dev = self._fitted()
+        out = dev.lml(variances, inv_ls, noise_var)
+        self._dev_fitted = out[4] == 0
+        self._dev_key = (self.input_dim, self._dev_key[1], np.asarray(variances).tobytes(),
+                         np.asarray(inv_ls).tobytes(), float(noise_var))
+        self._sig = None
+        return out
+
+    def _settle(self):
+        """After evaluations: is the device GP fitted at the values the objects hold?"""
+        desc = self.kern._desc(self.input_dim)
+        key = (desc[0], desc[1].tobytes(), desc[2].tobytes(), desc[3].tobytes(),
+               self.noise_var)
+        if self._dev_fitted and key == self._dev_key:
+            self._sig = (self.kern._signature(), self.noise_var)
+
+    def log_likelihood(self):
+        """``log p(y | X, theta)`` at the current hyper-parameters."""
+        self._fitted()
+        desc = self.kern._desc(self.input_dim)
+        ll, _, _, _, info = self._evaluate(desc[2], desc[3], self.noise_var)
+        self._settle()
+        if info != 0:
+            raise np.linalg.LinAlgError("not positive definite (pivot %d)" % info)
+        return ll
+
+    def objective_function(self):
+        return -self.log_likelihood()
+
+    def optimize(self, optimizer='lbfgsb', max_iters=1000, messages=False, fixed=()):
+        """Maximise the marginal likelihood over the hyper-parameters (L-BFGS-B on the
+        softplus-transformed values, GPy's defaults); every evaluation is one device
+        call.  ``fixed``: names to leave alone (``'noise_var'``, ``'<part>.variance'``,
+        ``'<part>.lengthscale'``; ``'variance'`` / ``'lengthscale'`` for a single
+        kernel).  The fitted values are written in place into ``kern`` / ``noise_var``
+        and the model is fitted at them.  Returns an object with ``f_opt``, ``x_opt``,
+        ``funct_eval``, ``status``."""
+        if optimizer not in ('lbfgsb', 'lbfgs', None):
+            raise NotImplementedError("optimizer %r (only 'lbfgsb')" % (optimizer,))
+        self._fitted()
+        params = _hyper.Parameters(self.kern, self.noise_var, self.input_dim, fixed)
+        try:
+            res = _hyper.optimize(params, self._evaluate, max_iters=max_iters,
+                                  messages=messages)
+        finally:
+            self.noise_var = params.noise_var
+            self._settle()
+        return res
+
+    def optimize_restarts(self, num_restarts=10, robust=True, **kwargs):
+        """``optimize`` from the current values and from ``num_restarts - 1`` random
+        starts (``N(0, 1)`` per transformed parameter, NumPy's global generator);
+        keeps the best."""
+        fixed = kwargs.pop('fixed', ())
+        if kwargs.pop('optimizer', 'lbfgsb') not in ('lbfgsb', 'lbfgs', None):
+            raise NotImplementedError("only 'lbfgsb'")
+        self._fitted()
+        params = _hyper.Parameters(self.kern, self.noise_var, self.input_dim, fixed)
+        try:
+            res = _hyper.optimize_restarts(params, self._evaluate, num_restarts=num_restarts,
+                                           robust=robust, **kwargs)
+        finally:
+            self.noise_var = params.noise_var
+            self._settle()
+        return res
 
     def parameters_changed(self):
         """Refit the device model with the current hyper-parameters NOW.  Not needed
