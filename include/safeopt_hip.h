@@ -32,6 +32,7 @@ extern "C" {
 #define SGP_MAX_PARTS 4    /* factors of a product kernel                      */
 #define SGP_MAX_GPS 8      /* objective + constraints                          */
 #define SGP_TOPK 16        /* expander candidates examined per pass            */
+#define SGP_MAX_JOINT 8192 /* rows of one joint prediction                     */
 
 /* kernel kinds: GPy.kern.RBF / Matern32 / Matern52 (Stationary.K_of_r)        */
 enum { SGP_RBF = 0, SGP_MATERN32 = 1, SGP_MATERN52 = 2 };
@@ -114,6 +115,22 @@ int sgp_gp_set_hyper(sgp_gp* gp, const double* variances, const double* inv_ls,
  * data returns the same bits.  On success the GP is fitted at theta.               */
 int sgp_gp_lml(sgp_gp* gp, const double* variances, const double* inv_ls,
                double noise_var, double* out, int* info);
+/* gp.predict_noiseless(Xnew, full_cov=True) (GPy: Posterior._raw_predict): mean (N), cov
+ * (N x N row-major, exactly symmetric).  cov = k(X*,X*) - V^T V, V = L^-1 k(X,X*); its
+ * diagonal is NOT clipped (GPy clips only the full_cov=False variance).  Strides as
+ * sgp_gp_predict; N <= SGP_MAX_JOINT.  cov may be NULL (mean only), mean may be NULL.
+ * Deterministic: the sums are formed in a fixed order.  Device memory: V (n x N) and cov.  */
+int sgp_gp_predict_cov(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
+                       int64_t stride_col, double* mean, double* cov);
+/* gp.posterior_samples_f(Xnew, size=S) with the caller's normals: out (N x S row-major) =
+ * mean 1^T + C Z, C the lower Cholesky factor of cov + jitter_used * I, Z (N x S row-major).
+ * Jitter as GPy's jitchol / sgp_gp_set_data: 0 first, then mean(diag cov) * 1e-6, times 10
+ * per retry, five retries; chol_info > 0 (also the return value) = pivot still not
+ * positive, out is then not written.  mean may be NULL.  Deterministic.  Device memory:
+ * three N_pad x N_pad arrays, N_pad = N rounded up to 32 -- 1.6 GB at N = SGP_MAX_JOINT.   */
+int sgp_gp_posterior_draw(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
+                          int64_t stride_col, const double* Z, int S, double* out,
+                          double* mean, int* chol_info, double* jitter_used);
 /* test hook: dense L^-1 (n x n, row-major) and alpha (n)                     */
 int sgp_gp_get_factor(sgp_gp* gp, double* Linv, double* alpha);
 /* gp.kern.K(X, X2) (gp_opt.py:847, 1093; utilities.py:89, 135): out is

@@ -33,6 +33,7 @@ Q, S, M, G, MEAN, VAR, CAND, WIDTH = 0, 1, 2, 3, 4, 5, 6, 7
 ARGMAX_MG_WIDTH, ARGMAX_UCB, ARGMAX_LCB = 0, 1, 2
 SWARM_TYPES = {"greedy": 0, "maximizers": 1, "expanders": 2, "safe_set": 3}
 MAX_D, MAX_PARTS, MAX_GPS, TOPK = 8, 4, 8, 16
+MAX_JOINT = 8192          # SGP_MAX_JOINT: rows of one joint prediction
 
 # name -> (restype, argtypes); mirrors include/safeopt_hip.h one to one
 PROTOTYPES = {
@@ -54,6 +55,11 @@ PROTOTYPES = {
     "sgp_gp_pop": (C.c_int, [vp]),
     "sgp_gp_predict": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
                                  C.c_int64, c_double_p, c_double_p]),
+    "sgp_gp_predict_cov": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
+                                     C.c_int64, c_double_p, c_double_p]),
+    "sgp_gp_posterior_draw": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
+                                        C.c_int64, c_double_p, C.c_int, c_double_p,
+                                        c_double_p, c_int_p, c_double_p]),
     "sgp_gp_get_factor": (C.c_int, [vp, c_double_p, c_double_p]),
     "sgp_kern_K": (C.c_int, [vp, C.c_int, C.c_int, c_int_p, c_double_p,
                              c_double_p, c_double_p, C.c_int64, c_double_p,
@@ -566,6 +572,51 @@ class DeviceGP(object):
                 self.h, dptr(Xnew), N, Xnew.strides[0] // it,
                 Xnew.strides[1] // it, dptr(mean), dptr(var)))
         return mean, var
+
+    def _joint_rows(self, Xnew):
+        Xnew = np.asarray(Xnew, dtype=np.float64)
+        if Xnew.ndim != 2 or Xnew.shape[1] != self.d:
+            Xnew = np.atleast_2d(Xnew).reshape(-1, self.d)
+        it = Xnew.itemsize
+        if Xnew.strides[0] % it or Xnew.strides[1] % it or \
+                min(Xnew.strides) < 0:
+            Xnew = np.ascontiguousarray(Xnew)
+        if Xnew.shape[0] > MAX_JOINT:
+            raise ValueError("%d rows in one joint prediction: at most SGP_MAX_JOINT = %d"
+                             % (Xnew.shape[0], MAX_JOINT))
+        return Xnew, Xnew.strides[0] // it, Xnew.strides[1] // it
+
+    def predict_cov(self, Xnew):
+        """Joint posterior of the rows of ``Xnew``: mean ``(N, 1)`` and covariance
+        ``(N, N)``, exactly symmetric, not clipped."""
+        Xnew, sr, sc = self._joint_rows(Xnew)
+        N = Xnew.shape[0]
+        mean = np.empty((N, 1))
+        cov = np.empty((N, N))
+        self.ctx.check(lib().sgp_gp_predict_cov(self.h, dptr(Xnew), N, sr, sc,
+                                                dptr(mean), dptr(cov)))
+        return mean, cov
+
+    def draw(self, Xnew, Z):
+        """``(out, mean, jitter_used)``: ``out = mean + C Z`` (N, S) for the caller's
+        normals ``Z`` (N, S), ``C`` the Cholesky factor of the joint covariance (+ GPy's
+        jitter when it is needed).  ``LinAlgError`` when no jitter makes it positive."""
+        Xnew, sr, sc = self._joint_rows(Xnew)
+        N = Xnew.shape[0]
+        Z = f64(Z)
+        if Z.ndim != 2 or Z.shape[0] != N or Z.shape[1] < 1 or N < 1:
+            raise ValueError("Z must be (N, S) with N = %d rows and S >= 1, got %r"
+                             % (N, Z.shape))
+        S = Z.shape[1]
+        out = np.empty((N, S))
+        mean = np.empty((N, 1))
+        info, jit = C.c_int(0), C.c_double(0)
+        rc = lib().sgp_gp_posterior_draw(self.h, dptr(Xnew), N, sr, sc, dptr(Z), S, dptr(out),
+                                         dptr(mean), C.byref(info), C.byref(jit))
+        if rc > 0 or info.value != 0:
+            raise np.linalg.LinAlgError(lib().sgp_last_error(self.ctx.h).decode())
+        self.ctx.check(rc)
+        return out, mean, jit.value
 
     def factor(self):
         Linv = np.empty((self.n, self.n))

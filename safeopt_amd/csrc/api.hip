@@ -334,16 +334,17 @@ static int fit_with_jitter(sgp_gp* gp, int* chol_info, double* jitter_used) {
   gp->jitter = 0.0;
   gp->factored = true;
   int info = 0;
-  SGP_TRY(factor_gp(gp, &info));
-  if (info != 0) {
-    const double diag_mean = gp->kern.kdiag + gp->noise_var + 1e-8;
-    double jitter = diag_mean * 1e-6;
-    for (int t = 0; t < 5 && info != 0 && std::isfinite(jitter); ++t) {
-      gp->jitter = jitter;
-      SGP_TRY(factor_gp(gp, &info));
-      jitter *= 10.0;
-    }
-  }
+  double jitter = 0.0;
+  SGP_TRY(jitchol_loop(
+      [&](double* dm) {
+        *dm = gp->kern.kdiag + gp->noise_var + 1e-8;
+        return 0;
+      },
+      [&](double j, int* i) {
+        gp->jitter = j;
+        return factor_gp(gp, i);
+      },
+      &info, &jitter));
   if (chol_info) *chol_info = info;
   if (jitter_used) *jitter_used = gp->jitter;
   if (info != 0) {
@@ -532,6 +533,34 @@ int sgp_gp_predict(sgp_gp* gp, const double* Xnew, int64_t N,
   SGP_TRY(sgp_d2h(ctx, mean, mv, size_t(N) * sizeof(double)));
   SGP_TRY(sgp_d2h(ctx, var, mv + N, size_t(N) * sizeof(double)));
   return 0;
+}
+
+// The checks sgp_gp_predict makes, for the joint calls (which also cap N).
+static int joint_ready(sgp_gp* gp, int64_t N) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
+  SGP_CHECK(ctx, N <= SGP_MAX_JOINT, "N = %lld rows in one joint prediction (SGP_MAX_JOINT = %d)",
+            (long long)N, SGP_MAX_JOINT);
+  return 0;
+}
+
+int sgp_gp_predict_cov(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
+                       int64_t stride_col, double* mean, double* cov) {
+  SGP_TRY(joint_ready(gp, N));
+  if (N <= 0 || (!mean && !cov)) return 0;
+  return joint_predict_cov(gp, Xnew, N, stride_row, stride_col, mean, cov);
+}
+
+int sgp_gp_posterior_draw(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
+                          int64_t stride_col, const double* Z, int S, double* out, double* mean,
+                          int* chol_info, double* jitter_used) {
+  SGP_TRY(joint_ready(gp, N));
+  SGP_CHECK(gp->ctx, S >= 0, "S = %d samples", S);
+  if (N <= 0 || S == 0) return 0;
+  return joint_posterior_draw(gp, Xnew, N, stride_row, stride_col, Z, S, out, mean, chol_info,
+                              jitter_used);
 }
 
 int sgp_gp_get_factor(sgp_gp* gp, double* Linv, double* alpha) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -151,6 +152,11 @@ enum ScratchSlot : int {
   kSlotManyW = 10,      // kept: their W operands
   kSlotManyFlags = 11,  // kept: their flags, the pass result behind them
   kSlotHot = 12,        // launch_expander_many / launch_lipschitz_many: the hot waves and rows
+  kSlotJointA = 13,     // joint.hip: Sigma (N_pad x N_pad), the Cholesky factor in its lower part
+  kSlotJointLi = 14,    // ... the inverse factor the recursion forms along the way
+  kSlotJointT = 15,     // ... and its workspace
+  kSlotJointZ = 16,     // ... Z | out of a draw (N x S each)
+  kSlotJointVt = 17,    // ... V transposed, for the VALU yardstick of the SYRK only
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }
@@ -294,8 +300,45 @@ int sgp_poison(sgp_ctx* ctx, void* p, size_t bytes);       // SGP_POISON=1: fill
 int sgp_h2d(sgp_ctx* ctx, void* dst, const void* src, size_t bytes);
 int sgp_d2h(sgp_ctx* ctx, void* dst, const void* src, size_t bytes);  // syncs
 
+// GPy's util.linalg.jitchol around any factorisation: attempt(jitter, &info) factorises with
+// that much added to the diagonal (info = 0, or the first pivot that is not positive); after a
+// failure at 0 the jitter starts at diag_mean() * 1e-6 -- asked for only then -- and grows
+// tenfold per retry, five retries.  *info / *jitter_used describe the last attempt.
+template <class DiagMean, class Attempt>
+inline int jitchol_loop(DiagMean diag_mean, Attempt attempt, int* info, double* jitter_used) {
+  *info = 0;
+  *jitter_used = 0.0;
+  SGP_TRY(attempt(0.0, info));
+  if (*info != 0) {
+    double dm = 0.0;
+    SGP_TRY(diag_mean(&dm));
+    double jitter = dm * 1e-6;
+    for (int t = 0; t < 5 && *info != 0 && std::isfinite(jitter); ++t) {
+      *jitter_used = jitter;
+      SGP_TRY(attempt(jitter, info));
+      jitter *= 10.0;
+    }
+  }
+  return 0;
+}
+
 // ---- kernel launchers (implemented in the .hip files) -----------------------
 // factor.hip
+// Cholesky factor (-> lower part of A) and its inverse (-> Li, zeroed by the caller) of the
+// s x s matrix A, s a multiple of 32; T: workspace; all three with pitch ld.  *info_dev
+// (zeroed by the caller) receives the first pivot that is not positive (1-based).
+int factor_dense(sgp_ctx* ctx, double* A, double* Li, double* T, int64_t ld, int s,
+                 int* info_dev);
+// C (m x n) = alpha A (m x k) op(B) + beta C, row-major, op(B) = B^T with B (n x k) when transB:
+// the VALU GEMM of the factorisation
+int gemm_dense(sgp_ctx* ctx, bool transB, int m, int n, int k, double alpha, const double* A,
+               int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
+// joint.hip: the bodies of sgp_gp_predict_cov / sgp_gp_posterior_draw behind the argument checks
+int joint_predict_cov(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
+                      int64_t stride_col, double* mean, double* cov);
+int joint_posterior_draw(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
+                         int64_t stride_col, const double* Z, int S, double* out, double* mean,
+                         int* chol_info, double* jitter_used);
 int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
                          int64_t n1, const double* X2, int64_t n2, double* out,
                          int64_t ld, int symmetric_diag, double diag_add,

@@ -359,6 +359,16 @@ __global__ void k_pad_rows(const double* X, const double* alpha, int n, int n_pa
 
 }  // namespace
 
+int factor_dense(sgp_ctx* ctx, double* A, double* Li, double* T, int64_t ld, int s,
+                 int* info_dev) {
+  return factor_rec(ctx, A, Li, T, ld, 0, s, info_dev);
+}
+
+int gemm_dense(sgp_ctx* ctx, bool transB, int m, int n, int k, double alpha, const double* A,
+               int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc) {
+  return gemm(ctx, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
+}
+
 int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
                          int64_t n1, const double* X2, int64_t n2, double* out,
                          int64_t ld, int symmetric_diag, double diag_add,

@@ -169,6 +169,11 @@ class GPRegression(object):
     result back into ``kern.variance`` / ``kern.lengthscale`` / ``noise_var``.
     The reference never calls ``gp.optimize()``: fit first, then build the
     ``SafeOpt`` object (its ``scaling='auto'`` reads ``kern.Kdiag`` once).
+    ``predict_noiseless`` / ``predict`` / ``_raw_predict`` take ``full_cov=True``
+    (the joint covariance of up to ``SGP_MAX_JOINT`` rows), and
+    ``posterior_samples_f`` / ``posterior_samples`` draw sample paths from it; the
+    normal numbers come from NumPy's global generator, everything else is computed
+    on the device.
     """
 
     def __init__(self, X, Y, kernel=None, noise_var=1., device=None):
@@ -335,9 +340,11 @@ class GPRegression(object):
 
     def predict_noiseless(self, Xnew, full_cov=False):
         """Posterior mean and variance of the latent function, ``(N,1)`` each;
-        the variance is clipped to ``[1e-15, inf)`` as in GPy."""
+        the variance is clipped to ``[1e-15, inf)`` as in GPy.  ``full_cov=True``: the
+        joint covariance ``(N, N)`` instead (exactly symmetric, not clipped -- GPy clips
+        only the variance), at most ``SGP_MAX_JOINT`` rows."""
         if full_cov:
-            raise NotImplementedError("full_cov is not on SafeOpt's path")
+            return self._fitted().predict_cov(Xnew)
         return self._fitted().predict(Xnew)
 
     def _raw_predict(self, Xnew, full_cov=False):
@@ -346,8 +353,33 @@ class GPRegression(object):
     def predict(self, Xnew, full_cov=False, include_likelihood=True):
         mean, var = self.predict_noiseless(Xnew, full_cov=full_cov)
         if include_likelihood:
-            var = var + self.noise_var
+            if full_cov:
+                # GPy's Gaussian likelihood: the noise is independent per point
+                var[np.diag_indices(var.shape[0])] += self.noise_var
+            else:
+                var = var + self.noise_var
         return mean, var
+
+    def posterior_samples_f(self, X, size=10):
+        """``size`` sample paths of the latent function at the rows of ``X``, ``(N, 1,
+        size)`` as in GPy: one ``np.random.randn(N, size)`` on the global generator, then
+        one device call (joint covariance, its Cholesky factor -- GPy's jitter when it is
+        needed -- and ``mean + C Z``)."""
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        dev = self._fitted()
+        N = X.shape[0]
+        if N > _hip.MAX_JOINT:
+            raise ValueError("%d rows in one joint prediction: at most SGP_MAX_JOINT = %d"
+                             % (N, _hip.MAX_JOINT))
+        Z = np.random.randn(N, int(size))
+        out, _, _ = dev.draw(X, Z)
+        return out[:, None, :]
+
+    def posterior_samples(self, X, size=10):
+        """``posterior_samples_f`` plus observation noise: ``sqrt(noise_var)`` times a
+        second draw ``np.random.randn(N, 1, size)``."""
+        f = self.posterior_samples_f(X, size=size)
+        return f + np.sqrt(self.noise_var) * np.random.randn(*f.shape)
 
 
 kern = _types.SimpleNamespace(Kern=_Kern, RBF=RBF, Matern32=Matern32, Matern52=Matern52,
