@@ -938,7 +938,7 @@ int sgp_grid_confidence(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
   SepLaunch sl;
   SGP_TRY(launch_sweep_conf(ctx, g->gpdev, host, G, g->d, sp, co,
                             sep_launch(g, gps, host, G, &sl), /*rows_sharded=*/true));
-  return finish_safe_partials(g, sweep_num_partials(ctx, g->N), out2);
+  return finish_safe_partials(g, ctx->sweep_partials, out2);
 }
 
 int sgp_grid_posterior(sgp_grid* g, sgp_gp* const* gps, int G) {

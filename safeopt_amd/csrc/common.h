@@ -394,7 +394,6 @@ struct FitnessArgs {
   double* values;
   uint8_t* safe;
 };
-int sweep_num_partials(const sgp_ctx* ctx, int64_t N);
 // rows_sharded: the rows are a rank's shard of a grid -- the sweep kernel is then chosen
 // by the GPs alone (the same on every rank), never by the number of rows
 int launch_sweep_conf(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_host,

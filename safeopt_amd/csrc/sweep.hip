@@ -16,7 +16,7 @@
 //     mean(pt) = alpha . K[:, pt]                      (2n flops / row)
 // K (n x N doubles, 4 GB per GP at n = 500, N = 1e6) is never written to memory.
 //
-// Work split: workgroup = NW waves, wave w owns 16 rows (the MFMA N dimension);
+// Work split: workgroup = kNW = 4 waves, wave w owns 16 rows (the MFMA N dimension);
 // the waves of a workgroup share the staged A chunk through LDS (LDS-DMA,
 // double buffered, one barrier per stage).  The rows of A are processed in
 // chunks of 16 MFMA row blocks (256 rows) held in 16 accumulator slots per wave;
@@ -56,10 +56,12 @@ namespace {
 
 constexpr int kJC = 16;                // training points per stage (one j-block)
 constexpr int kSteps = kJC / 4;        // MFMA k-steps per stage
+constexpr int kNW = 4;                 // waves per workgroup (two workgroups per CU)
+constexpr int kSL = 16;                // accumulator slots per wave
 
-// LDS layout for SL accumulator slots per wave (SL x 16 rows of L^-1 per chunk):
-//   [2][A chunk | training rows | alpha]  exp table  [NW] broadcast buffers
-// SL = 16: 256 VGPRs, two waves per SIMD (two 4-wave workgroups per CU).  (32
+// LDS layout for kSL accumulator slots per wave (kSL x 16 rows of L^-1 per chunk):
+//   [2][A chunk | training rows | alpha]  exp table  [kNW] broadcast buffers
+// 16 slots: 256 VGPRs, two waves per SIMD (two 4-wave workgroups per CU).  (32
 // slots with one wave per SIMD and AGPRs, 8-wave workgroups and an explicit
 // ping-pong of the two waves of a SIMD were measured and dropped:
 // profiles/r02/experiments.txt, commits 1869720 and ad93c1b.)
@@ -69,9 +71,9 @@ constexpr int kSteps = kJC / 4;        // MFMA k-steps per stage
 // 48 doubles per k-row up to d = 4 (Q rows of up to 6 GPs), 16 beyond (2 GPs) --
 // what keeps two workgroups per CU inside 160 KB of LDS.
 // R: alpha chunks of up to R riders behind the leader's (kSweepRide, see launch_posterior)
-template <int SL, int D, int R = 0>
+template <int D, int R = 0>
 struct Lay {
-  static constexpr int kATile = SL * kSteps * 64;           // doubles
+  static constexpr int kATile = kSL * kSteps * 64;          // doubles
   static constexpr int kXTile = kJC * D;
   static constexpr int kBuf = kATile + kXTile + kJC * (1 + R);   // + alpha chunk(s)
   static constexpr int kTabOff = 2 * kBuf;                  // exp table
@@ -80,8 +82,8 @@ struct Lay {
   static constexpr int kKbBuf = 4 * kKbRow;
   static constexpr int kQPad = kKbRow - 64;                 // doubles per k-row
   static constexpr int kQMaxG = kQPad / 8;                  // 16 rows x 2 G doubles
-  static constexpr size_t bytes(int nw) {
-    return (size_t(kKbOff) + size_t(nw) * kKbBuf) * sizeof(double);
+  static constexpr size_t bytes() {
+    return (size_t(kKbOff) + size_t(kNW) * kKbBuf) * sizeof(double);
   }
   // double2 number i of a wave's staged Q block -> offset (doubles) in its buffer
   static __device__ __forceinline__ int qoff(int i) {
@@ -130,13 +132,11 @@ enum : uint32_t {
 struct SweepParams {
   const GpDev* gps;
   int G;
-  int mode;
 #ifdef SGP_INSTRUMENT
   int ablate;      // timing experiments (scripts/ablate.py), see SGP_ABL
 #endif
   SweepPoints pts;
   ConfOut conf;
-  FitnessArgs fit;
   const StageEnt* stages;   // [nstages] one tile's stage sequence (all GPs)
   int nstages;
   // Small factors stay in LDS for the whole launch (n <= ~112 rows in all GPs together):
@@ -150,7 +150,6 @@ struct SweepParams {
   int nride[SGP_MAX_GPS];   // riders of GP g: the GPs g + 1 .. g + nride[g] share its
                             // factor AND its covariances (GpDev::share) and have no stages
                             // of their own -- their alpha . k is formed in g's stages
-  int slots;                // accumulator slots per wave: 16 or 32 (host only)
   SepLaunch sep;            // tensor grid + factor tables (instances with SEP > 0)
 #ifdef SGP_STAMPS
   unsigned long long* stamps;   // [blocks][4 waves][8] cycles per phase (debug build)
@@ -319,9 +318,9 @@ __device__ __forceinline__ void narrow_groups(int ngrp, double (&accx)[kMaxNg],
 // instructions per value.  (Instantiated with D = 1: the rows themselves are not read.)
 // RES: the factors are small enough to stay in LDS for the whole launch (SweepParams::
 // res_xbase) -- instances of their own, so that the streaming instances carry none of it.
-template <int D, int NW, int SL, int MODE, bool SINGLE, int R = 0, int SEP = 0, bool RES = false>
-__global__ __launch_bounds__(64 * NW, 2) void k_sweep(SweepParams p) {
-  constexpr int kTilePts = 16 * NW;
+template <int D, bool SINGLE, int R = 0, int SEP = 0, bool RES = false>
+__global__ __launch_bounds__(64 * kNW, 2) void k_sweep(SweepParams p) {
+  constexpr int kTilePts = 16 * kNW;
   // (2 kMaxNg doubles live across the evaluation: where the registers are to be had)
   constexpr bool kAnEarly = SEP > 0 && SEP <= 2 && !(SEP == 2 && R > 0);
   // d >= 5 (and products at d = 4): no registers for the raw row of this tile and of
@@ -334,10 +333,9 @@ __global__ __launch_bounds__(64 * NW, 2) void k_sweep(SweepParams p) {
   // of the full slots (measured per variant: with factor tables the table loads want
   // the head of the queue)
   constexpr bool kDmaLate = SEP > 0;
-  typedef Lay<SL, D, R> L;
+  typedef Lay<D, R> L;
   constexpr int kATile = L::kATile, kBuf = L::kBuf, kXTile = L::kXTile;
   constexpr int kTabOff = L::kTabOff, kKbOff = L::kKbOff, kKbBuf = L::kKbBuf;
-  constexpr bool conf = MODE == MODE_CONF;   // compile-time: no dead state
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const double* tab = lds + kTabOff;
   exp_tab_init(lds + kTabOff);   // visible after the first staging barrier
@@ -422,18 +420,18 @@ __global__ __launch_bounds__(64 * NW, 2) void k_sweep(SweepParams p) {
 
   // What a stage needs besides its table entry comes by LDS-DMA from absolute
   // addresses of the entry: the A chunk (position t = row block bend-1-t, 2 KB each;
-  // wave w copies positions w, w + NW, ..) and the block [16 d rows | 16 alpha] of the
+  // wave w copies positions w, w + kNW, ..) and the block [16 d rows | 16 alpha] of the
   // j-block (one instruction of one wave; SEP: the 16 alpha only), + the alpha
   // blocks of the riders behind it.
   auto prefetch_to = [&](const StageEnt& e, uint32_t a_dst, uint32_t x_dst) {
     const int nact = int(e.word & SW_NACT_MASK);
     const uint64_t src0 = e.a_src - uint64_t(uint32_t(wave)) * e.rs_bytes;
-    const uint64_t step = uint64_t(e.rs_bytes) * NW;
+    const uint64_t step = uint64_t(e.rs_bytes) * kNW;
 #pragma unroll
-    for (int i = 0; i < SL / NW; ++i)
-      if (nact > wave + NW * i)
-        dma_2k(src0 - uint64_t(i) * step, a_dst + uint32_t(wave + NW * i) * 2048u, voff);
-    if (wave == NW - 1) {
+    for (int i = 0; i < kSL / kNW; ++i)
+      if (nact > wave + kNW * i)
+        dma_2k(src0 - uint64_t(i) * step, a_dst + uint32_t(wave + kNW * i) * 2048u, voff);
+    if (wave == kNW - 1) {
       if (SEP > 0) {
         if (lane < 8) dma_1k(e.xa, x_dst + kXTile * 8u, voff);
       } else {
@@ -719,40 +717,36 @@ __global__ __launch_bounds__(64 * NW, 2) void k_sweep(SweepParams p) {
                 double2_t{lo, up};
         }
       };
-      if (conf) {
-        emit(g, mu, kdiag);
-        if (R > 0) {
-          // riders: the leader's |L^-1 k|^2, their own alpha . k and prior variance
+      emit(g, mu, kdiag);
+      if (R > 0) {
+        // riders: the leader's |L^-1 k|^2, their own alpha . k and prior variance
 #pragma unroll
-          for (int f = 0; f < R; ++f) {
-            if (f < nr_cur) {
-              const double mu_f = sum_lane_groups_valu(mean_r[f]);
-              mean_r[f] = 0.0;
-              emit(g + 1 + f, mu_f, gpc[g + 1 + f].kern.kdiag);
-            }
+        for (int f = 0; f < R; ++f) {
+          if (f < nr_cur) {
+            const double mu_f = sum_lane_groups_valu(mean_r[f]);
+            mean_r[f] = 0.0;
+            emit(g + 1 + f, mu_f, gpc[g + 1 + f].kern.kdiag);
           }
         }
       }
 
       if (wcur & SW_TILE_END) {
-        if (conf) {
-          if (p.conf.Q && p.G <= L::kQMaxG && !SGP_ABL(16)) {
-            const int64_t row0 = int64_t(tile) * kTilePts + wave * 16;
-            const int64_t rows_left = p.pts.N - row0;
-            const int nq = (rows_left >= 16 ? 16 : (rows_left > 0 ? int(rows_left) : 0)) * p.G;
-            __builtin_amdgcn_wave_barrier();
-            double2_t* dst = reinterpret_cast<double2_t*>(p.conf.Q) + row0 * p.G;
-            for (int i = lane; i < nq; i += 64)
-              __builtin_nontemporal_store(
-                  *reinterpret_cast<const double2_t*>(kbw + L::qoff(i)), dst + i);
-            __builtin_amdgcn_wave_barrier();
-          }
-          if (p.conf.S) {
-            if (writer) p.conf.S[row] = safe ? 1 : 0;
-            // running maximum of l0 over the safe rows (folded over the wave and
-            // written once, when the wave has walked all its tiles)
-            lmax = fmax(lmax, (writer && safe) ? l0 : -INFINITY);
-          }
+        if (p.conf.Q && p.G <= L::kQMaxG && !SGP_ABL(16)) {
+          const int64_t row0 = int64_t(tile) * kTilePts + wave * 16;
+          const int64_t rows_left = p.pts.N - row0;
+          const int nq = (rows_left >= 16 ? 16 : (rows_left > 0 ? int(rows_left) : 0)) * p.G;
+          __builtin_amdgcn_wave_barrier();
+          double2_t* dst = reinterpret_cast<double2_t*>(p.conf.Q) + row0 * p.G;
+          for (int i = lane; i < nq; i += 64)
+            __builtin_nontemporal_store(
+                *reinterpret_cast<const double2_t*>(kbw + L::qoff(i)), dst + i);
+          __builtin_amdgcn_wave_barrier();
+        }
+        if (p.conf.S) {
+          if (writer) p.conf.S[row] = safe ? 1 : 0;
+          // running maximum of l0 over the safe rows (folded over the wave and
+          // written once, when the wave has walked all its tiles)
+          lmax = fmax(lmax, (writer && safe) ? l0 : -INFINITY);
         }
         safe = true;
         l0 = 0.0;
@@ -787,13 +781,13 @@ __global__ __launch_bounds__(64 * NW, 2) void k_sweep(SweepParams p) {
   }
 #ifdef SGP_STAMPS
   if (lane == 0) {
-    unsigned long long* o = p.stamps + (size_t(blockIdx.x) * NW + wave) * 8;
+    unsigned long long* o = p.stamps + (size_t(blockIdx.x) * kNW + wave) * 8;
     for (int i = 0; i < 8; ++i) o[i] = stamp_acc[i];
   }
 #endif
-  if (conf && p.conf.S) {
+  if (p.conf.S) {
     lmax = wave_max(lmax);
-    if (lane == 0) p.conf.partial[int(blockIdx.x) * NW + wave] = lmax;
+    if (lane == 0) p.conf.partial[int(blockIdx.x) * kNW + wave] = lmax;
   }
 }
 
@@ -1698,9 +1692,6 @@ __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
 
 
 // ---- launch -----------------------------------------------------------------------
-// Waves per workgroup: 4 (two workgroups per CU).
-int sweep_waves() { return 4; }
-
 // The stage sequence of one tile: for every GP, for every chunk of 16 row blocks
 // of L^-1, the j-blocks 0 .. bend-1 (only the slots at or below the diagonal are
 // active).  Depends on the block counts only, so it is rebuilt (and uploaded)
@@ -1781,35 +1772,34 @@ int stage_table(sgp_ctx* ctx, const GpDev* gh, int Geff, int d, bool sep, int kI
 
 // persistent: as many workgroups as are resident at once (256 VGPRs per thread
 // -> 8 waves per CU) walk over the tiles
-int sweep_grid_blocks(int num_cu, int64_t N, int nw, int slots) {
-  (void)slots;
-  const int64_t ntiles = (N + 16 * nw - 1) / (16 * nw);
-  const int64_t resident = int64_t(num_cu) * (8 / nw);
+int sweep_grid_blocks(int num_cu, int64_t N) {
+  const int64_t ntiles = (N + 16 * kNW - 1) / (16 * kNW);
+  const int64_t resident = int64_t(num_cu) * (8 / kNW);
   return int(ntiles < resident ? ntiles : resident);
 }
 
-template <int D, int NW, int SL, int MODE, bool SINGLE, int R = 0, int SEP = 0>
+template <int D, bool SINGLE, int R = 0, int SEP = 0>
 int launch_sweep_v(sgp_ctx* ctx, const SweepParams& p, double flops) {
   static bool attr_set = false;
   if (!attr_set) {
     SGP_HIP(ctx, hipFuncSetAttribute(
-                     reinterpret_cast<const void*>(&k_sweep<D, NW, SL, MODE, SINGLE, R, SEP, false>),
+                     reinterpret_cast<const void*>(&k_sweep<D, SINGLE, R, SEP, false>),
                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                     int(Lay<SL, D, R>::bytes(NW))));
+                     int(Lay<D, R>::bytes())));
     SGP_HIP(ctx, hipFuncSetAttribute(
-                     reinterpret_cast<const void*>(&k_sweep<D, NW, SL, MODE, SINGLE, R, SEP, true>),
+                     reinterpret_cast<const void*>(&k_sweep<D, SINGLE, R, SEP, true>),
                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                     int(Lay<SL, D, R>::bytes(NW))));
+                     int(Lay<D, R>::bytes())));
     attr_set = true;
   }
-  const int nblocks = sweep_grid_blocks(ctx->num_cu, p.pts.N, NW, SL);
+  const int nblocks = sweep_grid_blocks(ctx->num_cu, p.pts.N);
   SweepTimer timer;
   SGP_TRY(timer.begin(ctx, flops));
   SweepParams pp = p;
   {
     // small factors: every stage's positions stay in LDS for the whole launch
     // (SGP_NO_RESIDENT=1 / sgp_ctx_set_sweep(+ 16): stream them, A/B runs)
-    typedef Lay<SL, D, R> L;
+    typedef Lay<D, R> L;
     static const bool off = getenv("SGP_NO_RESIDENT") != nullptr;
     const size_t xblk = size_t(L::kXTile + kJC * (1 + R)) * 8;
     const size_t need = size_t(ctx->stage_slots) * 2048 + size_t(p.nstages) * xblk;
@@ -1820,54 +1810,50 @@ int launch_sweep_v(sgp_ctx* ctx, const SweepParams& p, double flops) {
   static const int ablate = getenv("SGP_ABLATE") ? atoi(getenv("SGP_ABLATE")) : 0;
   pp.ablate = ablate;
 #endif
-  const size_t lds_bytes = Lay<SL, D, R>::bytes(NW);
+  const size_t lds_bytes = Lay<D, R>::bytes();
 #ifdef SGP_STAMPS
   static unsigned long long* stamps_dev = nullptr;
-  if (!stamps_dev) SGP_HIP(ctx, hipMalloc(&stamps_dev, size_t(4096) * NW * 8 * 8));
+  if (!stamps_dev) SGP_HIP(ctx, hipMalloc(&stamps_dev, size_t(4096) * kNW * 8 * 8));
   pp.stamps = stamps_dev;
 #endif
   if (pp.resident)
-    hipLaunchKernelGGL((k_sweep<D, NW, SL, MODE, SINGLE, R, SEP, true>), dim3(nblocks),
-                       dim3(64 * NW), lds_bytes, ctx->stream, pp);
+    hipLaunchKernelGGL((k_sweep<D, SINGLE, R, SEP, true>), dim3(nblocks),
+                       dim3(64 * kNW), lds_bytes, ctx->stream, pp);
   else
-    hipLaunchKernelGGL((k_sweep<D, NW, SL, MODE, SINGLE, R, SEP, false>), dim3(nblocks),
-                       dim3(64 * NW), lds_bytes, ctx->stream, pp);
+    hipLaunchKernelGGL((k_sweep<D, SINGLE, R, SEP, false>), dim3(nblocks),
+                       dim3(64 * kNW), lds_bytes, ctx->stream, pp);
   SGP_HIP(ctx, hipGetLastError());
 #ifdef SGP_STAMPS
   {
-    std::vector<unsigned long long> h(size_t(nblocks) * NW * 8);
+    std::vector<unsigned long long> h(size_t(nblocks) * kNW * 8);
     SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     SGP_HIP(ctx, hipMemcpy(h.data(), stamps_dev, h.size() * 8, hipMemcpyDeviceToHost));
     static const char* names[8] = {"prefetch", "evaluate", "narrow", "transpose", "slots",
                                    "fold+epilogue", "dma-wait", "barrier"};
     double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot = 0;
-    for (size_t w = 0; w < size_t(nblocks) * NW; ++w)
+    for (size_t w = 0; w < size_t(nblocks) * kNW; ++w)
       for (int i = 0; i < 8; ++i) sum[i] += double(h[w * 8 + i]);
     for (int i = 0; i < 8; ++i) tot += sum[i];
     fprintf(stderr, "stamps (ticks per wave, %% of loop):");
     for (int i = 0; i < 8; ++i)
-      fprintf(stderr, "  %s %.0f (%.1f%%)", names[i], sum[i] / (double(NW) * nblocks),
+      fprintf(stderr, "  %s %.0f (%.1f%%)", names[i], sum[i] / (double(kNW) * nblocks),
               100.0 * sum[i] / tot);
-    fprintf(stderr, "  | loop %.0f\n", tot / (double(NW) * nblocks));
+    fprintf(stderr, "  | loop %.0f\n", tot / (double(kNW) * nblocks));
   }
 #endif
   return timer.end(ctx);
 }
 
-template <int D, int NW, int SL>
-int launch_sweep_w(sgp_ctx* ctx, const SweepParams& p, double flops) {
+// the instance of an input dimension: with riders, one-part kernels, products
+template <int D>
+int launch_sweep_d(sgp_ctx* ctx, const SweepParams& p, double flops) {
   if constexpr (D <= 3) {       // (the d = 4 instance with riders would spill)
     bool riders = false;
     for (int g = 0; g < SGP_MAX_GPS; ++g) riders = riders || p.nride[g] > 0;
-    if (riders) return launch_sweep_v<D, NW, SL, MODE_CONF, true, kSweepRide>(ctx, p, flops);
+    if (riders) return launch_sweep_v<D, true, kSweepRide>(ctx, p, flops);
   }
-  return p.single ? launch_sweep_v<D, NW, SL, MODE_CONF, true>(ctx, p, flops)
-                  : launch_sweep_v<D, NW, SL, MODE_CONF, false>(ctx, p, flops);
-}
-
-template <int D>
-int launch_sweep_d(sgp_ctx* ctx, const SweepParams& p, double flops) {
-  return launch_sweep_w<D, 4, 16>(ctx, p, flops);
+  return p.single ? launch_sweep_v<D, true>(ctx, p, flops)
+                  : launch_sweep_v<D, false>(ctx, p, flops);
 }
 
 // tensor grid + RBF kernels: the instances that read factor tables (SEP axes; D = 1:
@@ -1876,39 +1862,36 @@ template <int SEP>
 int launch_sweep_sep(sgp_ctx* ctx, const SweepParams& p, double flops) {
   bool riders = false;
   for (int g = 0; g < SGP_MAX_GPS; ++g) riders = riders || p.nride[g] > 0;
-  if (riders) return launch_sweep_v<1, 4, 16, MODE_CONF, true, kSweepRide, SEP>(ctx, p, flops);
-  return launch_sweep_v<1, 4, 16, MODE_CONF, true, 0, SEP>(ctx, p, flops);
+  if (riders) return launch_sweep_v<1, true, kSweepRide, SEP>(ctx, p, flops);
+  return launch_sweep_v<1, true, 0, SEP>(ctx, p, flops);
 }
 
-int launch_posterior(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d, int Geff,
+int launch_posterior(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d, int Geff,
                      double flops, const SepLaunch* sep, bool rows_sharded, int64_t sel_rows);
 
+// fit: a swarm-fitness call (null: a confidence sweep into a.conf).
 // rows_sharded: the rows are a rank's shard of a grid (sgp_grid_*) -- the kernel is then
 // chosen by the GPs alone, never by the number of rows (same kernel on every rank).
 // sel_rows >= 0: the kernel is chosen as for that many rows (a rank's block of a sharded
 // swarm: the kernel of the whole swarm, sgp_swarm_run_shard)
-int launch_sweep(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d,
-                 const SepLaunch* sep = nullptr, bool rows_sharded = false,
-                 int64_t sel_rows = -1) {
+int launch_sweep(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d,
+                 const FitnessArgs* fit = nullptr, const SepLaunch* sep = nullptr,
+                 bool rows_sharded = false, int64_t sel_rows = -1) {
   // algorithmic flops: G * (n^2 + 2n) per row
   double flops = 0.0;
-  const int Geff =
-      (p.mode == MODE_FITNESS && p.fit.swarm_type == SGP_SWARM_GREEDY) ? 1
-                                                                       : p.G;
+  const int Geff = (fit && fit->swarm_type == SGP_SWARM_GREEDY) ? 1 : a.G;
   for (int g = 0; g < Geff; ++g)
-    flops += (double(gh[g].n) * gh[g].n + 2.0 * gh[g].n) * double(p.pts.N);
-  if (p.pts.N <= 0) return 0;
-  SweepParams q = p;
-  const bool fitness = p.mode == MODE_FITNESS;
-  if (fitness) {
+    flops += (double(gh[g].n) * gh[g].n + 2.0 * gh[g].n) * double(a.pts.N);
+  if (a.pts.N <= 0) return 0;
+  SweepArgs q = a;
+  if (fit) {
     // SafeOptSwarm._compute_particle_fitness (gp_opt.py:901-1013) = the posterior of
     // the swarm's GPs (the sweep, mean / var only) + the shaping of fitness.h on
     // those (k_fitness_small: one thread per particle).  The particles are few next
     // to a grid: the 16 bytes per (GP, particle) in between cost nothing, and the
     // sweep kernels need no second set of instances (which spilled registers).
-    const size_t np = size_t(Geff) * size_t(p.pts.N);
+    const size_t np = size_t(Geff) * size_t(a.pts.N);
     SGP_TRY(sgp_reserve(ctx, &ctx->pair_post, 2 * np * sizeof(double)));
-    q.mode = MODE_CONF;
     q.conf = ConfOut{};
     q.conf.mean = static_cast<double*>(ctx->pair_post.p);
     q.conf.var = q.conf.mean + np;
@@ -1916,58 +1899,42 @@ int launch_sweep(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d,
     for (int i = 0; i < SGP_MAX_GPS; ++i) q.conf.fmin[i] = -INFINITY;
   }
   int rc = launch_posterior(ctx, q, gh, d, Geff, flops, sep, rows_sharded, sel_rows);
-  if (rc != 0 || !fitness) return rc;
-  return launch_fitness_small(ctx, p.G, p.pts.N, q.conf.mean, q.conf.var, p.fit);
+  if (rc != 0 || !fit) return rc;
+  return launch_fitness_small(ctx, a.G, a.pts.N, q.conf.mean, q.conf.var, *fit);
 }
 
 // The confidence sweep proper: the paired-wave kernel from 257 rows of L^-1 on, the 4-wave
 // kernel below, the resident-factor kernel (sweep_mid.hip) for 49 .. 128 observations of
 // single-part kernels, the VALU kernel (sweep_tiny.hip) up to 48 observations.
-int launch_posterior(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d, int Geff,
+int launch_posterior(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d, int Geff,
                      double flops, const SepLaunch* sep, bool rows_sharded, int64_t sel_rows) {
-  if (tiny_sweep_wanted(ctx, gh, Geff, sel_rows >= 0 ? sel_rows : p.pts.N, rows_sharded)) {
+  if (tiny_sweep_wanted(ctx, gh, Geff, sel_rows >= 0 ? sel_rows : a.pts.N, rows_sharded)) {
     ctx->last_sweep = 3;
-    SweepArgs a{p.gps, p.G, p.mode, p.pts, p.conf, p.fit};
     return launch_sweep_tiny(ctx, a, gh, d, Geff, flops);    // (sets ctx->sweep_partials)
   }
-  if (mid_sweep_wanted(ctx, gh, Geff, d) || mid_passes_wanted(ctx, gh, Geff, sep, p.conf)) {
+  if (mid_sweep_wanted(ctx, gh, Geff, d) || mid_passes_wanted(ctx, gh, Geff, sep, a.conf)) {
     ctx->last_sweep = 6;
-    SweepArgs a{p.gps, p.G, p.mode, p.pts, p.conf, p.fit};
     return launch_sweep_mid(ctx, a, gh, d, Geff, flops, sep);   // (sets ctx->sweep_partials)
   }
   if (pair_sweep_wanted(ctx, gh, Geff)) {
     ctx->last_sweep = 2;
-    SweepArgs a{p.gps, p.G, p.mode, p.pts, p.conf, p.fit};
     return launch_sweep_pair(ctx, a, gh, d, Geff, flops, sep);   // (sets ctx->sweep_partials)
   }
   ctx->last_sweep = 1;
-  ctx->sweep_partials = sweep_grid_blocks(ctx->num_cu, p.pts.N, sweep_waves(), 16) *
-                        sweep_waves();
-  SweepParams q = p;
-  q.slots = 16;            // accumulator slots per wave
+  ctx->sweep_partials = sweep_grid_blocks(ctx->num_cu, a.pts.N) * kNW;
+  SweepParams q{};
+  q.gps = a.gps;
+  q.G = a.G;
+  q.pts = a.pts;
+  q.conf = a.conf;
   q.single = 1;
   for (int g = 0; g < Geff; ++g) q.single = q.single && gh[g].kern.n_parts == 1;
   // followers of a shared factor ride in their leader's stages (sweep_shared.h)
-  bool rides[SGP_MAX_GPS] = {};
-  static const bool no_ride = getenv("SGP_PAIR_RIDE") && atoi(getenv("SGP_PAIR_RIDE")) == 0;
-  for (int g = 0; g < SGP_MAX_GPS; ++g) q.nride[g] = 0;
   // (tensor-grid instances: one set of tables per leader, whatever the input dimension)
-  if (no_ride || !sweep_riders(gh, Geff, sep ? 1 : d, q.single != 0 || sep != nullptr,
-                               kSweepRide, 3, rides, q.nride))
-    for (int g = 0; g < SGP_MAX_GPS; ++g) {
-      rides[g] = false;
-      q.nride[g] = 0;
-    }
-  for (int g = 0, leader = 0; g < Geff; ++g) {
-    q.ride_delta[g] = 0;
-    if (!rides[g]) {
-      leader = g;
-      continue;
-    }
-    q.ride_delta[g] = (long long)(reinterpret_cast<intptr_t>(gh[g].XA) -
-                                  reinterpret_cast<intptr_t>(gh[leader].XA));
-  }
-  SGP_TRY(stage_table(ctx, gh, Geff, d, sep != nullptr, q.slots, rides, &q.stages, &q.nstages));
+  bool rides[SGP_MAX_GPS];
+  assign_riders(gh, Geff, sep ? 1 : d, q.single != 0 || sep != nullptr, kSweepRide, 3, rides,
+                q.nride, q.ride_delta);
+  SGP_TRY(stage_table(ctx, gh, Geff, d, sep != nullptr, kSL, rides, &q.stages, &q.nstages));
   if (sep) {
     q.sep = *sep;
     switch (sep->naxes) {
@@ -1994,37 +1961,18 @@ int launch_posterior(sgp_ctx* ctx, const SweepParams& p, const GpDev* gh, int d,
 
 }  // namespace
 
-// Number of partials of max l0[S] the LAST confidence sweep left in
-// ConfOut::partial (one per wave / wave pair of every launched workgroup).
-int sweep_num_partials(const sgp_ctx* ctx, int64_t N) {
-  (void)N;
-  return ctx->sweep_partials;
-}
-
 int launch_sweep_conf(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_host,
                       int G, int d, SweepPoints pts, ConfOut out, const SepLaunch* sep,
                       bool rows_sharded) {
-  SweepParams p{};
-  p.gps = gps_dev;
-  p.G = G;
-  p.mode = MODE_CONF;
-  p.pts = pts;
-  p.conf = out;
-  p.fit = FitnessArgs{};
-  return launch_sweep(ctx, p, gps_host, d, sep, rows_sharded);
+  return launch_sweep(ctx, SweepArgs{gps_dev, G, pts, out}, gps_host, d, nullptr, sep,
+                      rows_sharded);
 }
 
 int launch_sweep_fitness(sgp_ctx* ctx, const GpDev* gps_dev,
                          const GpDev* gps_host, int G, int d, SweepPoints pts,
                          FitnessArgs fa, int64_t sel_rows) {
-  SweepParams p{};
-  p.gps = gps_dev;
-  p.G = G;
-  p.mode = MODE_FITNESS;
-  p.pts = pts;
-  p.conf = ConfOut{};
-  p.fit = fa;
-  return launch_sweep(ctx, p, gps_host, d, nullptr, false, sel_rows);
+  return launch_sweep(ctx, SweepArgs{gps_dev, G, pts, ConfOut{}}, gps_host, d, &fa, nullptr,
+                      false, sel_rows);
 }
 
 

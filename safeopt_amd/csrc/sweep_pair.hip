@@ -156,7 +156,6 @@ struct PairParams {
   int G;
   SweepPoints pts;
   ConfOut conf;
-  FitnessArgs fit;
   const PStage* stages;   // [nstages] one tile's stage sequence (all GPs)
   int nstages;
   // Work split of the launch (pair_plan).  Workgroup w runs the tiles w, w + W, ..
@@ -411,14 +410,15 @@ __device__ __forceinline__ uint32_t cold_lane() {
 // per-tile state of the row epilogue (only the finishing wave of a pair has it)
 struct RowState {
   bool safe = true;
-  double l0 = 0.0, values = 0.0, interest = 1.0, total_pen = 0.0, lower = 0.0;
+  double l0 = 0.0;
   double lmax = -INFINITY;   // max l0 over the safe rows this wave has seen
 };
 
-// One GP's posterior at the wave's 16 rows -> confidence interval / fitness
-// shaping; at the end of a tile the rows leave.  `mu`, `var` are complete
-// (both halves of the pair); lane l works on row l & 15.
-template <int D, int MODE>
+// One GP's posterior at the wave's 16 rows -> its confidence interval and the
+// safe-set test (update_confidence_intervals + compute_safe_set, gp_opt.py:453-481);
+// at the end of a tile the rows leave.  `mu`, `var` are complete (both halves of
+// the pair); lane l works on row l & 15.
+template <int D>
 __device__ __forceinline__ void row_epilogue(const PairParams& p, RowState& rs,
                                              uint32_t w, int tile, int pr, int lane,
                                              double mu, double var, double* qst) {
@@ -427,95 +427,46 @@ __device__ __forceinline__ void row_epilogue(const PairParams& p, RowState& rs,
   // which multiplies, then adds)
 #pragma clang fp contract(off)
   typedef LayP<D> L;
-  constexpr bool conf = MODE == MODE_CONF;
   const double sd = sqrt(var);
   const int g = int(w >> PW_G_SHIFT) & 7;
   const int64_t row = int64_t(tile) * kTileRows + pr * 16 + (lane & 15);
   const bool writer = (row < p.pts.N) && (lane < 16);
-  const int st = p.fit.swarm_type;
-  if (conf) {
-    // update_confidence_intervals + compute_safe_set (gp_opt.py:453-481)
-    const double lo = mu - p.conf.beta * sd;
-    const double up = mu + p.conf.beta * sd;
-    if (g == 0) rs.l0 = lo;
-    rs.safe = rs.safe && (lo > p.conf.fmin[g]);
-    if (writer && !PGP_ABL(16)) {
-      __builtin_nontemporal_store(mu, p.conf.mean + int64_t(g) * p.pts.N + row);
-      __builtin_nontemporal_store(var, p.conf.var + int64_t(g) * p.pts.N + row);
-    }
-    // Q row = [l0, u0, l1, u1, ...] (gp_opt.py:375): collected in LDS, written
-    // as ONE contiguous block per wave at the end of the tile
-    if (p.conf.Q && lane < 16 && !PGP_ABL(16)) {
-      if (p.G <= L::kQMaxG)
-        *reinterpret_cast<double2_t*>(qst + (lane * p.G + g) * 2) = double2_t{lo, up};
-      else if (writer)
-        *reinterpret_cast<double2_t*>(p.conf.Q + (row * p.G + g) * 2) =
-            double2_t{lo, up};
-    }
-  } else {
-    // SafeOptSwarm._compute_particle_fitness, gp_opt.py:925-1013
-    const FitnessArgs& f = p.fit;
-    rs.lower = mu - f.beta * sd;
-    if (g == 0) {
-      rs.values = sd / f.scaling[0];
-      if (st == SGP_SWARM_EXPANDERS) rs.interest = double(p.G);
-      if (st == SGP_SWARM_MAXIMIZERS) {
-        const double upper = mu + f.beta * sd;
-        const double z = 10.0 * (upper - f.best_lower_bound) / f.scaling[0];
-        rs.interest = 1.0 / (1.0 + exp(-z));  // scipy.special.expit
-      }
-    } else {
-      rs.values = fmax(rs.values, sd / f.scaling[g]);
-    }
-    if (f.fmin[g] != -INFINITY) {
-      double slack = rs.lower - f.fmin[g];
-      rs.safe = rs.safe && (slack >= 0.0);
-      if (st != SGP_SWARM_SAFE_SET) {
-        slack = slack / f.scaling[g];
-        rs.total_pen += swarm_penalty(slack);
-        if (st == SGP_SWARM_EXPANDERS) {
-          // scipy.stats.norm.pdf(slack, scale=0.2)
-          const double z = slack / 0.2;
-          rs.interest *= exp(-0.5 * z * z) / 2.5066282746310002 / 0.2;
-        }
-      }
-    }
+  const double lo = mu - p.conf.beta * sd;
+  const double up = mu + p.conf.beta * sd;
+  if (g == 0) rs.l0 = lo;
+  rs.safe = rs.safe && (lo > p.conf.fmin[g]);
+  if (writer && !PGP_ABL(16)) {
+    __builtin_nontemporal_store(mu, p.conf.mean + int64_t(g) * p.pts.N + row);
+    __builtin_nontemporal_store(var, p.conf.var + int64_t(g) * p.pts.N + row);
+  }
+  // Q row = [l0, u0, l1, u1, ...] (gp_opt.py:375): collected in LDS, written
+  // as ONE contiguous block per wave at the end of the tile
+  if (p.conf.Q && lane < 16 && !PGP_ABL(16)) {
+    if (p.G <= L::kQMaxG)
+      *reinterpret_cast<double2_t*>(qst + (lane * p.G + g) * 2) = double2_t{lo, up};
+    else if (writer)
+      *reinterpret_cast<double2_t*>(p.conf.Q + (row * p.G + g) * 2) =
+          double2_t{lo, up};
   }
 
   if (w & PW_TILE_END) {
-    if (conf) {
-      if (p.conf.Q && p.G <= L::kQMaxG && !PGP_ABL(16)) {
-        const int64_t row0 = int64_t(tile) * kTileRows + pr * 16;
-        const int64_t left = p.pts.N - row0;
-        const int nq = (left >= 16 ? 16 : (left > 0 ? int(left) : 0)) * p.G;
-        __builtin_amdgcn_wave_barrier();
-        double2_t* dst = reinterpret_cast<double2_t*>(p.conf.Q) + row0 * p.G;
-        for (int i = lane; i < nq; i += 64)
-          __builtin_nontemporal_store(
-              *reinterpret_cast<const double2_t*>(qst + 2 * i), dst + i);
-        __builtin_amdgcn_wave_barrier();
-      }
-      if (p.conf.S) {
-        if (writer) p.conf.S[row] = rs.safe ? 1 : 0;
-        rs.lmax = fmax(rs.lmax, (writer && rs.safe) ? rs.l0 : -INFINITY);
-      }
-    } else if (writer) {
-      double out;
-      bool ok = rs.safe;
-      if (st == SGP_SWARM_GREEDY) {
-        out = rs.lower;
-        ok = true;
-      } else if (st == SGP_SWARM_SAFE_SET) {
-        out = rs.lower;
-      } else {
-        out = (rs.values + rs.total_pen) * rs.interest;
-      }
-      p.fit.values[row] = out;
-      p.fit.safe[row] = ok ? 1 : 0;
+    if (p.conf.Q && p.G <= L::kQMaxG && !PGP_ABL(16)) {
+      const int64_t row0 = int64_t(tile) * kTileRows + pr * 16;
+      const int64_t left = p.pts.N - row0;
+      const int nq = (left >= 16 ? 16 : (left > 0 ? int(left) : 0)) * p.G;
+      __builtin_amdgcn_wave_barrier();
+      double2_t* dst = reinterpret_cast<double2_t*>(p.conf.Q) + row0 * p.G;
+      for (int i = lane; i < nq; i += 64)
+        __builtin_nontemporal_store(
+            *reinterpret_cast<const double2_t*>(qst + 2 * i), dst + i);
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (p.conf.S) {
+      if (writer) p.conf.S[row] = rs.safe ? 1 : 0;
+      rs.lmax = fmax(rs.lmax, (writer && rs.safe) ? rs.l0 : -INFINITY);
     }
     rs.safe = true;
-    rs.l0 = rs.values = rs.total_pen = rs.lower = 0.0;
-    rs.interest = 1.0;
+    rs.l0 = 0.0;
   }
 }
 
@@ -526,11 +477,10 @@ __device__ __forceinline__ void row_epilogue(const PairParams& p, RowState& rs,
 // parts (SepLaunch, sweep.hip): a covariance is the product of SEP table entries -- one
 // 16-byte load per axis, lane and stage, requested a stage ahead -- instead of ~20 fp64
 // instructions per value.  (Instantiated with D = 1: the rows themselves are not read.)
-template <int D, int MODE, bool SINGLE, int H, int R, int SEP>
+template <int D, bool SINGLE, int H, int R, int SEP>
 __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
                                           const int lane, const int wave) {
   typedef LayP<D, R> L;
-  constexpr bool conf = MODE == MODE_CONF;
   // (32 more live registers across the evaluation: instances that would spill for
   // it -- d >= 6, product kernels -- do without)
   // (instances with riders: up to d = 3 -- at d = 4 the fetch spills -- and without the row
@@ -877,8 +827,8 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
     const double var = fmax(kdiag - ssq, 1e-15);  // GPy clip
     const int nr = R > 0 ? p.nride[g] : 0;
     // (the tile ends behind the last rider)
-    row_epilogue<D, MODE>(p, rs, nr > 0 ? pend_w & ~uint32_t(PW_TILE_END) : pend_w, pend_tile,
-                          pr, lane, mu, var, qst);
+    row_epilogue<D>(p, rs, nr > 0 ? pend_w & ~uint32_t(PW_TILE_END) : pend_w, pend_tile,
+                    pr, lane, mu, var, qst);
     if (R > 0) {
 #pragma unroll
       for (int f = 0; f < R; ++f) {
@@ -890,7 +840,7 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
           uint32_t wf = (pend_w & ~uint32_t((7u << PW_G_SHIFT) | PW_TILE_END)) |
                         (uint32_t(gf) << PW_G_SHIFT);
           if (f == nr - 1) wf |= pend_w & PW_TILE_END;
-          row_epilogue<D, MODE>(p, rs, wf, pend_tile, pr, lane, mu_f, var_f, qst);
+          row_epilogue<D>(p, rs, wf, pend_tile, pr, lane, mu_f, var_f, qst);
         }
       }
     }
@@ -1134,15 +1084,13 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
     for (int i = 0; i < 8; ++i) o[i] = stamp_acc[i];
   }
 #endif
-  if (H == kFin) {
-    if (conf && p.conf.S) {
-      const double m = wave_max(rs.lmax);
-      if (lane == 0) p.conf.partial[int(blockIdx.x) * kPairs + pr] = m;
-    }
+  if (H == kFin && p.conf.S) {
+    const double m = wave_max(rs.lmax);
+    if (lane == 0) p.conf.partial[int(blockIdx.x) * kPairs + pr] = m;
   }
 }
 
-template <int D, int MODE, bool SINGLE, int R = 0, int SEP = 0>
+template <int D, bool SINGLE, int R = 0, int SEP = 0>
 __global__ __launch_bounds__(512, 1) void k_sweep_pair(PairParams p) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   exp_tab_init(lds + LayP<D, R>::kTabOff);   // visible after the first barrier
@@ -1150,9 +1098,9 @@ __global__ __launch_bounds__(512, 1) void k_sweep_pair(PairParams p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave < 4)
-    pair_loop<D, MODE, SINGLE, 0, R, SEP>(p, lds, lane, wave);
+    pair_loop<D, SINGLE, 0, R, SEP>(p, lds, lane, wave);
   else
-    pair_loop<D, MODE, SINGLE, 1, R, SEP>(p, lds, lane, wave);
+    pair_loop<D, SINGLE, 1, R, SEP>(p, lds, lane, wave);
 }
 
 // Remainder tiles that were cut into runs of chunks (PairParams::split_*): the
@@ -1161,9 +1109,7 @@ __global__ __launch_bounds__(512, 1) void k_sweep_pair(PairParams p) {
 // row's posterior does not depend on whether its tile was split (same bits), and
 // the row epilogue runs exactly as in k_sweep_pair.  One 512-thread workgroup per
 // tile, wave / lane = the wave / lane of the sweep.
-template <int MODE>
 __global__ __launch_bounds__(512) void k_pair_split_finish(PairParams p) {
-  constexpr bool conf = MODE == MODE_CONF;
   __shared__ double sh_ex[kPairs][32];
   __shared__ __attribute__((aligned(16))) double sh_q[kPairs][LayP<1>::kQCap];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1195,11 +1141,11 @@ __global__ __launch_bounds__(512) void k_pair_split_finish(PairParams p) {
       const double var = fmax(p.gps[g].kern.kdiag - ssq_t, 1e-15);  // GPy clip
       uint32_t w = (uint32_t(g) << PW_G_SHIFT) | PW_GP_END;
       if (g == p.geff - 1) w |= PW_TILE_END;
-      row_epilogue<1, MODE>(p, rs, w, tile, pr, lane, mu_t, var, sh_q[pr]);
+      row_epilogue<1>(p, rs, w, tile, pr, lane, mu_t, var, sh_q[pr]);
     }
     __syncthreads();
   }
-  if (half == 1 && conf && p.conf.S) {
+  if (half == 1 && p.conf.S) {
     const double m = wave_max(rs.lmax);
     if (lane == 0) p.conf.partial[p.split_partial0 + pt * kPairs + pr] = m;
   }
@@ -1400,12 +1346,12 @@ PairPlan pair_plan(const sgp_ctx* ctx, int64_t N) {
   return pl;
 }
 
-template <int D, int MODE, bool SINGLE, int R = 0, int SEP = 0>
+template <int D, bool SINGLE, int R = 0, int SEP = 0>
 int launch_pair_v(sgp_ctx* ctx, const PairParams& p, double flops) {
   static bool attr_set = false;
   if (!attr_set) {
     SGP_HIP(ctx, hipFuncSetAttribute(
-                     reinterpret_cast<const void*>(&k_sweep_pair<D, MODE, SINGLE, R, SEP>),
+                     reinterpret_cast<const void*>(&k_sweep_pair<D, SINGLE, R, SEP>),
                      hipFuncAttributeMaxDynamicSharedMemorySize,
                      int(LayP<D, R>::bytes())));
     attr_set = true;
@@ -1439,10 +1385,10 @@ int launch_pair_v(sgp_ctx* ctx, const PairParams& p, double flops) {
   if (!stamps_dev) SGP_HIP(ctx, hipMalloc(&stamps_dev, size_t(4096) * 64 * 8));
   pp.stamps = stamps_dev;
 #endif
-  hipLaunchKernelGGL((k_sweep_pair<D, MODE, SINGLE, R, SEP>), dim3(nblocks), dim3(512),
+  hipLaunchKernelGGL((k_sweep_pair<D, SINGLE, R, SEP>), dim3(nblocks), dim3(512),
                      (LayP<D, R>::bytes()), ctx->stream, pp);
   if (pl.parts > 0)
-    hipLaunchKernelGGL((k_pair_split_finish<MODE>), dim3(pl.count), dim3(512), 0,
+    hipLaunchKernelGGL(k_pair_split_finish, dim3(pl.count), dim3(512), 0,
                        ctx->stream, pp);
   SGP_HIP(ctx, hipGetLastError());
 #ifdef PGP_STAMPS
@@ -1473,10 +1419,10 @@ int launch_pair_v(sgp_ctx* ctx, const PairParams& p, double flops) {
 template <int D>
 int launch_pair_d(sgp_ctx* ctx, const PairParams& p, bool single, bool riders, double flops) {
   if constexpr (D <= 4) {
-    if (riders) return launch_pair_v<D, MODE_CONF, true, kMaxRide>(ctx, p, flops);
+    if (riders) return launch_pair_v<D, true, kMaxRide>(ctx, p, flops);
   }
-  return single ? launch_pair_v<D, MODE_CONF, true>(ctx, p, flops)
-                : launch_pair_v<D, MODE_CONF, false>(ctx, p, flops);
+  return single ? launch_pair_v<D, true>(ctx, p, flops)
+                : launch_pair_v<D, false>(ctx, p, flops);
 }
 
 }  // namespace
@@ -1495,11 +1441,6 @@ bool pair_sweep_wanted(const sgp_ctx* ctx, const GpDev* gh, int Geff) {
   return np > 256;
 }
 
-int pair_sweep_partials(const sgp_ctx* ctx, int64_t N) {
-  (void)N;
-  return ctx->sweep_partials;     // set by the launch (pair_plan)
-}
-
 int launch_sweep_pair(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d,
                       int Geff, double flops, const SepLaunch* sep) {
   PairParams p{};
@@ -1507,43 +1448,25 @@ int launch_sweep_pair(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d,
   p.G = a.G;
   p.pts = a.pts;
   p.conf = a.conf;
-  p.fit = a.fit;
   p.geff = Geff;
   p.shared_mask = 0;
   for (int g = 0; g < Geff; ++g)
     if (gh[g].share >= 0) p.shared_mask |= 1u << g;
-  // (a.mode is MODE_CONF: launch_sweep turns a fitness call into posterior + shaping)
   bool single = true;
   for (int g = 0; g < Geff; ++g) single = single && gh[g].kern.n_parts == 1;
-  bool rides[SGP_MAX_GPS] = {};
-  static const bool no_ride = getenv("SGP_PAIR_RIDE") && atoi(getenv("SGP_PAIR_RIDE")) == 0;
-  for (int g = 0; g < SGP_MAX_GPS; ++g) {
-    p.nride[g] = 0;
-    p.ride_delta[g] = 0;
-  }
-  const bool riders = !no_ride && sweep_riders(gh, Geff, d, single, kMaxRide, 4, rides, p.nride);
+  // followers of a shared factor ride in their leader's stages (sweep_shared.h)
+  bool rides[SGP_MAX_GPS];
+  const bool riders =
+      assign_riders(gh, Geff, d, single, kMaxRide, 4, rides, p.nride, p.ride_delta);
   // (factor tables: the instances without riders; a launch with riders evaluates)
   if (riders) sep = nullptr;
-  if (!riders)
-    for (int g = 0; g < Geff; ++g) {
-      rides[g] = false;
-      p.nride[g] = 0;
-    }
-  for (int g = 0, leader = 0; g < Geff; ++g) {
-    if (!rides[g]) {
-      leader = g;
-      continue;
-    }
-    p.ride_delta[g] = (long long)(reinterpret_cast<intptr_t>(gh[g].XA) -
-                                  reinterpret_cast<intptr_t>(gh[leader].XA));
-  }
   SGP_TRY(pair_stage_table(ctx, gh, Geff, d, sep != nullptr, rides, &p.stages, &p.nstages));
   if (sep) {
     p.sep = *sep;
     switch (sep->naxes) {
-      case 1: return launch_pair_v<1, MODE_CONF, true, 0, 1>(ctx, p, flops);
-      case 2: return launch_pair_v<1, MODE_CONF, true, 0, 2>(ctx, p, flops);
-      case 3: return launch_pair_v<1, MODE_CONF, true, 0, 3>(ctx, p, flops);
+      case 1: return launch_pair_v<1, true, 0, 1>(ctx, p, flops);
+      case 2: return launch_pair_v<1, true, 0, 2>(ctx, p, flops);
+      case 3: return launch_pair_v<1, true, 0, 3>(ctx, p, flops);
     }
     sgp_set_error(ctx, "factor tables with %d axes", sep->naxes);
     return -2;

@@ -2,19 +2,16 @@
 // kernel for small factors; sweep_pair.hip: the paired-wave kernel).
 #pragma once
 
+#include <stdlib.h>
+
 #include "kern_eval.h"
-#include "fitness.h"
 
-enum { MODE_CONF = 0, MODE_FITNESS = 1 };
-
-// What a sweep launch works on (both kernels).
+// What a sweep launch works on (every kernel).
 struct SweepArgs {
   const GpDev* gps;
   int G;
-  int mode;
   SweepPoints pts;
   ConfOut conf;
-  FitnessArgs fit;
 };
 
 // hipEvent pair around a sweep launch on the library's own stream
@@ -170,6 +167,30 @@ inline bool sweep_riders(const GpDev* gh, int Geff, int d, bool single, int max_
   return any;
 }
 
+// The riders of a launch as its kernel sees them: rides / nride as above (all clear when
+// nothing rides or SGP_PAIR_RIDE=0, A/B runs) and ride_delta[g], the bytes from the XA of
+// rider g's leader to its own.  Arrays of SGP_MAX_GPS.  Returns whether any GP rides.
+inline bool assign_riders(const GpDev* gh, int Geff, int d, bool single, int max_ride,
+                          int max_d, bool* rides, int* nride, long long* ride_delta) {
+  static const bool no_ride = getenv("SGP_PAIR_RIDE") && atoi(getenv("SGP_PAIR_RIDE")) == 0;
+  for (int g = 0; g < SGP_MAX_GPS; ++g) {
+    rides[g] = false;
+    nride[g] = 0;
+    ride_delta[g] = 0;
+  }
+  if (no_ride || !sweep_riders(gh, Geff, d, single, max_ride, max_d, rides, nride))
+    return false;     // (sweep_riders marks nothing when it returns false)
+  for (int g = 0, leader = 0; g < Geff; ++g) {
+    if (!rides[g]) {
+      leader = g;
+      continue;
+    }
+    ride_delta[g] = (long long)(reinterpret_cast<intptr_t>(gh[g].XA) -
+                                reinterpret_cast<intptr_t>(gh[leader].XA));
+  }
+  return true;
+}
+
 // a wave-uniform pointer, pinned to scalar registers
 template <typename T>
 __device__ __forceinline__ const T* uniform_ptr(const T* q) {
@@ -188,7 +209,6 @@ int launch_sweep_tiny(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d, 
 
 // sweep_pair.hip
 bool pair_sweep_wanted(const sgp_ctx* ctx, const GpDev* gh, int Geff);
-int pair_sweep_partials(const sgp_ctx* ctx, int64_t N);
 // sweep_mid.hip: the resident-factor kernel for 49 .. 128 observations (mid_sweep_wanted)
 int launch_sweep_mid(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d, int Geff,
                      double flops, const SepLaunch* sep);
