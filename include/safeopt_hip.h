@@ -33,6 +33,8 @@ extern "C" {
 #define SGP_MAX_GPS 8      /* objective + constraints                          */
 #define SGP_TOPK 16        /* expander candidates examined per pass            */
 #define SGP_MAX_JOINT 8192 /* rows of one joint prediction                     */
+#define SGP_MAX_PATHS 64   /* sample paths of one call                         */
+#define SGP_MAX_FEATURES 16384 /* random Fourier features of a sample path     */
 
 /* kernel kinds: GPy.kern.RBF / Matern32 / Matern52 (Stationary.K_of_r)        */
 enum { SGP_RBF = 0, SGP_MATERN32 = 1, SGP_MATERN52 = 2 };
@@ -131,6 +133,34 @@ int sgp_gp_predict_cov(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride
 int sgp_gp_posterior_draw(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
                           int64_t stride_col, const double* Z, int S, double* out,
                           double* mean, int* chol_info, double* jitter_used);
+/* ---- posterior sample PATHS by pathwise conditioning (Wilson et al. 2020, "Efficiently
+ * sampling functions from Gaussian process posteriors").  A path is a function: a random-
+ * Fourier-feature draw from the prior plus a kernel-weighted update from the data,
+ *   phi_i(x)   = sqrt(2 v / m) cos(omega_i . x + b_i)        i = 1 .. m,  v = prod_p v_p
+ *   prior_s(x) = sum_i W[i,s] phi_i(x)
+ *   V[:,s]     = alpha - Ky^-1 (Phi(X) W[:,s] + E[:,s])      Phi(X)[j,i] = phi_i(X_j)
+ *   f_s(x)     = prior_s(x) + sum_j k(x, X_j) V[j,s]
+ * with Ky = K + (noise_var + 1e-8) I (+ the jitter of the fit), L and alpha of the GP as they
+ * stand.  O(m + n) per row and path, no N x N matrix (sgp_gp_posterior_draw stops at
+ * SGP_MAX_JOINT rows), evaluated anywhere, any number of times.  The caller brings the random
+ * numbers (safeopt_amd/paths.py draws them with NumPy): Omega (m x d row-major; omega_i = the
+ * sum over the parts of a draw from the part's spectral measure), phase (m; uniform on
+ * [0, 2 pi)), W (m x S row-major; standard normal), E (n x S row-major; normal with variance
+ * noise_var + 1e-8).  1 <= m <= SGP_MAX_FEATURES, 1 <= S <= SGP_MAX_PATHS; the GP must be
+ * fitted.  Every sum is formed in a fixed order (no atomics): the same inputs give the same
+ * bits, and a row's values do not depend on the other rows of the call.
+ *
+ * sgp_gp_path_weights: V_out (n x S row-major).  Phi(X) W is formed by the kernel that
+ * evaluates the paths, with the training rows as the points; Ky^-1 is applied as
+ * L^-T (L^-1 u) from the resident dense L^-1.                                            */
+int sgp_gp_path_weights(sgp_gp* gp, const double* Omega, const double* phase, int m,
+                        const double* W, const double* E, int S, double* V_out);
+/* out (N x S row-major) = f_s at the rows of Xnew (strides as sgp_gp_predict; N is not
+ * limited; N <= 0 returns 0 and writes nothing).  One kernel: [Phi(x) | k(x, X)] times
+ * [W ; V] on the fp64 matrix pipe, the features and covariances evaluated on the fly.     */
+int sgp_gp_paths_eval(sgp_gp* gp, const double* Omega, const double* phase, int m,
+                      const double* W, const double* V, int S, const double* Xnew, int64_t N,
+                      int64_t stride_row, int64_t stride_col, double* out);
 /* test hook: dense L^-1 (n x n, row-major) and alpha (n)                     */
 int sgp_gp_get_factor(sgp_gp* gp, double* Linv, double* alpha);
 /* gp.kern.K(X, X2) (gp_opt.py:847, 1093; utilities.py:89, 135): out is
@@ -404,6 +434,16 @@ int sgp_grid_unmark_expanders(sgp_grid* grid, const int64_t* gidx, int m);
  * value = -inf and gidx = -1 when the masked set is empty.                   */
 int sgp_grid_argmax(sgp_grid* grid, int mode, const double* scaling,
                     double* value, int64_t* gidx);
+/* The paths of sgp_gp_paths_eval over the grid's RESIDENT rows (nothing is uploaded per
+ * row), the same bits.  values (N x S row-major) may be NULL.  best_val[S] / best_idx[S]
+ * (both or neither): per path the maximum and its GLOBAL row (global_offset + local row),
+ * over all rows (mask = 0) or over the rows of the safe set S (mask = 1); the lowest row
+ * wins a tie; -inf / -1 when no row qualifies.  The arg-max is an epilogue of the
+ * evaluation (per-workgroup partial pairs, one small final kernel): with values == NULL
+ * no N x S array exists anywhere.  A Thompson pick inside the safe set.                  */
+int sgp_grid_paths(sgp_grid* grid, sgp_gp* gp, const double* Omega, const double* phase, int m,
+                   const double* W, const double* V, int S, int mask, double* values,
+                   double* best_val, int64_t* best_idx);
 /* copy a resident array to the host: Q (N,2G) f64 | S/M/G (N) u8 |
  * mean/var (G,N) f64                                                         */
 /* S / M / G of the shard from the host: the reference's arrays are mutated in place

@@ -34,6 +34,8 @@ ARGMAX_MG_WIDTH, ARGMAX_UCB, ARGMAX_LCB = 0, 1, 2
 SWARM_TYPES = {"greedy": 0, "maximizers": 1, "expanders": 2, "safe_set": 3}
 MAX_D, MAX_PARTS, MAX_GPS, TOPK = 8, 4, 8, 16
 MAX_JOINT = 8192          # SGP_MAX_JOINT: rows of one joint prediction
+MAX_PATHS = 64            # SGP_MAX_PATHS: sample paths of one call
+MAX_FEATURES = 16384      # SGP_MAX_FEATURES: random Fourier features of a sample path
 
 # name -> (restype, argtypes); mirrors include/safeopt_hip.h one to one
 PROTOTYPES = {
@@ -60,6 +62,14 @@ PROTOTYPES = {
     "sgp_gp_posterior_draw": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
                                         C.c_int64, c_double_p, C.c_int, c_double_p,
                                         c_double_p, c_int_p, c_double_p]),
+    "sgp_gp_path_weights": (C.c_int, [vp, c_double_p, c_double_p, C.c_int, c_double_p,
+                                      c_double_p, C.c_int, c_double_p]),
+    "sgp_gp_paths_eval": (C.c_int, [vp, c_double_p, c_double_p, C.c_int, c_double_p,
+                                    c_double_p, C.c_int, c_double_p, C.c_int64, C.c_int64,
+                                    C.c_int64, c_double_p]),
+    "sgp_grid_paths": (C.c_int, [vp, vp, c_double_p, c_double_p, C.c_int, c_double_p,
+                                 c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
+                                 c_i64_p]),
     "sgp_gp_get_factor": (C.c_int, [vp, c_double_p, c_double_p]),
     "sgp_kern_K": (C.c_int, [vp, C.c_int, C.c_int, c_int_p, c_double_p,
                              c_double_p, c_double_p, C.c_int64, c_double_p,
@@ -618,6 +628,46 @@ class DeviceGP(object):
         self.ctx.check(rc)
         return out, mean, jit.value
 
+    def _path_args(self, Omega, phase, W):
+        Omega = f64(Omega).reshape(-1, self.d)
+        m = Omega.shape[0]
+        phase = f64(phase).reshape(m)
+        W = f64(W)
+        if W.ndim != 2 or W.shape[0] != m:
+            raise ValueError("W must be (m, S) with m = %d features, got %r" % (m, W.shape))
+        return Omega, phase, W, m, W.shape[1]
+
+    def path_weights(self, Omega, phase, W, E):
+        """Data weights ``V = alpha - Ky^-1 (Phi(X) W + E)`` (n, S) of sample paths
+        (``sgp_gp_path_weights``; safeopt_amd/paths.py has the formulas)."""
+        Omega, phase, W, m, S = self._path_args(Omega, phase, W)
+        E = f64(E)
+        if E.shape != (self.n, S):
+            raise ValueError("E must be (n, S) = (%d, %d), got %r" % (self.n, S, E.shape))
+        V = np.empty((self.n, S))
+        self.ctx.check(lib().sgp_gp_path_weights(self.h, dptr(Omega), dptr(phase), m, dptr(W),
+                                                 dptr(E), S, dptr(V)))
+        return V
+
+    def paths_eval(self, Omega, phase, W, V, Xnew):
+        """The sample paths at the rows of ``Xnew``: ``(N, S)`` (``sgp_gp_paths_eval``)."""
+        Omega, phase, W, m, S = self._path_args(Omega, phase, W)
+        V = f64(V)
+        if V.shape != (self.n, S):
+            raise ValueError("V must be (n, S) = (%d, %d), got %r" % (self.n, S, V.shape))
+        Xnew = np.asarray(Xnew, dtype=np.float64)
+        if Xnew.ndim != 2 or Xnew.shape[1] != self.d:
+            Xnew = np.atleast_2d(Xnew).reshape(-1, self.d)
+        it = Xnew.itemsize
+        if Xnew.strides[0] % it or Xnew.strides[1] % it or min(Xnew.strides) < 0:
+            Xnew = np.ascontiguousarray(Xnew)
+        N = Xnew.shape[0]
+        out = np.empty((N, S))
+        self.ctx.check(lib().sgp_gp_paths_eval(
+            self.h, dptr(Omega), dptr(phase), m, dptr(W), dptr(V), S, dptr(Xnew), N,
+            Xnew.strides[0] // it, Xnew.strides[1] // it, dptr(out)))
+        return out
+
     def factor(self):
         Linv = np.empty((self.n, self.n))
         alpha = np.empty(self.n)
@@ -1068,6 +1118,23 @@ class DeviceGrid(object):
         self.ctx.check(lib().sgp_grid_argmax(self.h, int(mode), dptr(scaling),
                                              C.byref(v), C.byref(i)))
         return v.value, i.value
+
+    def paths(self, gp, Omega, phase, W, V, mask=False, values=False, best=True):
+        """Sample paths of ``gp`` over the resident rows (``sgp_grid_paths``): ``(values (N, S)
+        or None, best value (S), its global row (S))`` -- the arg-max over all rows, or over
+        the rows of the safe set with ``mask``; -inf / -1 when no row qualifies."""
+        Omega, phase, W, m, S = gp._path_args(Omega, phase, W)
+        V = f64(V)
+        if V.shape != (gp.n, S):
+            raise ValueError("V must be (n, S) = (%d, %d), got %r" % (gp.n, S, V.shape))
+        vals = np.empty((self.N, S)) if values else None
+        bv = np.empty(S) if best else None
+        bi = np.empty(S, dtype=np.int64) if best else None
+        self.ctx.check(lib().sgp_grid_paths(
+            self.h, gp.h, dptr(Omega), dptr(phase), m, dptr(W), dptr(V), S, int(bool(mask)),
+            None if vals is None else dptr(vals), None if bv is None else dptr(bv),
+            None if bi is None else bi.ctypes.data_as(c_i64_p)))
+        return vals, bv, bi
 
     def download(self, what, out=None):
         if what == Q:

@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(PKG, "libsafeopt_hip.so")
 SOURCES = ["api.hip", "sweep.hip", "sweep_pair.hip", "sweep_mid.hip", "sweep_tiny.hip",
            "step_small.hip",
-           "factor.hip", "hyper.hip", "joint.hip", "sets.hip", "swarm.hip"]
+           "factor.hip", "hyper.hip", "joint.hip", "paths.hip", "sets.hip", "swarm.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "kern_eval.h", "fitness.h",
                                             "small_path.h", "sweep_shared.h",
                                             "sweep_slots.h", "set_order.h",

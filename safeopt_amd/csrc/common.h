@@ -157,6 +157,10 @@ enum ScratchSlot : int {
   kSlotJointT = 15,     // ... and its workspace
   kSlotJointZ = 16,     // ... Z | out of a draw (N x S each)
   kSlotJointVt = 17,    // ... V transposed, for the VALU yardstick of the SYRK only
+  kSlotPathOm = 18,     // paths.hip: [omega | b] of the features
+  kSlotPathB = 19,      // ... [amp W ; V], zero padded
+  kSlotPathOut = 20,    // ... path values (rows x S); path_weights' U | E | T | V
+  kSlotPathPart = 21,   // ... per-workgroup (value, row) partials of the arg-max, the result
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }

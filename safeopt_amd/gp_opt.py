@@ -426,6 +426,11 @@ class _HipGridBackend(object):
     def download(self, what):
         return self.grid.download(what)
 
+    def paths(self, pp, mask, values):
+        """Sample paths ``pp`` (of one of this backend's GPs) over the resident rows."""
+        return self.grid.paths(pp.device, pp.Omega, pp.phase, pp.W, pp.V, mask=mask,
+                               values=values)
+
 
 class SafeOpt(GaussianProcessOptimization):
     """Safe Bayesian optimisation over a discretised parameter set.
@@ -1304,6 +1309,42 @@ class SafeOpt(GaussianProcessOptimization):
             self._certify_first_candidate(beta, self.fmin != -np.inf,
                                           self._front_of(out5, x_c, mu_c, q_c,
                                                          (flags, val, idx)), exact=True)
+
+    def thompson_points(self, size=8, features=1024, within='safe', return_values=False):
+        """``size`` Thompson picks: sample paths of the objective GP (``gps[0]``,
+        ``GPRegression.posterior_paths(size, features)``) evaluated over the whole resident
+        grid, and per path the row that maximises it inside the current safe set ``S`` -- a
+        batch of distinct-by-chance safe query points for experiments that run in parallel.
+
+        Returns ``(x (size, d_parameters), values (size,))``: the maximisers, context columns
+        stripped as ``optimize()`` strips them, and the paths' values there; with
+        ``return_values=True`` also the ``(N, size)`` array of all path values.
+        ``within='all'`` ignores ``S``: the arg-max over every row -- NOT a safe pick, for
+        diagnostics and unconstrained problems only.  Raises ``RuntimeError`` when no row is
+        safe.  One rank only.  Changes no state of the optimiser -- except that in-place edits
+        of ``opt.Q`` / ``opt.S`` still pending are flushed to the device first, as before a
+        set pass (an edited ``Q`` is uploaded and ``S`` recomputed from it); the random
+        numbers come from NumPy's global generator."""
+        if within not in ('safe', 'all'):
+            raise ValueError("within must be 'safe' or 'all', got %r" % (within,))
+        if self._comm.world > 1:
+            raise NotImplementedError(
+                "thompson_points runs on one rank, this optimiser has a communicator of %d: "
+                "the sharded merge (identical paths on every rank, one all-gather of the "
+                "per-path maxima) is not implemented" % self._comm.world)
+        if not hasattr(self._backend, 'paths'):
+            raise NotImplementedError("this grid backend evaluates no sample paths")
+        self._flush_Q()
+        self._flush_masks()
+        safe = within == 'safe'
+        if safe and self._any_safe is not None and not self._any_safe:
+            raise RuntimeError('There are no safe points to sample in.')
+        pp = self.gp.posterior_paths(size=size, features=features)
+        values, best, idx = self._backend.paths(pp, safe, return_values)
+        if np.any(idx < 0):
+            raise RuntimeError('There are no safe points to sample in.')
+        x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
+        return (x, best, values) if return_values else (x, best)
 
     def get_maximum(self, context=None):
         """Best lower bound inside the safe set: ``(x, l)`` or ``None``."""

@@ -25,6 +25,7 @@ import numpy as np
 
 from . import _hip
 from . import hyper as _hyper
+from . import paths as _paths
 
 __all__ = ["kern", "models"]
 
@@ -173,7 +174,8 @@ class GPRegression(object):
     (the joint covariance of up to ``SGP_MAX_JOINT`` rows), and
     ``posterior_samples_f`` / ``posterior_samples`` draw sample paths from it; the
     normal numbers come from NumPy's global generator, everything else is computed
-    on the device.
+    on the device.  ``posterior_paths`` draws sample paths as functions (pathwise
+    conditioning): no row limit, evaluated anywhere and again.
     """
 
     def __init__(self, X, Y, kernel=None, noise_var=1., device=None):
@@ -374,6 +376,32 @@ class GPRegression(object):
         Z = np.random.randn(N, int(size))
         out, _, _ = dev.draw(X, Z)
         return out[:, None, :]
+
+    def _paths_token(self):
+        """What a ``PosteriorPaths`` snapshot belongs to: the device GP and its data version,
+        and the hyper-parameters as the objects hold them now."""
+        dev = self._dev
+        return (None if dev is None else (dev.serial, dev.version),
+                self.kern._signature(), self.noise_var)
+
+    def posterior_paths(self, size=16, features=1024):
+        """``size`` posterior sample paths as FUNCTIONS (pathwise conditioning, Wilson et al.
+        2020): a ``PosteriorPaths`` whose ``paths(X)`` returns ``(N, 1, size)`` like
+        ``posterior_samples_f`` -- but for any number of rows, again and again, the same bits
+        for the same rows.  ``features`` random Fourier features carry the prior draw; the
+        random numbers come from NumPy's global generator in the order ``safeopt_amd.paths``
+        documents (``np.random.seed`` pins the paths), the data weights and every evaluation
+        are device calls.  A snapshot of the GP as it is now: after ``set_XY`` or an edited
+        hyper-parameter ``paths`` raises ``ValueError``.  Approximate in the prior term only
+        (error ~ ``features ** -0.5``); the data update is exact."""
+        dev = self._fitted()
+        desc = self.kern._desc(self.input_dim)
+        Om, b, W, E = _paths.draw_path_inputs((desc[1], desc[3]), self.noise_var, dev.n,
+                                              self.input_dim, size, features)
+        V = dev.path_weights(Om, b, W, E)
+        return _paths.PosteriorPaths(Om, b, W, V,
+                                     lambda X: dev.paths_eval(Om, b, W, V, X),
+                                     self._paths_token, device=dev)
 
     def posterior_samples(self, X, size=10):
         """``posterior_samples_f`` plus observation noise: ``sqrt(noise_var)`` times a

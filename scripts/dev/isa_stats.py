@@ -9,7 +9,8 @@ import subprocess
 import sys
 
 
-def main(path, flt=None):
+def kernels(path):
+    """[(demangled name without arguments, body text)] of every function of the listing."""
     names, bodies, cur = [], [], None
     for line in open(path):
         m = re.match(r"^(_Z\w+):", line)
@@ -24,11 +25,14 @@ def main(path, flt=None):
                 cur.append(line)
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True,
                          text=True).stdout.split("\n")
-    for name, body in zip(dem, bodies):
-        name = name.replace("(anonymous namespace)::", "").split("(")[0]
+    return [(name.replace("(anonymous namespace)::", "").split("(")[0], "".join(body))
+            for name, body in zip(dem, bodies)]
+
+
+def main(path, flt=None):
+    for name, txt in kernels(path):
         if flt and flt not in name:
             continue
-        txt = "".join(body)
         c = lambda pat: len(re.findall(pat, txt))
         print("%-44s insts %6d mfma %5d writelane %3d readlane %3d scratch %3d waitcnt %4d "
               "branch %4d ds %4d v_mov %4d" % (
