@@ -459,6 +459,26 @@ int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
                       const double* fmin, const double* scaling,
                       double best_lower_bound, double* values, uint8_t* safe);
 
+/* The fitness of a THOMPSON swarm: a swarm that climbs one posterior sample path f of GP 0
+ * (one column of sgp_gp_path_weights: Omega (m x d), phase (m), w (m), v (n)) inside the
+ * safe region.  With mu_g, var_g the posterior of GP g at x and lower_g = mu_g - beta
+ * sqrt(var_g), for every GP with a finite fmin[g]:
+ *   slack = lower_g - fmin[g];  safe &= slack >= 0;  total_pen += penalty(slack / scaling[g])
+ * (the penalty and safety rule of SGP_SWARM_MAXIMIZERS), and
+ *   values = f(x) / scaling[0] + total_pen.
+ * The posterior is formed by the kernels sgp_swarm_fitness takes for that P and n; the path
+ * term f(x) = sum_i amp w_i cos(omega_i . x + b_i) + sum_j k(x, X_j) v_j is one more launch:
+ * a row kernel on the fp64 VALU, 16 lanes per particle, no Phi or k(x, X) in memory.  Sums in
+ * a fixed order, no atomics: a particle's value depends on its coordinates and the path
+ * alone -- not on P, its row or the launch -- and the same inputs give the same bits.
+ * Limits and failures of sgp_gp_paths_eval (1 <= m <= SGP_MAX_FEATURES, GP 0 fitted);
+ * P <= 0 returns 0 and writes nothing.  particles (P,d) row-major; values (P) f64; safe
+ * (P) u8.                                                                      */
+int sgp_swarm_fitness_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                           int64_t P, double beta, const double* fmin, const double* scaling,
+                           const double* Omega, const double* phase, int m, const double* w,
+                           const double* v, double* values, uint8_t* safe);
+
 /* ---- SafeOptSwarm safe-set growth (gp_opt.py:1089-1111) ---------------------
  * After a maximizer / expander swarm run the reference appends, in order, every
  * best position B_j (n,d row-major) whose prior correlation
@@ -488,6 +508,23 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
                   double* global_best, const double* velocity_scale,
                   const double* bounds, int init, int iters, double inertia0,
                   double step, const double* rand, uint64_t seed);
+
+/* sgp_swarm_run for a Thompson swarm: the fitness is that of sgp_swarm_fitness_path, the
+ * state arrays, init / iters / inertia, rand and seed as for sgp_swarm_run.  One call is the
+ * whole run: the path is staged on the device once per call, nothing but the state arrays
+ * crosses PCIe.  A path run ALWAYS takes the general launches -- move, fitness (posterior,
+ * shaping, path term), personal bests, global best -- also for a swarm the one-workgroup
+ * step of sgp_swarm_run would take (a 20-particle Thompson swarm simply uses them): with
+ * rand != NULL the run is bit-identical to the host loop over sgp_swarm_fitness_path.
+ * One rank.  P <= 0 returns 0 and writes nothing.                              */
+int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                       const double* fmin, const double* scaling, int64_t P, double* positions,
+                       double* velocities, double* best_positions, double* best_values,
+                       double* global_best, const double* velocity_scale,
+                       const double* bounds, int init, int iters, double inertia0,
+                       double step, const double* rand, uint64_t seed,
+                       const double* Omega, const double* phase, int m, const double* w,
+                       const double* v);
 
 /* sgp_swarm_run on a rank's contiguous block of particles [p0, p0 + P) of a swarm
  * of P_total (shard_range): the state arrays hold the block's P rows.  After the

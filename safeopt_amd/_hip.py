@@ -157,6 +157,10 @@ PROTOTYPES = {
                                     C.c_int64, C.c_double, c_double_p,
                                     c_double_p, C.c_double, c_double_p,
                                     c_u8_p]),
+    "sgp_swarm_fitness_path": (C.c_int, [vp, vpp, C.c_int, c_double_p, C.c_int64,
+                                         C.c_double, c_double_p, c_double_p,
+                                         c_double_p, c_double_p, C.c_int, c_double_p,
+                                         c_double_p, c_double_p, c_u8_p]),
     "sgp_swarm_grow": (C.c_int, [vp, vp, c_double_p, C.c_int64, c_double_p,
                                  C.c_int64, C.c_double, C.c_double, c_u8_p]),
     "sgp_swarm_run": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
@@ -165,6 +169,13 @@ PROTOTYPES = {
                                 c_double_p, c_double_p, c_double_p, C.c_int,
                                 C.c_int, C.c_double, C.c_double, c_double_p,
                                 C.c_uint64]),
+    "sgp_swarm_run_path": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                     c_double_p, c_double_p, C.c_int64,
+                                     c_double_p, c_double_p, c_double_p, c_double_p,
+                                     c_double_p, c_double_p, c_double_p, C.c_int,
+                                     C.c_int, C.c_double, C.c_double, c_double_p,
+                                     C.c_uint64, c_double_p, c_double_p, C.c_int,
+                                     c_double_p, c_double_p]),
     "sgp_swarm_run_shard": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
                                       c_double_p, c_double_p, C.c_double, C.c_int64,
                                       c_double_p, c_double_p, c_double_p, c_double_p,
@@ -1212,3 +1223,55 @@ def swarm_fitness(ctx, gps, swarm_type, particles, beta, fmin, scaling,
             float(best_lower_bound), dptr(values),
             safe.ctypes.data_as(c_u8_p)))
     return values, safe.view(np.bool_)
+
+
+def _swarm_path_args(gp, path):
+    """``(Omega, phase, m, w, v)`` of ONE sample path, checked against its GP."""
+    Omega, phase, w, v = path
+    Omega = f64(Omega).reshape(-1, gp.d)
+    m = Omega.shape[0]
+    phase, w, v = f64(phase), f64(w), f64(v)
+    if phase.shape != (m,) or w.shape != (m,):
+        raise ValueError("phase and w must be (m,) with m = %d features, got %r and %r"
+                         % (m, phase.shape, w.shape))
+    if v.shape != (gp.n,):
+        raise ValueError("v must be (n,) = (%d,), got %r" % (gp.n, v.shape))
+    return Omega, phase, m, w, v
+
+
+def swarm_fitness_path(ctx, gps, particles, beta, fmin, scaling, path):
+    """Fitness and safety of ``particles`` for a Thompson swarm (``sgp_swarm_fitness_path``):
+    ``path = (Omega, phase, w, v)``, one sample path of ``gps[0]`` with contiguous 1-D ``w``
+    and ``v`` (a column of a ``PosteriorPaths``)."""
+    d = gps[0].d
+    particles = f64(particles).reshape(-1, d)
+    P = particles.shape[0]
+    Omega, phase, m, w, v = _swarm_path_args(gps[0], path)
+    values = np.empty(P)
+    safe = np.empty(P, dtype=np.uint8)
+    if P:
+        ctx.check(lib().sgp_swarm_fitness_path(
+            ctx.h, _gp_array(gps), len(gps), dptr(particles), P, float(beta),
+            dptr(f64(fmin)), dptr(f64(scaling)), dptr(Omega), dptr(phase), m, dptr(w),
+            dptr(v), dptr(values), safe.ctypes.data_as(c_u8_p)))
+    return values, safe.view(np.bool_)
+
+
+def swarm_run_path(ctx, gps, beta, fmin, scaling, positions, velocities, best_positions,
+                   best_values, global_best, velocity_scale, bounds, init, iters, inertia0,
+                   step, rand, path, seed=0):
+    """Whole PSO run of a Thompson swarm on the device (``sgp_swarm_run_path``); the state
+    arrays are updated in place, ``path`` as for :func:`swarm_fitness_path`."""
+    P = positions.shape[0]
+    for a in (positions, velocities, best_positions, best_values, global_best):
+        assert a.dtype == np.float64 and a.flags.c_contiguous
+    bnd = None if bounds is None else f64(bounds)
+    rnd = None if rand is None else f64(rand).ravel()
+    Omega, phase, m, w, v = _swarm_path_args(gps[0], path)
+    ctx.check(lib().sgp_swarm_run_path(
+        ctx.h, _gp_array(gps), len(gps), float(beta), dptr(f64(fmin)), dptr(f64(scaling)),
+        P, dptr(positions), dptr(velocities), dptr(best_positions), dptr(best_values),
+        dptr(global_best), dptr(f64(velocity_scale)), None if bnd is None else dptr(bnd),
+        int(bool(init)), int(iters), float(inertia0), float(step),
+        None if rnd is None else dptr(rnd), int(seed), dptr(Omega), dptr(phase), m, dptr(w),
+        dptr(v)))

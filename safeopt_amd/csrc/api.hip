@@ -2197,6 +2197,58 @@ int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   return 0;
 }
 
+// The fitness of a Thompson swarm: the posterior and the shaping as for sgp_swarm_fitness
+// (kSwarmThompson in fitness.h leaves the penalty in the values), then the path term on
+// top (k_swarm_path, paths.hip).
+int sgp_swarm_fitness_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                           int64_t P, double beta, const double* fmin, const double* scaling,
+                           const double* Omega, const double* phase, int m, const double* w,
+                           const double* v, double* values, uint8_t* safe) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
+  SGP_CHECK(ctx, gps[0]->ctx == ctx, "GP 0 lives in another context (device %d) than the "
+            "call (device %d)", gps[0]->ctx ? gps[0]->ctx->device : -1, ctx->device);
+  SGP_TRY(swarm_path_ready(gps[0], m));
+  if (P <= 0) return 0;
+  const int d = gps[0]->kern.d;
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(collect_gps(ctx, gps, G, d, host));
+  const size_t nd = size_t(P) * 8;
+  double* stage;
+  char* work;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, nd * d, &stage));
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, nd * d + nd + size_t(P) + sizeof(GpDev) * SGP_MAX_GPS + 64,
+                      &work));
+  double* pts = reinterpret_cast<double*>(work);
+  double* dval = reinterpret_cast<double*>(work + nd * d);
+  GpDev* gdev = reinterpret_cast<GpDev*>(work + nd * d + nd);
+  uint8_t* dsafe = reinterpret_cast<uint8_t*>(work + nd * d + nd + sizeof(GpDev) * SGP_MAX_GPS);
+  SGP_TRY(sgp_h2d(ctx, stage, particles, nd * d));
+  SGP_TRY(launch_import_points(ctx, stage, P, d, d, 1, pts));
+  SGP_TRY(sgp_h2d(ctx, gdev, host, sizeof(GpDev) * G));
+  SwarmPath path;
+  SGP_TRY(swarm_path_stage(gps[0], Omega, phase, m, w, v, &path));
+  FitnessArgs fa{};
+  fa.swarm_type = kSwarmThompson;
+  fa.beta = beta;
+  for (int i = 0; i < SGP_MAX_GPS; ++i) {
+    fa.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
+    fa.scaling[i] = (i < G) ? scaling[i] : 1.0;
+  }
+  fa.values = dval;
+  fa.safe = dsafe;
+  const SweepPoints sp{pts, P, 1, P};
+  if (small_path_pays_all(gps, G, P)) {
+    SGP_TRY(fitness_small(ctx, gdev, host, G, stage, P, fa));
+  } else {
+    SGP_TRY(launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa));
+  }
+  SGP_TRY(launch_swarm_path(ctx, gdev, d, path, sp, fa.scaling[0], dval));
+  SGP_TRY(sgp_d2h(ctx, values, dval, nd));
+  SGP_TRY(sgp_d2h(ctx, safe, dsafe, size_t(P)));
+  return 0;
+}
+
 // SwarmOptimization.init_swarm / run_swarm (swarm.py:61-146) with the state in
 // HBM and the fitness fused in: one call = the whole run, one host round trip.
 // The particles [p0, p0 + P) of a swarm of Pt; P < Pt: a rank's block of a sharded
@@ -2208,9 +2260,12 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
                      double* global_best, const double* velocity_scale,
                      const double* bounds, int init, int iters, double inertia0,
                      double step_size, const double* rand, uint64_t seed, int64_t p0,
-                     int64_t Pt) {
+                     int64_t Pt, const SwarmPath* path = nullptr) {
+  // path: the staged sample path of a Thompson swarm (sgp_swarm_run_path, swarm_type =
+  // kSwarmThompson); such a run always takes the general launches below
   SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, swarm_type >= SGP_SWARM_GREEDY && swarm_type <= SGP_SWARM_SAFE_SET,
+  SGP_CHECK(ctx, path ? swarm_type == kSwarmThompson
+                      : swarm_type >= SGP_SWARM_GREEDY && swarm_type <= SGP_SWARM_SAFE_SET,
             "Invalid swarm type %d", swarm_type);
   SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
   SGP_CHECK(ctx, P >= 1 && iters >= 0, "bad swarm size %lld / iterations %d",
@@ -2280,7 +2335,7 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   const bool few_swept = Pt <= kSmallSwarm && !few;
   const double* r = drand;
   double inertia = inertia0;
-  if ((few || few_swept) && !shard) {
+  if ((few || few_swept) && !shard && !path) {
     // small swarm: three launches per iteration -- k(X, particles), the block
     // products on the matrix cores, and ONE workgroup for everything else
     // (fitness, bests, and the move that opens the next iteration)
@@ -2343,8 +2398,10 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
     // small swarm takes these launches, the arithmetic of k_pso_small_step)
     const bool few_points = small_path_pays_all(gps, G, Pt);
     auto fitness = [&]() -> int {
-      return few_points ? fitness_small(ctx, gdev, host, G, dpos, P, fa)
-                        : launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa, Pt);
+      SGP_TRY(few_points ? fitness_small(ctx, gdev, host, G, dpos, P, fa)
+                         : launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa, Pt));
+      // a Thompson swarm: the path term on top of the penalty the shaping left
+      return path ? launch_swarm_path(ctx, gdev, d, *path, sp, fa.scaling[0], dval) : 0;
     };
     // personal bests, then the global best: of the block, or merged over the ranks
     auto bests = [&](int is_init) -> int {
@@ -2389,6 +2446,28 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
                    positions, velocities, best_positions, best_values, global_best,
                    velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, 0, P);
+}
+
+int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                       const double* fmin, const double* scaling, int64_t P, double* positions,
+                       double* velocities, double* best_positions, double* best_values,
+                       double* global_best, const double* velocity_scale,
+                       const double* bounds, int init, int iters, double inertia0,
+                       double step_size, const double* rand, uint64_t seed,
+                       const double* Omega, const double* phase, int m, const double* w,
+                       const double* v) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
+  SGP_CHECK(ctx, gps[0]->ctx == ctx, "GP 0 lives in another context (device %d) than the "
+            "call (device %d)", gps[0]->ctx ? gps[0]->ctx->device : -1, ctx->device);
+  SGP_TRY(swarm_path_ready(gps[0], m));
+  if (P <= 0) return 0;
+  // staged ONCE per call; nothing in swarm_run asks for the two slots it lives in
+  SwarmPath path;
+  SGP_TRY(swarm_path_stage(gps[0], Omega, phase, m, w, v, &path));
+  return swarm_run(ctx, gps, G, kSwarmThompson, beta, fmin, scaling, 0.0, P, positions,
+                   velocities, best_positions, best_values, global_best, velocity_scale, bounds,
+                   init, iters, inertia0, step_size, rand, seed, 0, P, &path);
 }
 
 int sgp_swarm_run_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,

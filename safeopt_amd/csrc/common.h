@@ -389,6 +389,9 @@ struct ConfOut {
   double beta;
   double fmin[SGP_MAX_GPS];
 };
+// The swarm type of sgp_swarm_fitness_path / sgp_swarm_run_path inside the library (the
+// public entry points that take a swarm type keep to SGP_SWARM_GREEDY .. SGP_SWARM_SAFE_SET)
+constexpr int kSwarmThompson = 4;
 struct FitnessArgs {
   int swarm_type;
   double beta;
@@ -419,6 +422,21 @@ int launch_verify_axes(sgp_grid* g, int* mismatch_dev);
 int launch_sweep_fitness(sgp_ctx* ctx, const GpDev* gps_dev,
                          const GpDev* gps_host, int G, int d, SweepPoints pts,
                          FitnessArgs fa, int64_t sel_rows = -1);
+// paths.hip: ONE sample path of GP 0 as the fitness term of a Thompson swarm
+struct SwarmPath {
+  const double* om;   // [m16][d + 1]: frequency | phase, zero rows behind m
+  const double* wv;   // [m16] amp w (zeros behind m), then [n_pad] v (zero padded)
+  int m16;            // features rounded up to 16
+  int ncov;           // the GP's n_pad
+};
+// the argument checks of sgp_gp_paths_eval for one path
+int swarm_path_ready(sgp_gp* gp, int m);
+// stages the path on the device (once per entry-point call)
+int swarm_path_stage(sgp_gp* gp, const double* Omega, const double* phase, int m,
+                     const double* w, const double* v, SwarmPath* out);
+// values[p] = f(x_p) / scaling0 + values[p] over the rows of pts, gps_dev[0] the path's GP
+int launch_swarm_path(sgp_ctx* ctx, const GpDev* gps_dev, int d, const SwarmPath& path,
+                      SweepPoints pts, double scaling0, double* values);
 // few-points posterior / small-swarm step: small_path.h
 constexpr int kSmallPoints = 4096;   // few-points posterior path (factor.hip)
 constexpr int kSmallSwarm = 64;     // ... with the whole PSO step in one workgroup (swarm.hip)

@@ -18,6 +18,12 @@ __device__ __forceinline__ double swarm_penalty(double slack) {
 // One particle from the posterior of its G GPs (post(g, &mu, &var)): the value
 // the swarm maximises and the particle's safety flag.  Same formulas, same order
 // as the sweep's epilogue.
+// kSwarmThompson (sgp_swarm_*_path, internal): the maximizers' safety rule and
+// penalty with the uncertainty term replaced by the value of a sample path and
+// interest = 1,
+//   value = f(x) / scaling[0] + total_pen.
+// The path term is not a function of the posterior: *value is total_pen here and
+// k_swarm_path (paths.hip) completes it, in that operation order.
 template <typename Post>
 __device__ __forceinline__ void shape_particle(const FitnessArgs& f, int G, Post post,
                                                double* value, bool* is_safe) {
@@ -59,6 +65,9 @@ __device__ __forceinline__ void shape_particle(const FitnessArgs& f, int G, Post
     *is_safe = true;
   } else if (st == SGP_SWARM_SAFE_SET) {
     *value = lower;
+    *is_safe = safe;
+  } else if (st == kSwarmThompson) {
+    *value = total_pen;
     *is_safe = safe;
   } else {
     *value = (values + total_pen) * interest;

@@ -337,7 +337,102 @@ int path_stage(sgp_gp* gp, const double* Omega, const double* phase, int m, cons
   return 0;
 }
 
+
+// ---- one path at the particles of a swarm (sgp_swarm_fitness_path / sgp_swarm_run_path) ------
+// values[p] = f(x_p) / scaling0 + values[p]: the path term of a Thompson swarm's fitness on
+// top of the penalty the shaping pass (fitness.h, kSwarmThompson) left in values[p],
+//   f(x) = sum_i amp w_i cos(omega_i . x + b_i) + sum_j k(x, X_j) v_j.
+// A ROW kernel: one column has nothing for the matrix pipe to share between columns, so the
+// m + n cosines and covariances of a row are VALU work and the products with them.  16
+// lanes per particle (4 particles a wave, 16 a workgroup): lane l = (kq, c) = (l & 3, l >> 2)
+// takes the features l, l + 16, ... and, of every fourth block of 16 training rows (jb = c,
+// c + 4, ...), the rows 16 jb + kq + 4 s -- the access pattern of k_paths, KernFast::many<4>.
+// Each lane sums its terms in that order into one accumulator, then the 16 lanes fold by
+// xor 1, 2, 4, 8 (IEEE addition commutes: every lane ends with the same bits).  The order
+// depends on m and n alone: a particle's value does not depend on P, on its row or on the
+// launch.  No atomics; neither Phi nor k(x, X) reaches memory.
+constexpr int kRowLanes = 16;        // lanes of a particle
+constexpr int kRowParticles = 16;    // particles of a workgroup
+
+template <int D>
+__global__ __launch_bounds__(256) void k_swarm_path(const GpDev* gps, SwarmPath sp,
+                                                    SweepPoints pts, double scaling0,
+                                                    double* values) {
+  __shared__ double tab[kExpTabSize];
+  exp_tab_init(tab);
+  __syncthreads();
+  const GpDev& gp = gps[0];
+  const int tid = threadIdx.x, l = tid & (kRowLanes - 1), kq = l & 3, c = l >> 2;
+  const int64_t p = int64_t(blockIdx.x) * kRowParticles + (tid >> 4);
+  const int64_t r = p < pts.N ? p : pts.N - 1;    // (a spare group repeats the last row)
+  KernFast<D> kf(gp.kern);
+  double x[D], xs[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = pts.base[r * pts.stride_row + k * pts.stride_col];
+  kf.prep(x, xs);
+  double acc = 0.0;
+  // ---- features: cos(omega_i . x + b_i) amp w_i (a padded feature: cos(0) times zero)
+  for (int i = l; i < sp.m16; i += kRowLanes) {
+    const double* om = sp.om + int64_t(i) * (D + 1);
+    double arg = om[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) arg = fma(om[k], x[k], arg);
+    acc = fma(cos(arg), sp.wv[i], acc);
+  }
+  // ---- covariances: k(x, X_j) v_j (a padded training row: finite times zero)
+  const double* v = sp.wv + sp.m16;
+  for (int jb = c; jb < sp.ncov / 16; jb += 4) {
+    double av[4];
+    kf.template many<4>(xs, gp.Xs + int64_t(16 * jb + kq) * D, 4 * D, tab, av);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc = fma(av[s], v[16 * jb + 4 * s + kq], acc);
+  }
+#pragma unroll
+  for (int o = 1; o < kRowLanes; o <<= 1) acc += __shfl_xor(acc, o, 64);
+  if (l == 0 && p < pts.N) values[p] = acc / scaling0 + values[p];
+}
 }  // namespace
+
+int swarm_path_ready(sgp_gp* gp, int m) { return path_ready(gp, m, 1); }
+
+// [omega | b], then [amp w ; v], zero padded: features to 16 (one per lane of a particle),
+// training rows to the GP's n_pad
+int swarm_path_stage(sgp_gp* gp, const double* Omega, const double* phase, int m,
+                     const double* w, const double* v, SwarmPath* out) {
+  sgp_ctx* ctx = gp->ctx;
+  const int d = gp->kern.d;
+  const int m16 = (m + kRowLanes - 1) / kRowLanes * kRowLanes;
+  std::vector<double> om(size_t(m16) * (d + 1), 0.0), wv(size_t(m16) + gp->n_pad, 0.0);
+  const double amp = std::sqrt(2.0 * gp->kern.kdiag / double(m));
+  for (int i = 0; i < m; ++i) {
+    for (int k = 0; k < d; ++k) om[size_t(i) * (d + 1) + k] = Omega[size_t(i) * d + k];
+    om[size_t(i) * (d + 1) + d] = phase[i];
+    wv[i] = amp * w[i];
+  }
+  for (int64_t j = 0; j < gp->n; ++j) wv[size_t(m16) + j] = v[j];
+  double *om_dev, *wv_dev;
+  SGP_TRY(sgp_scratch(ctx, kSlotPathOm, om.size() * sizeof(double), &om_dev));
+  SGP_TRY(sgp_scratch(ctx, kSlotPathB, wv.size() * sizeof(double), &wv_dev));
+  SGP_TRY(sgp_h2d(ctx, om_dev, om.data(), om.size() * sizeof(double)));
+  SGP_TRY(sgp_h2d(ctx, wv_dev, wv.data(), wv.size() * sizeof(double)));
+  *out = SwarmPath{om_dev, wv_dev, m16, gp->n_pad};
+  return 0;
+}
+
+int launch_swarm_path(sgp_ctx* ctx, const GpDev* gps_dev, int d, const SwarmPath& path,
+                      SweepPoints pts, double scaling0, double* values) {
+  if (pts.N <= 0) return 0;
+  const int64_t nwg = (pts.N + kRowParticles - 1) / kRowParticles;
+  SGP_CHECK(ctx, nwg <= INT32_MAX, "%lld particles are too many for one launch",
+            (long long)pts.N);
+#define CALL(DD)                                                                              \
+  hipLaunchKernelGGL(k_swarm_path<DD>, dim3(unsigned(nwg)), dim3(256), 0, ctx->stream, gps_dev, \
+                     path, pts, scaling0, values)
+  PATH_DISPATCH(d, CALL)
+#undef CALL
+  SGP_HIP(ctx, hipGetLastError());
+  return 0;
+}
 
 int sgp_gp_path_weights(sgp_gp* gp, const double* Omega, const double* phase, int m,
                         const double* W, const double* E, int S, double* V_out) {

@@ -1372,6 +1372,19 @@ def _step_into_band(value_at, lo=0.94, hi=0.95, v_max=1000., tol=1e-5):
             return v
 
 
+def thompson_pick(best_positions, best_values, safe):
+    """The pick of one Thompson swarm: the personal best with the largest value among
+    those that are ``safe``, the lowest index among equal values -- ``(x, index)``.
+    ``RuntimeError`` when none is safe."""
+    best_values = np.asarray(best_values, dtype=float)
+    safe = np.asarray(safe, dtype=bool)
+    rows = np.flatnonzero(safe)
+    if rows.size == 0:
+        raise RuntimeError('There are no safe points to sample in.')
+    i = int(rows[int(np.argmax(best_values[rows]))])      # (argmax: first among equals)
+    return np.array(np.asarray(best_positions)[i], dtype=float), i
+
+
 class SafeOptSwarm(GaussianProcessOptimization):
     """SafeOpt for higher dimensions with adaptive swarm discretisation.
 
@@ -1484,6 +1497,91 @@ class SafeOptSwarm(GaussianProcessOptimization):
             devs[0].ctx, devs, swarm_type, particles, beta, self.fmin,
             self.scaling, self.best_lower_bound)
         return values, safe
+
+    def _compute_path_fitness(self, path, particles):
+        """Fitness and safety of ``particles`` for a Thompson swarm on the sample path
+        ``path = (Omega, phase, w, v)`` of the objective GP: ``values = f(x) / scaling[0] +``
+        the maximizers' penalty, ``safe`` the maximizers' safety flag
+        (``sgp_swarm_fitness_path``).  The fitness callback of the host loop."""
+        beta = self.beta(self.t)
+        particles = np.atleast_2d(particles)
+        devs = [g._fitted() for g in self.gps]
+        return _hip.swarm_fitness_path(devs[0].ctx, devs, particles, beta, self.fmin,
+                                       self.scaling, path)
+
+    def thompson_points(self, size=8, features=1024, max_iters=None, return_paths=False):
+        """``size`` Thompson picks without a grid: per posterior sample path of the
+        objective GP (``gps[0]``, ``GPRegression.posterior_paths(size, features)``) one swarm
+        climbs the path, held inside the safe region by the penalty and safety rule of the
+        maximizers swarm -- a batch of safe query points for experiments that run in
+        parallel, from three or four input dimensions up.
+
+        The fitness of a particle is ``f_s(x) / scaling[0] + total_pen`` (``csrc/fitness.h``),
+        evaluated on the device inside the swarm iteration; every swarm starts from
+        ``swarm_size`` draws from the safe set ``S`` (no fixed points) and runs ``max_iters``
+        (default ``self.max_iters``) iterations.  The pick of a path is the personal best
+        with the largest value among those that are safe under the current posterior (one
+        ``safe_set`` fitness call; ``init_swarm`` does not mask, and ``_recheck_safe_set`` may
+        keep unsafe points), the lowest index among equals.
+
+        Returns ``(x (size, d), values (size,))`` with ``values[s] = pp.paths(x[s][None])[0, 0,
+        s]``; with ``return_paths=True`` also the ``PosteriorPaths`` ``pp``.  Raises
+        ``RuntimeError`` when the safe set is empty or a swarm ends with no safe personal
+        best, ``ValueError`` for more than ``SGP_MAX_PATHS`` paths, ``NotImplementedError``
+        with a communicator of more than one rank.
+
+        Changes no state of the optimiser beyond what ``_recheck_safe_set`` does at the start
+        of every swarm run (it may drop points that are no longer safe): ``S`` does not grow,
+        ``greedy_point``, ``best_lower_bound`` and the greedy / maximizers / expanders swarm
+        objects are untouched.  NumPy's global generator is consumed in this order:
+
+        1. ``pso='device-rng'`` only: one ``randint`` for the key of the device generator;
+        2. the ``posterior_paths`` draw (``safeopt_amd/paths.py`` documents its order);
+        3. per path: one ``randint(len(S), size=swarm_size)`` for the start positions, then
+           what a swarm of that ``pso`` draws today -- ``'host'``: ``rand(swarm_size, d)`` in
+           ``init_swarm`` and ``rand(2 swarm_size, d)`` per iteration; ``'device'``: the same
+           numbers as ``rand(swarm_size d)`` and ``rand(2 swarm_size d max_iters)``, one C
+           call each; ``'device-rng'``: nothing.
+
+        Out of scope: Thompson swarms split over ranks; ``SafeOpt.thompson_points`` on N
+        ranks; running all ``size`` swarms as one launch with per-swarm global bests; paths
+        of the constraint GPs (the constraints enter through their confidence bounds)."""
+        size = int(size)
+        if size > _hip.MAX_PATHS:
+            raise ValueError("size = %d paths, at most SGP_MAX_PATHS = %d per call"
+                             % (size, _hip.MAX_PATHS))
+        if self._comm.world > 1:
+            raise NotImplementedError(
+                "thompson_points runs on one rank, this optimiser has a communicator of %d: "
+                "the sharded Thompson swarm (sgp_swarm_run_path on a rank's block of the "
+                "particles, the global best merged over the ranks) is not implemented"
+                % self._comm.world)
+        self._recheck_safe_set()
+        iters = int(max_iters or self.max_iters)
+        swarm = None                      # pso='host': a reference loop per path
+        if isinstance(self.swarms['maximizers'], DeviceSwarmOptimization):
+            swarm = DeviceSwarmOptimization(
+                self.swarm_size, self.optimal_velocities, self, 'thompson',
+                bounds=self.bounds, rng=self.swarms['maximizers']._rng)
+        pp = self.gp.posterior_paths(size, features)
+        x = np.empty((size, self.gp.input_dim))
+        for s in range(size):
+            path = (pp.Omega, pp.phase, np.ascontiguousarray(pp.W[:, s]),
+                    np.ascontiguousarray(pp.V[:, s]))
+            picks = np.random.randint(self.S.shape[0], size=self.swarm_size)
+            if swarm is None:
+                run = SwarmOptimization(self.swarm_size, self.optimal_velocities,
+                                        partial(self._compute_path_fitness, path),
+                                        bounds=self.bounds)
+            else:
+                run = swarm
+                run.set_path(path)
+            run.init_swarm(self.S[picks, :])
+            run.run_swarm(iters)
+            _, safe = self._compute_particle_fitness('safe_set', run.best_positions)
+            x[s], _ = thompson_pick(run.best_positions, run.best_values, safe)
+        values = np.array([pp.paths(x[s][None])[0, 0, s] for s in range(size)])
+        return (x, values, pp) if return_paths else (x, values)
 
     # -- one swarm run, in the steps of gp_opt.py:1015-1134 -------------------------
     def _recheck_safe_set(self):

@@ -112,6 +112,11 @@ def _hip_swarm_types():
     return _hip.SWARM_TYPES
 
 
+#: type code of the Thompson swarm in the Philox seed mix (``_hip.SWARM_TYPES`` holds 0..3,
+#: the types ``sgp_swarm_fitness`` takes; a Thompson swarm has entry points of its own)
+THOMPSON_CODE = 4
+
+
 class DeviceSwarmOptimization(SwarmOptimization):
     """The same swarm with its state in HBM: ``init_swarm`` and ``run_swarm``
     are one C-ABI call each (``sgp_swarm_run``) -- velocity / position update,
@@ -136,16 +141,27 @@ class DeviceSwarmOptimization(SwarmOptimization):
     draws the numbers of the block's global elements.  After a run
     ``best_positions`` / ``best_values`` are gathered over the ranks (the whole
     swarm on every rank); ``positions`` / ``velocities`` stay the rank's block.
+
+    ``swarm_type='thompson'``: the fitness is the value of one posterior sample path of
+    the owner's objective GP under the maximizers' penalty and safety rule
+    (``sgp_swarm_fitness_path`` / ``sgp_swarm_run_path``); ``set_path(path)`` with ``path =
+    (Omega, phase, w, v)`` comes before ``init_swarm``.  One rank only.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
                  rng='numpy', seed=None, comm=None):
         super(DeviceSwarmOptimization, self).__init__(
             swarm_size, velocity, None, bounds=bounds)
+        del self.fitness          # (the base class stored None over the method below)
         if rng not in ('numpy', 'device'):
             raise ValueError("rng must be 'numpy' or 'device'")
         from .dist import LocalComm, shard_range
         self._comm = comm if comm is not None else LocalComm()
+        if swarm_type == 'thompson' and self._comm.world > 1:
+            raise NotImplementedError(
+                "a Thompson swarm runs on one rank, this communicator has %d: the sharded "
+                "run of sgp_swarm_run_path (a rank's block of the particles, the global "
+                "best merged over the ranks) is not implemented" % self._comm.world)
         self._rows = shard_range(swarm_size, self._comm.rank, self._comm.world)
         self._owner = owner
         self._type = swarm_type
@@ -156,11 +172,27 @@ class DeviceSwarmOptimization(SwarmOptimization):
         # expanders swarms of one optimiser must not draw the same numbers
         if rng == 'device' and seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
-        self._seed = (int(seed or 0) * 4 + _hip_swarm_types()[swarm_type]) & (2 ** 43 - 1)
+        code = THOMPSON_CODE if swarm_type == 'thompson' else _hip_swarm_types()[swarm_type]
+        self._seed = (int(seed or 0) * 4 + code) & (2 ** 43 - 1)
         self._calls = 0
+        self._path = None
         self.global_best = np.zeros(self.ndim)
 
+    def set_path(self, path):
+        """The sample path ``(Omega, phase, w, v)`` a Thompson swarm climbs from the next
+        ``init_swarm`` on."""
+        if self._type != 'thompson':
+            raise ValueError("only a 'thompson' swarm takes a path, this is %r" % (self._type,))
+        self._path = path
+
+    def _need_path(self):
+        if self._path is None:
+            raise ValueError("a 'thompson' swarm needs set_path(path) before init_swarm")
+        return self._path
+
     def fitness(self, positions):                 # kept for API parity
+        if self._type == 'thompson':
+            return self._owner._compute_path_fitness(self._need_path(), positions)
         return self._owner._compute_particle_fitness(self._type, positions)
 
     def _device_run(self, init, iters, inertia0, step):
@@ -170,6 +202,16 @@ class DeviceSwarmOptimization(SwarmOptimization):
         P, d = self.positions.shape
         rand = None
         self._calls += 1
+        if self._type == 'thompson':
+            path = self._need_path()
+            if self._rng == 'numpy':
+                rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
+            _hip.swarm_run_path(
+                devs[0].ctx, devs, o.beta(o.t), o.fmin, o.scaling, self.positions,
+                self.velocities, self.best_positions, self.best_values, self.global_best,
+                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
+                inertia0, step, rand, path, seed=(self._seed << 20) + self._calls)
+            return
         if self._comm.world == 1:
             if self._rng == 'numpy':
                 rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
@@ -219,6 +261,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
         return np.ascontiguousarray(full[:, :-1]), np.ascontiguousarray(full[:, -1])
 
     def init_swarm(self, positions):
+        if self._type == 'thompson':
+            self._need_path()
         positions = np.ascontiguousarray(positions, dtype=float)
         if self._comm.world > 1:
             lo, hi = self._rows
