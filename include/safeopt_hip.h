@@ -444,6 +444,19 @@ int sgp_grid_argmax(sgp_grid* grid, int mode, const double* scaling,
 int sgp_grid_paths(sgp_grid* grid, sgp_gp* gp, const double* Omega, const double* phase, int m,
                    const double* W, const double* V, int S, int mask, double* values,
                    double* best_val, int64_t* best_idx);
+/* sgp_grid_paths on a grid whose context has a communicator (sgp_comm_init or
+ * sgp_comm_init_host): the N-rank Thompson pick.  Every rank evaluates the paths over its
+ * resident rows; its S records (best value, GLOBAL row) are all-gathered -- in stream on
+ * RCCL, through the host transport otherwise -- and one small kernel merges the world x S
+ * records per path: the largest value, the lowest global row among equals; a shard without
+ * a qualifying row (-inf / -1) never wins against one with a row, and no qualifying row on
+ * any shard gives -inf / -1.  Every rank returns the same best_val[S] / best_idx[S], after
+ * ONE read-back of the merged result.  values (the rank's N_local x S block) stays optional
+ * and rank-local.  Every rank must pass the same paths and make the call (a collective).
+ * Without a communicator (one rank) it equals sgp_grid_paths.                             */
+int sgp_grid_paths_comm(sgp_grid* grid, sgp_gp* gp, const double* Omega, const double* phase,
+                        int m, const double* W, const double* V, int S, int mask,
+                        double* values, double* best_val, int64_t* best_idx);
 /* copy a resident array to the host: Q (N,2G) f64 | S/M/G (N) u8 |
  * mean/var (G,N) f64                                                         */
 /* S / M / G of the shard from the host: the reference's arrays are mutated in place
@@ -516,7 +529,8 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
  * shaping, path term), personal bests, global best -- also for a swarm the one-workgroup
  * step of sgp_swarm_run would take (a 20-particle Thompson swarm simply uses them): with
  * rand != NULL the run is bit-identical to the host loop over sgp_swarm_fitness_path.
- * One rank.  P <= 0 returns 0 and writes nothing.                              */
+ * The whole swarm in one call (a rank's block: sgp_swarm_run_path_shard).  P <= 0 returns
+ * 0 and writes nothing.                                                        */
 int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
                        const double* fmin, const double* scaling, int64_t P, double* positions,
                        double* velocities, double* best_positions, double* best_values,
@@ -546,6 +560,20 @@ int sgp_swarm_run_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
                         const double* bounds, int init, int iters, double inertia0,
                         double step, const double* rand, uint64_t seed, int64_t p0,
                         int64_t P_total);
+
+/* sgp_swarm_run_path on a rank's block [p0, p0 + P) of a Thompson swarm of P_total: the
+ * block, the merge of the global best after init and after every iteration, the Philox
+ * indexing and the layout of rand are those of sgp_swarm_run_shard; the path is staged once
+ * per call on every rank (every rank passes the same path).  p0 = 0, P = P_total is
+ * sgp_swarm_run_path; P < P_total needs a communicator on ctx, and P >= 1 on every rank. */
+int sgp_swarm_run_path_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                             const double* fmin, const double* scaling, int64_t P,
+                             double* positions, double* velocities, double* best_positions,
+                             double* best_values, double* global_best,
+                             const double* velocity_scale, const double* bounds, int init,
+                             int iters, double inertia0, double step, const double* rand,
+                             uint64_t seed, const double* Omega, const double* phase, int m,
+                             const double* w, const double* v, int64_t p0, int64_t P_total);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------
  * The only cross-rank traffic of the path is a handful of scalars per

@@ -70,6 +70,9 @@ PROTOTYPES = {
     "sgp_grid_paths": (C.c_int, [vp, vp, c_double_p, c_double_p, C.c_int, c_double_p,
                                  c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
                                  c_i64_p]),
+    "sgp_grid_paths_comm": (C.c_int, [vp, vp, c_double_p, c_double_p, C.c_int, c_double_p,
+                                      c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
+                                      c_i64_p]),
     "sgp_gp_get_factor": (C.c_int, [vp, c_double_p, c_double_p]),
     "sgp_kern_K": (C.c_int, [vp, C.c_int, C.c_int, c_int_p, c_double_p,
                              c_double_p, c_double_p, C.c_int64, c_double_p,
@@ -176,6 +179,13 @@ PROTOTYPES = {
                                      C.c_int, C.c_double, C.c_double, c_double_p,
                                      C.c_uint64, c_double_p, c_double_p, C.c_int,
                                      c_double_p, c_double_p]),
+    "sgp_swarm_run_path_shard": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                           c_double_p, c_double_p, C.c_int64,
+                                           c_double_p, c_double_p, c_double_p, c_double_p,
+                                           c_double_p, c_double_p, c_double_p, C.c_int,
+                                           C.c_int, C.c_double, C.c_double, c_double_p,
+                                           C.c_uint64, c_double_p, c_double_p, C.c_int,
+                                           c_double_p, c_double_p, C.c_int64, C.c_int64]),
     "sgp_swarm_run_shard": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
                                       c_double_p, c_double_p, C.c_double, C.c_int64,
                                       c_double_p, c_double_p, c_double_p, c_double_p,
@@ -1130,10 +1140,12 @@ class DeviceGrid(object):
                                              C.byref(v), C.byref(i)))
         return v.value, i.value
 
-    def paths(self, gp, Omega, phase, W, V, mask=False, values=False, best=True):
+    def paths(self, gp, Omega, phase, W, V, mask=False, values=False, best=True, comm=False):
         """Sample paths of ``gp`` over the resident rows (``sgp_grid_paths``): ``(values (N, S)
         or None, best value (S), its global row (S))`` -- the arg-max over all rows, or over
-        the rows of the safe set with ``mask``; -inf / -1 when no row qualifies."""
+        the rows of the safe set with ``mask``; -inf / -1 when no row qualifies.  ``comm``:
+        ``sgp_grid_paths_comm`` -- the arg-max over the rows of ALL ranks of the context's
+        communicator, the same on every rank (``values`` stays this rank's block)."""
         Omega, phase, W, m, S = gp._path_args(Omega, phase, W)
         V = f64(V)
         if V.shape != (gp.n, S):
@@ -1141,7 +1153,8 @@ class DeviceGrid(object):
         vals = np.empty((self.N, S)) if values else None
         bv = np.empty(S) if best else None
         bi = np.empty(S, dtype=np.int64) if best else None
-        self.ctx.check(lib().sgp_grid_paths(
+        call = lib().sgp_grid_paths_comm if comm else lib().sgp_grid_paths
+        self.ctx.check(call(
             self.h, gp.h, dptr(Omega), dptr(phase), m, dptr(W), dptr(V), S, int(bool(mask)),
             None if vals is None else dptr(vals), None if bv is None else dptr(bv),
             None if bi is None else bi.ctypes.data_as(c_i64_p)))
@@ -1165,6 +1178,13 @@ class DeviceGrid(object):
             np.copyto(out, buf)
             return out
         return buf
+
+
+def grid_paths_comm(grid, gp, Omega, phase, W, V, mask=False, values=False, best=True):
+    """``DeviceGrid.paths`` merged over the ranks of the grid's communicator
+    (``sgp_grid_paths_comm``): every rank gets the arg-max over the rows of all ranks; a
+    collective -- every rank calls it, with the same paths."""
+    return grid.paths(gp, Omega, phase, W, V, mask=mask, values=values, best=best, comm=True)
 
 
 def swarm_grow(ctx, gp, S, B, scale2, thr=0.95):
@@ -1259,19 +1279,26 @@ def swarm_fitness_path(ctx, gps, particles, beta, fmin, scaling, path):
 
 def swarm_run_path(ctx, gps, beta, fmin, scaling, positions, velocities, best_positions,
                    best_values, global_best, velocity_scale, bounds, init, iters, inertia0,
-                   step, rand, path, seed=0):
+                   step, rand, path, seed=0, shard=None):
     """Whole PSO run of a Thompson swarm on the device (``sgp_swarm_run_path``); the state
-    arrays are updated in place, ``path`` as for :func:`swarm_fitness_path`."""
+    arrays are updated in place, ``path`` as for :func:`swarm_fitness_path`.
+
+    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
+    ``P_total`` sharded over the ranks of ``ctx``'s communicator
+    (``sgp_swarm_run_path_shard``), as for :func:`swarm_run`."""
     P = positions.shape[0]
     for a in (positions, velocities, best_positions, best_values, global_best):
         assert a.dtype == np.float64 and a.flags.c_contiguous
     bnd = None if bounds is None else f64(bounds)
     rnd = None if rand is None else f64(rand).ravel()
     Omega, phase, m, w, v = _swarm_path_args(gps[0], path)
-    ctx.check(lib().sgp_swarm_run_path(
-        ctx.h, _gp_array(gps), len(gps), float(beta), dptr(f64(fmin)), dptr(f64(scaling)),
-        P, dptr(positions), dptr(velocities), dptr(best_positions), dptr(best_values),
-        dptr(global_best), dptr(f64(velocity_scale)), None if bnd is None else dptr(bnd),
-        int(bool(init)), int(iters), float(inertia0), float(step),
-        None if rnd is None else dptr(rnd), int(seed), dptr(Omega), dptr(phase), m, dptr(w),
-        dptr(v)))
+    args = (ctx.h, _gp_array(gps), len(gps), float(beta), dptr(f64(fmin)), dptr(f64(scaling)),
+            P, dptr(positions), dptr(velocities), dptr(best_positions), dptr(best_values),
+            dptr(global_best), dptr(f64(velocity_scale)), None if bnd is None else dptr(bnd),
+            int(bool(init)), int(iters), float(inertia0), float(step),
+            None if rnd is None else dptr(rnd), int(seed), dptr(Omega), dptr(phase), m, dptr(w),
+            dptr(v))
+    if shard is None:
+        ctx.check(lib().sgp_swarm_run_path(*args))
+    else:
+        ctx.check(lib().sgp_swarm_run_path_shard(*(args + (int(shard[0]), int(shard[1])))))

@@ -1726,7 +1726,7 @@ static int coll_allreduce_max_i32(sgp_ctx* ctx, int32_t* dev, size_t n) {
 }
 
 // recv (device) = the nbytes of every rank, in rank order
-static int coll_allgather(sgp_ctx* ctx, const void* send, void* recv, size_t nbytes) {
+int coll_allgather(sgp_ctx* ctx, const void* send, void* recv, size_t nbytes) {
   if (ctx->comm) {
     SGP_NCCL(ctx, g_rccl.AllGather(send, recv, nbytes, ncclInt8,
                                    static_cast<ncclComm_t>(ctx->comm), ctx->stream));
@@ -1745,7 +1745,7 @@ static int coll_allgather(sgp_ctx* ctx, const void* send, void* recv, size_t nby
 }
 
 // have_comm(ctx) -- or the error of a rank of several without a communicator
-static int comm_or_single(sgp_ctx* ctx, bool* comm) {
+int comm_or_single(sgp_ctx* ctx, bool* comm) {
   *comm = have_comm(ctx);
   SGP_CHECK(ctx, *comm || ctx->world <= 1,
             "rank %d of %d has no communicator in the grid's context: the "
@@ -2448,6 +2448,31 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
                    velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, 0, P);
 }
 
+// sgp_swarm_run_path (p0 = 0, Pt = P) and sgp_swarm_run_path_shard
+static int swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                          const double* fmin, const double* scaling, int64_t P,
+                          double* positions, double* velocities, double* best_positions,
+                          double* best_values, double* global_best,
+                          const double* velocity_scale, const double* bounds, int init,
+                          int iters, double inertia0, double step_size, const double* rand,
+                          uint64_t seed, const double* Omega, const double* phase, int m,
+                          const double* w, const double* v, int64_t p0, int64_t Pt) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
+  SGP_CHECK(ctx, gps[0]->ctx == ctx, "GP 0 lives in another context (device %d) than the "
+            "call (device %d)", gps[0]->ctx ? gps[0]->ctx->device : -1, ctx->device);
+  SGP_TRY(swarm_path_ready(gps[0], m));
+  // (an empty block of a sharded swarm is an error of swarm_run, not a silent return: the
+  // other ranks would wait in the all-gather)
+  if (P <= 0 && Pt <= 0) return 0;
+  // staged ONCE per call; nothing in swarm_run asks for the two slots it lives in
+  SwarmPath path;
+  SGP_TRY(swarm_path_stage(gps[0], Omega, phase, m, w, v, &path));
+  return swarm_run(ctx, gps, G, kSwarmThompson, beta, fmin, scaling, 0.0, P, positions,
+                   velocities, best_positions, best_values, global_best, velocity_scale, bounds,
+                   init, iters, inertia0, step_size, rand, seed, p0, Pt, &path);
+}
+
 int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
                        const double* fmin, const double* scaling, int64_t P, double* positions,
                        double* velocities, double* best_positions, double* best_values,
@@ -2456,18 +2481,23 @@ int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
                        double step_size, const double* rand, uint64_t seed,
                        const double* Omega, const double* phase, int m, const double* w,
                        const double* v) {
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
-  SGP_CHECK(ctx, gps[0]->ctx == ctx, "GP 0 lives in another context (device %d) than the "
-            "call (device %d)", gps[0]->ctx ? gps[0]->ctx->device : -1, ctx->device);
-  SGP_TRY(swarm_path_ready(gps[0], m));
-  if (P <= 0) return 0;
-  // staged ONCE per call; nothing in swarm_run asks for the two slots it lives in
-  SwarmPath path;
-  SGP_TRY(swarm_path_stage(gps[0], Omega, phase, m, w, v, &path));
-  return swarm_run(ctx, gps, G, kSwarmThompson, beta, fmin, scaling, 0.0, P, positions,
-                   velocities, best_positions, best_values, global_best, velocity_scale, bounds,
-                   init, iters, inertia0, step_size, rand, seed, 0, P, &path);
+  return swarm_run_path(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
+                        best_positions, best_values, global_best, velocity_scale, bounds, init,
+                        iters, inertia0, step_size, rand, seed, Omega, phase, m, w, v, 0, P);
+}
+
+int sgp_swarm_run_path_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                             const double* fmin, const double* scaling, int64_t P,
+                             double* positions, double* velocities, double* best_positions,
+                             double* best_values, double* global_best,
+                             const double* velocity_scale, const double* bounds, int init,
+                             int iters, double inertia0, double step_size, const double* rand,
+                             uint64_t seed, const double* Omega, const double* phase, int m,
+                             const double* w, const double* v, int64_t p0, int64_t P_total) {
+  return swarm_run_path(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
+                        best_positions, best_values, global_best, velocity_scale, bounds, init,
+                        iters, inertia0, step_size, rand, seed, Omega, phase, m, w, v, p0,
+                        P_total);
 }
 
 int sgp_swarm_run_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,

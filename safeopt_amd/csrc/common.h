@@ -437,8 +437,14 @@ int swarm_path_stage(sgp_gp* gp, const double* Omega, const double* phase, int m
 // values[p] = f(x_p) / scaling0 + values[p] over the rows of pts, gps_dev[0] the path's GP
 int launch_swarm_path(sgp_ctx* ctx, const GpDev* gps_dev, int d, const SwarmPath& path,
                       SweepPoints pts, double scaling0, double* values);
+// api.hip: the context's collectives on DEVICE operands -- RCCL in stream, or the host
+// transport of sgp_comm_init_host (sgp_grid_paths_comm merges its records behind one)
+// (defined inside api.hip's extern "C" block)
+extern "C" int comm_or_single(sgp_ctx* ctx, bool* comm);   // is there one?  Error: rank of several without
+// recv (device) = the nbytes of every rank, in rank order
+extern "C" int coll_allgather(sgp_ctx* ctx, const void* send, void* recv, size_t nbytes);
 // few-points posterior / small-swarm step: small_path.h
-constexpr int kSmallPoints = 4096;   // few-points posterior path (factor.hip)
+constexpr int kSmallPoints = 4096;  // few-points posterior path (factor.hip)
 constexpr int kSmallSwarm = 64;     // ... with the whole PSO step in one workgroup (swarm.hip)
 struct ExpanderArgs {
   const double* Wpack;   // [G][n_pad_max/4][64] MFMA A-operand (cand x j)

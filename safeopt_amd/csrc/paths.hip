@@ -27,6 +27,7 @@
 // of the rows, for the grid's resident rows against the same rows passed in.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <vector>
 
@@ -220,6 +221,27 @@ __global__ __launch_bounds__(256) void k_paths_final(const double* pval, const l
     out_v[s] = sv[0];
     out_i[s] = si[0] == kNoRow ? -1 : int64_t(si[0]) + goff;
   }
+}
+
+// The ranks' records -> the result of the whole grid (sgp_grid_paths_comm).  A record is what
+// k_paths_final leaves: [Sp] best values | [Sp] GLOBAL rows (-1: no row of that shard
+// qualified); recs holds `world` of them in rank order.  Thread s folds path s in the order of
+// take_better -- the largest value, the lowest global row among equals; a record without a row
+// never wins against one with a row -- and writes out[s] | out[Sp + s] (-inf / -1 when no
+// shard qualified).  world x S pairs: one workgroup.
+__global__ __launch_bounds__(64) void k_paths_merge(const double* recs, int world, int S, int Sp,
+                                                    double* out) {
+  const int s = threadIdx.x;
+  if (s >= S) return;
+  double v = -INFINITY;
+  long long i = kNoRow;
+  for (int r = 0; r < world; ++r) {
+    const double* rec = recs + int64_t(r) * 2 * Sp;
+    const long long i2 = reinterpret_cast<const long long*>(rec + Sp)[s];
+    if (i2 >= 0) take_better(v, i, rec[s], i2);
+  }
+  out[s] = i == kNoRow ? -INFINITY : v;
+  reinterpret_cast<long long*>(out + Sp)[s] = i == kNoRow ? -1 : i;
 }
 
 // ---- V = alpha 1^T - L^-T (L^-1 (U + E)) from the dense inverse factor ----------------------
@@ -498,9 +520,11 @@ int sgp_gp_paths_eval(sgp_gp* gp, const double* Omega, const double* phase, int 
   return 0;
 }
 
-int sgp_grid_paths(sgp_grid* g, sgp_gp* gp, const double* Omega, const double* phase, int m,
-                   const double* W, const double* V, int S, int mask, double* values,
-                   double* best_val, int64_t* best_idx) {
+// sgp_grid_paths, and with `merge` sgp_grid_paths_comm: the shard's records all-gathered over
+// the context's communicator and merged on the device before the one read-back.
+static int grid_paths(sgp_grid* g, sgp_gp* gp, const double* Omega, const double* phase, int m,
+                      const double* W, const double* V, int S, int mask, double* values,
+                      double* best_val, int64_t* best_idx, bool merge) {
   SGP_TRY(path_ready(gp, m, S));
   sgp_ctx* ctx = gp->ctx;
   SGP_CHECK(ctx, g->ctx == ctx, "the GP lives in another context (device %d) than the grid "
@@ -519,11 +543,17 @@ int sgp_grid_paths(sgp_grid* g, sgp_gp* gp, const double* Omega, const double* p
   if (values)
     SGP_TRY(sgp_scratch(ctx, kSlotPathOut, size_t(g->N) * S * sizeof(double), &pa.values));
   const int nwg = path_blocks(g->N);
+  bool comm = false;
+  if (merge && best_val) SGP_TRY(comm_or_single(ctx, &comm));
+  const int world = comm ? ctx->world : 1;
   double* res = nullptr;
   if (best_val) {
-    // [nwg][Sp] values | [nwg][Sp] rows | [Sp] best values | [Sp] best rows
+    // [nwg][Sp] values | [nwg][Sp] rows | [Sp] best values | [Sp] best rows; with a
+    // communicator behind them: the ranks' [2 Sp] records | the merged [Sp] values | [Sp] rows
     double* part;
-    SGP_TRY(sgp_scratch(ctx, kSlotPathPart, 2 * (size_t(nwg) + 1) * pa.Sp * sizeof(double), &part));
+    const size_t recs = comm ? size_t(world) + 1 : 0;
+    SGP_TRY(sgp_scratch(ctx, kSlotPathPart,
+                        2 * (size_t(nwg) + 1 + recs) * pa.Sp * sizeof(double), &part));
     pa.pval = part;
     pa.pidx = reinterpret_cast<long long*>(part + size_t(nwg) * pa.Sp);
     res = part + 2 * size_t(nwg) * pa.Sp;
@@ -533,9 +563,39 @@ int sgp_grid_paths(sgp_grid* g, sgp_gp* gp, const double* Omega, const double* p
     hipLaunchKernelGGL(k_paths_final, dim3(unsigned(S)), dim3(256), 0, ctx->stream, pa.pval,
                        pa.pidx, nwg, pa.Sp, g->goff, res, reinterpret_cast<int64_t*>(res + pa.Sp));
     SGP_HIP(ctx, hipGetLastError());
-    SGP_TRY(sgp_d2h(ctx, best_val, res, size_t(S) * sizeof(double)));
-    SGP_TRY(sgp_d2h(ctx, best_idx, res + pa.Sp, size_t(S) * sizeof(int64_t)));
+    if (comm) {
+      // (the record's entries behind S are never read: k_paths_merge stops at S)
+      double* all = res + 2 * size_t(pa.Sp);
+      double* merged = all + 2 * size_t(world) * pa.Sp;
+      SGP_TRY(coll_allgather(ctx, res, all, 2 * size_t(pa.Sp) * sizeof(double)));
+      hipLaunchKernelGGL(k_paths_merge, dim3(1), dim3(64), 0, ctx->stream, all, world, S, pa.Sp,
+                         merged);
+      SGP_HIP(ctx, hipGetLastError());
+      res = merged;
+    }
+    if (merge) {
+      // one read-back of the result
+      double h[2 * SGP_MAX_PATHS];
+      SGP_TRY(sgp_d2h(ctx, h, res, 2 * size_t(pa.Sp) * sizeof(double)));
+      memcpy(best_val, h, size_t(S) * sizeof(double));
+      memcpy(best_idx, h + pa.Sp, size_t(S) * sizeof(int64_t));
+    } else {
+      SGP_TRY(sgp_d2h(ctx, best_val, res, size_t(S) * sizeof(double)));
+      SGP_TRY(sgp_d2h(ctx, best_idx, res + pa.Sp, size_t(S) * sizeof(int64_t)));
+    }
   }
   if (values) SGP_TRY(sgp_d2h(ctx, values, pa.values, size_t(g->N) * S * sizeof(double)));
   return 0;
+}
+
+int sgp_grid_paths(sgp_grid* g, sgp_gp* gp, const double* Omega, const double* phase, int m,
+                   const double* W, const double* V, int S, int mask, double* values,
+                   double* best_val, int64_t* best_idx) {
+  return grid_paths(g, gp, Omega, phase, m, W, V, S, mask, values, best_val, best_idx, false);
+}
+
+int sgp_grid_paths_comm(sgp_grid* g, sgp_gp* gp, const double* Omega, const double* phase, int m,
+                        const double* W, const double* V, int S, int mask, double* values,
+                        double* best_val, int64_t* best_idx) {
+  return grid_paths(g, gp, Omega, phase, m, W, V, S, mask, values, best_val, best_idx, true);
 }

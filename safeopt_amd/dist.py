@@ -23,7 +23,8 @@ import time
 import numpy as np
 
 __all__ = ["shard_range", "allgather_rows", "LocalComm", "RcclComm", "SocketComm", "init_from_env",
-           "merge_topk", "merge_argmax", "launch_check"]
+           "merge_topk", "merge_argmax", "merge_path_records", "check_same_paths",
+           "launch_check"]
 
 
 def shard_range(N, rank, world):
@@ -54,6 +55,31 @@ def allgather_rows(comm, part, counts=None, count_dtype=np.int64):
     buf[:part.shape[0]] = part
     allp = comm.allgather(buf)
     return np.concatenate([allp[r][:c] for r, c in enumerate(counts)])
+
+
+def _digest48(arrays):
+    """48 bits of a hash of the arrays' shapes and bytes, as a float (exact in a double)."""
+    import hashlib
+    h = hashlib.blake2b(digest_size=6)
+    for a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        h.update(repr(a.shape).encode())
+        h.update(a.tobytes())
+    return float(int.from_bytes(h.digest(), "little"))
+
+
+def check_same_paths(comm, pp):
+    """``ValueError`` -- on EVERY rank, so that none is left waiting in a later collective --
+    unless all ranks hold the same sample paths ``pp`` (``Omega, phase, W, V``): an SPMD run
+    draws them from the same seed on every rank.  One ``allreduce_max`` of ``[h, -h]``, ``h``
+    a 48-bit digest."""
+    h = _digest48((pp.Omega, pp.phase, pp.W, pp.V))
+    red = comm.allreduce_max(np.array([h, -h]))
+    if red[0] != -red[1]:
+        raise ValueError(
+            "the ranks hold different sample paths (digest %012x on rank %d, the ranks' digests "
+            "span %012x .. %012x): seed NumPy's global generator alike on every rank before "
+            "thompson_points" % (int(h), comm.rank, int(-red[1]), int(red[0])))
 
 
 class LocalComm(object):
@@ -462,3 +488,17 @@ def merge_argmax(values, idxs):
     values, idxs = values[keep], idxs[keep]
     best = np.lexsort((idxs, -values))[0]
     return float(values[best]), int(idxs[best])
+
+
+def merge_path_records(values, idxs):
+    """Per path the global arg-max from the ranks' records: ``values`` / ``idxs`` are
+    ``(world, S)`` -- what ``sgp_grid_paths`` returns on every shard, -inf / -1 where no row
+    of a shard qualified -- merged column by column with :func:`merge_argmax` (the host form
+    of ``k_paths_merge``).  Returns ``(best values (S), global rows (S) int64)``."""
+    values = np.asarray(values, dtype=np.float64)
+    idxs = np.asarray(idxs, dtype=np.int64)
+    S = values.shape[1]
+    bv, bi = np.empty(S), np.empty(S, dtype=np.int64)
+    for s in range(S):
+        bv[s], bi[s] = merge_argmax(values[:, s], idxs[:, s])
+    return bv, bi

@@ -31,7 +31,8 @@ import weakref
 import numpy as np
 
 from . import _hip
-from .dist import LocalComm, allgather_rows, merge_argmax, merge_topk, shard_range
+from .dist import (LocalComm, allgather_rows, check_same_paths, merge_argmax,
+                   merge_path_records, merge_topk, shard_range)
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
 
 __all__ = ['SafeOpt', 'SafeOptSwarm']
@@ -426,10 +427,11 @@ class _HipGridBackend(object):
     def download(self, what):
         return self.grid.download(what)
 
-    def paths(self, pp, mask, values):
-        """Sample paths ``pp`` (of one of this backend's GPs) over the resident rows."""
+    def paths(self, pp, mask, values, comm=False):
+        """Sample paths ``pp`` (of one of this backend's GPs) over the resident rows; ``comm``:
+        the arg-max merged over the ranks in the grid's stream (``sgp_grid_paths_comm``)."""
         return self.grid.paths(pp.device, pp.Omega, pp.phase, pp.W, pp.V, mask=mask,
-                               values=values)
+                               values=values, comm=comm)
 
 
 class SafeOpt(GaussianProcessOptimization):
@@ -1321,26 +1323,57 @@ class SafeOpt(GaussianProcessOptimization):
         ``return_values=True`` also the ``(N, size)`` array of all path values.
         ``within='all'`` ignores ``S``: the arg-max over every row -- NOT a safe pick, for
         diagnostics and unconstrained problems only.  Raises ``RuntimeError`` when no row is
-        safe.  One rank only.  Changes no state of the optimiser -- except that in-place edits
+        safe.  Changes no state of the optimiser -- except that in-place edits
         of ``opt.Q`` / ``opt.S`` still pending are flushed to the device first, as before a
         set pass (an edited ``Q`` is uploaded and ``S`` recomputed from it); the random
-        numbers come from NumPy's global generator."""
+        numbers come from NumPy's global generator.
+
+        N ranks (SPMD, as ``optimize()``: the same seed and the same call on every rank):
+        every rank draws the same paths -- the draws of one rank, so NumPy's generator ends
+        where the one-rank run leaves it; one ``allreduce_max`` of a digest verifies it and
+        raises ``ValueError`` on every rank otherwise -- and evaluates them over its shard.
+        The per-path maxima are merged over the ranks, the lowest global row among equal
+        values: in the grid's stream with an in-stream communicator
+        (``sgp_grid_paths_comm``, one device round trip), else by one all-gather of the
+        ranks' records and ``dist.merge_path_records``; both give the bits of the one-rank
+        run, on every rank.  ``return_values=True`` gathers the ``(N, size)`` array in
+        global row order on every rank.  "No row is safe" raises on every rank, after the
+        collective."""
         if within not in ('safe', 'all'):
             raise ValueError("within must be 'safe' or 'all', got %r" % (within,))
-        if self._comm.world > 1:
+        comm = self._comm
+        world = comm.world
+        if world > 1 and not all(callable(getattr(comm, f, None))
+                                 for f in ('allreduce_max', 'allgather')):
             raise NotImplementedError(
-                "thompson_points runs on one rank, this optimiser has a communicator of %d: "
-                "the sharded merge (identical paths on every rank, one all-gather of the "
-                "per-path maxima) is not implemented" % self._comm.world)
+                "thompson_points on more than one rank merges the ranks' picks through the "
+                "communicator's allreduce_max and allgather: this communicator of %d ranks "
+                "implements neither" % world)
         if not hasattr(self._backend, 'paths'):
             raise NotImplementedError("this grid backend evaluates no sample paths")
         self._flush_Q()
         self._flush_masks()
         safe = within == 'safe'
-        if safe and self._any_safe is not None and not self._any_safe:
+        # (N ranks: raised behind the collective, where every rank is sure to arrive)
+        if world == 1 and safe and self._any_safe is not None and not self._any_safe:
             raise RuntimeError('There are no safe points to sample in.')
         pp = self.gp.posterior_paths(size=size, features=features)
-        values, best, idx = self._backend.paths(pp, safe, return_values)
+        if world == 1:
+            values, best, idx = self._backend.paths(pp, safe, return_values)
+        else:
+            check_same_paths(comm, pp)
+            if getattr(comm, 'in_stream', False):
+                values, best, idx = self._backend.paths(pp, safe, return_values, comm=True)
+            else:
+                values, bv, bi = self._backend.paths(pp, safe, return_values)
+                rec = np.empty((2, bv.shape[0]))
+                rec[0], rec[1] = bv, bi                           # (rows < 2^53)
+                rec = comm.allgather(rec)
+                best, idx = merge_path_records(rec[:, 0], rec[:, 1].astype(np.int64))
+            if return_values:
+                N = self.inputs.shape[0]
+                values = allgather_rows(comm, values, [
+                    hi - lo for lo, hi in (shard_range(N, r, world) for r in range(world))])
         if np.any(idx < 0):
             raise RuntimeError('There are no safe points to sample in.')
         x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
@@ -1527,8 +1560,18 @@ class SafeOptSwarm(GaussianProcessOptimization):
         Returns ``(x (size, d), values (size,))`` with ``values[s] = pp.paths(x[s][None])[0, 0,
         s]``; with ``return_paths=True`` also the ``PosteriorPaths`` ``pp``.  Raises
         ``RuntimeError`` when the safe set is empty or a swarm ends with no safe personal
-        best, ``ValueError`` for more than ``SGP_MAX_PATHS`` paths, ``NotImplementedError``
-        with a communicator of more than one rank.
+        best, ``ValueError`` for more than ``SGP_MAX_PATHS`` paths.
+
+        N ranks (``comm=``; SPMD, the same seed and call on every rank): every swarm is
+        split over the ranks by particle as the other swarms are
+        (``sgp_swarm_run_path_shard``: the path staged on every rank, the global best merged
+        on the device after every iteration); every rank draws what one rank draws -- one
+        ``allreduce_max`` of a digest verifies that the ranks hold the same paths,
+        ``ValueError`` on every rank otherwise -- and the final ``safe_set`` fitness call and
+        the pick run replicated on the gathered personal bests: the bits of the one-rank run
+        on every rank.  The global best is merged in the stream of the communicator's device
+        context; a communicator of several ranks without one is refused
+        (``NotImplementedError``) before any draw.
 
         Changes no state of the optimiser beyond what ``_recheck_safe_set`` does at the start
         of every swarm run (it may drop points that are no longer safe): ``S`` does not grow,
@@ -1543,27 +1586,30 @@ class SafeOptSwarm(GaussianProcessOptimization):
            numbers as ``rand(swarm_size d)`` and ``rand(2 swarm_size d max_iters)``, one C
            call each; ``'device-rng'``: nothing.
 
-        Out of scope: Thompson swarms split over ranks; ``SafeOpt.thompson_points`` on N
-        ranks; running all ``size`` swarms as one launch with per-swarm global bests; paths
-        of the constraint GPs (the constraints enter through their confidence bounds)."""
+        Out of scope: running all ``size`` swarms as one launch with per-swarm global bests;
+        paths of the constraint GPs (the constraints enter through their confidence
+        bounds)."""
         size = int(size)
         if size > _hip.MAX_PATHS:
             raise ValueError("size = %d paths, at most SGP_MAX_PATHS = %d per call"
                              % (size, _hip.MAX_PATHS))
-        if self._comm.world > 1:
+        world = self._comm.world
+        if world > 1 and getattr(self._comm, 'ctx', None) is None:
+            # (what the constructor asks of a communicator of several ranks)
             raise NotImplementedError(
-                "thompson_points runs on one rank, this optimiser has a communicator of %d: "
-                "the sharded Thompson swarm (sgp_swarm_run_path on a rank's block of the "
-                "particles, the global best merged over the ranks) is not implemented"
-                % self._comm.world)
+                "the sharded Thompson swarm merges the global best in the stream of the "
+                "communicator's device context: a merge over this host-only communicator of "
+                "%d ranks is not implemented" % world)
         self._recheck_safe_set()
         iters = int(max_iters or self.max_iters)
         swarm = None                      # pso='host': a reference loop per path
         if isinstance(self.swarms['maximizers'], DeviceSwarmOptimization):
             swarm = DeviceSwarmOptimization(
                 self.swarm_size, self.optimal_velocities, self, 'thompson',
-                bounds=self.bounds, rng=self.swarms['maximizers']._rng)
+                bounds=self.bounds, rng=self.swarms['maximizers']._rng, comm=self._comm)
         pp = self.gp.posterior_paths(size, features)
+        if world > 1:
+            check_same_paths(self._comm, pp)
         x = np.empty((size, self.gp.input_dim))
         for s in range(size):
             path = (pp.Omega, pp.phase, np.ascontiguousarray(pp.W[:, s]),

@@ -145,7 +145,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
     ``swarm_type='thompson'``: the fitness is the value of one posterior sample path of
     the owner's objective GP under the maximizers' penalty and safety rule
     (``sgp_swarm_fitness_path`` / ``sgp_swarm_run_path``); ``set_path(path)`` with ``path =
-    (Omega, phase, w, v)`` comes before ``init_swarm``.  One rank only.
+    (Omega, phase, w, v)`` comes before ``init_swarm``; with ``comm`` it is sharded like
+    every other swarm (``sgp_swarm_run_path_shard``), every rank holding the same path.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
@@ -157,11 +158,10 @@ class DeviceSwarmOptimization(SwarmOptimization):
             raise ValueError("rng must be 'numpy' or 'device'")
         from .dist import LocalComm, shard_range
         self._comm = comm if comm is not None else LocalComm()
-        if swarm_type == 'thompson' and self._comm.world > 1:
+        if self._comm.world > 1 and not callable(getattr(self._comm, 'allgather', None)):
             raise NotImplementedError(
-                "a Thompson swarm runs on one rank, this communicator has %d: the sharded "
-                "run of sgp_swarm_run_path (a rank's block of the particles, the global "
-                "best merged over the ranks) is not implemented" % self._comm.world)
+                "a sharded swarm gathers its personal bests through the communicator's "
+                "allgather: this communicator of %d ranks implements none" % self._comm.world)
         self._rows = shard_range(swarm_size, self._comm.rank, self._comm.world)
         self._owner = owner
         self._type = swarm_type
@@ -202,19 +202,17 @@ class DeviceSwarmOptimization(SwarmOptimization):
         P, d = self.positions.shape
         rand = None
         self._calls += 1
-        if self._type == 'thompson':
-            path = self._need_path()
-            if self._rng == 'numpy':
-                rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
-            _hip.swarm_run_path(
-                devs[0].ctx, devs, o.beta(o.t), o.fmin, o.scaling, self.positions,
-                self.velocities, self.best_positions, self.best_values, self.global_best,
-                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
-                inertia0, step, rand, path, seed=(self._seed << 20) + self._calls)
-            return
+        path = self._need_path() if self._type == 'thompson' else None
         if self._comm.world == 1:
             if self._rng == 'numpy':
                 rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
+            if path is not None:
+                _hip.swarm_run_path(
+                    devs[0].ctx, devs, o.beta(o.t), o.fmin, o.scaling, self.positions,
+                    self.velocities, self.best_positions, self.best_values, self.global_best,
+                    np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
+                    inertia0, step, rand, path, seed=(self._seed << 20) + self._calls)
+                return
             _hip.swarm_run(
                 devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
                 o.best_lower_bound, self.positions, self.velocities,
@@ -239,13 +237,21 @@ class DeviceSwarmOptimization(SwarmOptimization):
                 at += 2 * P * d
             rand = np.concatenate(parts) if parts else None
         loc = self._local
-        _hip.swarm_run(
-            devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
-            o.best_lower_bound, self.positions, self.velocities,
-            loc['best_positions'], loc['best_values'], self.global_best,
-            np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init,
-            iters, inertia0, step, rand,
-            seed=(self._seed << 20) + self._calls, shard=(lo, self.swarm_size))
+        if path is not None:
+            _hip.swarm_run_path(
+                devs[0].ctx, devs, o.beta(o.t), o.fmin, o.scaling, self.positions,
+                self.velocities, loc['best_positions'], loc['best_values'], self.global_best,
+                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
+                inertia0, step, rand, path, seed=(self._seed << 20) + self._calls,
+                shard=(lo, self.swarm_size))
+        else:
+            _hip.swarm_run(
+                devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
+                o.best_lower_bound, self.positions, self.velocities,
+                loc['best_positions'], loc['best_values'], self.global_best,
+                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init,
+                iters, inertia0, step, rand,
+                seed=(self._seed << 20) + self._calls, shard=(lo, self.swarm_size))
         self.best_positions, self.best_values = self._gather(
             loc['best_positions'], loc['best_values'])
 

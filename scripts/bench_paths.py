@@ -2,7 +2,7 @@
 """Cost of posterior sample paths over a grid (``sgp_grid_paths``, csrc/paths.hip).
 
     python scripts/bench_paths.py [--rows 1000000] [--n 500] [--reps 3] [--figures FILE]
-                                  [--out profiles/paths/SUMMARY.txt]
+                                  [--gpus N] [--out profiles/paths/SUMMARY.txt]
 
 The config-3 shape: a 1000 x 1000 grid, n = 500 observations, Matern52-ARD at d = 2.  Per
 m in {256, 1024, 4096} x S in {1, 16, 64}: milliseconds of the path kernel (the per-launch
@@ -12,7 +12,10 @@ it the fp64 VALU instructions of one feature evaluation, counted in the feature 
 kernel's ISA with the parser of scripts/dev/isa_stats.py (``isa_counts``), and the fraction of
 the fp64 VALU roof that count implies at the measured time per (row, feature).  For context the
 exact ``posterior_samples_f`` at N = 8192.  ``--figures``: the error ratios that
-tests/test_gpu_paths.py wrote (SGP_PATHS_FIGURES) go into the summary.
+tests/test_gpu_paths.py wrote (SGP_PATHS_FIGURES) go into the summary.  ``--gpus N`` starts N
+ranks, one per GPU, each with its shard of the rows, and times the N-rank pick
+(``sgp_grid_paths_comm``: the shard's kernel, the all-gather of the records, the merge) on
+rank 0.
 """
 import argparse, json, os, re, subprocess, sys, tempfile, time
 ROOT = os.environ.get("SGP_BENCH_PACKAGE_ROOT") or \
@@ -71,19 +74,47 @@ def timed(ctx, fn, reps):
     return float(np.median(ms))
 
 
+def spawn(n, argv):
+    """``--gpus N``: N ranks, one per GPU, in the torchrun-style environment
+    ``dist.init_from_env`` reads (as scripts/swarm_optimize.py starts them); rank 0 prints."""
+    import socket, subprocess
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    nonce = "%d-%x" % (os.getpid(), int(time.time() * 1e6))
+    procs = []
+    for r in range(n):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n),
+                   LOCAL_WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port), SAFEOPT_RDZV_NONCE=nonce)
+        env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv,
+                                      env=env, stdout=subprocess.PIPE if r == 0 else
+                                      subprocess.DEVNULL, text=True))
+    out, _ = procs[0].communicate()
+    rcs = [procs[0].returncode] + [p.wait() for p in procs[1:]]
+    sys.stdout.write(out)
+    if any(rcs):
+        sys.exit("ranks exited with %r" % (rcs,))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1000000)
     ap.add_argument("--n", type=int, default=500)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--figures")
+    ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--out")
     a = ap.parse_args()
-    isa = isa_counts()            # before any GPU time: raises without toolchain or kernel
+    if a.gpus > 1 and "RANK" not in os.environ:
+        return spawn(a.gpus, sys.argv[1:])
+    # before any GPU time: raises without toolchain or kernel (rank 0 reports: it alone counts)
+    isa = isa_counts() if os.environ.get("RANK", "0") == "0" else None
     import safeopt_amd
     import safeopt_amd.gpy as gpy
-    from safeopt_amd import _hip, paths as P
-    ctx = _hip.Context.default()
+    from safeopt_amd import _hip, dist, paths as P
+    ctx, comm = dist.init_from_env()
     side = int(round(a.rows ** 0.5))
     grid_rows = safeopt_amd.linearly_spaced_combinations([(-5., 5.)] * 2, side)
     rng = np.random.RandomState(0)
@@ -94,28 +125,33 @@ def main():
         return gpy.models.GPRegression(X, Y, gpy.kern.Matern52(2, 1.7, [0.9, 1.5], ARD=True),
                                        noise_var=NOISE)
     gp, gp1 = model(a.n), model(1)
-    grid = _hip.DeviceGrid(ctx, grid_rows, 1)
+    # (every rank draws the same numbers from `rng`: the ranks hold the same GPs and paths)
+    lo, hi = dist.shard_range(grid_rows.shape[0], comm.rank, comm.world)
+    grid = _hip.DeviceGrid(ctx, grid_rows[lo:hi], 1, lo)
 
     def run(g, m, S):
         dev = g._fitted()
         desc = g.kern._desc(2)
         Om, b, W, E = P.draw_path_inputs((desc[1], desc[3]), NOISE, dev.n, 2, S, m, rng=rng)
         V = dev.path_weights(Om, b, W, E)
-        return timed(ctx, lambda: grid.paths(dev, Om, b, W, V), a.reps)
+        return timed(ctx, lambda: grid.paths(dev, Om, b, W, V, comm=comm.world > 1), a.reps)
 
     rows = []
     for m in (256, 1024, 4096):
         for S in (1, 16, 64):
             rows.append({"m": m, "S": S, "ms": run(gp, m, S), "features_ms": run(gp1, m, S),
                          "covariances_ms": run(gp, 1, S)})
+    if comm.rank:
+        return
     # the exact draw, for context
     Xs = grid_rows[rng.permutation(grid_rows.shape[0])[:8192]]
     t0 = time.perf_counter()
     gp.posterior_samples_f(Xs, size=16)
     exact_ms = (time.perf_counter() - t0) * 1e3
     N = grid_rows.shape[0]
-    lines = ["sgp_grid_paths, %d rows (d = 2), n = %d, Matern52-ARD; kernel ms (hipEvents), median of %d"
-             % (N, a.n, a.reps),
+    lines = ["%s, %d rows (d = 2)%s, n = %d, Matern52-ARD; kernel ms (hipEvents), median of %d"
+             % ("sgp_grid_paths_comm" if comm.world > 1 else "sgp_grid_paths", N,
+                " over %d ranks" % comm.world if comm.world > 1 else "", a.n, a.reps),
              "    m     S   total ms  features (n = 1)  covariances (m = 1)   ns / (row feature)"]
     for r in rows:
         r["ns_per_feature"] = r["features_ms"] * 1e6 / (N * r["m"])
@@ -148,7 +184,7 @@ def main():
                         fig.get("evaluation_abs", float("nan"))))
     else:
         lines.append("error ratios of tests/test_gpu_paths.py: not measured (no --figures file)")
-    line = json.dumps({"bench": "paths", "rows": rows, "isa": isa, "exact_8192_ms": exact_ms,
+    line = json.dumps({"bench": "paths", "gpus": comm.world, "rows": rows, "isa": isa, "exact_8192_ms": exact_ms,
                        "figures": fig})
     print(line)
     print("\n".join(lines))
