@@ -35,12 +35,13 @@ extern "C" {
 #define SGP_MAX_JOINT 8192 /* rows of one joint prediction                     */
 #define SGP_MAX_PATHS 64   /* sample paths of one call                         */
 #define SGP_MAX_FEATURES 16384 /* random Fourier features of a sample path     */
+#define SGP_MAX_BATCH 64   /* query points of one hallucinated batch           */
 
 /* kernel kinds: GPy.kern.RBF / Matern32 / Matern52 (Stationary.K_of_r)        */
 enum { SGP_RBF = 0, SGP_MATERN32 = 1, SGP_MATERN52 = 2 };
 /* sgp_grid_download selectors                                                 */
 enum { SGP_Q = 0, SGP_S = 1, SGP_M = 2, SGP_G = 3, SGP_MEAN = 4, SGP_VAR = 5,
-       SGP_CAND = 6, SGP_WIDTH = 7 };
+       SGP_CAND = 6, SGP_WIDTH = 7, SGP_VAR_H = 8 };
 /* sgp_grid_argmax modes                                                       */
 enum { SGP_ARGMAX_MG_WIDTH = 0, SGP_ARGMAX_UCB = 1, SGP_ARGMAX_LCB = 2 };
 /* sgp_swarm_fitness swarm types (gp_opt.py:901-1013)                          */
@@ -163,6 +164,15 @@ int sgp_gp_paths_eval(sgp_gp* gp, const double* Omega, const double* phase, int 
                       int64_t stride_row, int64_t stride_col, double* out);
 /* test hook: dense L^-1 (n x n, row-major) and alpha (n)                     */
 int sgp_gp_get_factor(sgp_gp* gp, double* Linv, double* alpha);
+/* A second GP with the state of src, device to device: kernel, noise, jitter, training data,
+ * L^-1, alpha, the record of the last append, and row capacity for at least SGP_MAX_BATCH
+ * one-row appends.  The packed operands are formed again from the copied L^-1 by the kernels
+ * that formed the source's: the clone predicts the bits of src.  It is appended to, refitted
+ * and destroyed independently of src (src is only read, and may be destroyed first); clones of
+ * GPs that share a factor (sgp_ctx_set_share) share among themselves after equal appends.
+ * What SafeOpt.optimize_batch appends its pending picks to: sgp_gp_append followed by
+ * sgp_gp_pop does not give a GP back bit for bit (pop recomputes alpha).                 */
+int sgp_gp_clone(sgp_gp* src, sgp_gp** out);
 /* gp.kern.K(X, X2) (gp_opt.py:847, 1093; utilities.py:89, 135): out is
  * (n1,n2) row-major; X1 (n1,d), X2 (n2,d) row-major.                         */
 int sgp_kern_K(sgp_ctx* ctx, int d, int n_parts, const int* kinds,
@@ -457,8 +467,28 @@ int sgp_grid_paths(sgp_grid* grid, sgp_gp* gp, const double* Omega, const double
 int sgp_grid_paths_comm(sgp_grid* grid, sgp_gp* gp, const double* Omega, const double* phase,
                         int m, const double* W, const double* V, int S, int mask,
                         double* values, double* best_val, int64_t* best_idx);
+/* One pick of a batch by hallucinated observations (GP-BUCB, Desautels et al. 2014, on
+ * SafeOpt's rule, safeopt/gp_opt.py:635-649; the reference has no batch mode).  gps are CLONES
+ * (sgp_gp_clone) of the grid's GPs, every one with the pending pick x* appended
+ * (sgp_gp_append; any y: only the variance is read) -- checked as sgp_grid_rank1_update
+ * checks its records.  In one pass over the rows, per GP i,
+ *   var_h_i(x) = max(v_i(x) - c_i(x)^2 / s2_i, 1e-15),   c, s2 as in sgp_grid_rank1_update,
+ * v = the resident var (first != 0: the first downdate of a batch; var_h is never read before
+ * it is written) or var_h as the pick before left it, and the intervals
+ * l = mean - beta sqrt(var_h), u = mean + beta sqrt(var_h) from the RESIDENT mean.  Then the
+ * arg-max of
+ *   mode SGP_ARGMAX_MG_WIDTH: max_i (u_i - l_i) / scaling_i over the rows of M | G,
+ *   mode SGP_ARGMAX_UCB:      u_0 over the rows of S,
+ * over the rows that are not among picked[n_picked] (GLOBAL rows, n_picked <= SGP_MAX_BATCH);
+ * the lowest global row wins among equal values; value = -inf, gidx = -1 when no row is
+ * eligible (var_h is downdated all the same).  Q, S, M, G, mean and var are only read.  One
+ * launch of the row kernel, a small final kernel, one read-back.  One rank.  var_h (G,N) is
+ * a buffer of the grid, allocated by the first call: sgp_grid_download(SGP_VAR_H).        */
+int sgp_grid_batch_next(sgp_grid* grid, sgp_gp* const* gps, int G, int first, int mode,
+                        double beta, const double* scaling, const int64_t* picked,
+                        int n_picked, double* value, int64_t* gidx);
 /* copy a resident array to the host: Q (N,2G) f64 | S/M/G (N) u8 |
- * mean/var (G,N) f64                                                         */
+ * mean/var/var_h (G,N) f64 (var_h: after a sgp_grid_batch_next)              */
 /* S / M / G of the shard from the host: the reference's arrays are mutated in place
  * (safeopt/gp_opt.py:481, 505-506, 511, 615) and user code may write into them; the next
  * arg-max (get_new_query_point, gp_opt.py:635-649) reads what was uploaded.            */

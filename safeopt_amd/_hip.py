@@ -29,13 +29,14 @@ HOST_ALLREDUCE_I32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_
 HOST_ALLGATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 
 RBF, MATERN32, MATERN52 = 0, 1, 2
-Q, S, M, G, MEAN, VAR, CAND, WIDTH = 0, 1, 2, 3, 4, 5, 6, 7
+Q, S, M, G, MEAN, VAR, CAND, WIDTH, VAR_H = 0, 1, 2, 3, 4, 5, 6, 7, 8
 ARGMAX_MG_WIDTH, ARGMAX_UCB, ARGMAX_LCB = 0, 1, 2
 SWARM_TYPES = {"greedy": 0, "maximizers": 1, "expanders": 2, "safe_set": 3}
 MAX_D, MAX_PARTS, MAX_GPS, TOPK = 8, 4, 8, 16
 MAX_JOINT = 8192          # SGP_MAX_JOINT: rows of one joint prediction
 MAX_PATHS = 64            # SGP_MAX_PATHS: sample paths of one call
 MAX_FEATURES = 16384      # SGP_MAX_FEATURES: random Fourier features of a sample path
+MAX_BATCH = 64            # SGP_MAX_BATCH: query points of one hallucinated batch
 
 # name -> (restype, argtypes); mirrors include/safeopt_hip.h one to one
 PROTOTYPES = {
@@ -74,6 +75,9 @@ PROTOTYPES = {
                                       c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
                                       c_i64_p]),
     "sgp_gp_get_factor": (C.c_int, [vp, c_double_p, c_double_p]),
+    "sgp_gp_clone": (C.c_int, [vp, vpp]),
+    "sgp_grid_batch_next": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_int, C.c_double,
+                                      c_double_p, c_i64_p, C.c_int, c_double_p, c_i64_p]),
     "sgp_kern_K": (C.c_int, [vp, C.c_int, C.c_int, c_int_p, c_double_p,
                              c_double_p, c_double_p, C.c_int64, c_double_p,
                              C.c_int64, c_double_p]),
@@ -689,6 +693,26 @@ class DeviceGP(object):
             Xnew.strides[0] // it, Xnew.strides[1] // it, dptr(out)))
         return out
 
+    def clone(self):
+        """A second device GP with this one's state (``sgp_gp_clone``): the same bits in the
+        data, ``L^-1``, ``alpha`` and the packed operands, and room for ``MAX_BATCH`` more
+        appends.  Appending to it, refitting or destroying it leaves this GP alone, and it
+        outlives this GP."""
+        h = vp()
+        self.ctx.check(lib().sgp_gp_clone(self.h, C.byref(h)))
+        twin = object.__new__(DeviceGP)
+        twin.ctx, twin.d, twin.h = self.ctx, self.d, h
+        twin.n_parts, twin.n, twin.jitter = self.n_parts, self.n, self.jitter
+        twin.version, twin.appended = self.version, self.appended
+        twin.serial = next(DeviceGP._serials)
+        return twin
+
+    def destroy(self):
+        """Release the device GP now (a private copy whose owner is done with it)."""
+        if getattr(self, "h", None):
+            lib().sgp_gp_destroy(self.h)
+            self.h = None
+
     def factor(self):
         Linv = np.empty((self.n, self.n))
         alpha = np.empty(self.n)
@@ -1138,6 +1162,21 @@ class DeviceGrid(object):
         i = C.c_int64(0)
         self.ctx.check(lib().sgp_grid_argmax(self.h, int(mode), dptr(scaling),
                                              C.byref(v), C.byref(i)))
+        return v.value, i.value
+
+    def batch_next(self, gps, first, mode, beta, scaling, picked):
+        """One pick of a hallucinated batch (``sgp_grid_batch_next``): ``gps`` are clones with
+        the pending pick appended; ``(value, global row)`` of the best row of the mask that is
+        not in ``picked``, ``(-inf, -1)`` when none is left.  ``first``: the downdate starts
+        from the resident variances instead of the hallucinated ones (``download(VAR_H)``)."""
+        scaling = f64(scaling)
+        picked = np.ascontiguousarray(picked, dtype=np.int64).reshape(-1)
+        v = C.c_double(0)
+        i = C.c_int64(0)
+        self.ctx.check(lib().sgp_grid_batch_next(
+            self.h, _gp_array(gps), len(gps), int(bool(first)), int(mode), float(beta),
+            dptr(scaling), picked.ctypes.data_as(c_i64_p), int(picked.size), C.byref(v),
+            C.byref(i)))
         return v.value, i.value
 
     def paths(self, gp, Omega, phase, W, V, mask=False, values=False, best=True, comm=False):

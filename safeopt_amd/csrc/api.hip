@@ -580,6 +580,80 @@ int sgp_gp_get_factor(sgp_gp* gp, double* Linv, double* alpha) {
   return 0;
 }
 
+// A second GP with the state of src.  The buffers that carry state (X, Y, L^-1, alpha, the
+// append record) are copied device to device at the pitch of the clone, which has room for
+// SGP_MAX_BATCH more rows; the workspaces of a refit (Kmat, work) are left to the first refit;
+// the operands of the sweeps come from publish_gp, i.e. from the kernels that formed the
+// source's out of the same L^-1, X and alpha.
+int sgp_gp_clone(sgp_gp* src, sgp_gp** out) {
+  *out = nullptr;
+  sgp_ctx* ctx = src->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, src->n > 0, "GP has no data");
+  SGP_CHECK(ctx, src->factored, "GP is not fitted (infeasible hyper-parameters)");
+  sgp_gp* gp = nullptr;
+  {
+    int kinds[SGP_MAX_PARTS];
+    double variances[SGP_MAX_PARTS], inv_ls[SGP_MAX_PARTS * SGP_MAX_D];
+    const KernDesc& k = src->kern;
+    for (int p = 0; p < k.n_parts; ++p) {
+      kinds[p] = k.kind[p];
+      variances[p] = k.variance[p];
+      for (int a = 0; a < k.d; ++a) inv_ls[p * k.d + a] = k.inv_ls[p][a];
+    }
+    SGP_TRY(sgp_gp_create(ctx, k.d, k.n_parts, kinds, variances, inv_ls, src->noise_var, &gp));
+  }
+  gp->kern = src->kern;              // (the very bytes: collect_gps compares descriptors)
+  gp->jitter = src->jitter;
+  gp->n = src->n;
+  gp->n_pad = src->n_pad;
+  gp->n_f = src->n_f;
+  gp->data_version = src->data_version;
+  gp->xhost = src->xhost;
+  gp->xhash = src->xhash;
+  gp->prov = src->prov;
+  gp->upd_valid = src->upd_valid;
+  gp->factored = true;
+  const int d = src->kern.d, ld0 = src->ld;
+  const int ld = std::max(ld0, int((src->n + SGP_MAX_BATCH + 63) / 64) * 64);
+  gp->ld = ld;
+  auto fail = [&](int rc) {
+    sgp_gp_destroy(gp);
+    return rc;
+  };
+  struct {
+    DevBuf* dst;
+    const DevBuf* from;
+    size_t bytes, copy;
+  } bufs[] = {
+      {&gp->X, &src->X, size_t(ld) * d * 8, size_t(ld0) * d * 8},
+      {&gp->Y, &src->Y, size_t(ld) * 8, size_t(ld0) * 8},
+      {&gp->alpha, &src->alpha, size_t(ld + 16) * 8, size_t(ld0 + 16) * 8},
+      {&gp->updw, &src->updw, size_t(ld + 16) * 8, size_t(ld0 + 16) * 8},
+      {&gp->upd, &src->upd, size_t(SGP_MAX_D + 2) * 8, size_t(SGP_MAX_D + 2) * 8},
+      {&gp->tvec, nullptr, size_t(ld) * 8 + 64, 0},
+      {&gp->Linv, nullptr, size_t(ld) * ld * 8, 0}};
+  for (auto& b : bufs) {
+    if (sgp_reserve(ctx, b.dst, b.bytes) != 0) return fail(-1);
+    if (b.copy && hipMemcpyAsync(b.dst->p, b.from->p, b.copy, hipMemcpyDeviceToDevice,
+                                 ctx->stream) != hipSuccess) {
+      sgp_set_error(ctx, "sgp_gp_clone: device copy failed");
+      return fail(-1);
+    }
+  }
+  // L^-1: zero above the diagonal and behind the data at the new pitch, as factor_gp leaves it
+  if (hipMemsetAsync(gp->Linv.p, 0, size_t(ld) * ld * 8, ctx->stream) != hipSuccess ||
+      hipMemcpy2DAsync(gp->Linv.p, size_t(ld) * 8, src->Linv.p, size_t(ld0) * 8,
+                       size_t(ld0) * 8, size_t(ld0), hipMemcpyDeviceToDevice,
+                       ctx->stream) != hipSuccess) {
+    sgp_set_error(ctx, "sgp_gp_clone: device copy of L^-1 failed");
+    return fail(-1);
+  }
+  if (int rc = publish_gp(gp)) return fail(rc);
+  *out = gp;
+  return 0;
+}
+
 int sgp_kern_K(sgp_ctx* ctx, int d, int n_parts, const int* kinds,
                const double* variances, const double* inv_ls, const double* X1,
                int64_t n1, const double* X2, int64_t n2, double* out) {
@@ -684,6 +758,7 @@ void sgp_grid_destroy(sgp_grid* g) {
                   g->Gm,  g->cand, g->w,    g->partial, g->gpdev, g->scal};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  if (g->var_h) (void)hipFree(g->var_h);
   if (g->ax_vals.p) (void)hipFree(g->ax_vals.p);
   for (DevBuf& b : g->sep_tab)
     if (b.p) (void)hipFree(b.p);
@@ -1129,6 +1204,59 @@ int sgp_grid_argmax(sgp_grid* g, int mode, const double* scaling, double* value,
   return 0;
 }
 
+// One pick of a hallucinated batch: csrc/batch.hip.  The GPs are clones that carry the append
+// record of the pending pick; nothing the real step left on the grid is written.
+int sgp_grid_batch_next(sgp_grid* g, sgp_gp* const* gps, int G, int first, int mode,
+                        double beta, const double* scaling, const int64_t* picked,
+                        int n_picked, double* value, int64_t* gidx) {
+  sgp_ctx* ctx = g->ctx;
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
+  SGP_CHECK(ctx, mode == SGP_ARGMAX_MG_WIDTH || mode == SGP_ARGMAX_UCB,
+            "sgp_grid_batch_next: mode %d is not SGP_ARGMAX_MG_WIDTH / SGP_ARGMAX_UCB", mode);
+  SGP_CHECK(ctx, n_picked >= 0 && n_picked <= SGP_MAX_BATCH,
+            "sgp_grid_batch_next: %d rows picked before (SGP_MAX_BATCH = %d)", n_picked,
+            SGP_MAX_BATCH);
+  SGP_CHECK(ctx, ctx->world <= 1, "sgp_grid_batch_next runs on one rank (this is rank %d of %d)",
+            ctx->rank, ctx->world);
+  for (int i = 0; i < G; ++i)
+    SGP_CHECK(ctx, gps[i]->upd_valid, "GP %d has no append record for a hallucinated downdate",
+              i);
+  SGP_CHECK(ctx, first || g->var_h, "sgp_grid_batch_next: first = 0 before a first downdate");
+  const size_t vbytes = size_t(g->N) * g->G * sizeof(double);
+  if (!g->var_h) {
+    SGP_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&g->var_h), vbytes));
+    ++ctx->n_allocs;
+    SGP_TRY(sgp_poison(ctx, g->var_h, vbytes));
+  }
+  const int nb = batch_num_blocks(g->N);
+  void* scr;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, batch_scratch_bytes(nb), &scr));
+  const BatchScratch bs = batch_scratch(scr, nb);
+  BatchArgs ba{};
+  ba.mean = g->mean;
+  ba.var_in = first ? g->var : g->var_h;
+  ba.var_out = g->var_h;
+  ba.S = g->S;
+  ba.M = g->M;
+  ba.Gm = g->Gm;
+  ba.mode = mode;
+  ba.beta = beta;
+  for (int i = 0; i < SGP_MAX_GPS; ++i) ba.scaling[i] = (i < G) ? scaling[i] : 1.0;
+  ba.goff = g->goff;
+  ba.n_picked = n_picked;
+  for (int k = 0; k < n_picked; ++k) ba.picked[k] = picked[k];
+  ba.part_v = bs.part_v;
+  ba.part_i = bs.part_i;
+  SweepPoints sp{g->pts, g->N, 1, g->N};
+  SGP_TRY(launch_batch_pick(ctx, g->gpdev, G, g->d, sp, ba, bs.res_v, bs.res_i));
+  char res[16];
+  SGP_TRY(sgp_d2h(ctx, res, bs.res_v, 16));
+  memcpy(value, res, 8);
+  memcpy(gidx, res + 8, 8);
+  return 0;
+}
+
 int sgp_grid_upload_mask(sgp_grid* g, int what, const uint8_t* mask) {
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
@@ -1150,6 +1278,9 @@ int sgp_grid_download(sgp_grid* g, int what, void* out) {
     case SGP_VAR: return sgp_d2h(ctx, out, g->var, N * G * 8);
     case SGP_CAND: return sgp_d2h(ctx, out, g->cand, N);     // expander candidates
     case SGP_WIDTH: return sgp_d2h(ctx, out, g->w, N * 8);   // max_i (u_i - l_i)
+    case SGP_VAR_H:
+      SGP_CHECK(ctx, g->var_h, "no hallucinated variances yet (sgp_grid_batch_next)");
+      return sgp_d2h(ctx, out, g->var_h, N * G * 8);
   }
   sgp_set_error(ctx, "unknown array selector %d", what);
   return -2;

@@ -134,7 +134,8 @@ enum ScratchSlot : int {
                         // sets_fused[_comm]
   kSlotPartials = 2,    // per-workgroup partials of the sets.hip launchers (candidates, topk,
                         // argmax[_marked], the fused front, read by its fold); set_axes'
-                        // mismatch count; fitness_small's mean | var
+                        // mismatch count; fitness_small's mean | var; a batch pick's pairs
+                        // and result (BatchScratch)
   kSlotStage = 3,       // host rows staged for a launch: gp_predict, kern_K, grid_create,
                         // swarm_fitness, swarm_run's random numbers; factor.hip: append_gp,
                         // expander_operands_all
@@ -265,6 +266,8 @@ struct sgp_grid {
   double* Q = nullptr;       // [N][2G]
   double* mean = nullptr;    // [G][N]
   double* var = nullptr;     // [G][N]
+  double* var_h = nullptr;   // [G][N] hallucinated variances of a batch (sgp_grid_batch_next):
+                             // allocated by the first batch, written before it is read
   uint8_t* S = nullptr;      // [N]
   uint8_t* M = nullptr;
   uint8_t* Gm = nullptr;
@@ -494,6 +497,46 @@ struct Rank1Args {
 int rank1_num_blocks(int64_t N);
 int launch_rank1(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d,
                  SweepPoints pts, Rank1Args ra);
+
+// batch.hip: one pick of a hallucinated batch (sgp_grid_batch_next).  Every GP carries the
+// append record of the previous pick: var_out = max(var_in - c(x)^2 / s2, 1e-15) per row and
+// GP (var_in = the resident var for the first downdate of a batch, var_h afterwards), the
+// intervals mean -+ beta sqrt(var_out), and the masked arg-max of their value over the rows
+// not picked before, in the same pass.
+struct BatchArgs {
+  const double* mean;       // [G][N] resident, read only
+  const double* var_in;     // [G][N]
+  double* var_out;          // [G][N] (may be var_in: a row is read and written by one lane)
+  const uint8_t* S;         // [N] masks, read only
+  const uint8_t* M;
+  const uint8_t* Gm;
+  int mode;                 // SGP_ARGMAX_MG_WIDTH | SGP_ARGMAX_UCB
+  double beta;
+  double scaling[SGP_MAX_GPS];
+  int64_t goff;
+  int n_picked;
+  int64_t picked[SGP_MAX_BATCH];   // global rows
+  double* part_v;           // [blocks] best value of the workgroup's rows
+  int64_t* part_i;          // [blocks] ... and its global row (-1: no eligible row)
+};
+int batch_num_blocks(int64_t N);
+// The scratch of a pick, in kSlotPartials: [nb] values | [nb] rows | value | row -- the
+// per-workgroup pairs and the pair the final kernel leaves behind them (read back together)
+struct BatchScratch {
+  double* part_v;
+  int64_t* part_i;
+  double* res_v;
+  int64_t* res_i;
+};
+inline size_t batch_scratch_bytes(int nb) { return (size_t(nb) + 1) * 16; }
+inline BatchScratch batch_scratch(void* base, int nb) {
+  double* v = static_cast<double*>(base);
+  int64_t* i = reinterpret_cast<int64_t*>(v + nb);
+  return BatchScratch{v, i, reinterpret_cast<double*>(i + nb), i + nb + 1};
+}
+// the downdate and the per-workgroup pairs, then the final pair into (res_v, res_i)
+int launch_batch_pick(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d, SweepPoints pts,
+                      BatchArgs ba, double* res_v, int64_t* res_i);
 
 // sweep_tiny.hip: do the GPs of a launch go through the VALU kernel (every one with at most
 // 48 observations)?

@@ -427,6 +427,47 @@ class _HipGridBackend(object):
     def download(self, what):
         return self.grid.download(what)
 
+    def batch(self, inputs, row0, size, mode, beta, scaling, want_var=False):
+        """The rows of a batch by hallucinated observations behind the pick ``row0`` of the
+        real step (``SafeOpt.optimize_batch`` has the definition): private clones of the GPs,
+        and per further pick one append of the pick before to every clone -- with ``y = 0``:
+        only the variance is read -- and one ``sgp_grid_batch_next``.  ``inputs``: the rows
+        of the grid on the host (global row -> x).  Returns ``(rows, downdates, var_h)``:
+        the global rows picked, how many of them the hallucinated variances ``var_h``
+        ``(G, N)`` account for (None without ``want_var``).  The user's GPs and the resident
+        posterior, intervals and sets are only read; the clones are released on every way
+        out."""
+        devs = self._dev()
+        if not self.posterior_is_current():
+            # (intervals assigned by hand, or data added since the last sweep: the downdates
+            # start from the posterior of the GPs as they are)
+            self.refresh_posterior()
+        rows, downdates, clones = [int(row0)], 0, []
+        try:
+            for b in range(1, size):
+                if not clones:
+                    for dv in devs:
+                        clones.append(dv.clone())
+                x = np.asarray(inputs[rows[-1]], dtype=float)
+                if not all([c.append(x, 0.0) for c in clones]):
+                    logging.getLogger(__name__).info(
+                        "optimize_batch: pick %d (row %d) is determined to rounding by the "
+                        "picks before it (non-positive pivot of the bordered append): the "
+                        "batch ends with %d points", b - 1, rows[-1], len(rows))
+                    break
+                _v, i = self.grid.batch_next(clones, downdates == 0, mode, beta, scaling, rows)
+                downdates += 1
+                if i < 0:
+                    break
+                rows.append(int(i))
+            var_h = None
+            if want_var:
+                var_h = self.grid.download(_hip.VAR_H if downdates else _hip.VAR)
+        finally:
+            for c in clones:
+                c.destroy()
+        return np.asarray(rows, dtype=np.int64), downdates, var_h
+
     def paths(self, pp, mask, values, comm=False):
         """Sample paths ``pp`` (of one of this backend's GPs) over the resident rows; ``comm``:
         the arg-max merged over the ranks in the grid's stream (``sgp_grid_paths_comm``)."""
@@ -1311,6 +1352,66 @@ class SafeOpt(GaussianProcessOptimization):
             self._certify_first_candidate(beta, self.fmin != -np.inf,
                                           self._front_of(out5, x_c, mu_c, q_c,
                                                          (flags, val, idx)), exact=True)
+
+    def optimize_batch(self, size=8, context=None, ucb=False, return_state=False):
+        """``k <= size`` query points from SafeOpt's own rule for experiments that run in
+        parallel, spread out because every pick accounts for the ones before it: the GP-BUCB
+        construction (Desautels et al. 2014) on SafeOpt.  The posterior variance depends on
+        where one measures, not on what one measures, so a pending pick is "hallucinated"
+        into the model: the means stay, the widths shrink around it.
+
+        1. ``x_0 = self.optimize(context=context, ucb=ucb)``, the unchanged step: row 0 of
+           the result is what ``optimize()`` returns, and the optimiser's state afterwards
+           is the state after ``optimize()``.
+        2. With ``mean_i``, ``var_i`` the resident posterior of GP ``i``,
+           ``beta = self.beta(self.t)`` and ``var^0 = var``: for ``b = 1 .. size - 1`` and
+           EVERY GP ``i`` (``add_new_data_point`` feeds all of them),
+           ``var^b_i(x) = max(var^{b-1}_i(x) - c_i(x)^2 / s2_i, 1e-15)``, where ``c_i(x)`` is
+           the posterior covariance of GP ``i`` between row ``x`` and ``x_{b-1}`` given the
+           real data and the hallucinated inputs ``x_0 .. x_{b-2}``, and
+           ``s2_i = c_i(x_{b-1}) + noise_i + 1e-8``.  Hallucinated intervals:
+           ``l = mean - beta sqrt(var^b)``, ``u = mean + beta sqrt(var^b)``.
+        3. ``x_b`` = the row that maximises, among the rows not picked before in this call
+           (picks are distinct rows by construction; the lowest row wins among equal values):
+           ``max_i (u_i - l_i) / scaling_i`` over the rows of ``M | G`` (``ucb=False``), or
+           ``u_0`` over the rows of ``S`` (``ucb=True``).
+        4. The batch ends early, with ``k < size`` rows, when no eligible row is left, or when
+           the bordered append of a hallucinated point meets a non-positive pivot (the point
+           is determined to rounding already; logged at ``logging.INFO``, not an error).
+
+        Safety is untouched: ``S``, ``M``, ``G`` and every bound compared with ``fmin`` are
+        those of the real data; hallucinated widths only rank rows inside sets the real data
+        certified.  Nothing real changes: ``Q / S / M / G``, the resident posterior and the
+        GPs are the bits ``optimize()`` left (the points are appended to private device
+        copies of the GPs), so ``add_new_data_point`` + ``optimize()`` afterwards give what
+        they give after a plain ``optimize()``.  An ``opt.Q`` edited by hand influences step 1
+        and the sets only: the hallucinated intervals are built from the posterior of the GPs.
+
+        Returns ``X (k, d_parameters)``, context columns stripped as ``optimize()`` strips
+        them; with ``return_state=True`` ``(X, rows (k,) int64, var_h (G, N))``: the global
+        rows picked and the hallucinated variances after the last downdate (tests, plots).
+        ``size`` above ``SGP_MAX_BATCH`` (64) raises ``ValueError``; more than one rank raises
+        ``NotImplementedError`` before anything runs."""
+        size = int(size)
+        if size < 1 or size > _hip.MAX_BATCH:
+            raise ValueError("size must be in 1 .. SGP_MAX_BATCH = %d, got %d"
+                             % (_hip.MAX_BATCH, size))
+        if self._comm.world > 1:
+            raise NotImplementedError("optimize_batch runs on one rank (this communicator has "
+                                      "%d)" % self._comm.world)
+        if not hasattr(self._backend, 'batch'):
+            raise NotImplementedError("this grid backend hallucinates no observations")
+        x0 = self.optimize(context=context, ucb=ucb)
+        mode = _hip.ARGMAX_UCB if ucb else _hip.ARGMAX_MG_WIDTH
+        cached = self._argmax_cache
+        # (the row of x_0: the arg-max optimize() took -- its cache, or the same pass again)
+        row0 = cached[1] if (not ucb and cached is not None) else self._global_argmax(mode)[1]
+        rows, _downdates, var_h = self._backend.batch(
+            self.inputs, row0, size, mode, self.beta(self.t), self.scaling,
+            want_var=return_state)
+        X = self.inputs[rows, :self.inputs.shape[1] - self.num_contexts]
+        X[0] = x0
+        return (X, rows, var_h) if return_state else X
 
     def thompson_points(self, size=8, features=1024, within='safe', return_values=False):
         """``size`` Thompson picks: sample paths of the objective GP (``gps[0]``,
