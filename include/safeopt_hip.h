@@ -522,6 +522,29 @@ int sgp_swarm_fitness_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double
                            const double* Omega, const double* phase, int m, const double* w,
                            const double* v, double* values, uint8_t* safe);
 
+/* The fitness of a HALLUCINATED swarm (GP-BUCB on SafeOptSwarm's rule):
+ * clones[g] is a private copy of gps[g] (sgp_gp_clone) with the b pending picks of a batch
+ * appended (sgp_gp_append; any y: only the variance is read), 1 <= b <= SGP_MAX_BATCH, the
+ * same b for every GP.  With t_j(x) = (row n_g + j of the clone's L^-1) . k(X', x),
+ *   down_g(x) = sum_j t_j(x)^2  (j = 0 .. b-1, in that order),
+ *   var_h_g(x) = max(var_g(x) - down_g(x), 1e-15),
+ * the width term is values = max_g sqrt(var_h_g) / scaling[g]; the lower and upper bounds,
+ * both interests, the slack, the penalty and `safe` are those of sgp_swarm_fitness, bit for
+ * bit, from the real mean and variance: hallucinated widths rank points, safety is never
+ * judged on them.  The result is (values + total_pen) * interest.  swarm_type is
+ * SGP_SWARM_MAXIMIZERS or SGP_SWARM_EXPANDERS.  The real posterior is formed by the kernels
+ * sgp_swarm_fitness takes for that P and n; down is one more launch in front of the shaping
+ * pass: a row kernel on the fp64 VALU that evaluates k(X', x) on the fly, sums in a fixed
+ * order, no atomics -- down of a particle depends on its coordinates and the clones alone,
+ * not on P, its row or the launch.  var_h (G,P) receives the hallucinated variances, or NULL.
+ * Refused: another swarm type, a clone whose n is not gps[g].n + b for one common b in
+ * 1 .. SGP_MAX_BATCH, a clone or GP in another context, a clone with another input
+ * dimension or kernel than its GP.  P <= 0 returns 0 and writes nothing.        */
+int sgp_swarm_fitness_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                           int swarm_type, const double* particles, int64_t P, double beta,
+                           const double* fmin, const double* scaling, double best_lower_bound,
+                           double* values, uint8_t* safe, double* var_h);
+
 /* ---- SafeOptSwarm safe-set growth (gp_opt.py:1089-1111) ---------------------
  * After a maximizer / expander swarm run the reference appends, in order, every
  * best position B_j (n,d row-major) whose prior correlation
@@ -569,6 +592,20 @@ int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
                        double step, const double* rand, uint64_t seed,
                        const double* Omega, const double* phase, int m, const double* w,
                        const double* v);
+
+/* sgp_swarm_run for a hallucinated swarm: the fitness is that of sgp_swarm_fitness_hall,
+ * everything else as for sgp_swarm_run.  Like a path run it ALWAYS takes the general
+ * launches -- move, fitness (downdate, posterior, shaping), personal bests, global best --
+ * never the one-workgroup step of a small swarm: with rand != NULL the run is bit-identical
+ * to the host loop over sgp_swarm_fitness_hall.  The whole swarm in one call.  The refusals
+ * of sgp_swarm_fitness_hall; P <= 0 returns 0 and writes nothing.               */
+int sgp_swarm_run_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                       int swarm_type, double beta, const double* fmin, const double* scaling,
+                       double best_lower_bound, int64_t P, double* positions,
+                       double* velocities, double* best_positions, double* best_values,
+                       double* global_best, const double* velocity_scale,
+                       const double* bounds, int init, int iters, double inertia0,
+                       double step, const double* rand, uint64_t seed);
 
 /* sgp_swarm_run on a rank's contiguous block of particles [p0, p0 + P) of a swarm
  * of P_total (shard_range): the state arrays hold the block's P rows.  After the

@@ -168,6 +168,10 @@ PROTOTYPES = {
                                          C.c_double, c_double_p, c_double_p,
                                          c_double_p, c_double_p, C.c_int, c_double_p,
                                          c_double_p, c_double_p, c_u8_p]),
+    "sgp_swarm_fitness_hall": (C.c_int, [vp, vpp, vpp, C.c_int, C.c_int, c_double_p,
+                                         C.c_int64, C.c_double, c_double_p,
+                                         c_double_p, C.c_double, c_double_p,
+                                         c_u8_p, c_double_p]),
     "sgp_swarm_grow": (C.c_int, [vp, vp, c_double_p, C.c_int64, c_double_p,
                                  C.c_int64, C.c_double, C.c_double, c_u8_p]),
     "sgp_swarm_run": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
@@ -176,6 +180,12 @@ PROTOTYPES = {
                                 c_double_p, c_double_p, c_double_p, C.c_int,
                                 C.c_int, C.c_double, C.c_double, c_double_p,
                                 C.c_uint64]),
+    "sgp_swarm_run_hall": (C.c_int, [vp, vpp, vpp, C.c_int, C.c_int, C.c_double,
+                                     c_double_p, c_double_p, C.c_double, C.c_int64,
+                                     c_double_p, c_double_p, c_double_p, c_double_p,
+                                     c_double_p, c_double_p, c_double_p, C.c_int,
+                                     C.c_int, C.c_double, C.c_double, c_double_p,
+                                     C.c_uint64]),
     "sgp_swarm_run_path": (C.c_int, [vp, vpp, C.c_int, C.c_double,
                                      c_double_p, c_double_p, C.c_int64,
                                      c_double_p, c_double_p, c_double_p, c_double_p,
@@ -1341,3 +1351,48 @@ def swarm_run_path(ctx, gps, beta, fmin, scaling, positions, velocities, best_po
         ctx.check(lib().sgp_swarm_run_path(*args))
     else:
         ctx.check(lib().sgp_swarm_run_path_shard(*(args + (int(shard[0]), int(shard[1])))))
+
+
+def swarm_fitness_hall(ctx, gps, clones, swarm_type, particles, beta, fmin, scaling,
+                       best_lower_bound, want_var=False):
+    """Fitness and safety of ``particles`` for a hallucinated swarm
+    (``sgp_swarm_fitness_hall``): ``clones[g]`` is ``gps[g].clone()`` with the pending picks
+    of the batch appended.  The width term comes from the clones' variance, everything else
+    from ``gps``.  ``want_var``: also the hallucinated variances, ``(G, P)``."""
+    d = gps[0].d
+    if len(clones) != len(gps):
+        raise ValueError("%d clones for %d GPs" % (len(clones), len(gps)))
+    particles = f64(particles).reshape(-1, d)
+    P = particles.shape[0]
+    values = np.empty(P)
+    safe = np.empty(P, dtype=np.uint8)
+    var_h = np.empty((len(gps), P)) if want_var else None
+    ctx.check(lib().sgp_swarm_fitness_hall(
+        ctx.h, _gp_array(gps), _gp_array(clones), len(gps), SWARM_TYPES[swarm_type],
+        dptr(particles), P, float(beta), dptr(f64(fmin)), dptr(f64(scaling)),
+        float(best_lower_bound), dptr(values), safe.ctypes.data_as(c_u8_p),
+        None if var_h is None else dptr(var_h)))
+    if want_var:
+        return values, safe.view(np.bool_), var_h
+    return values, safe.view(np.bool_)
+
+
+def swarm_run_hall(ctx, gps, clones, swarm_type, beta, fmin, scaling, best_lower_bound,
+                   positions, velocities, best_positions, best_values, global_best,
+                   velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0):
+    """Whole PSO run of a hallucinated swarm on the device (``sgp_swarm_run_hall``); the state
+    arrays are updated in place, ``clones`` as for :func:`swarm_fitness_hall`."""
+    P = positions.shape[0]
+    if len(clones) != len(gps):
+        raise ValueError("%d clones for %d GPs" % (len(clones), len(gps)))
+    for a in (positions, velocities, best_positions, best_values, global_best):
+        assert a.dtype == np.float64 and a.flags.c_contiguous
+    bnd = None if bounds is None else f64(bounds)
+    rnd = None if rand is None else f64(rand).ravel()
+    ctx.check(lib().sgp_swarm_run_hall(
+        ctx.h, _gp_array(gps), _gp_array(clones), len(gps), SWARM_TYPES[swarm_type],
+        float(beta), dptr(f64(fmin)), dptr(f64(scaling)), float(best_lower_bound), P,
+        dptr(positions), dptr(velocities), dptr(best_positions), dptr(best_values),
+        dptr(global_best), dptr(f64(velocity_scale)), None if bnd is None else dptr(bnd),
+        int(bool(init)), int(iters), float(inertia0), float(step),
+        None if rnd is None else dptr(rnd), int(seed)))

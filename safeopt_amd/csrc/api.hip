@@ -2282,14 +2282,52 @@ static bool small_path_pays_all(sgp_gp* const* gps, int G, int64_t P) {
 }
 
 // ---- swarm ----------------------------------------------------------------------
-int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
-                      const double* particles, int64_t P, double beta,
-                      const double* fmin, const double* scaling,
-                      double best_lower_bound, double* values, uint8_t* safe) {
+// The clones of a hallucinated swarm (sgp_swarm_fitness_hall / sgp_swarm_run_hall) against
+// the GPs they were cloned from: maximizers or expanders, every clone in the call's context
+// with the source's input dimension and kernel and gps[g].n + b observations for ONE b in
+// 1 .. SGP_MAX_BATCH.  host: their descriptors, `share` as collect_gps sets it.
+static int hall_clones(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                       int swarm_type, GpDev* host, int* b_out) {
+  SGP_CHECK(ctx, swarm_type == SGP_SWARM_MAXIMIZERS || swarm_type == SGP_SWARM_EXPANDERS,
+            "a hallucinated swarm is a maximizers or an expanders swarm, not type %d",
+            swarm_type);
+  SGP_CHECK(ctx, G >= 1 && G <= SGP_MAX_GPS && gps[0], "no GP");
+  SGP_CHECK(ctx, clones != nullptr, "no clones");
+  for (int g = 0; g < G; ++g) {
+    SGP_CHECK(ctx, gps[g] && clones[g], "GP %d or its clone is missing", g);
+    SGP_CHECK(ctx, gps[g]->ctx == ctx && clones[g]->ctx == ctx,
+              "GP %d or its clone lives in another context than the call (device %d)", g,
+              ctx->device);
+    SGP_CHECK(ctx, clones[g]->kern.d == gps[g]->kern.d &&
+                       memcmp(&clones[g]->kern, &gps[g]->kern, sizeof(KernDesc)) == 0,
+              "clone %d has another input dimension or kernel than its GP", g);
+  }
+  const int64_t b = clones[0]->n - gps[0]->n;
+  SGP_CHECK(ctx, b >= 1 && b <= SGP_MAX_BATCH,
+            "clone 0 holds %lld observations, its GP %lld: 1 .. %d pending picks",
+            (long long)clones[0]->n, (long long)gps[0]->n, SGP_MAX_BATCH);
+  for (int g = 1; g < G; ++g)
+    SGP_CHECK(ctx, clones[g]->n == gps[g]->n + b,
+              "clone %d holds %lld observations, its GP %lld: not the %lld pending picks of "
+              "clone 0", g, (long long)clones[g]->n, (long long)gps[g]->n, (long long)b);
+  SGP_TRY(collect_gps(ctx, clones, G, gps[0]->kern.d, host));
+  *b_out = int(b);
+  return 0;
+}
+
+// sgp_swarm_fitness, and with clones sgp_swarm_fitness_hall: the same launches for the real
+// posterior, the downdate (launch_swarm_down) in front of the shaping pass
+static int swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                         int swarm_type, const double* particles, int64_t P, double beta,
+                         const double* fmin, const double* scaling, double best_lower_bound,
+                         double* values, uint8_t* safe, double* var_h) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, swarm_type >= SGP_SWARM_GREEDY && swarm_type <= SGP_SWARM_SAFE_SET,
             "Invalid swarm type %d", swarm_type);
   SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
+  GpDev chost[SGP_MAX_GPS];
+  int b = 0;
+  if (clones) SGP_TRY(hall_clones(ctx, gps, clones, G, swarm_type, chost, &b));
   if (P <= 0) return 0;
   const int d = gps[0]->kern.d;
   GpDev host[SGP_MAX_GPS];
@@ -2298,12 +2336,18 @@ int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   double* stage;
   char* work;
   SGP_TRY(sgp_scratch(ctx, kSlotStage, nd * d, &stage));
-  SGP_TRY(sgp_scratch(ctx, kSlotWork, nd * d + nd + size_t(P) + sizeof(GpDev) * SGP_MAX_GPS + 64,
-                      &work));
+  // points | values | GP descriptors | safe (padded to 8 bytes) | with clones: their
+  // descriptors | down [G][P] | var_h [G][P]
+  const size_t plain = nd * d + nd + sizeof(GpDev) * SGP_MAX_GPS + (size_t(P) + 7) / 8 * 8;
+  const size_t hall = clones ? sizeof(GpDev) * SGP_MAX_GPS + 2 * size_t(G) * nd : 0;
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, plain + hall + 64, &work));
   double* pts = reinterpret_cast<double*>(work);
   double* dval = reinterpret_cast<double*>(work + nd * d);
   GpDev* gdev = reinterpret_cast<GpDev*>(work + nd * d + nd);
   uint8_t* dsafe = reinterpret_cast<uint8_t*>(work + nd * d + nd + sizeof(GpDev) * SGP_MAX_GPS);
+  GpDev* cdev = reinterpret_cast<GpDev*>(work + plain);
+  double* ddown = reinterpret_cast<double*>(cdev + SGP_MAX_GPS);
+  double* dvarh = ddown + size_t(G) * size_t(P);
   SGP_TRY(sgp_h2d(ctx, stage, particles, nd * d));
   SGP_TRY(launch_import_points(ctx, stage, P, d, d, 1, pts));
   SGP_TRY(sgp_h2d(ctx, gdev, host, sizeof(GpDev) * G));
@@ -2317,15 +2361,39 @@ int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   }
   fa.values = dval;
   fa.safe = dsafe;
+  const SweepPoints sp{pts, P, 1, P};
+  if (clones) {
+    SGP_TRY(sgp_h2d(ctx, cdev, chost, sizeof(GpDev) * G));
+    SGP_TRY(launch_swarm_down(ctx, cdev, G, d, b, sp, ddown));
+    fa.down = ddown;
+    fa.var_h = var_h ? dvarh : nullptr;
+  }
   if (small_path_pays_all(gps, G, P)) {
     SGP_TRY(fitness_small(ctx, gdev, host, G, stage, P, fa));
   } else {
-    SweepPoints sp{pts, P, 1, P};
     SGP_TRY(launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa));
   }
   SGP_TRY(sgp_d2h(ctx, values, dval, nd));
   SGP_TRY(sgp_d2h(ctx, safe, dsafe, size_t(P)));
+  if (clones && var_h) SGP_TRY(sgp_d2h(ctx, var_h, dvarh, size_t(G) * nd));
   return 0;
+}
+
+int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                      const double* particles, int64_t P, double beta,
+                      const double* fmin, const double* scaling,
+                      double best_lower_bound, double* values, uint8_t* safe) {
+  return swarm_fitness(ctx, gps, nullptr, G, swarm_type, particles, P, beta, fmin, scaling,
+                       best_lower_bound, values, safe, nullptr);
+}
+
+int sgp_swarm_fitness_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                           int swarm_type, const double* particles, int64_t P, double beta,
+                           const double* fmin, const double* scaling, double best_lower_bound,
+                           double* values, uint8_t* safe, double* var_h) {
+  SGP_CHECK(ctx, clones != nullptr, "no clones");
+  return swarm_fitness(ctx, gps, clones, G, swarm_type, particles, P, beta, fmin, scaling,
+                       best_lower_bound, values, safe, var_h);
 }
 
 // The fitness of a Thompson swarm: the posterior and the shaping as for sgp_swarm_fitness
@@ -2391,9 +2459,12 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
                      double* global_best, const double* velocity_scale,
                      const double* bounds, int init, int iters, double inertia0,
                      double step_size, const double* rand, uint64_t seed, int64_t p0,
-                     int64_t Pt, const SwarmPath* path = nullptr) {
+                     int64_t Pt, const SwarmPath* path = nullptr,
+                     sgp_gp* const* clones = nullptr) {
   // path: the staged sample path of a Thompson swarm (sgp_swarm_run_path, swarm_type =
   // kSwarmThompson); such a run always takes the general launches below
+  // clones: a hallucinated swarm (sgp_swarm_run_hall): the downdate in front of every
+  // shaping pass; the general launches as well
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, path ? swarm_type == kSwarmThompson
                       : swarm_type >= SGP_SWARM_GREEDY && swarm_type <= SGP_SWARM_SAFE_SET,
@@ -2410,18 +2481,24 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
             "context (sgp_comm_init / sgp_comm_init_host)", (long long)P, (long long)Pt);
   const int world = comm ? ctx->world : 1;
   const int d = gps[0]->kern.d;
-  GpDev host[SGP_MAX_GPS];
+  GpDev host[SGP_MAX_GPS], chost[SGP_MAX_GPS];
+  int hall_b = 0;
+  if (clones) SGP_TRY(hall_clones(ctx, gps, clones, G, swarm_type, chost, &hall_b));
   SGP_TRY(collect_gps(ctx, gps, G, d, host));
   const size_t nd = size_t(P) * d * 8, nv = size_t(P) * 8;
   const size_t nrand = rand ? (size_t(init ? 1 : 0) + 2 * size_t(iters)) * nd : 0;
   // pos | vel | best | best_values | values | gbest | vscale | bounds | gpdev |
-  // this rank's record | the gathered records (shard: value | index | x[d] each) | safe
+  // this rank's record | the gathered records (shard: value | index | x[d] each) | safe |
+  // with clones, from the next multiple of 64 bytes: their descriptors | down [G][P]
   const size_t nrec = size_t(2 + d);
   const size_t recs = shard ? (1 + size_t(world)) * nrec * 8 : 0;
   const size_t small = size_t(d) * 8 * 4 + sizeof(GpDev) * SGP_MAX_GPS + recs + 64;
+  const size_t plain = 3 * nd + 2 * nv + small + size_t(P);
+  const size_t hall_off = (plain + 63) / 64 * 64;
+  const size_t hall = clones ? sizeof(GpDev) * SGP_MAX_GPS + size_t(G) * nv : 0;
   char* buf;
   double* drand = nullptr;
-  SGP_TRY(sgp_scratch(ctx, kSlotWork, 3 * nd + 2 * nv + small + size_t(P), &buf));
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, clones ? hall_off + hall : plain, &buf));
   if (rand) SGP_TRY(sgp_scratch(ctx, kSlotStage, nrand, &drand));
   double* dpos = reinterpret_cast<double*>(buf);
   double* dvel = reinterpret_cast<double*>(buf + nd);
@@ -2435,6 +2512,8 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   double* drec = reinterpret_cast<double*>(gdev + SGP_MAX_GPS);
   double* drecs = drec + nrec;
   uint8_t* dsafe = reinterpret_cast<uint8_t*>(drec) + recs;
+  GpDev* cdev = reinterpret_cast<GpDev*>(buf + hall_off);
+  double* ddown = reinterpret_cast<double*>(cdev + SGP_MAX_GPS);
   SGP_TRY(sgp_h2d(ctx, dpos, positions, nd));
   if (!init) {
     SGP_TRY(sgp_h2d(ctx, dvel, velocities, nd));
@@ -2446,6 +2525,7 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   if (bounds) SGP_TRY(sgp_h2d(ctx, dbd, bounds, size_t(d) * 16));
   if (rand) SGP_TRY(sgp_h2d(ctx, drand, rand, nrand));
   SGP_TRY(sgp_h2d(ctx, gdev, host, sizeof(GpDev) * G));
+  if (clones) SGP_TRY(sgp_h2d(ctx, cdev, chost, sizeof(GpDev) * G));
   FitnessArgs fa{};
   fa.swarm_type = swarm_type;
   fa.beta = beta;
@@ -2456,6 +2536,7 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   }
   fa.values = dval;
   fa.safe = dsafe;
+  if (clones) fa.down = ddown;
   const SweepPoints sp{dpos, P, d, 1};          // row-major (P, d) in place
   // (the paths and the posterior kernel follow the whole swarm: same bits on every rank)
   const bool few = Pt <= kSmallSwarm && small_path_pays_all(gps, G, Pt);
@@ -2466,7 +2547,7 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   const bool few_swept = Pt <= kSmallSwarm && !few;
   const double* r = drand;
   double inertia = inertia0;
-  if ((few || few_swept) && !shard && !path) {
+  if ((few || few_swept) && !shard && !path && !clones) {
     // small swarm: three launches per iteration -- k(X, particles), the block
     // products on the matrix cores, and ONE workgroup for everything else
     // (fitness, bests, and the move that opens the next iteration)
@@ -2529,6 +2610,8 @@ static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
     // small swarm takes these launches, the arithmetic of k_pso_small_step)
     const bool few_points = small_path_pays_all(gps, G, Pt);
     auto fitness = [&]() -> int {
+      // a hallucinated swarm: what the pending picks take off the variances, for the shaping
+      if (clones) SGP_TRY(launch_swarm_down(ctx, cdev, G, d, hall_b, sp, ddown));
       SGP_TRY(few_points ? fitness_small(ctx, gdev, host, G, dpos, P, fa)
                          : launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa, Pt));
       // a Thompson swarm: the path term on top of the penalty the shaping left
@@ -2577,6 +2660,26 @@ int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
   return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
                    positions, velocities, best_positions, best_values, global_best,
                    velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, 0, P);
+}
+
+int sgp_swarm_run_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                       int swarm_type, double beta, const double* fmin, const double* scaling,
+                       double best_lower_bound, int64_t P, double* positions,
+                       double* velocities, double* best_positions, double* best_values,
+                       double* global_best, const double* velocity_scale,
+                       const double* bounds, int init, int iters, double inertia0,
+                       double step_size, const double* rand, uint64_t seed) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, clones != nullptr, "no clones");
+  if (P <= 0) {
+    GpDev chost[SGP_MAX_GPS];
+    int b;
+    return hall_clones(ctx, gps, clones, G, swarm_type, chost, &b);
+  }
+  return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
+                   positions, velocities, best_positions, best_values, global_best,
+                   velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, 0, P,
+                   nullptr, clones);
 }
 
 // sgp_swarm_run_path (p0 = 0, Pt = P) and sgp_swarm_run_path_shard

@@ -403,6 +403,11 @@ struct FitnessArgs {
   double best_lower_bound;
   double* values;
   uint8_t* safe;
+  // a hallucinated swarm (sgp_swarm_*_hall; null otherwise): [G][P] what the pending picks
+  // of the batch take off the variance (launch_swarm_down) -- the width term alone sees
+  // var_h = max(var - down, 1e-15); var_h: [G][P] receives it, or null
+  const double* down;
+  double* var_h;
 };
 // rows_sharded: the rows are a rank's shard of a grid -- the sweep kernel is then chosen
 // by the GPs alone (the same on every rank), never by the number of rows
@@ -440,6 +445,11 @@ int swarm_path_stage(sgp_gp* gp, const double* Omega, const double* phase, int m
 // values[p] = f(x_p) / scaling0 + values[p] over the rows of pts, gps_dev[0] the path's GP
 int launch_swarm_path(sgp_ctx* ctx, const GpDev* gps_dev, int d, const SwarmPath& path,
                       SweepPoints pts, double scaling0, double* values);
+// swarm_batch.hip: down[g][p] = sum_j t_j(x_p)^2 over the b tail rows of clone g's L^-1 (the
+// pending picks of a hallucinated batch), for the rows of pts; the clones' descriptors with
+// GpDev::share as collect_gps sets it
+int launch_swarm_down(sgp_ctx* ctx, const GpDev* clones_dev, int G, int d, int b,
+                      SweepPoints pts, double* down);
 // api.hip: the context's collectives on DEVICE operands -- RCCL in stream, or the host
 // transport of sgp_comm_init_host (sgp_grid_paths_comm merges its records behind one)
 // (defined inside api.hip's extern "C" block)

@@ -24,9 +24,21 @@ __device__ __forceinline__ double swarm_penalty(double slack) {
 //   value = f(x) / scaling[0] + total_pen.
 // The path term is not a function of the posterior: *value is total_pen here and
 // k_swarm_path (paths.hip) completes it, in that operation order.
-template <typename Post>
+// HALL (a hallucinated swarm, sgp_swarm_*_hall; maximizers and expanders): down(g) is what
+// the pending picks of the batch take off the variance of GP g here, and the `values` term
+// ALONE is formed from sd_h = sqrt(max(var - down, 1e-15)); lower, upper, both interests,
+// the slack, the penalty and the safety flag stay those of the real posterior.  var_h(g, v)
+// receives the hallucinated variance.
+struct NoDown {
+  __device__ __forceinline__ double operator()(int) const { return 0.0; }
+};
+struct NoVarH {
+  __device__ __forceinline__ void operator()(int, double) const {}
+};
+template <bool HALL = false, typename Post, typename Down = NoDown, typename VarH = NoVarH>
 __device__ __forceinline__ void shape_particle(const FitnessArgs& f, int G, Post post,
-                                               double* value, bool* is_safe) {
+                                               double* value, bool* is_safe,
+                                               Down down = Down(), VarH var_h = VarH()) {
   const int st = f.swarm_type;
   const int Geff = (st == SGP_SWARM_GREEDY) ? 1 : G;
   bool safe = true;
@@ -35,9 +47,15 @@ __device__ __forceinline__ void shape_particle(const FitnessArgs& f, int G, Post
     double mu, var;
     post(g, &mu, &var);
     const double sd = sqrt(var);
+    double sd_w = sd;                    // the standard deviation of the width term
+    if (HALL) {
+      const double vh = fmax(var - down(g), 1e-15);
+      var_h(g, vh);
+      sd_w = sqrt(vh);
+    }
     lower = mu - f.beta * sd;
     if (g == 0) {
-      values = sd / f.scaling[0];
+      values = sd_w / f.scaling[0];
       if (st == SGP_SWARM_EXPANDERS) interest = double(G);
       if (st == SGP_SWARM_MAXIMIZERS) {
         const double upper = mu + f.beta * sd;
@@ -45,7 +63,7 @@ __device__ __forceinline__ void shape_particle(const FitnessArgs& f, int G, Post
         interest = 1.0 / (1.0 + exp(-z));  // scipy.special.expit
       }
     } else {
-      values = fmax(values, sd / f.scaling[g]);
+      values = fmax(values, sd_w / f.scaling[g]);
     }
     if (f.fmin[g] != -INFINITY) {
       double slack = lower - f.fmin[g];

@@ -365,6 +365,28 @@ __global__ void k_fitness_small(int G, int64_t P, const double* mean,
   f.safe[i] = ok ? 1 : 0;
 }
 
+// The same for a hallucinated swarm (f.down, launch_swarm_down in front of it): the width
+// term from var_h = max(var - down, 1e-15), everything else from the real posterior.
+__global__ void k_fitness_hall(int G, int64_t P, const double* mean, const double* var,
+                               FitnessArgs f) {
+  const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  double out;
+  bool ok;
+  shape_particle<true>(
+      f, G,
+      [&](int g, double* mu, double* v) {
+        *mu = mean[int64_t(g) * P + i];
+        *v = var[int64_t(g) * P + i];
+      },
+      &out, &ok, [&](int g) { return f.down[int64_t(g) * P + i]; },
+      [&](int g, double vh) {
+        if (f.var_h) f.var_h[int64_t(g) * P + i] = vh;
+      });
+  f.values[i] = out;
+  f.safe[i] = ok ? 1 : 0;
+}
+
 // One PSO iteration of a small swarm (P <= kSmallSwarm) behind the two posterior launches
 // (k_small_kb, k_small_mfma), in ONE workgroup: block sums -> mean / var of every
 // GP, fitness, personal bests, global best (first index on ties) and the move
@@ -505,8 +527,12 @@ int launch_pso_gbest_merge(sgp_ctx* ctx, const double* recs, int world, int d, d
 
 int launch_fitness_small(sgp_ctx* ctx, int G, int64_t P, const double* mean,
                          const double* var, FitnessArgs fa) {
-  hipLaunchKernelGGL(k_fitness_small, dim3(unsigned((P + 255) / 256)), dim3(256),
-                     0, ctx->stream, G, P, mean, var, fa);
+  if (fa.down)
+    hipLaunchKernelGGL(k_fitness_hall, dim3(unsigned((P + 255) / 256)), dim3(256),
+                       0, ctx->stream, G, P, mean, var, fa);
+  else
+    hipLaunchKernelGGL(k_fitness_small, dim3(unsigned((P + 255) / 256)), dim3(256),
+                       0, ctx->stream, G, P, mean, var, fa);
   SGP_HIP(ctx, hipGetLastError());
   return 0;
 }

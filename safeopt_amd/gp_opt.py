@@ -1519,6 +1519,58 @@ def thompson_pick(best_positions, best_values, safe):
     return np.array(np.asarray(best_positions)[i], dtype=float), i
 
 
+def swarm_batch_choice(sd_maxi, sd_exp, scaling, fmin, threshold, ucb=False):
+    """Step 3 of ``SafeOptSwarm.optimize_batch``: which swarm's candidate becomes the next
+    pick -- ``optimize()``'s rule on the HALLUCINATED standard deviations.  ``sd_maxi`` /
+    ``sd_exp``: ``(G,)`` standard deviations of every GP at the maximizers' / expanders'
+    candidate, or ``None`` for a swarm that yielded none.  The maximiser's value is
+    ``sd_maxi[0] / scaling[0]``, the expander's ``max_g sd_exp[g] / scaling[g]`` over the GPs
+    with a finite ``fmin`` and ``sd_exp[g] >= threshold`` (0 when none counts); the maximiser
+    wins only when strictly larger, and always with ``ucb``.  Returns ``'maximizers'``,
+    ``'expanders'`` or ``None`` (no candidate: the batch ends)."""
+    scaling = np.asarray(scaling, dtype=float)
+    if ucb or sd_exp is None:
+        return None if sd_maxi is None else 'maximizers'
+    if sd_maxi is None:
+        return 'expanders'
+    sd_exp = np.asarray(sd_exp, dtype=float)
+    counts = (sd_exp >= threshold) & (np.asarray(fmin, dtype=float) != -np.inf)
+    v_exp = np.max(np.where(counts, sd_exp, 0.) / scaling)
+    v_maxi = float(np.asarray(sd_maxi, dtype=float)[0]) / scaling[0]
+    return 'maximizers' if v_maxi > v_exp else 'expanders'
+
+
+def swarm_batch_loop(x0, sd0, size, devs, next_pick):
+    """Steps 2 and 4 of ``SafeOptSwarm.optimize_batch`` behind the real pick ``x0`` (``sd0``:
+    the real standard deviations there): private clones of the device GPs ``devs``, and per
+    further pick one append of the pick before to every clone -- with ``y = 0``: only the
+    variance is read -- and one ``next_pick(clones) -> (x, sd_h (G,))`` or ``None``.  Ends
+    early at a non-positive pivot of an append (logged at ``logging.INFO``) or when there is
+    no candidate; the clones are released on every way out.  Returns ``(X (k, d), sd_h (k,
+    G))``."""
+    X, sds, clones = [np.array(x0, dtype=float)], [np.array(sd0, dtype=float)], []
+    try:
+        for b in range(1, size):
+            if not clones:
+                for dv in devs:
+                    clones.append(dv.clone())
+            if not all([c.append(X[-1], 0.0) for c in clones]):
+                logging.getLogger(__name__).info(
+                    "optimize_batch: pick %d is determined to rounding by the picks before "
+                    "it (non-positive pivot of the bordered append): the batch ends with %d "
+                    "points", b - 1, len(X))
+                break
+            got = next_pick(clones)
+            if got is None:
+                break
+            X.append(np.array(got[0], dtype=float))
+            sds.append(np.array(got[1], dtype=float))
+    finally:
+        for c in clones:
+            c.destroy()
+    return np.vstack(X), np.vstack(sds)
+
+
 class SafeOptSwarm(GaussianProcessOptimization):
     """SafeOpt for higher dimensions with adaptive swarm discretisation.
 
@@ -1642,6 +1694,118 @@ class SafeOptSwarm(GaussianProcessOptimization):
         devs = [g._fitted() for g in self.gps]
         return _hip.swarm_fitness_path(devs[0].ctx, devs, particles, beta, self.fmin,
                                        self.scaling, path)
+
+    def _compute_hall_fitness(self, swarm_type, clones, particles):
+        """Fitness and safety of ``particles`` for a hallucinated ``'maximizers'`` or
+        ``'expanders'`` swarm: the width term from the variance of ``clones`` (the device GPs'
+        clones with the pending picks appended), everything else -- bounds, interest, penalty,
+        ``safe`` -- from the real GPs (``sgp_swarm_fitness_hall``).  The fitness callback of
+        the host loop."""
+        beta = self.beta(self.t)
+        particles = np.atleast_2d(particles)
+        devs = [g._fitted() for g in self.gps]
+        return _hip.swarm_fitness_hall(devs[0].ctx, devs, clones, swarm_type, particles, beta,
+                                       self.fmin, self.scaling, self.best_lower_bound)
+
+    def optimize_batch(self, size=8, ucb=False, max_iters=None, return_state=False):
+        """``k <= size`` query points from SafeOptSwarm's own rule for experiments that run
+        in parallel, without a grid: the GP-BUCB construction (Desautels et al. 2014) of
+        ``SafeOpt.optimize_batch`` on the swarms.  A pending pick is "hallucinated" into
+        private copies of the GPs: the means stay, the widths shrink around it.
+
+        1. ``x_0 = self.optimize(ucb=ucb)``, the unchanged step: row 0 is what ``optimize()``
+           returns, and the optimiser's state afterwards -- ``S``, ``greedy_point``,
+           ``best_lower_bound``, ``t``, the three swarm objects, the GPs -- is the state
+           after ``optimize()``.
+        2. Every GP's device handle is cloned; for ``b = 1 .. size - 1`` the pick ``x_{b-1}``
+           is appended to every clone and a hallucinated maximizers swarm and (unless
+           ``ucb``) a hallucinated expanders swarm run: swarm objects of their own, each
+           from ``swarm_size`` draws of ``S`` (no fixed points), ``max_iters`` (default
+           ``self.max_iters``) iterations.  Their fitness is ``(values + total_pen) *
+           interest`` with ``values = max_g sqrt(var_h_g) / scaling_g`` from the hallucinated
+           variance ``var_h_g = max(var_g - down_g, 1e-15)`` and everything else -- lower and
+           upper bounds, the interest, the penalty, the safety flag -- from the real
+           posterior (``csrc/fitness.h``).  A swarm's candidate is the personal best with the
+           largest value among those safe under one real ``'safe_set'`` fitness call, the
+           lowest index among equals (``thompson_pick``'s rule); a swarm with no safe
+           personal best yields none.
+        3. Between the two candidates ``optimize()``'s rule decides, on the hallucinated
+           standard deviations there (``swarm_batch_choice``); no candidate ends the batch.
+        4. The batch also ends early, with ``k < size`` rows, when the bordered append of a
+           pick meets a non-positive pivot (logged at ``logging.INFO``, not an error).  The
+           clones are released on every way out.
+
+        Safety is untouched: hallucinated widths only rank points inside what the real data
+        certified; no bound compared with ``fmin`` is a hallucinated one.  Nothing real
+        changes after step 1: ``S`` neither grows nor is rechecked in the hallucinated runs,
+        so ``add_new_data_point`` + ``optimize()`` afterwards give what they give after a
+        plain ``optimize()`` under the same seed.
+
+        Returns ``X (k, d)``, ``1 <= k <= size``; with ``return_state=True`` ``(X, sd_h (k,
+        G))``: the hallucinated standard deviation of every GP at every pick when it was
+        picked (row 0: the real ones).  ``size`` outside ``1 .. SGP_MAX_BATCH`` (64) raises
+        ``ValueError``; more than one rank raises ``NotImplementedError`` before anything
+        runs or is drawn.
+
+        NumPy's global generator is consumed in this order:
+
+        1. what ``optimize(ucb=ucb)`` draws;
+        2. ``size > 1`` and ``pso='device-rng'`` only: one ``randint`` for the key of the
+           maximizers swarm's device generator, then (unless ``ucb``) one for the expanders';
+        3. per pick ``b``, for the maximizers swarm and then (unless ``ucb``) the expanders
+           swarm: one ``randint(len(S), size=swarm_size)`` for the start positions, then
+           what a swarm of that ``pso`` draws -- ``'host'``: ``rand(swarm_size, d)`` in
+           ``init_swarm`` and ``rand(2 swarm_size, d)`` per iteration; ``'device'``: the same
+           numbers as ``rand(swarm_size d)`` and ``rand(2 swarm_size d max_iters)``, one C
+           call each; ``'device-rng'``: nothing.
+
+        Out of scope: N ranks; growing ``S`` from hallucinated runs; all picks or both
+        swarms in one launch."""
+        size = int(size)
+        if size < 1 or size > _hip.MAX_BATCH:
+            raise ValueError("size must be in 1 .. SGP_MAX_BATCH = %d, got %d"
+                             % (_hip.MAX_BATCH, size))
+        if self._comm.world > 1:
+            raise NotImplementedError("optimize_batch runs on one rank (this communicator has "
+                                      "%d)" % self._comm.world)
+        x0 = np.array(self.optimize(ucb=ucb), dtype=float)
+        sd0 = np.sqrt([gp.predict_noiseless(x0[None, :])[1].item() for gp in self.gps])
+        iters = int(max_iters or self.max_iters)
+        types = ['maximizers'] if ucb else ['maximizers', 'expanders']
+        swarms = {}                       # pso='host': a reference loop per run
+        if size > 1 and isinstance(self.swarms['maximizers'], DeviceSwarmOptimization):
+            swarms = {t: DeviceSwarmOptimization(
+                self.swarm_size, self.optimal_velocities, self, t, bounds=self.bounds,
+                rng=self.swarms['maximizers']._rng) for t in types}
+
+        def candidate(swarm_type, clones):
+            picks = np.random.randint(self.S.shape[0], size=self.swarm_size)
+            if swarms:
+                run = swarms[swarm_type]
+                run.set_clones(clones)
+            else:
+                run = SwarmOptimization(
+                    self.swarm_size, self.optimal_velocities,
+                    partial(self._compute_hall_fitness, swarm_type, clones),
+                    bounds=self.bounds)
+            run.init_swarm(self.S[picks, :])
+            run.run_swarm(iters)
+            _, safe = self._compute_particle_fitness('safe_set', run.best_positions)
+            if not np.any(safe):
+                return None
+            x, _ = thompson_pick(run.best_positions, run.best_values, safe)
+            return x, np.sqrt([c.predict(x[None, :])[1].item() for c in clones])
+
+        def next_pick(clones):
+            found = {t: candidate(t, clones) for t in types}
+            which = swarm_batch_choice(
+                None if found['maximizers'] is None else found['maximizers'][1],
+                None if found.get('expanders') is None else found['expanders'][1],
+                self.scaling, self.fmin, self.threshold, ucb=ucb)
+            return None if which is None else found[which]
+
+        X, sd_h = swarm_batch_loop(x0, sd0, size, [g._fitted() for g in self.gps], next_pick)
+        return (X, sd_h) if return_state else X
 
     def thompson_points(self, size=8, features=1024, max_iters=None, return_paths=False):
         """``size`` Thompson picks without a grid: per posterior sample path of the

@@ -147,6 +147,11 @@ class DeviceSwarmOptimization(SwarmOptimization):
     (``sgp_swarm_fitness_path`` / ``sgp_swarm_run_path``); ``set_path(path)`` with ``path =
     (Omega, phase, w, v)`` comes before ``init_swarm``; with ``comm`` it is sharded like
     every other swarm (``sgp_swarm_run_path_shard``), every rank holding the same path.
+
+    ``set_clones(clones)`` on a ``'maximizers'`` or ``'expanders'`` swarm: a hallucinated
+    swarm of ``SafeOptSwarm.optimize_batch`` -- the width term of the fitness comes from the
+    clones of the owner's GPs, which carry the pending picks (``sgp_swarm_fitness_hall`` /
+    ``sgp_swarm_run_hall``); one rank only.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
@@ -176,6 +181,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
         self._seed = (int(seed or 0) * 4 + code) & (2 ** 43 - 1)
         self._calls = 0
         self._path = None
+        self._clones = None
         self.global_best = np.zeros(self.ndim)
 
     def set_path(self, path):
@@ -185,6 +191,20 @@ class DeviceSwarmOptimization(SwarmOptimization):
             raise ValueError("only a 'thompson' swarm takes a path, this is %r" % (self._type,))
         self._path = path
 
+    def set_clones(self, clones):
+        """The clones of the owner's device GPs with the pending picks of a batch appended:
+        from the next ``init_swarm`` on the swarm is a hallucinated one (``None``: a plain
+        one again)."""
+        if clones is not None:
+            if self._type not in ('maximizers', 'expanders'):
+                raise ValueError("only a 'maximizers' or an 'expanders' swarm takes clones, "
+                                 "this is %r" % (self._type,))
+            if self._comm.world > 1:
+                raise NotImplementedError("a hallucinated swarm runs on one rank (this "
+                                          "communicator has %d)" % self._comm.world)
+            clones = list(clones)
+        self._clones = clones
+
     def _need_path(self):
         if self._path is None:
             raise ValueError("a 'thompson' swarm needs set_path(path) before init_swarm")
@@ -193,6 +213,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
     def fitness(self, positions):                 # kept for API parity
         if self._type == 'thompson':
             return self._owner._compute_path_fitness(self._need_path(), positions)
+        if self._clones is not None:
+            return self._owner._compute_hall_fitness(self._type, self._clones, positions)
         return self._owner._compute_particle_fitness(self._type, positions)
 
     def _device_run(self, init, iters, inertia0, step):
@@ -212,6 +234,14 @@ class DeviceSwarmOptimization(SwarmOptimization):
                     self.velocities, self.best_positions, self.best_values, self.global_best,
                     np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
                     inertia0, step, rand, path, seed=(self._seed << 20) + self._calls)
+                return
+            if self._clones is not None:
+                _hip.swarm_run_hall(
+                    devs[0].ctx, devs, self._clones, self._type, o.beta(o.t), o.fmin,
+                    o.scaling, o.best_lower_bound, self.positions, self.velocities,
+                    self.best_positions, self.best_values, self.global_best,
+                    np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
+                    inertia0, step, rand, seed=(self._seed << 20) + self._calls)
                 return
             _hip.swarm_run(
                 devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
