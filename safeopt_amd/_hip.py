@@ -1249,51 +1249,6 @@ def swarm_grow(ctx, gp, S, B, scale2, thr=0.95):
     return accept.view(np.bool_)
 
 
-def swarm_run(ctx, gps, swarm_type, beta, fmin, scaling, best_lower_bound,
-              positions, velocities, best_positions, best_values, global_best,
-              velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0,
-              shard=None):
-    """Whole PSO run on the device; the state arrays are updated in place.
-
-    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
-    ``P_total`` sharded over the ranks of ``ctx``'s communicator
-    (``sgp_swarm_run_shard``); ``global_best`` comes back as the whole swarm's."""
-    P = positions.shape[0]
-    for a in (positions, velocities, best_positions, best_values, global_best):
-        assert a.dtype == np.float64 and a.flags.c_contiguous
-    bnd = None if bounds is None else f64(bounds)
-    rnd = None if rand is None else f64(rand).ravel()
-    args = (ctx.h, _gp_array(gps), len(gps), SWARM_TYPES[swarm_type], float(beta),
-            dptr(f64(fmin)), dptr(f64(scaling)), float(best_lower_bound), P,
-            dptr(positions), dptr(velocities), dptr(best_positions),
-            dptr(best_values), dptr(global_best), dptr(f64(velocity_scale)),
-            None if bnd is None else dptr(bnd), int(bool(init)), int(iters),
-            float(inertia0), float(step), None if rnd is None else dptr(rnd),
-            int(seed))
-    if shard is None:
-        ctx.check(lib().sgp_swarm_run(*args))
-    else:
-        ctx.check(lib().sgp_swarm_run_shard(*(args + (int(shard[0]), int(shard[1])))))
-
-
-def swarm_fitness(ctx, gps, swarm_type, particles, beta, fmin, scaling,
-                  best_lower_bound):
-    d = gps[0].d
-    particles = f64(particles).reshape(-1, d)
-    P = particles.shape[0]
-    fmin = f64(fmin)
-    scaling = f64(scaling)
-    values = np.empty(P)
-    safe = np.empty(P, dtype=np.uint8)
-    if P:
-        ctx.check(lib().sgp_swarm_fitness(
-            ctx.h, _gp_array(gps), len(gps), SWARM_TYPES[swarm_type],
-            dptr(particles), P, float(beta), dptr(fmin), dptr(scaling),
-            float(best_lower_bound), dptr(values),
-            safe.ctypes.data_as(c_u8_p)))
-    return values, safe.view(np.bool_)
-
-
 def _swarm_path_args(gp, path):
     """``(Omega, phase, m, w, v)`` of ONE sample path, checked against its GP."""
     Omega, phase, w, v = path
@@ -1308,22 +1263,106 @@ def _swarm_path_args(gp, path):
     return Omega, phase, m, w, v
 
 
+def _swarm_call(ctx, name, gps, swarm_type, path, clones):
+    """The C symbol ``sgp_swarm_<name>[_path|_hall]`` of a swarm variant, the head of its
+    argument list -- ``ctx, gps[, clones], G[, swarm type]`` -- and the staged-on-the-host
+    path arguments that close it (``path = (Omega, phase, w, v)``, one sample path of
+    ``gps[0]``; ``clones[g]``: ``gps[g].clone()`` with the pending picks appended)."""
+    head, tail = (ctx.h, _gp_array(gps)), ()
+    if clones is not None:
+        if len(clones) != len(gps):
+            raise ValueError("%d clones for %d GPs" % (len(clones), len(gps)))
+        name, head = name + "_hall", head + (_gp_array(clones),)
+    head += (len(gps),)
+    if path is not None:
+        Omega, phase, m, w, v = _swarm_path_args(gps[0], path)
+        name, tail = name + "_path", (dptr(Omega), dptr(phase), m, dptr(w), dptr(v))
+    else:
+        head += (SWARM_TYPES[swarm_type],)
+    return name, head, tail
+
+
+def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=None,
+               shard=None):
+    """Every whole PSO run on the device: ``fit = (beta, fmin, scaling, best_lower_bound)``,
+    ``state = (positions, velocities, best_positions, best_values, global_best,
+    velocity_scale, bounds)`` -- the first five updated in place -- and ``schedule = (init,
+    iters, inertia0, step, rand, seed)``, the structs of the C side.  ``path`` (a Thompson
+    swarm; ``swarm_type`` and the best lower bound are not used), ``clones`` (a hallucinated
+    swarm) and ``shard = (p0, P_total)`` pick the entry point."""
+    beta, fmin, scaling, best_lower_bound = fit
+    init, iters, inertia0, step, rand, seed = schedule
+    P = state[0].shape[0]
+    if clones is not None and (path is not None or shard is not None):
+        raise NotImplementedError("a hallucinated swarm is a whole maximizers or expanders "
+                                  "swarm on one rank")
+    name, head, tail = _swarm_call(ctx, "sgp_swarm_run", gps, swarm_type, path, clones)
+    for a in state[:5]:
+        assert a.dtype == np.float64 and a.flags.c_contiguous
+    vscale = f64(state[5])
+    bnd = None if state[6] is None else f64(state[6])
+    rnd = None if rand is None else f64(rand).ravel()
+    args = head + (float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
+    if path is None:
+        args += (float(best_lower_bound),)
+    args += (P,) + tuple(dptr(a) for a in state[:5]) + (
+        dptr(vscale), None if bnd is None else dptr(bnd), int(bool(init)), int(iters),
+        float(inertia0), float(step), None if rnd is None else dptr(rnd), int(seed)) + tail
+    if shard is not None:
+        name, args = name + "_shard", args + (int(shard[0]), int(shard[1]))
+    ctx.check(getattr(lib(), name)(*args))
+
+
+def _swarm_fitness(ctx, gps, swarm_type, particles, fit, path=None, clones=None,
+                   want_var=False):
+    """Every swarm fitness call: ``(values, safe)`` of ``particles``, with ``want_var`` (a
+    hallucinated swarm's) also the hallucinated variances ``(G, P)``; ``fit``, ``path`` and
+    ``clones`` as for :func:`_swarm_run`."""
+    beta, fmin, scaling, best_lower_bound = fit
+    name, head, tail = _swarm_call(ctx, "sgp_swarm_fitness", gps, swarm_type, path, clones)
+    particles = f64(particles).reshape(-1, gps[0].d)
+    P = particles.shape[0]
+    values = np.empty(P)
+    safe = np.empty(P, dtype=np.uint8)
+    var_h = np.empty((len(gps), P)) if want_var else None
+    args = head + (dptr(particles), P, float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
+    if path is None:
+        args += (float(best_lower_bound),)
+    args += tail + (dptr(values), safe.ctypes.data_as(c_u8_p))
+    if clones is not None:
+        args += (None if var_h is None else dptr(var_h),)
+    if P or clones is not None:        # (an empty hallucinated call still checks its clones)
+        ctx.check(getattr(lib(), name)(*args))
+    if want_var:
+        return values, safe.view(np.bool_), var_h
+    return values, safe.view(np.bool_)
+
+
+def swarm_run(ctx, gps, swarm_type, beta, fmin, scaling, best_lower_bound,
+              positions, velocities, best_positions, best_values, global_best,
+              velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0,
+              shard=None):
+    """Whole PSO run on the device; the state arrays are updated in place.
+
+    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
+    ``P_total`` sharded over the ranks of ``ctx``'s communicator
+    (``sgp_swarm_run_shard``); ``global_best`` comes back as the whole swarm's."""
+    _swarm_run(ctx, gps, swarm_type, (beta, fmin, scaling, best_lower_bound),
+               (positions, velocities, best_positions, best_values, global_best,
+                velocity_scale, bounds), (init, iters, inertia0, step, rand, seed), shard=shard)
+
+
+def swarm_fitness(ctx, gps, swarm_type, particles, beta, fmin, scaling,
+                  best_lower_bound):
+    return _swarm_fitness(ctx, gps, swarm_type, particles,
+                          (beta, fmin, scaling, best_lower_bound))
+
+
 def swarm_fitness_path(ctx, gps, particles, beta, fmin, scaling, path):
     """Fitness and safety of ``particles`` for a Thompson swarm (``sgp_swarm_fitness_path``):
     ``path = (Omega, phase, w, v)``, one sample path of ``gps[0]`` with contiguous 1-D ``w``
     and ``v`` (a column of a ``PosteriorPaths``)."""
-    d = gps[0].d
-    particles = f64(particles).reshape(-1, d)
-    P = particles.shape[0]
-    Omega, phase, m, w, v = _swarm_path_args(gps[0], path)
-    values = np.empty(P)
-    safe = np.empty(P, dtype=np.uint8)
-    if P:
-        ctx.check(lib().sgp_swarm_fitness_path(
-            ctx.h, _gp_array(gps), len(gps), dptr(particles), P, float(beta),
-            dptr(f64(fmin)), dptr(f64(scaling)), dptr(Omega), dptr(phase), m, dptr(w),
-            dptr(v), dptr(values), safe.ctypes.data_as(c_u8_p)))
-    return values, safe.view(np.bool_)
+    return _swarm_fitness(ctx, gps, None, particles, (beta, fmin, scaling, 0.0), path=path)
 
 
 def swarm_run_path(ctx, gps, beta, fmin, scaling, positions, velocities, best_positions,
@@ -1335,22 +1374,10 @@ def swarm_run_path(ctx, gps, beta, fmin, scaling, positions, velocities, best_po
     ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
     ``P_total`` sharded over the ranks of ``ctx``'s communicator
     (``sgp_swarm_run_path_shard``), as for :func:`swarm_run`."""
-    P = positions.shape[0]
-    for a in (positions, velocities, best_positions, best_values, global_best):
-        assert a.dtype == np.float64 and a.flags.c_contiguous
-    bnd = None if bounds is None else f64(bounds)
-    rnd = None if rand is None else f64(rand).ravel()
-    Omega, phase, m, w, v = _swarm_path_args(gps[0], path)
-    args = (ctx.h, _gp_array(gps), len(gps), float(beta), dptr(f64(fmin)), dptr(f64(scaling)),
-            P, dptr(positions), dptr(velocities), dptr(best_positions), dptr(best_values),
-            dptr(global_best), dptr(f64(velocity_scale)), None if bnd is None else dptr(bnd),
-            int(bool(init)), int(iters), float(inertia0), float(step),
-            None if rnd is None else dptr(rnd), int(seed), dptr(Omega), dptr(phase), m, dptr(w),
-            dptr(v))
-    if shard is None:
-        ctx.check(lib().sgp_swarm_run_path(*args))
-    else:
-        ctx.check(lib().sgp_swarm_run_path_shard(*(args + (int(shard[0]), int(shard[1])))))
+    _swarm_run(ctx, gps, None, (beta, fmin, scaling, 0.0),
+               (positions, velocities, best_positions, best_values, global_best,
+                velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
+               path=path, shard=shard)
 
 
 def swarm_fitness_hall(ctx, gps, clones, swarm_type, particles, beta, fmin, scaling,
@@ -1359,22 +1386,9 @@ def swarm_fitness_hall(ctx, gps, clones, swarm_type, particles, beta, fmin, scal
     (``sgp_swarm_fitness_hall``): ``clones[g]`` is ``gps[g].clone()`` with the pending picks
     of the batch appended.  The width term comes from the clones' variance, everything else
     from ``gps``.  ``want_var``: also the hallucinated variances, ``(G, P)``."""
-    d = gps[0].d
-    if len(clones) != len(gps):
-        raise ValueError("%d clones for %d GPs" % (len(clones), len(gps)))
-    particles = f64(particles).reshape(-1, d)
-    P = particles.shape[0]
-    values = np.empty(P)
-    safe = np.empty(P, dtype=np.uint8)
-    var_h = np.empty((len(gps), P)) if want_var else None
-    ctx.check(lib().sgp_swarm_fitness_hall(
-        ctx.h, _gp_array(gps), _gp_array(clones), len(gps), SWARM_TYPES[swarm_type],
-        dptr(particles), P, float(beta), dptr(f64(fmin)), dptr(f64(scaling)),
-        float(best_lower_bound), dptr(values), safe.ctypes.data_as(c_u8_p),
-        None if var_h is None else dptr(var_h)))
-    if want_var:
-        return values, safe.view(np.bool_), var_h
-    return values, safe.view(np.bool_)
+    return _swarm_fitness(ctx, gps, swarm_type, particles,
+                          (beta, fmin, scaling, best_lower_bound), clones=clones,
+                          want_var=want_var)
 
 
 def swarm_run_hall(ctx, gps, clones, swarm_type, beta, fmin, scaling, best_lower_bound,
@@ -1382,17 +1396,7 @@ def swarm_run_hall(ctx, gps, clones, swarm_type, beta, fmin, scaling, best_lower
                    velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0):
     """Whole PSO run of a hallucinated swarm on the device (``sgp_swarm_run_hall``); the state
     arrays are updated in place, ``clones`` as for :func:`swarm_fitness_hall`."""
-    P = positions.shape[0]
-    if len(clones) != len(gps):
-        raise ValueError("%d clones for %d GPs" % (len(clones), len(gps)))
-    for a in (positions, velocities, best_positions, best_values, global_best):
-        assert a.dtype == np.float64 and a.flags.c_contiguous
-    bnd = None if bounds is None else f64(bounds)
-    rnd = None if rand is None else f64(rand).ravel()
-    ctx.check(lib().sgp_swarm_run_hall(
-        ctx.h, _gp_array(gps), _gp_array(clones), len(gps), SWARM_TYPES[swarm_type],
-        float(beta), dptr(f64(fmin)), dptr(f64(scaling)), float(best_lower_bound), P,
-        dptr(positions), dptr(velocities), dptr(best_positions), dptr(best_values),
-        dptr(global_best), dptr(f64(velocity_scale)), None if bnd is None else dptr(bnd),
-        int(bool(init)), int(iters), float(inertia0), float(step),
-        None if rnd is None else dptr(rnd), int(seed)))
+    _swarm_run(ctx, gps, swarm_type, (beta, fmin, scaling, best_lower_bound),
+               (positions, velocities, best_positions, best_values, global_best,
+                velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
+               clones=clones)

@@ -20,7 +20,7 @@ OUT = os.path.join(PKG, "libsafeopt_hip.so")
 SOURCES = ["api.hip", "batch.hip", "sweep.hip", "sweep_pair.hip", "sweep_mid.hip", "sweep_tiny.hip",
            "step_small.hip",
            "factor.hip", "hyper.hip", "joint.hip", "paths.hip", "sets.hip", "swarm.hip",
-           "swarm_batch.hip"]
+           "swarm_api.hip", "swarm_batch.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "kern_eval.h", "fitness.h",
                                             "small_path.h", "sweep_shared.h",
                                             "sweep_slots.h", "set_order.h",

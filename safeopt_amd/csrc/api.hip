@@ -102,6 +102,9 @@ int fill_kern(sgp_ctx* ctx, KernDesc* kd, int d, int n_parts, const int* kinds,
   return 0;
 }
 
+}  // namespace
+
+// (common.h: swarm_api.hip collects its GPs the same way)
 int collect_gps(sgp_ctx* ctx, sgp_gp* const* gps, int G, int d, GpDev* host) {
   SGP_CHECK(ctx, G >= 1 && G <= SGP_MAX_GPS, "%d GPs, supported 1..%d", G,
             SGP_MAX_GPS);
@@ -135,6 +138,7 @@ int collect_gps(sgp_ctx* ctx, sgp_gp* const* gps, int G, int d, GpDev* host) {
   return 0;
 }
 
+namespace {
 // FNV-1a over the bytes of training rows, chained row by row (sgp_gp::xhash)
 uint64_t hash_rows(uint64_t h, const double* rows, size_t count) {
   const unsigned char* b = reinterpret_cast<const unsigned char*>(rows);
@@ -2257,516 +2261,7 @@ int sgp_grid_sets_fused_comm(sgp_grid* g, sgp_gp* const* gps, int G, double beta
   return read_result(g, res, nres, {out5, x_top, mean_top, q_top, flags, value, gidx, max_l_out});
 }
 
-// Fitness of P <= kSmallPoints particles (row-major, device) through the
-// small-point posterior path: mean / var per GP, then the shaping kernel.
-static int fitness_small(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_host,
-                         int G, const double* pts_rowmajor, int64_t P,
-                         const FitnessArgs& fa) {
-  const int Geff = (fa.swarm_type == SGP_SWARM_GREEDY) ? 1 : G;
-  double* mv;
-  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(2) * SGP_MAX_GPS * kSmallPoints * sizeof(double),
-                      &mv));
-  SmallBufs sb;
-  SGP_TRY(small_reserve(ctx, gps_host, Geff, int(P), &sb));
-  double* mean = mv;
-  double* var = mv + size_t(SGP_MAX_GPS) * kSmallPoints;
-  SGP_TRY(posterior_small_all(ctx, gps_dev, gps_host, Geff, pts_rowmajor, int(P), sb,
-                              mean, var));
-  return launch_fitness_small(ctx, G, P, mean, var, fa);
-}
-
-static bool small_path_pays_all(sgp_gp* const* gps, int G, int64_t P) {
-  for (int g = 0; g < G; ++g)
-    if (!small_path_pays(gps[g], P)) return false;
-  return true;
-}
-
-// ---- swarm ----------------------------------------------------------------------
-// The clones of a hallucinated swarm (sgp_swarm_fitness_hall / sgp_swarm_run_hall) against
-// the GPs they were cloned from: maximizers or expanders, every clone in the call's context
-// with the source's input dimension and kernel and gps[g].n + b observations for ONE b in
-// 1 .. SGP_MAX_BATCH.  host: their descriptors, `share` as collect_gps sets it.
-static int hall_clones(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
-                       int swarm_type, GpDev* host, int* b_out) {
-  SGP_CHECK(ctx, swarm_type == SGP_SWARM_MAXIMIZERS || swarm_type == SGP_SWARM_EXPANDERS,
-            "a hallucinated swarm is a maximizers or an expanders swarm, not type %d",
-            swarm_type);
-  SGP_CHECK(ctx, G >= 1 && G <= SGP_MAX_GPS && gps[0], "no GP");
-  SGP_CHECK(ctx, clones != nullptr, "no clones");
-  for (int g = 0; g < G; ++g) {
-    SGP_CHECK(ctx, gps[g] && clones[g], "GP %d or its clone is missing", g);
-    SGP_CHECK(ctx, gps[g]->ctx == ctx && clones[g]->ctx == ctx,
-              "GP %d or its clone lives in another context than the call (device %d)", g,
-              ctx->device);
-    SGP_CHECK(ctx, clones[g]->kern.d == gps[g]->kern.d &&
-                       memcmp(&clones[g]->kern, &gps[g]->kern, sizeof(KernDesc)) == 0,
-              "clone %d has another input dimension or kernel than its GP", g);
-  }
-  const int64_t b = clones[0]->n - gps[0]->n;
-  SGP_CHECK(ctx, b >= 1 && b <= SGP_MAX_BATCH,
-            "clone 0 holds %lld observations, its GP %lld: 1 .. %d pending picks",
-            (long long)clones[0]->n, (long long)gps[0]->n, SGP_MAX_BATCH);
-  for (int g = 1; g < G; ++g)
-    SGP_CHECK(ctx, clones[g]->n == gps[g]->n + b,
-              "clone %d holds %lld observations, its GP %lld: not the %lld pending picks of "
-              "clone 0", g, (long long)clones[g]->n, (long long)gps[g]->n, (long long)b);
-  SGP_TRY(collect_gps(ctx, clones, G, gps[0]->kern.d, host));
-  *b_out = int(b);
-  return 0;
-}
-
-// sgp_swarm_fitness, and with clones sgp_swarm_fitness_hall: the same launches for the real
-// posterior, the downdate (launch_swarm_down) in front of the shaping pass
-static int swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
-                         int swarm_type, const double* particles, int64_t P, double beta,
-                         const double* fmin, const double* scaling, double best_lower_bound,
-                         double* values, uint8_t* safe, double* var_h) {
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, swarm_type >= SGP_SWARM_GREEDY && swarm_type <= SGP_SWARM_SAFE_SET,
-            "Invalid swarm type %d", swarm_type);
-  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
-  GpDev chost[SGP_MAX_GPS];
-  int b = 0;
-  if (clones) SGP_TRY(hall_clones(ctx, gps, clones, G, swarm_type, chost, &b));
-  if (P <= 0) return 0;
-  const int d = gps[0]->kern.d;
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, d, host));
-  const size_t nd = size_t(P) * 8;
-  double* stage;
-  char* work;
-  SGP_TRY(sgp_scratch(ctx, kSlotStage, nd * d, &stage));
-  // points | values | GP descriptors | safe (padded to 8 bytes) | with clones: their
-  // descriptors | down [G][P] | var_h [G][P]
-  const size_t plain = nd * d + nd + sizeof(GpDev) * SGP_MAX_GPS + (size_t(P) + 7) / 8 * 8;
-  const size_t hall = clones ? sizeof(GpDev) * SGP_MAX_GPS + 2 * size_t(G) * nd : 0;
-  SGP_TRY(sgp_scratch(ctx, kSlotWork, plain + hall + 64, &work));
-  double* pts = reinterpret_cast<double*>(work);
-  double* dval = reinterpret_cast<double*>(work + nd * d);
-  GpDev* gdev = reinterpret_cast<GpDev*>(work + nd * d + nd);
-  uint8_t* dsafe = reinterpret_cast<uint8_t*>(work + nd * d + nd + sizeof(GpDev) * SGP_MAX_GPS);
-  GpDev* cdev = reinterpret_cast<GpDev*>(work + plain);
-  double* ddown = reinterpret_cast<double*>(cdev + SGP_MAX_GPS);
-  double* dvarh = ddown + size_t(G) * size_t(P);
-  SGP_TRY(sgp_h2d(ctx, stage, particles, nd * d));
-  SGP_TRY(launch_import_points(ctx, stage, P, d, d, 1, pts));
-  SGP_TRY(sgp_h2d(ctx, gdev, host, sizeof(GpDev) * G));
-  FitnessArgs fa{};
-  fa.swarm_type = swarm_type;
-  fa.beta = beta;
-  fa.best_lower_bound = best_lower_bound;
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    fa.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
-    fa.scaling[i] = (i < G) ? scaling[i] : 1.0;
-  }
-  fa.values = dval;
-  fa.safe = dsafe;
-  const SweepPoints sp{pts, P, 1, P};
-  if (clones) {
-    SGP_TRY(sgp_h2d(ctx, cdev, chost, sizeof(GpDev) * G));
-    SGP_TRY(launch_swarm_down(ctx, cdev, G, d, b, sp, ddown));
-    fa.down = ddown;
-    fa.var_h = var_h ? dvarh : nullptr;
-  }
-  if (small_path_pays_all(gps, G, P)) {
-    SGP_TRY(fitness_small(ctx, gdev, host, G, stage, P, fa));
-  } else {
-    SGP_TRY(launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa));
-  }
-  SGP_TRY(sgp_d2h(ctx, values, dval, nd));
-  SGP_TRY(sgp_d2h(ctx, safe, dsafe, size_t(P)));
-  if (clones && var_h) SGP_TRY(sgp_d2h(ctx, var_h, dvarh, size_t(G) * nd));
-  return 0;
-}
-
-int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
-                      const double* particles, int64_t P, double beta,
-                      const double* fmin, const double* scaling,
-                      double best_lower_bound, double* values, uint8_t* safe) {
-  return swarm_fitness(ctx, gps, nullptr, G, swarm_type, particles, P, beta, fmin, scaling,
-                       best_lower_bound, values, safe, nullptr);
-}
-
-int sgp_swarm_fitness_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
-                           int swarm_type, const double* particles, int64_t P, double beta,
-                           const double* fmin, const double* scaling, double best_lower_bound,
-                           double* values, uint8_t* safe, double* var_h) {
-  SGP_CHECK(ctx, clones != nullptr, "no clones");
-  return swarm_fitness(ctx, gps, clones, G, swarm_type, particles, P, beta, fmin, scaling,
-                       best_lower_bound, values, safe, var_h);
-}
-
-// The fitness of a Thompson swarm: the posterior and the shaping as for sgp_swarm_fitness
-// (kSwarmThompson in fitness.h leaves the penalty in the values), then the path term on
-// top (k_swarm_path, paths.hip).
-int sgp_swarm_fitness_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
-                           int64_t P, double beta, const double* fmin, const double* scaling,
-                           const double* Omega, const double* phase, int m, const double* w,
-                           const double* v, double* values, uint8_t* safe) {
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
-  SGP_CHECK(ctx, gps[0]->ctx == ctx, "GP 0 lives in another context (device %d) than the "
-            "call (device %d)", gps[0]->ctx ? gps[0]->ctx->device : -1, ctx->device);
-  SGP_TRY(swarm_path_ready(gps[0], m));
-  if (P <= 0) return 0;
-  const int d = gps[0]->kern.d;
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(collect_gps(ctx, gps, G, d, host));
-  const size_t nd = size_t(P) * 8;
-  double* stage;
-  char* work;
-  SGP_TRY(sgp_scratch(ctx, kSlotStage, nd * d, &stage));
-  SGP_TRY(sgp_scratch(ctx, kSlotWork, nd * d + nd + size_t(P) + sizeof(GpDev) * SGP_MAX_GPS + 64,
-                      &work));
-  double* pts = reinterpret_cast<double*>(work);
-  double* dval = reinterpret_cast<double*>(work + nd * d);
-  GpDev* gdev = reinterpret_cast<GpDev*>(work + nd * d + nd);
-  uint8_t* dsafe = reinterpret_cast<uint8_t*>(work + nd * d + nd + sizeof(GpDev) * SGP_MAX_GPS);
-  SGP_TRY(sgp_h2d(ctx, stage, particles, nd * d));
-  SGP_TRY(launch_import_points(ctx, stage, P, d, d, 1, pts));
-  SGP_TRY(sgp_h2d(ctx, gdev, host, sizeof(GpDev) * G));
-  SwarmPath path;
-  SGP_TRY(swarm_path_stage(gps[0], Omega, phase, m, w, v, &path));
-  FitnessArgs fa{};
-  fa.swarm_type = kSwarmThompson;
-  fa.beta = beta;
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    fa.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
-    fa.scaling[i] = (i < G) ? scaling[i] : 1.0;
-  }
-  fa.values = dval;
-  fa.safe = dsafe;
-  const SweepPoints sp{pts, P, 1, P};
-  if (small_path_pays_all(gps, G, P)) {
-    SGP_TRY(fitness_small(ctx, gdev, host, G, stage, P, fa));
-  } else {
-    SGP_TRY(launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa));
-  }
-  SGP_TRY(launch_swarm_path(ctx, gdev, d, path, sp, fa.scaling[0], dval));
-  SGP_TRY(sgp_d2h(ctx, values, dval, nd));
-  SGP_TRY(sgp_d2h(ctx, safe, dsafe, size_t(P)));
-  return 0;
-}
-
-// SwarmOptimization.init_swarm / run_swarm (swarm.py:61-146) with the state in
-// HBM and the fitness fused in: one call = the whole run, one host round trip.
-// The particles [p0, p0 + P) of a swarm of Pt; P < Pt: a rank's block of a sharded
-// swarm (sgp_swarm_run_shard) -- the global best goes through the record all-gather.
-static int swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
-                     double beta, const double* fmin, const double* scaling,
-                     double best_lower_bound, int64_t P, double* positions,
-                     double* velocities, double* best_positions, double* best_values,
-                     double* global_best, const double* velocity_scale,
-                     const double* bounds, int init, int iters, double inertia0,
-                     double step_size, const double* rand, uint64_t seed, int64_t p0,
-                     int64_t Pt, const SwarmPath* path = nullptr,
-                     sgp_gp* const* clones = nullptr) {
-  // path: the staged sample path of a Thompson swarm (sgp_swarm_run_path, swarm_type =
-  // kSwarmThompson); such a run always takes the general launches below
-  // clones: a hallucinated swarm (sgp_swarm_run_hall): the downdate in front of every
-  // shaping pass; the general launches as well
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, path ? swarm_type == kSwarmThompson
-                      : swarm_type >= SGP_SWARM_GREEDY && swarm_type <= SGP_SWARM_SAFE_SET,
-            "Invalid swarm type %d", swarm_type);
-  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
-  SGP_CHECK(ctx, P >= 1 && iters >= 0, "bad swarm size %lld / iterations %d",
-            (long long)P, iters);
-  SGP_CHECK(ctx, p0 >= 0 && p0 + P <= Pt, "bad block [%lld, %lld) of a swarm of %lld",
-            (long long)p0, (long long)(p0 + P), (long long)Pt);
-  const bool shard = P < Pt;
-  const bool comm = have_comm(ctx);
-  SGP_CHECK(ctx, comm || !shard,
-            "a block of %lld of a swarm of %lld particles needs a communicator in the "
-            "context (sgp_comm_init / sgp_comm_init_host)", (long long)P, (long long)Pt);
-  const int world = comm ? ctx->world : 1;
-  const int d = gps[0]->kern.d;
-  GpDev host[SGP_MAX_GPS], chost[SGP_MAX_GPS];
-  int hall_b = 0;
-  if (clones) SGP_TRY(hall_clones(ctx, gps, clones, G, swarm_type, chost, &hall_b));
-  SGP_TRY(collect_gps(ctx, gps, G, d, host));
-  const size_t nd = size_t(P) * d * 8, nv = size_t(P) * 8;
-  const size_t nrand = rand ? (size_t(init ? 1 : 0) + 2 * size_t(iters)) * nd : 0;
-  // pos | vel | best | best_values | values | gbest | vscale | bounds | gpdev |
-  // this rank's record | the gathered records (shard: value | index | x[d] each) | safe |
-  // with clones, from the next multiple of 64 bytes: their descriptors | down [G][P]
-  const size_t nrec = size_t(2 + d);
-  const size_t recs = shard ? (1 + size_t(world)) * nrec * 8 : 0;
-  const size_t small = size_t(d) * 8 * 4 + sizeof(GpDev) * SGP_MAX_GPS + recs + 64;
-  const size_t plain = 3 * nd + 2 * nv + small + size_t(P);
-  const size_t hall_off = (plain + 63) / 64 * 64;
-  const size_t hall = clones ? sizeof(GpDev) * SGP_MAX_GPS + size_t(G) * nv : 0;
-  char* buf;
-  double* drand = nullptr;
-  SGP_TRY(sgp_scratch(ctx, kSlotWork, clones ? hall_off + hall : plain, &buf));
-  if (rand) SGP_TRY(sgp_scratch(ctx, kSlotStage, nrand, &drand));
-  double* dpos = reinterpret_cast<double*>(buf);
-  double* dvel = reinterpret_cast<double*>(buf + nd);
-  double* dbest = reinterpret_cast<double*>(buf + 2 * nd);
-  double* dbv = reinterpret_cast<double*>(buf + 3 * nd);
-  double* dval = reinterpret_cast<double*>(buf + 3 * nd + nv);
-  double* dgb = reinterpret_cast<double*>(buf + 3 * nd + 2 * nv);
-  double* dvs = dgb + d;
-  double* dbd = dvs + d;                       // 2 d entries
-  GpDev* gdev = reinterpret_cast<GpDev*>(dbd + 2 * d);
-  double* drec = reinterpret_cast<double*>(gdev + SGP_MAX_GPS);
-  double* drecs = drec + nrec;
-  uint8_t* dsafe = reinterpret_cast<uint8_t*>(drec) + recs;
-  GpDev* cdev = reinterpret_cast<GpDev*>(buf + hall_off);
-  double* ddown = reinterpret_cast<double*>(cdev + SGP_MAX_GPS);
-  SGP_TRY(sgp_h2d(ctx, dpos, positions, nd));
-  if (!init) {
-    SGP_TRY(sgp_h2d(ctx, dvel, velocities, nd));
-    SGP_TRY(sgp_h2d(ctx, dbest, best_positions, nd));
-    SGP_TRY(sgp_h2d(ctx, dbv, best_values, nv));
-    SGP_TRY(sgp_h2d(ctx, dgb, global_best, size_t(d) * 8));
-  }
-  SGP_TRY(sgp_h2d(ctx, dvs, velocity_scale, size_t(d) * 8));
-  if (bounds) SGP_TRY(sgp_h2d(ctx, dbd, bounds, size_t(d) * 16));
-  if (rand) SGP_TRY(sgp_h2d(ctx, drand, rand, nrand));
-  SGP_TRY(sgp_h2d(ctx, gdev, host, sizeof(GpDev) * G));
-  if (clones) SGP_TRY(sgp_h2d(ctx, cdev, chost, sizeof(GpDev) * G));
-  FitnessArgs fa{};
-  fa.swarm_type = swarm_type;
-  fa.beta = beta;
-  fa.best_lower_bound = best_lower_bound;
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    fa.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
-    fa.scaling[i] = (i < G) ? scaling[i] : 1.0;
-  }
-  fa.values = dval;
-  fa.safe = dsafe;
-  if (clones) fa.down = ddown;
-  const SweepPoints sp{dpos, P, d, 1};          // row-major (P, d) in place
-  // (the paths and the posterior kernel follow the whole swarm: same bits on every rank)
-  const bool few = Pt <= kSmallSwarm && small_path_pays_all(gps, G, Pt);
-  // a small swarm against GPs with few observations (SafeOptSwarm's defaults on the
-  // reference's own examples: 20 particles, n <= 20): the posterior is one sweep launch
-  // (sweep_tiny.hip up to 48 observations), everything else of the iteration the same ONE
-  // workgroup as on the few-points path -- two launches per iteration instead of five
-  const bool few_swept = Pt <= kSmallSwarm && !few;
-  const double* r = drand;
-  double inertia = inertia0;
-  if ((few || few_swept) && !shard && !path && !clones) {
-    // small swarm: three launches per iteration -- k(X, particles), the block
-    // products on the matrix cores, and ONE workgroup for everything else
-    // (fitness, bests, and the move that opens the next iteration)
-    const int Geff = (swarm_type == SGP_SWARM_GREEDY) ? 1 : G;
-    SmallBufs sb{};
-    ConfOut post{};
-    if (few) {
-      SGP_TRY(small_reserve(ctx, host, Geff, int(P), &sb));
-    } else {
-      const size_t np = size_t(Geff) * size_t(P);
-      SGP_TRY(sgp_reserve(ctx, &ctx->pair_post, 2 * np * sizeof(double)));
-      post.mean = static_cast<double*>(ctx->pair_post.p);
-      post.var = post.mean + np;
-      for (int i = 0; i < SGP_MAX_GPS; ++i) post.fmin[i] = -INFINITY;
-    }
-    PsoSmallArgs ps{};
-    ps.pos = dpos;
-    ps.vel = dvel;
-    ps.best = dbest;
-    ps.best_values = dbv;
-    ps.gbest = dgb;
-    ps.vscale = dvs;
-    ps.bounds = bounds ? dbd : nullptr;
-    ps.seed = seed;
-    ps.P = int(P);
-    ps.d = d;
-    auto step = [&](int is_init, int it_next) -> int {   // it_next < 0: no move
-      if (few)
-        SGP_TRY(posterior_small_all(ctx, gdev, host, Geff, dpos, int(P), sb, nullptr,
-                                    nullptr));
-      else
-        SGP_TRY(launch_sweep_conf(ctx, gdev, host, Geff, d, sp, post));
-      ps.init = is_init;
-      ps.move = it_next >= 0;
-      ps.rand = r;
-      ps.draw = uint32_t(it_next + 1);
-      ps.inertia = inertia;
-      SGP_TRY(launch_pso_small_step(ctx, gdev, G, sb, fa, ps, few ? nullptr : post.mean,
-                                    few ? nullptr : post.var));
-      if (ps.move) {
-        if (r) r += 2 * size_t(P) * d;
-        inertia += step_size;
-      }
-      return 0;
-    };
-    if (init) {
-      SGP_TRY(launch_pso_init_vel(ctx, P, d, dvel, dvs, r, seed));
-      if (r) r += size_t(P) * d;
-      SGP_TRY(step(1, iters > 0 ? 0 : -1));
-    } else if (iters > 0) {
-      SGP_TRY(launch_pso_move(ctx, P, d, dpos, dvel, dbest, dgb, dvs,
-                              bounds ? dbd : nullptr, inertia, r, seed, 1u));
-      if (r) r += 2 * size_t(P) * d;
-      inertia += step_size;
-    }
-    for (int it = 0; it < iters; ++it)
-      SGP_TRY(step(0, it + 1 < iters ? it + 1 : -1));
-  } else {
-    // (up to kSmallPoints particles still take the few-points posterior; a block of a
-    // small swarm takes these launches, the arithmetic of k_pso_small_step)
-    const bool few_points = small_path_pays_all(gps, G, Pt);
-    auto fitness = [&]() -> int {
-      // a hallucinated swarm: what the pending picks take off the variances, for the shaping
-      if (clones) SGP_TRY(launch_swarm_down(ctx, cdev, G, d, hall_b, sp, ddown));
-      SGP_TRY(few_points ? fitness_small(ctx, gdev, host, G, dpos, P, fa)
-                         : launch_sweep_fitness(ctx, gdev, host, G, d, sp, fa, Pt));
-      // a Thompson swarm: the path term on top of the penalty the shaping left
-      return path ? launch_swarm_path(ctx, gdev, d, *path, sp, fa.scaling[0], dval) : 0;
-    };
-    // personal bests, then the global best: of the block, or merged over the ranks
-    auto bests = [&](int is_init) -> int {
-      if (!shard)
-        return launch_pso_best(ctx, P, d, dval, dsafe, dpos, dbest, dbv, dgb, is_init);
-      SGP_TRY(launch_pso_best(ctx, P, d, dval, dsafe, dpos, dbest, dbv, dgb, is_init, drec,
-                              p0));
-      SGP_TRY(coll_allgather(ctx, drec, drecs, nrec * 8));
-      return launch_pso_gbest_merge(ctx, drecs, world, d, dgb);
-    };
-    const int64_t e0 = p0 * d, e2 = Pt * d + p0 * d;
-    if (init) {
-      SGP_TRY(launch_pso_init_vel(ctx, P, d, dvel, dvs, r, seed, e0));
-      if (r) r += size_t(P) * d;
-      SGP_TRY(fitness());
-      SGP_TRY(bests(1));
-    }
-    for (int it = 0; it < iters; ++it) {
-      SGP_TRY(launch_pso_move(ctx, P, d, dpos, dvel, dbest, dgb, dvs,
-                              bounds ? dbd : nullptr, inertia, r, seed,
-                              uint32_t(it + 1), e0, e2));
-      if (r) r += 2 * size_t(P) * d;
-      inertia += step_size;
-      SGP_TRY(fitness());
-      SGP_TRY(bests(0));
-    }
-  }
-  SGP_TRY(sgp_d2h(ctx, positions, dpos, nd));
-  SGP_TRY(sgp_d2h(ctx, velocities, dvel, nd));
-  SGP_TRY(sgp_d2h(ctx, best_positions, dbest, nd));
-  SGP_TRY(sgp_d2h(ctx, best_values, dbv, nv));
-  return sgp_d2h(ctx, global_best, dgb, size_t(d) * 8);
-}
-
-int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
-                  double beta, const double* fmin, const double* scaling,
-                  double best_lower_bound, int64_t P, double* positions,
-                  double* velocities, double* best_positions, double* best_values,
-                  double* global_best, const double* velocity_scale,
-                  const double* bounds, int init, int iters, double inertia0,
-                  double step_size, const double* rand, uint64_t seed) {
-  return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
-                   positions, velocities, best_positions, best_values, global_best,
-                   velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, 0, P);
-}
-
-int sgp_swarm_run_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
-                       int swarm_type, double beta, const double* fmin, const double* scaling,
-                       double best_lower_bound, int64_t P, double* positions,
-                       double* velocities, double* best_positions, double* best_values,
-                       double* global_best, const double* velocity_scale,
-                       const double* bounds, int init, int iters, double inertia0,
-                       double step_size, const double* rand, uint64_t seed) {
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, clones != nullptr, "no clones");
-  if (P <= 0) {
-    GpDev chost[SGP_MAX_GPS];
-    int b;
-    return hall_clones(ctx, gps, clones, G, swarm_type, chost, &b);
-  }
-  return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
-                   positions, velocities, best_positions, best_values, global_best,
-                   velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, 0, P,
-                   nullptr, clones);
-}
-
-// sgp_swarm_run_path (p0 = 0, Pt = P) and sgp_swarm_run_path_shard
-static int swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
-                          const double* fmin, const double* scaling, int64_t P,
-                          double* positions, double* velocities, double* best_positions,
-                          double* best_values, double* global_best,
-                          const double* velocity_scale, const double* bounds, int init,
-                          int iters, double inertia0, double step_size, const double* rand,
-                          uint64_t seed, const double* Omega, const double* phase, int m,
-                          const double* w, const double* v, int64_t p0, int64_t Pt) {
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
-  SGP_CHECK(ctx, gps[0]->ctx == ctx, "GP 0 lives in another context (device %d) than the "
-            "call (device %d)", gps[0]->ctx ? gps[0]->ctx->device : -1, ctx->device);
-  SGP_TRY(swarm_path_ready(gps[0], m));
-  // (an empty block of a sharded swarm is an error of swarm_run, not a silent return: the
-  // other ranks would wait in the all-gather)
-  if (P <= 0 && Pt <= 0) return 0;
-  // staged ONCE per call; nothing in swarm_run asks for the two slots it lives in
-  SwarmPath path;
-  SGP_TRY(swarm_path_stage(gps[0], Omega, phase, m, w, v, &path));
-  return swarm_run(ctx, gps, G, kSwarmThompson, beta, fmin, scaling, 0.0, P, positions,
-                   velocities, best_positions, best_values, global_best, velocity_scale, bounds,
-                   init, iters, inertia0, step_size, rand, seed, p0, Pt, &path);
-}
-
-int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
-                       const double* fmin, const double* scaling, int64_t P, double* positions,
-                       double* velocities, double* best_positions, double* best_values,
-                       double* global_best, const double* velocity_scale,
-                       const double* bounds, int init, int iters, double inertia0,
-                       double step_size, const double* rand, uint64_t seed,
-                       const double* Omega, const double* phase, int m, const double* w,
-                       const double* v) {
-  return swarm_run_path(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
-                        best_positions, best_values, global_best, velocity_scale, bounds, init,
-                        iters, inertia0, step_size, rand, seed, Omega, phase, m, w, v, 0, P);
-}
-
-int sgp_swarm_run_path_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
-                             const double* fmin, const double* scaling, int64_t P,
-                             double* positions, double* velocities, double* best_positions,
-                             double* best_values, double* global_best,
-                             const double* velocity_scale, const double* bounds, int init,
-                             int iters, double inertia0, double step_size, const double* rand,
-                             uint64_t seed, const double* Omega, const double* phase, int m,
-                             const double* w, const double* v, int64_t p0, int64_t P_total) {
-  return swarm_run_path(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
-                        best_positions, best_values, global_best, velocity_scale, bounds, init,
-                        iters, inertia0, step_size, rand, seed, Omega, phase, m, w, v, p0,
-                        P_total);
-}
-
-int sgp_swarm_run_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
-                        double beta, const double* fmin, const double* scaling,
-                        double best_lower_bound, int64_t P, double* positions,
-                        double* velocities, double* best_positions, double* best_values,
-                        double* global_best, const double* velocity_scale,
-                        const double* bounds, int init, int iters, double inertia0,
-                        double step_size, const double* rand, uint64_t seed, int64_t p0,
-                        int64_t P_total) {
-  return swarm_run(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
-                   positions, velocities, best_positions, best_values, global_best,
-                   velocity_scale, bounds, init, iters, inertia0, step_size, rand, seed, p0,
-                   P_total);
-}
-
-// SafeOptSwarm safe-set growth, gp_opt.py:1089-1111 (kernels in swarm.hip).
-int sgp_swarm_grow(sgp_ctx* ctx, sgp_gp* gp0, const double* S, int64_t m,
-                   const double* B, int64_t n, double scale2, double thr,
-                   uint8_t* accept) {
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, gp0 != nullptr, "no GP");
-  SGP_CHECK(ctx, m >= 0 && n >= 0 && n <= INT32_MAX, "bad sizes m=%lld n=%lld",
-            (long long)m, (long long)n);
-  if (n == 0) return 0;
-  const int d = gp0->kern.d;
-  const GrowLayout l = grow_layout(m, n, d);          // (common.h)
-  char* buf;
-  SGP_TRY(sgp_scratch(ctx, kSlotWork, l.bytes + 64, &buf));
-  const GrowBufs gb = grow_bufs(buf, l);
-  SGP_TRY(sgp_h2d(ctx, gb.S, S, size_t(m) * d * 8));
-  SGP_TRY(sgp_h2d(ctx, gb.B, B, size_t(n) * d * 8));
-  SGP_TRY(launch_swarm_grow(ctx, gp0->kern, gb.S, m, gb.B, int(n), scale2, thr, gb));
-  return sgp_d2h(ctx, accept, gb.accept, size_t(n));
-}
+// ---- swarm: the sgp_swarm_* entry points live in swarm_api.hip ------------------------
 
 // ---- timing ---------------------------------------------------------------------
 int64_t sgp_ctx_alloc_count(sgp_ctx* ctx) { return ctx ? ctx->n_allocs : -1; }

@@ -137,9 +137,11 @@ enum ScratchSlot : int {
                         // mismatch count; fitness_small's mean | var; a batch pick's pairs
                         // and result (BatchScratch)
   kSlotStage = 3,       // host rows staged for a launch: gp_predict, kern_K, grid_create,
-                        // swarm_fitness, swarm_run's random numbers; factor.hip: append_gp,
-                        // expander_operands_all
-  kSlotWork = 4,        // gp_predict's points, kern_K's matrix, the swarm entry points' state
+                        // swarm_fitness, swarm_run's random numbers (swarm_api.hip);
+                        // factor.hip: append_gp, expander_operands_all
+  kSlotWork = 4,        // gp_predict's points, kern_K's matrix; swarm_api.hip: the block of a
+                        // fitness call (SwarmFitLayout), a run (SwarmRunLayout), swarm_grow
+                        // (GrowLayout)
   kSlotGpDev = 5,       // gp_predict's GP descriptor
   kSlotSmall = 6,       // small_reserve (few-points path), upload_local_idx,
                         // comm_allreduce_max, comm_allgather
@@ -306,6 +308,8 @@ inline int sgp_scratch(sgp_ctx* ctx, ScratchSlot slot, size_t bytes, T** out) {
 int sgp_poison(sgp_ctx* ctx, void* p, size_t bytes);       // SGP_POISON=1: fill a fresh allocation with 0xFF
 int sgp_h2d(sgp_ctx* ctx, void* dst, const void* src, size_t bytes);
 int sgp_d2h(sgp_ctx* ctx, void* dst, const void* src, size_t bytes);  // syncs
+// host[g] = descriptor of gps[g] (fitted, in ctx, input dimension d), GpDev::share set
+int collect_gps(sgp_ctx* ctx, sgp_gp* const* gps, int G, int d, GpDev* host);
 
 // GPy's util.linalg.jitchol around any factorisation: attempt(jitter, &info) factorises with
 // that much added to the diagonal (info = 0, or the first pivot that is not positive); after a
@@ -450,6 +454,30 @@ int launch_swarm_path(sgp_ctx* ctx, const GpDev* gps_dev, int d, const SwarmPath
 // GpDev::share as collect_gps sets it
 int launch_swarm_down(sgp_ctx* ctx, const GpDev* clones_dev, int G, int d, int b,
                       SweepPoints pts, double* down);
+// swarm_api.hip: what the eight sgp_swarm_fitness* / sgp_swarm_run* entry points hand to the
+// one fitness routine and the one run routine.
+struct SwarmSpec {             // what the fitness is
+  sgp_gp* const* gps;
+  int G;
+  int swarm_type;              // SGP_SWARM_*, or kSwarmThompson with a path
+  double beta;
+  const double* fmin;          // [G]
+  const double* scaling;       // [G]
+  double best_lower_bound;
+  const SwarmPath* path;       // a Thompson swarm: the STAGED path; null otherwise
+  sgp_gp* const* clones;       // a hallucinated swarm: [G]; null otherwise
+};
+struct SwarmState {            // the caller's arrays (host), rows [p0, p0 + P) of a swarm of Pt
+  double *positions, *velocities, *best_positions, *best_values, *global_best;
+  const double *velocity_scale, *bounds;   // bounds may be null
+  int64_t P, p0, Pt;
+};
+struct PsoSchedule {
+  int init, iters;
+  double inertia0, step_size;
+  const double* rand;          // null: the device generator with `seed`
+  uint64_t seed;
+};
 // api.hip: the context's collectives on DEVICE operands -- RCCL in stream, or the host
 // transport of sgp_comm_init_host (sgp_grid_paths_comm merges its records behind one)
 // (defined inside api.hip's extern "C" block)
@@ -691,6 +719,132 @@ inline GrowBufs grow_bufs(char* base, const GrowLayout& l) {
 }
 int launch_swarm_grow(sgp_ctx* ctx, const KernDesc& kd, const double* S, int64_t m,
                       const double* B, int n, double scale2, double thr, const GrowBufs& gb);
+// The block of a swarm fitness call in kSlotWork (swarm_fitness, swarm_api.hip), P particles
+// of d columns against G GPs:
+//   pts[d][P] f64 | values[P] f64 | gpdev[SGP_MAX_GPS] | safe[P] u8 (padded to 8 B) |
+//   with clones: clones[SGP_MAX_GPS] | down[G][P] f64 | var_h[G][P] f64
+// and 64 bytes of slack behind the last region.
+static_assert(sizeof(GpDev) % 8 == 0, "GpDev arrays keep what follows them 8-byte aligned");
+struct SwarmFitLayout {
+  size_t pts, values, gpdev, safe, clones, down, var_h, bytes;
+};
+struct SwarmFitBufs {
+  double *pts, *values;
+  GpDev* gpdev;
+  uint8_t* safe;
+  GpDev* clones;
+  double *down, *var_h;
+};
+constexpr SwarmFitLayout swarm_fit_layout(int64_t P, int d, int G, bool clones) {
+  const size_t nv = size_t(P) * 8, gd = sizeof(GpDev) * SGP_MAX_GPS;
+  const size_t hall = clones ? size_t(G) * nv : 0;
+  SwarmFitLayout l{};
+  l.pts = 0;
+  l.values = l.pts + nv * d;
+  l.gpdev = l.values + nv;
+  l.safe = l.gpdev + gd;
+  l.clones = l.safe + (size_t(P) + 7) / 8 * 8;
+  l.down = l.clones + (clones ? gd : 0);
+  l.var_h = l.down + hall;
+  l.bytes = l.var_h + hall + 64;
+  return l;
+}
+inline SwarmFitBufs swarm_fit_bufs(char* base, const SwarmFitLayout& l) {
+  return SwarmFitBufs{reinterpret_cast<double*>(base + l.pts),
+                      reinterpret_cast<double*>(base + l.values),
+                      reinterpret_cast<GpDev*>(base + l.gpdev),
+                      reinterpret_cast<uint8_t*>(base + l.safe),
+                      reinterpret_cast<GpDev*>(base + l.clones),
+                      reinterpret_cast<double*>(base + l.down),
+                      reinterpret_cast<double*>(base + l.var_h)};
+}
+// The block of a swarm run in kSlotWork (swarm_run, swarm_api.hip), the rank's P particles;
+// world: the ranks of a sharded run, 0 for a whole swarm:
+//   pos | vel | best [P][d] f64 each | best_values | values [P] f64 each |
+//   gbest[d] | vscale[d] | bounds[2 d] | gpdev[SGP_MAX_GPS] |
+//   sharded: this rank's record, then the gathered ones (value | index | x[d] each) |
+//   safe[P] u8 | 64 bytes of slack |
+//   with clones, from the next multiple of 64 bytes: clones[SGP_MAX_GPS] | down[G][P] f64
+struct SwarmRunLayout {
+  size_t pos, vel, best, best_values, values, gbest, vscale, bounds, gpdev, rec, recs, safe,
+      clones, down, bytes;
+};
+struct SwarmRunBufs {
+  double *pos, *vel, *best, *best_values, *values, *gbest, *vscale, *bounds;
+  GpDev* gpdev;
+  double *rec, *recs;
+  uint8_t* safe;
+  GpDev* clones;
+  double* down;
+};
+constexpr size_t swarm_rec_bytes(int d) { return size_t(2 + d) * 8; }
+constexpr SwarmRunLayout swarm_run_layout(int64_t P, int d, int G, int world, bool clones) {
+  const size_t nd = size_t(P) * d * 8, nv = size_t(P) * 8, dd = size_t(d) * 8;
+  const size_t gd = sizeof(GpDev) * SGP_MAX_GPS, nrec = swarm_rec_bytes(d);
+  SwarmRunLayout l{};
+  l.pos = 0;
+  l.vel = l.pos + nd;
+  l.best = l.vel + nd;
+  l.best_values = l.best + nd;
+  l.values = l.best_values + nv;
+  l.gbest = l.values + nv;
+  l.vscale = l.gbest + dd;
+  l.bounds = l.vscale + dd;
+  l.gpdev = l.bounds + 2 * dd;
+  l.rec = l.gpdev + gd;
+  l.recs = l.rec + (world ? nrec : 0);
+  l.safe = l.recs + size_t(world) * nrec;
+  const size_t plain = l.safe + size_t(P) + 64;
+  l.clones = (plain + 63) / 64 * 64;
+  l.down = l.clones + gd;
+  l.bytes = clones ? l.down + size_t(G) * nv : plain;
+  return l;
+}
+inline SwarmRunBufs swarm_run_bufs(char* base, const SwarmRunLayout& l) {
+  auto f64 = [base](size_t off) { return reinterpret_cast<double*>(base + off); };
+  return SwarmRunBufs{f64(l.pos), f64(l.vel), f64(l.best), f64(l.best_values), f64(l.values),
+                      f64(l.gbest), f64(l.vscale), f64(l.bounds),
+                      reinterpret_cast<GpDev*>(base + l.gpdev), f64(l.rec), f64(l.recs),
+                      reinterpret_cast<uint8_t*>(base + l.safe),
+                      reinterpret_cast<GpDev*>(base + l.clones), f64(l.down)};
+}
+// Every f64 / GpDev region of the two layouts starts on an 8-byte boundary, a region ends
+// where the next one starts or in front of it, the last one inside `bytes`.
+constexpr bool swarm_fit_layout_ok(int64_t P, int d, int G, bool clones) {
+  const SwarmFitLayout l = swarm_fit_layout(P, d, G, clones);
+  const size_t nv = size_t(P) * 8, gd = sizeof(GpDev) * SGP_MAX_GPS, np = size_t(P);
+  const size_t at[] = {l.pts, l.values, l.gpdev, l.safe, l.clones, l.down, l.var_h, l.bytes};
+  const size_t len[] = {nv * d, nv, gd, np, gd, size_t(G) * nv, size_t(G) * nv};
+  const int n = clones ? 7 : 4;
+  for (int i = 0; i < n; ++i) {
+    if (i != 3 && at[i] % 8 != 0) return false;            // (3: safe, bytes)
+    if (at[i] + len[i] > (i + 1 < n ? at[i + 1] : l.bytes)) return false;
+  }
+  return true;
+}
+constexpr bool swarm_run_layout_ok(int64_t P, int d, int G, int world, bool clones) {
+  const SwarmRunLayout l = swarm_run_layout(P, d, G, world, clones);
+  const size_t nd = size_t(P) * d * 8, nv = size_t(P) * 8, dd = size_t(d) * 8;
+  const size_t gd = sizeof(GpDev) * SGP_MAX_GPS, nrec = swarm_rec_bytes(d);
+  const size_t at[] = {l.pos, l.vel, l.best, l.best_values, l.values, l.gbest, l.vscale,
+                       l.bounds, l.gpdev, l.rec, l.recs, l.safe, l.clones, l.down};
+  const size_t len[] = {nd, nd, nd, nv, nv, dd, dd, 2 * dd, gd, world ? nrec : 0,
+                        size_t(world) * nrec, size_t(P), gd, size_t(G) * nv};
+  const int n = clones ? 14 : 12;
+  for (int i = 0; i < n; ++i) {
+    if (i != 11 && at[i] % 8 != 0) return false;           // (11: safe, bytes)
+    if (at[i] + len[i] > (i + 1 < n ? at[i + 1] : l.bytes)) return false;
+  }
+  return !clones || l.clones % 64 == 0;
+}
+static_assert(swarm_fit_layout_ok(1, 1, 1, false) && swarm_fit_layout_ok(1, 1, 1, true) &&
+                  swarm_fit_layout_ok(65, 3, SGP_MAX_GPS, true) &&
+                  swarm_fit_layout_ok(33, 3, 2, false),
+              "SwarmFitLayout: a region is misaligned or overlaps its neighbour");
+static_assert(swarm_run_layout_ok(1, 1, 1, 0, false) && swarm_run_layout_ok(1, 1, 1, 0, true) &&
+                  swarm_run_layout_ok(65, 3, SGP_MAX_GPS, 0, true) &&
+                  swarm_run_layout_ok(33, 3, 2, 4, false),
+              "SwarmRunLayout: a region is misaligned or overlaps its neighbour");
 // The swarm kernels take the rank's block of particles [p0, p0 + P) of a swarm of P_total:
 // e0 / e2 are the global element indices of the block's first r1 / r2 number on the
 // device generator (0 / P d for a whole swarm).

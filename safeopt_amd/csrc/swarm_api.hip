@@ -1,0 +1,470 @@
+// The swarm entry points of the C ABI (include/safeopt_hip.h): host-side launch sequences
+// around the kernels of swarm.hip, paths.hip, swarm_batch.hip and the posterior sweeps.
+// Eight exported fitness / run functions fill SwarmSpec / SwarmState / PsoSchedule
+// (common.h) and share ONE fitness routine and ONE run routine.
+#include <string.h>
+
+#include <cmath>
+
+#include "common.h"
+#include "small_path.h"
+
+// Fitness of P <= kSmallPoints particles (row-major, device) through the
+// small-point posterior path: mean / var per GP, then the shaping kernel.
+static int fitness_small(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_host,
+                         int G, const double* pts_rowmajor, int64_t P,
+                         const FitnessArgs& fa) {
+  const int Geff = (fa.swarm_type == SGP_SWARM_GREEDY) ? 1 : G;
+  double* mv;
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, size_t(2) * SGP_MAX_GPS * kSmallPoints * sizeof(double),
+                      &mv));
+  SmallBufs sb;
+  SGP_TRY(small_reserve(ctx, gps_host, Geff, int(P), &sb));
+  double* mean = mv;
+  double* var = mv + size_t(SGP_MAX_GPS) * kSmallPoints;
+  SGP_TRY(posterior_small_all(ctx, gps_dev, gps_host, Geff, pts_rowmajor, int(P), sb,
+                              mean, var));
+  return launch_fitness_small(ctx, G, P, mean, var, fa);
+}
+
+static bool small_path_pays_all(sgp_gp* const* gps, int G, int64_t P) {
+  for (int g = 0; g < G; ++g)
+    if (!small_path_pays(gps[g], P)) return false;
+  return true;
+}
+
+// The clones of a hallucinated swarm (sgp_swarm_fitness_hall / sgp_swarm_run_hall) against
+// the GPs they were cloned from: maximizers or expanders, every clone in the call's context
+// with the source's input dimension and kernel and gps[g].n + b observations for ONE b in
+// 1 .. SGP_MAX_BATCH.  host: their descriptors, `share` as collect_gps sets it.
+static int hall_clones(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                       int swarm_type, GpDev* host, int* b_out) {
+  SGP_CHECK(ctx, swarm_type == SGP_SWARM_MAXIMIZERS || swarm_type == SGP_SWARM_EXPANDERS,
+            "a hallucinated swarm is a maximizers or an expanders swarm, not type %d",
+            swarm_type);
+  SGP_CHECK(ctx, G >= 1 && G <= SGP_MAX_GPS && gps[0], "no GP");
+  SGP_CHECK(ctx, clones != nullptr, "no clones");
+  for (int g = 0; g < G; ++g) {
+    SGP_CHECK(ctx, gps[g] && clones[g], "GP %d or its clone is missing", g);
+    SGP_CHECK(ctx, gps[g]->ctx == ctx && clones[g]->ctx == ctx,
+              "GP %d or its clone lives in another context than the call (device %d)", g,
+              ctx->device);
+    SGP_CHECK(ctx, clones[g]->kern.d == gps[g]->kern.d &&
+                       memcmp(&clones[g]->kern, &gps[g]->kern, sizeof(KernDesc)) == 0,
+              "clone %d has another input dimension or kernel than its GP", g);
+  }
+  const int64_t b = clones[0]->n - gps[0]->n;
+  SGP_CHECK(ctx, b >= 1 && b <= SGP_MAX_BATCH,
+            "clone 0 holds %lld observations, its GP %lld: 1 .. %d pending picks",
+            (long long)clones[0]->n, (long long)gps[0]->n, SGP_MAX_BATCH);
+  for (int g = 1; g < G; ++g)
+    SGP_CHECK(ctx, clones[g]->n == gps[g]->n + b,
+              "clone %d holds %lld observations, its GP %lld: not the %lld pending picks of "
+              "clone 0", g, (long long)clones[g]->n, (long long)gps[g]->n, (long long)b);
+  SGP_TRY(collect_gps(ctx, clones, G, gps[0]->kern.d, host));
+  *b_out = int(b);
+  return 0;
+}
+
+// type, beta, best lower bound, and fmin / scaling padded to SGP_MAX_GPS
+static FitnessArgs make_fitness_args(const SwarmSpec& s) {
+  FitnessArgs fa{};
+  fa.swarm_type = s.swarm_type;
+  fa.beta = s.beta;
+  fa.best_lower_bound = s.best_lower_bound;
+  for (int i = 0; i < SGP_MAX_GPS; ++i) {
+    fa.fmin[i] = (i < s.G) ? s.fmin[i] : -INFINITY;
+    fa.scaling[i] = (i < s.G) ? s.scaling[i] : 1.0;
+  }
+  return fa;
+}
+
+// The checks a Thompson entry point makes in front of its early return; behind that
+// return it stages the path (swarm_path_stage: ONCE per call; neither routine below asks
+// for the two slots the path lives in)
+static int path_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, int m) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
+  SGP_CHECK(ctx, gps[0]->ctx == ctx, "GP 0 lives in another context (device %d) than the "
+            "call (device %d)", gps[0]->ctx ? gps[0]->ctx->device : -1, ctx->device);
+  return swarm_path_ready(gps[0], m);
+}
+
+// The order of the argument checks, per entry point, that the two routines keep ("type":
+// "Invalid swarm type"; "clones": the checks of hall_clones, its collect_gps of the clones
+// last; "path": GP 0's context, then swarm_path_ready; "GPs": collect_gps of the GPs):
+//   sgp_swarm_fitness       type, "no GP", return 0 if P <= 0, GPs
+//   sgp_swarm_fitness_hall  "no clones", type, "no GP", clones, return 0 if P <= 0, GPs
+//   sgp_swarm_fitness_path  "no GP", path, return 0 if P <= 0, GPs
+//   sgp_swarm_run[_shard]   type, "no GP", "bad swarm size", "bad block", "needs a
+//                           communicator", GPs
+//   sgp_swarm_run_hall      "no clones"; P <= 0: clones, return; else type, "no GP", "bad
+//                           swarm size" (iterations), "bad block", communicator, clones, GPs
+//   sgp_swarm_run_path[_shard]  "no GP", path, return 0 if P <= 0 and P_total <= 0, then as
+//                           sgp_swarm_run_shard (an empty block of a sharded swarm is the
+//                           "bad swarm size" error, not a silent return: the other ranks
+//                           would wait in the all-gather)
+// A Thompson call passes "type" and the second "no GP" by construction.
+
+// All three fitness entry points: import the points, the real posterior and the shaping
+// pass (few-points path or sweep), with clones the downdate (launch_swarm_down) in front of
+// the shaping, with a path the path term (launch_swarm_path) behind it.
+static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particles, int64_t P,
+                         double* values, uint8_t* safe, double* var_h) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, s.path ? s.swarm_type == kSwarmThompson
+                        : s.swarm_type >= SGP_SWARM_GREEDY && s.swarm_type <= SGP_SWARM_SAFE_SET,
+            "Invalid swarm type %d", s.swarm_type);
+  SGP_CHECK(ctx, s.G >= 1 && s.gps[0], "no GP");
+  const int G = s.G;
+  GpDev host[SGP_MAX_GPS], chost[SGP_MAX_GPS];
+  int b = 0;
+  if (s.clones) SGP_TRY(hall_clones(ctx, s.gps, s.clones, G, s.swarm_type, chost, &b));
+  if (P <= 0) return 0;
+  const int d = s.gps[0]->kern.d;
+  SGP_TRY(collect_gps(ctx, s.gps, G, d, host));
+  const size_t nv = size_t(P) * 8;
+  const SwarmFitLayout l = swarm_fit_layout(P, d, G, s.clones != nullptr);   // (common.h)
+  double* stage;
+  char* work;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, nv * d, &stage));
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, l.bytes, &work));
+  const SwarmFitBufs fb = swarm_fit_bufs(work, l);
+  SGP_TRY(sgp_h2d(ctx, stage, particles, nv * d));
+  SGP_TRY(launch_import_points(ctx, stage, P, d, d, 1, fb.pts));
+  SGP_TRY(sgp_h2d(ctx, fb.gpdev, host, sizeof(GpDev) * G));
+  FitnessArgs fa = make_fitness_args(s);
+  fa.values = fb.values;
+  fa.safe = fb.safe;
+  const SweepPoints sp{fb.pts, P, 1, P};
+  if (s.clones) {
+    SGP_TRY(sgp_h2d(ctx, fb.clones, chost, sizeof(GpDev) * G));
+    SGP_TRY(launch_swarm_down(ctx, fb.clones, G, d, b, sp, fb.down));
+    fa.down = fb.down;
+    fa.var_h = var_h ? fb.var_h : nullptr;
+  }
+  if (small_path_pays_all(s.gps, G, P)) {
+    SGP_TRY(fitness_small(ctx, fb.gpdev, host, G, stage, P, fa));
+  } else {
+    SGP_TRY(launch_sweep_fitness(ctx, fb.gpdev, host, G, d, sp, fa));
+  }
+  // (kSwarmThompson in fitness.h leaves the penalty in the values: the path term on top)
+  if (s.path)
+    SGP_TRY(launch_swarm_path(ctx, fb.gpdev, d, *s.path, sp, fa.scaling[0], fb.values));
+  SGP_TRY(sgp_d2h(ctx, values, fb.values, nv));
+  SGP_TRY(sgp_d2h(ctx, safe, fb.safe, size_t(P)));
+  if (s.clones && var_h) SGP_TRY(sgp_d2h(ctx, var_h, fb.var_h, size_t(G) * nv));
+  return 0;
+}
+
+// SwarmOptimization.init_swarm / run_swarm (swarm.py:61-146) with the state in
+// HBM and the fitness fused in: one call = the whole run, one host round trip.
+// The particles [p0, p0 + P) of a swarm of Pt; P < Pt: a rank's block of a sharded
+// swarm -- the global best goes through the record all-gather.
+// s.path: a Thompson swarm, s.clones: a hallucinated swarm (the downdate in front of every
+// shaping pass); both always take the general launches below.
+static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
+                     const PsoSchedule& sch) {
+  const int G = s.G, init = sch.init, iters = sch.iters;
+  const int64_t P = st.P, p0 = st.p0, Pt = st.Pt;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, s.path ? s.swarm_type == kSwarmThompson
+                        : s.swarm_type >= SGP_SWARM_GREEDY && s.swarm_type <= SGP_SWARM_SAFE_SET,
+            "Invalid swarm type %d", s.swarm_type);
+  SGP_CHECK(ctx, G >= 1 && s.gps[0], "no GP");
+  SGP_CHECK(ctx, P >= 1 && iters >= 0, "bad swarm size %lld / iterations %d",
+            (long long)P, iters);
+  SGP_CHECK(ctx, p0 >= 0 && p0 + P <= Pt, "bad block [%lld, %lld) of a swarm of %lld",
+            (long long)p0, (long long)(p0 + P), (long long)Pt);
+  const bool shard = P < Pt;
+  bool comm;
+  SGP_TRY(comm_or_single(ctx, &comm));   // (several ranks always come with a communicator)
+  SGP_CHECK(ctx, comm || !shard,
+            "a block of %lld of a swarm of %lld particles needs a communicator in the "
+            "context (sgp_comm_init / sgp_comm_init_host)", (long long)P, (long long)Pt);
+  const int world = comm ? ctx->world : 1;
+  const int d = s.gps[0]->kern.d;
+  GpDev host[SGP_MAX_GPS], chost[SGP_MAX_GPS];
+  int hall_b = 0;
+  if (s.clones) SGP_TRY(hall_clones(ctx, s.gps, s.clones, G, s.swarm_type, chost, &hall_b));
+  SGP_TRY(collect_gps(ctx, s.gps, G, d, host));
+  const size_t nd = size_t(P) * d * 8, nv = size_t(P) * 8;
+  const size_t nrand = sch.rand ? (size_t(init ? 1 : 0) + 2 * size_t(iters)) * nd : 0;
+  const SwarmRunLayout l =
+      swarm_run_layout(P, d, G, shard ? world : 0, s.clones != nullptr);   // (common.h)
+  char* buf;
+  double* drand = nullptr;
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, l.bytes, &buf));
+  if (sch.rand) SGP_TRY(sgp_scratch(ctx, kSlotStage, nrand, &drand));
+  const SwarmRunBufs rb = swarm_run_bufs(buf, l);
+  const double* dbounds = st.bounds ? rb.bounds : nullptr;
+  SGP_TRY(sgp_h2d(ctx, rb.pos, st.positions, nd));
+  if (!init) {
+    SGP_TRY(sgp_h2d(ctx, rb.vel, st.velocities, nd));
+    SGP_TRY(sgp_h2d(ctx, rb.best, st.best_positions, nd));
+    SGP_TRY(sgp_h2d(ctx, rb.best_values, st.best_values, nv));
+    SGP_TRY(sgp_h2d(ctx, rb.gbest, st.global_best, size_t(d) * 8));
+  }
+  SGP_TRY(sgp_h2d(ctx, rb.vscale, st.velocity_scale, size_t(d) * 8));
+  if (st.bounds) SGP_TRY(sgp_h2d(ctx, rb.bounds, st.bounds, size_t(d) * 16));
+  if (sch.rand) SGP_TRY(sgp_h2d(ctx, drand, sch.rand, nrand));
+  SGP_TRY(sgp_h2d(ctx, rb.gpdev, host, sizeof(GpDev) * G));
+  if (s.clones) SGP_TRY(sgp_h2d(ctx, rb.clones, chost, sizeof(GpDev) * G));
+  FitnessArgs fa = make_fitness_args(s);
+  fa.values = rb.values;
+  fa.safe = rb.safe;
+  if (s.clones) fa.down = rb.down;
+  const SweepPoints sp{rb.pos, P, d, 1};          // row-major (P, d) in place
+  // (the paths and the posterior kernel follow the whole swarm: same bits on every rank)
+  const bool few = Pt <= kSmallSwarm && small_path_pays_all(s.gps, G, Pt);
+  // a small swarm against GPs with few observations (SafeOptSwarm's defaults on the
+  // reference's own examples: 20 particles, n <= 20): the posterior is one sweep launch
+  // (sweep_tiny.hip up to 48 observations), everything else of the iteration the same ONE
+  // workgroup as on the few-points path -- two launches per iteration instead of five
+  const bool few_swept = Pt <= kSmallSwarm && !few;
+  const double* r = drand;
+  double inertia = sch.inertia0;
+  if ((few || few_swept) && !shard && !s.path && !s.clones) {
+    // small swarm: three launches per iteration -- k(X, particles), the block
+    // products on the matrix cores, and ONE workgroup for everything else
+    // (fitness, bests, and the move that opens the next iteration)
+    const int Geff = (s.swarm_type == SGP_SWARM_GREEDY) ? 1 : G;
+    SmallBufs sb{};
+    ConfOut post{};
+    if (few) {
+      SGP_TRY(small_reserve(ctx, host, Geff, int(P), &sb));
+    } else {
+      const size_t np = size_t(Geff) * size_t(P);
+      SGP_TRY(sgp_reserve(ctx, &ctx->pair_post, 2 * np * sizeof(double)));
+      post.mean = static_cast<double*>(ctx->pair_post.p);
+      post.var = post.mean + np;
+      for (int i = 0; i < SGP_MAX_GPS; ++i) post.fmin[i] = -INFINITY;
+    }
+    PsoSmallArgs ps{};
+    ps.pos = rb.pos;
+    ps.vel = rb.vel;
+    ps.best = rb.best;
+    ps.best_values = rb.best_values;
+    ps.gbest = rb.gbest;
+    ps.vscale = rb.vscale;
+    ps.bounds = dbounds;
+    ps.seed = sch.seed;
+    ps.P = int(P);
+    ps.d = d;
+    auto step = [&](int is_init, int it_next) -> int {   // it_next < 0: no move
+      if (few)
+        SGP_TRY(posterior_small_all(ctx, rb.gpdev, host, Geff, rb.pos, int(P), sb, nullptr,
+                                    nullptr));
+      else
+        SGP_TRY(launch_sweep_conf(ctx, rb.gpdev, host, Geff, d, sp, post));
+      ps.init = is_init;
+      ps.move = it_next >= 0;
+      ps.rand = r;
+      ps.draw = uint32_t(it_next + 1);
+      ps.inertia = inertia;
+      SGP_TRY(launch_pso_small_step(ctx, rb.gpdev, G, sb, fa, ps, few ? nullptr : post.mean,
+                                    few ? nullptr : post.var));
+      if (ps.move) {
+        if (r) r += 2 * size_t(P) * d;
+        inertia += sch.step_size;
+      }
+      return 0;
+    };
+    if (init) {
+      SGP_TRY(launch_pso_init_vel(ctx, P, d, rb.vel, rb.vscale, r, sch.seed));
+      if (r) r += size_t(P) * d;
+      SGP_TRY(step(1, iters > 0 ? 0 : -1));
+    } else if (iters > 0) {
+      SGP_TRY(launch_pso_move(ctx, P, d, rb.pos, rb.vel, rb.best, rb.gbest, rb.vscale, dbounds,
+                              inertia, r, sch.seed, 1u));
+      if (r) r += 2 * size_t(P) * d;
+      inertia += sch.step_size;
+    }
+    for (int it = 0; it < iters; ++it)
+      SGP_TRY(step(0, it + 1 < iters ? it + 1 : -1));
+  } else {
+    // (up to kSmallPoints particles still take the few-points posterior; a block of a
+    // small swarm takes these launches, the arithmetic of k_pso_small_step)
+    const bool few_points = small_path_pays_all(s.gps, G, Pt);
+    auto fitness = [&]() -> int {
+      // a hallucinated swarm: what the pending picks take off the variances, for the shaping
+      if (s.clones) SGP_TRY(launch_swarm_down(ctx, rb.clones, G, d, hall_b, sp, rb.down));
+      SGP_TRY(few_points ? fitness_small(ctx, rb.gpdev, host, G, rb.pos, P, fa)
+                         : launch_sweep_fitness(ctx, rb.gpdev, host, G, d, sp, fa, Pt));
+      // a Thompson swarm: the path term on top of the penalty the shaping left
+      return s.path ? launch_swarm_path(ctx, rb.gpdev, d, *s.path, sp, fa.scaling[0], rb.values)
+                    : 0;
+    };
+    // personal bests, then the global best: of the block, or merged over the ranks
+    auto bests = [&](int is_init) -> int {
+      if (!shard)
+        return launch_pso_best(ctx, P, d, rb.values, rb.safe, rb.pos, rb.best, rb.best_values,
+                               rb.gbest, is_init);
+      SGP_TRY(launch_pso_best(ctx, P, d, rb.values, rb.safe, rb.pos, rb.best, rb.best_values,
+                              rb.gbest, is_init, rb.rec, p0));
+      SGP_TRY(coll_allgather(ctx, rb.rec, rb.recs, swarm_rec_bytes(d)));
+      return launch_pso_gbest_merge(ctx, rb.recs, world, d, rb.gbest);
+    };
+    const int64_t e0 = p0 * d, e2 = Pt * d + p0 * d;
+    if (init) {
+      SGP_TRY(launch_pso_init_vel(ctx, P, d, rb.vel, rb.vscale, r, sch.seed, e0));
+      if (r) r += size_t(P) * d;
+      SGP_TRY(fitness());
+      SGP_TRY(bests(1));
+    }
+    for (int it = 0; it < iters; ++it) {
+      SGP_TRY(launch_pso_move(ctx, P, d, rb.pos, rb.vel, rb.best, rb.gbest, rb.vscale, dbounds,
+                              inertia, r, sch.seed, uint32_t(it + 1), e0, e2));
+      if (r) r += 2 * size_t(P) * d;
+      inertia += sch.step_size;
+      SGP_TRY(fitness());
+      SGP_TRY(bests(0));
+    }
+  }
+  SGP_TRY(sgp_d2h(ctx, st.positions, rb.pos, nd));
+  SGP_TRY(sgp_d2h(ctx, st.velocities, rb.vel, nd));
+  SGP_TRY(sgp_d2h(ctx, st.best_positions, rb.best, nd));
+  SGP_TRY(sgp_d2h(ctx, st.best_values, rb.best_values, nv));
+  return sgp_d2h(ctx, st.global_best, rb.gbest, size_t(d) * 8);
+}
+
+// A Thompson run: check, stage the path, run
+static int swarm_run_path(sgp_ctx* ctx, SwarmSpec s, const SwarmState& st,
+                          const PsoSchedule& sch, const double* const pin[4], int m) {
+  SGP_TRY(path_checks(ctx, s.gps, s.G, m));
+  if (st.P <= 0 && st.Pt <= 0) return 0;
+  SwarmPath path;
+  SGP_TRY(swarm_path_stage(s.gps[0], pin[0], pin[1], m, pin[2], pin[3], &path));
+  s.path = &path;
+  return swarm_run(ctx, s, st, sch);
+}
+
+extern "C" {
+
+int sgp_swarm_fitness(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                      const double* particles, int64_t P, double beta,
+                      const double* fmin, const double* scaling,
+                      double best_lower_bound, double* values, uint8_t* safe) {
+  const SwarmSpec s{gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, nullptr, nullptr};
+  return swarm_fitness(ctx, s, particles, P, values, safe, nullptr);
+}
+
+int sgp_swarm_fitness_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                           int swarm_type, const double* particles, int64_t P, double beta,
+                           const double* fmin, const double* scaling, double best_lower_bound,
+                           double* values, uint8_t* safe, double* var_h) {
+  SGP_CHECK(ctx, clones != nullptr, "no clones");
+  const SwarmSpec s{gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, nullptr, clones};
+  return swarm_fitness(ctx, s, particles, P, values, safe, var_h);
+}
+
+int sgp_swarm_fitness_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                           int64_t P, double beta, const double* fmin, const double* scaling,
+                           const double* Omega, const double* phase, int m, const double* w,
+                           const double* v, double* values, uint8_t* safe) {
+  SGP_TRY(path_checks(ctx, gps, G, m));
+  if (P <= 0) return 0;
+  SwarmPath path;
+  SGP_TRY(swarm_path_stage(gps[0], Omega, phase, m, w, v, &path));
+  const SwarmSpec s{gps, G, kSwarmThompson, beta, fmin, scaling, 0.0, &path, nullptr};
+  return swarm_fitness(ctx, s, particles, P, values, safe, nullptr);
+}
+
+int sgp_swarm_run(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                  double beta, const double* fmin, const double* scaling,
+                  double best_lower_bound, int64_t P, double* positions,
+                  double* velocities, double* best_positions, double* best_values,
+                  double* global_best, const double* velocity_scale,
+                  const double* bounds, int init, int iters, double inertia0,
+                  double step_size, const double* rand, uint64_t seed) {
+  return sgp_swarm_run_shard(ctx, gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, P,
+                             positions, velocities, best_positions, best_values, global_best,
+                             velocity_scale, bounds, init, iters, inertia0, step_size, rand,
+                             seed, 0, P);
+}
+
+int sgp_swarm_run_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, int swarm_type,
+                        double beta, const double* fmin, const double* scaling,
+                        double best_lower_bound, int64_t P, double* positions,
+                        double* velocities, double* best_positions, double* best_values,
+                        double* global_best, const double* velocity_scale,
+                        const double* bounds, int init, int iters, double inertia0,
+                        double step_size, const double* rand, uint64_t seed, int64_t p0,
+                        int64_t P_total) {
+  const SwarmSpec s{gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, nullptr, nullptr};
+  const SwarmState st{positions, velocities, best_positions, best_values, global_best,
+                      velocity_scale, bounds, P, p0, P_total};
+  return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});
+}
+
+int sgp_swarm_run_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                       int swarm_type, double beta, const double* fmin, const double* scaling,
+                       double best_lower_bound, int64_t P, double* positions,
+                       double* velocities, double* best_positions, double* best_values,
+                       double* global_best, const double* velocity_scale,
+                       const double* bounds, int init, int iters, double inertia0,
+                       double step_size, const double* rand, uint64_t seed) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, clones != nullptr, "no clones");
+  if (P <= 0) {
+    GpDev chost[SGP_MAX_GPS];
+    int b;
+    return hall_clones(ctx, gps, clones, G, swarm_type, chost, &b);
+  }
+  const SwarmSpec s{gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, nullptr, clones};
+  const SwarmState st{positions, velocities, best_positions, best_values, global_best,
+                      velocity_scale, bounds, P, 0, P};
+  return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});
+}
+
+int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                       const double* fmin, const double* scaling, int64_t P, double* positions,
+                       double* velocities, double* best_positions, double* best_values,
+                       double* global_best, const double* velocity_scale,
+                       const double* bounds, int init, int iters, double inertia0,
+                       double step_size, const double* rand, uint64_t seed,
+                       const double* Omega, const double* phase, int m, const double* w,
+                       const double* v) {
+  return sgp_swarm_run_path_shard(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
+                                  best_positions, best_values, global_best, velocity_scale,
+                                  bounds, init, iters, inertia0, step_size, rand, seed, Omega,
+                                  phase, m, w, v, 0, P);
+}
+
+int sgp_swarm_run_path_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                             const double* fmin, const double* scaling, int64_t P,
+                             double* positions, double* velocities, double* best_positions,
+                             double* best_values, double* global_best,
+                             const double* velocity_scale, const double* bounds, int init,
+                             int iters, double inertia0, double step_size, const double* rand,
+                             uint64_t seed, const double* Omega, const double* phase, int m,
+                             const double* w, const double* v, int64_t p0, int64_t P_total) {
+  const SwarmSpec s{gps, G, kSwarmThompson, beta, fmin, scaling, 0.0, nullptr, nullptr};
+  const SwarmState st{positions, velocities, best_positions, best_values, global_best,
+                      velocity_scale, bounds, P, p0, P_total};
+  const double* const pin[4] = {Omega, phase, w, v};
+  return swarm_run_path(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed},
+                        pin, m);
+}
+
+// SafeOptSwarm safe-set growth, gp_opt.py:1089-1111 (kernels in swarm.hip).
+int sgp_swarm_grow(sgp_ctx* ctx, sgp_gp* gp0, const double* S, int64_t m,
+                   const double* B, int64_t n, double scale2, double thr,
+                   uint8_t* accept) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, gp0 != nullptr, "no GP");
+  SGP_CHECK(ctx, m >= 0 && n >= 0 && n <= INT32_MAX, "bad sizes m=%lld n=%lld",
+            (long long)m, (long long)n);
+  if (n == 0) return 0;
+  const int d = gp0->kern.d;
+  const GrowLayout l = grow_layout(m, n, d);          // (common.h)
+  char* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotWork, l.bytes + 64, &buf));
+  const GrowBufs gb = grow_bufs(buf, l);
+  SGP_TRY(sgp_h2d(ctx, gb.S, S, size_t(m) * d * 8));
+  SGP_TRY(sgp_h2d(ctx, gb.B, B, size_t(n) * d * 8));
+  SGP_TRY(launch_swarm_grow(ctx, gp0->kern, gb.S, m, gb.B, int(n), scale2, thr, gb));
+  return sgp_d2h(ctx, accept, gb.accept, size_t(n));
+}
+
+}  // extern "C"

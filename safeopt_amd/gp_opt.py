@@ -1676,24 +1676,24 @@ class SafeOptSwarm(GaussianProcessOptimization):
         ``'greedy' | 'maximizers' | 'expanders' | 'safe_set'``."""
         if swarm_type not in _hip.SWARM_TYPES:
             raise AssertionError("Invalid swarm type")
+        return self._swarm_fitness(swarm_type, particles)
+
+    def _swarm_fitness(self, swarm_type, particles, **variant):
+        """What the three fitness callbacks share: the current ``beta``, the fitted device
+        GPs and this optimiser's ``fmin`` / ``scaling`` / best lower bound; ``variant``:
+        ``path=`` or ``clones=`` of ``_hip._swarm_fitness``."""
         beta = self.beta(self.t)
-        particles = np.atleast_2d(particles)
         devs = [g._fitted() for g in self.gps]
-        values, safe = _hip.swarm_fitness(
-            devs[0].ctx, devs, swarm_type, particles, beta, self.fmin,
-            self.scaling, self.best_lower_bound)
-        return values, safe
+        return _hip._swarm_fitness(devs[0].ctx, devs, swarm_type, np.atleast_2d(particles),
+                                   (beta, self.fmin, self.scaling, self.best_lower_bound),
+                                   **variant)
 
     def _compute_path_fitness(self, path, particles):
         """Fitness and safety of ``particles`` for a Thompson swarm on the sample path
         ``path = (Omega, phase, w, v)`` of the objective GP: ``values = f(x) / scaling[0] +``
         the maximizers' penalty, ``safe`` the maximizers' safety flag
         (``sgp_swarm_fitness_path``).  The fitness callback of the host loop."""
-        beta = self.beta(self.t)
-        particles = np.atleast_2d(particles)
-        devs = [g._fitted() for g in self.gps]
-        return _hip.swarm_fitness_path(devs[0].ctx, devs, particles, beta, self.fmin,
-                                       self.scaling, path)
+        return self._swarm_fitness(None, particles, path=path)
 
     def _compute_hall_fitness(self, swarm_type, clones, particles):
         """Fitness and safety of ``particles`` for a hallucinated ``'maximizers'`` or
@@ -1701,11 +1701,28 @@ class SafeOptSwarm(GaussianProcessOptimization):
         clones with the pending picks appended), everything else -- bounds, interest, penalty,
         ``safe`` -- from the real GPs (``sgp_swarm_fitness_hall``).  The fitness callback of
         the host loop."""
-        beta = self.beta(self.t)
-        particles = np.atleast_2d(particles)
-        devs = [g._fitted() for g in self.gps]
-        return _hip.swarm_fitness_hall(devs[0].ctx, devs, clones, swarm_type, particles, beta,
-                                       self.fmin, self.scaling, self.best_lower_bound)
+        return self._swarm_fitness(swarm_type, particles, clones=clones)
+
+    def _side_swarm_pick(self, swarm, configure, fitness, iters, empty_ok=False):
+        """One side swarm of ``optimize_batch`` / ``thompson_points`` and its pick ``(x,
+        index)``: ``swarm_size`` draws of ``S`` as start positions (one ``randint``), then the
+        device swarm ``swarm`` after ``configure(swarm)`` -- or, ``swarm is None``
+        (``pso='host'``), a reference loop over the callback ``fitness`` -- runs ``iters``
+        iterations; the pick is ``thompson_pick`` among the personal bests that are safe under
+        one real ``'safe_set'`` fitness call.  None is safe: ``RuntimeError``, or ``None``
+        with ``empty_ok``."""
+        picks = np.random.randint(self.S.shape[0], size=self.swarm_size)
+        if swarm is None:
+            swarm = SwarmOptimization(self.swarm_size, self.optimal_velocities, fitness,
+                                      bounds=self.bounds)
+        else:
+            configure(swarm)
+        swarm.init_swarm(self.S[picks, :])
+        swarm.run_swarm(iters)
+        _, safe = self._compute_particle_fitness('safe_set', swarm.best_positions)
+        if empty_ok and not np.any(safe):
+            return None
+        return thompson_pick(swarm.best_positions, swarm.best_values, safe)
 
     def optimize_batch(self, size=8, ucb=False, max_iters=None, return_state=False):
         """``k <= size`` query points from SafeOptSwarm's own rule for experiments that run
@@ -1779,21 +1796,12 @@ class SafeOptSwarm(GaussianProcessOptimization):
                 rng=self.swarms['maximizers']._rng) for t in types}
 
         def candidate(swarm_type, clones):
-            picks = np.random.randint(self.S.shape[0], size=self.swarm_size)
-            if swarms:
-                run = swarms[swarm_type]
-                run.set_clones(clones)
-            else:
-                run = SwarmOptimization(
-                    self.swarm_size, self.optimal_velocities,
-                    partial(self._compute_hall_fitness, swarm_type, clones),
-                    bounds=self.bounds)
-            run.init_swarm(self.S[picks, :])
-            run.run_swarm(iters)
-            _, safe = self._compute_particle_fitness('safe_set', run.best_positions)
-            if not np.any(safe):
+            pick = self._side_swarm_pick(
+                swarms.get(swarm_type), lambda run: run.set_clones(clones),
+                partial(self._compute_hall_fitness, swarm_type, clones), iters, empty_ok=True)
+            if pick is None:
                 return None
-            x, _ = thompson_pick(run.best_positions, run.best_values, safe)
+            x = pick[0]
             return x, np.sqrt([c.predict(x[None, :])[1].item() for c in clones])
 
         def next_pick(clones):
@@ -1879,18 +1887,9 @@ class SafeOptSwarm(GaussianProcessOptimization):
         for s in range(size):
             path = (pp.Omega, pp.phase, np.ascontiguousarray(pp.W[:, s]),
                     np.ascontiguousarray(pp.V[:, s]))
-            picks = np.random.randint(self.S.shape[0], size=self.swarm_size)
-            if swarm is None:
-                run = SwarmOptimization(self.swarm_size, self.optimal_velocities,
-                                        partial(self._compute_path_fitness, path),
-                                        bounds=self.bounds)
-            else:
-                run = swarm
-                run.set_path(path)
-            run.init_swarm(self.S[picks, :])
-            run.run_swarm(iters)
-            _, safe = self._compute_particle_fitness('safe_set', run.best_positions)
-            x[s], _ = thompson_pick(run.best_positions, run.best_values, safe)
+            x[s], _ = self._side_swarm_pick(
+                swarm, lambda run: run.set_path(path),
+                partial(self._compute_path_fitness, path), iters)
         values = np.array([pp.paths(x[s][None])[0, 0, s] for s in range(size)])
         return (x, values, pp) if return_paths else (x, values)
 

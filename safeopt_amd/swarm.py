@@ -221,69 +221,44 @@ class DeviceSwarmOptimization(SwarmOptimization):
         from . import _hip
         o = self._owner
         devs = [g._fitted() for g in o.gps]
-        P, d = self.positions.shape
-        rand = None
+        sharded = self._comm.world > 1
+        d = self.positions.shape[1]
+        P = self.swarm_size if sharded else self.positions.shape[0]
         self._calls += 1
         path = self._need_path() if self._type == 'thompson' else None
-        if self._comm.world == 1:
-            if self._rng == 'numpy':
-                rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
-            if path is not None:
-                _hip.swarm_run_path(
-                    devs[0].ctx, devs, o.beta(o.t), o.fmin, o.scaling, self.positions,
-                    self.velocities, self.best_positions, self.best_values, self.global_best,
-                    np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
-                    inertia0, step, rand, path, seed=(self._seed << 20) + self._calls)
-                return
-            if self._clones is not None:
-                _hip.swarm_run_hall(
-                    devs[0].ctx, devs, self._clones, self._type, o.beta(o.t), o.fmin,
-                    o.scaling, o.best_lower_bound, self.positions, self.velocities,
-                    self.best_positions, self.best_values, self.global_best,
-                    np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
-                    inertia0, step, rand, seed=(self._seed << 20) + self._calls)
-                return
-            _hip.swarm_run(
-                devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
-                o.best_lower_bound, self.positions, self.velocities,
-                self.best_positions, self.best_values, self.global_best,
-                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init,
-                iters, inertia0, step, rand,
-                seed=(self._seed << 20) + self._calls)
-            return
-        lo, hi = self._rows
-        P = self.swarm_size
+        rand = None
         if self._rng == 'numpy':
+            # the whole swarm's numbers on every rank, as one rank draws them
             rand = np.random.rand((P * d if init else 0) + 2 * P * d * iters)
-            # this rank's rows of every draw: init's (P, d), then per iteration the r1 and
-            # r2 rows of (2 P, d)
-            parts, at = [], 0
-            if init:
-                parts.append(rand[lo * d:hi * d])
-                at = P * d
-            for _ in range(iters):
-                it = rand[at:at + 2 * P * d]
-                parts += [it[lo * d:hi * d], it[(P + lo) * d:(P + hi) * d]]
-                at += 2 * P * d
-            rand = np.concatenate(parts) if parts else None
-        loc = self._local
-        if path is not None:
-            _hip.swarm_run_path(
-                devs[0].ctx, devs, o.beta(o.t), o.fmin, o.scaling, self.positions,
-                self.velocities, loc['best_positions'], loc['best_values'], self.global_best,
-                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init, iters,
-                inertia0, step, rand, path, seed=(self._seed << 20) + self._calls,
-                shard=(lo, self.swarm_size))
-        else:
-            _hip.swarm_run(
-                devs[0].ctx, devs, self._type, o.beta(o.t), o.fmin, o.scaling,
-                o.best_lower_bound, self.positions, self.velocities,
-                loc['best_positions'], loc['best_values'], self.global_best,
-                np.broadcast_to(self.velocity_scale, (d,)), self.bounds, init,
-                iters, inertia0, step, rand,
-                seed=(self._seed << 20) + self._calls, shard=(lo, self.swarm_size))
-        self.best_positions, self.best_values = self._gather(
-            loc['best_positions'], loc['best_values'])
+            if sharded:
+                rand = self._rows_of_draws(rand, init, iters)
+        # (sharded: the rank's block of the personal bests is the run's state between calls)
+        best_positions, best_values = (
+            (self._local['best_positions'], self._local['best_values']) if sharded
+            else (self.best_positions, self.best_values))
+        _hip._swarm_run(
+            devs[0].ctx, devs, self._type, (o.beta(o.t), o.fmin, o.scaling, o.best_lower_bound),
+            (self.positions, self.velocities, best_positions, best_values, self.global_best,
+             np.broadcast_to(self.velocity_scale, (d,)), self.bounds),
+            (init, iters, inertia0, step, rand, (self._seed << 20) + self._calls),
+            path=path, clones=self._clones,
+            shard=(self._rows[0], self.swarm_size) if sharded else None)
+        if sharded:
+            self.best_positions, self.best_values = self._gather(best_positions, best_values)
+
+    def _rows_of_draws(self, rand, init, iters):
+        """This rank's rows of every draw of the whole swarm: init's ``(P, d)``, then per
+        iteration the r1 and r2 rows of ``(2 P, d)``."""
+        (lo, hi), P, d = self._rows, self.swarm_size, self.positions.shape[1]
+        parts, at = [], 0
+        if init:
+            parts.append(rand[lo * d:hi * d])
+            at = P * d
+        for _ in range(iters):
+            it = rand[at:at + 2 * P * d]
+            parts += [it[lo * d:hi * d], it[(P + lo) * d:(P + hi) * d]]
+            at += 2 * P * d
+        return np.concatenate(parts) if parts else None
 
     def _gather(self, best_positions, best_values):
         """The whole swarm's personal bests on every rank (blocks padded to one size)."""

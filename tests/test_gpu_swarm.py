@@ -225,3 +225,61 @@ def test_device_pso_few_points_path_bit_identical(mods, swarm_size):
                     np.array(sw.best_values), np.array(sw.global_best)))
     for a, b in zip(out[0], out[1]):
         assert_array_equal(a, b)
+
+
+_SHARD_GPS = {}
+
+
+def _shard_gps(gpy, n):
+    """d = 2, two GPs with ``n`` observations each; built once."""
+    if n not in _SHARD_GPS:
+        X = np.random.default_rng(40 + n).uniform(-1.5, 1.5, size=(n, 2))
+        _SHARD_GPS[n] = [gpy.models.GPRegression(X, smooth(X, 5 + i) + 0.4,
+                                                 kernels(gpy.kern, "RBF", 2), noise_var=0.05 ** 2)
+                         for i in range(2)]
+    return _SHARD_GPS[n]
+
+
+@pytest.mark.parametrize("rng", ["numpy", "philox"])
+@pytest.mark.parametrize("n,P", [(12, 20), (12, 65), (150, 20)])
+def test_shard_entry_points_with_the_whole_swarm_are_the_plain_ones(mods, n, P, rng):
+    """include/safeopt_hip.h: with ``p0 = 0`` and ``P_total = P`` on a context without a
+    communicator ``sgp_swarm_run_shard`` is ``sgp_swarm_run`` and ``sgp_swarm_run_path_shard``
+    (a path of 32 features) is ``sgp_swarm_run_path`` -- the same bits in all five state
+    arrays, with the numbers shipped and with the device generator.  n = 12: 20 particles
+    run in one workgroup behind a sweep launch, 65 take the general launches; n = 150, 20
+    particles: one workgroup behind the few-points posterior."""
+    _, gpy, _, _ = mods
+    from safeopt_amd import _hip
+    gps = _shard_gps(gpy, n)
+    devs = [g._fitted() for g in gps]
+    ctx, lib, dp, d = devs[0].ctx, _hip.lib(), _hip.dptr, 2
+    assert ctx.comm_count() == 1                               # no communicator
+    np.random.seed(17)
+    pp = gps[0].posterior_paths(size=1, features=32)
+    Om, phase = _hip.f64(pp.Omega), _hip.f64(pp.phase)
+    w, v = np.ascontiguousarray(pp.W[:, 0]), np.ascontiguousarray(pp.V[:, 0])
+    fmin, scaling = np.array([-0.2, -0.5]), np.array([1.3, 1.1])
+    vscale, bounds = np.array([0.2, 0.3]), np.array([[-2., 2.], [-2., 2.]])
+    start = np.random.default_rng(3).uniform(-1, 1, size=(P, d))
+    init, iters = 1, 3
+    rand = np.random.default_rng(9).random((init + 2 * iters) * P * d) if rng == "numpy" else None
+
+    def run(name, head, tail):
+        state = [start.copy(), np.empty((P, d)), np.empty((P, d)), np.empty(P), np.empty(d)]
+        args = (ctx.h, _hip._gp_array(devs), 2) + head + (P,) + tuple(dp(a) for a in state) + (
+            dp(vscale), dp(bounds), init, iters, 1.0, -0.2, None if rand is None else dp(rand),
+            12345) + tail
+        ctx.check(getattr(lib, name)(*args))
+        return state
+
+    plain = (_hip.SWARM_TYPES["maximizers"], 2.0, dp(fmin), dp(scaling), 0.1)
+    thompson = (2.0, dp(fmin), dp(scaling))
+    path = (dp(Om), dp(phase), 32, dp(w), dp(v))
+    for name, head, tail in (("sgp_swarm_run", plain, ()), ("sgp_swarm_run_path", thompson, path)):
+        whole = run(name, head, tail)
+        block = run(name + "_shard", head, tail + (0, P))
+        for a, b in zip(whole, block):
+            assert_array_equal(a.view(np.uint64), b.view(np.uint64))
+        assert not np.array_equal(whole[0], start)            # the swarm really moved
+        assert np.all(np.isfinite(whole[3]))
