@@ -697,7 +697,9 @@ int64_t sgp_ctx_alloc_count(sgp_ctx* ctx);
  * double buffer instead of keeping them in LDS for the launch (same bits either
  * way); + 32: the paired-wave kernel runs one 16-point block of training points per
  * stage instead of merging the thin stages of a triangular chunk (the schedule until
- * round 5: another summation order, same results within rounding).  Same results
+ * round 5: another summation order, same results within rounding); + 64: in the paired-wave kernel a GP with the
+ * training inputs and kernel of the GP in front evaluates its own covariances instead
+ * of receiving that GP's (same bits either way, tests/test_gpu_pair_hand.py).  Same results
  * within rounding between the two kernels; the switch exists for A/B measurements and tests.  Returns
  * the previous setting.                                                        */
 int sgp_ctx_set_sweep(sgp_ctx* ctx, int which);
@@ -707,7 +709,8 @@ int sgp_ctx_set_sweep(sgp_ctx* ctx, int which);
  * at most 48 observations (csrc/sweep_tiny.hip -- the regime of the reference's own
  * examples), 4 = the few-points path (csrc/factor.hip), 5 = the one-launch step of a
  * small grid (csrc/step_small.hip), 6 = the resident-factor kernel for 49 .. 128
- * observations (csrc/sweep_mid.hip).                                                */
+ * observations (csrc/sweep_mid.hip); + 256: the paired-wave kernel handed covariances
+ * from a GP to GPs with the same inputs and kernel (see sgp_ctx_set_sweep, + 64).    */
 int sgp_ctx_last_sweep(sgp_ctx* ctx);
 
 /* Multi-output case: consecutive GPs of a launch with bit-identical training

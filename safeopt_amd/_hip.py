@@ -382,7 +382,9 @@ class Context(object):
         chunks, '-notables': no factor tables on tensor grids (set_axes), '-streamed':
         small factors go through the 4-wave kernel's double buffer instead of staying
         in LDS for the launch, '-unmerged': the paired kernel runs one j-block per stage
-        (the schedule until round 5; merged stages: csrc/sweep_pair.hip); or the integer
+        (the schedule until round 5; merged stages: csrc/sweep_pair.hip), '-nohand': GPs
+        with the inputs and kernel of the GP in front evaluate their own covariances
+        instead of receiving the leader's (csrc/sweep_pair.hip, "hand-down"); or the integer
         of sgp_ctx_set_sweep.  Returns the
         previous setting (a name)."""
         names = ("auto", "classic", "pair", "mid", "auto-nosplit", "classic-nosplit",
@@ -390,6 +392,7 @@ class Context(object):
         names = names + tuple(n + "-notables" if n else None for n in names)
         names = names + tuple(n + "-streamed" if n else None for n in names)
         names = names + tuple(n + "-unmerged" if n else None for n in names)
+        names = names + tuple(n + "-nohand" if n else None for n in names)
 
         def code(w):          # a name, or the integer of sgp_ctx_set_sweep
             return int(w) if isinstance(w, (int, np.integer)) else names.index(w)
@@ -405,7 +408,12 @@ class Context(object):
         """Kernel of the last posterior sweep: 'classic' | 'pair' | 'tiny' | 'few-points' |
         'step-small' | 'mid'."""
         return (None, "classic", "pair", "tiny", "few-points",
-                "step-small", "mid")[int(lib().sgp_ctx_last_sweep(self.h))]
+                "step-small", "mid")[int(lib().sgp_ctx_last_sweep(self.h)) & 255]
+
+    def last_sweep_handed(self):
+        """Did the last posterior sweep hand covariances from a GP to GPs with the same
+        inputs and kernel (the paired kernel's hand-down, csrc/sweep_pair.hip)?"""
+        return bool(int(lib().sgp_ctx_last_sweep(self.h)) & 256)
 
     # -- RCCL
     @staticmethod

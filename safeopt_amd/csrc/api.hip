@@ -134,6 +134,22 @@ int collect_gps(sgp_ctx* ctx, sgp_gp* const* gps, int G, int d, GpDev* host) {
           memcmp(a->xhost.data(), b->xhost.data(), a->xhost.size() * sizeof(double)) == 0)
         host[g].share = host[g - 1].share >= 0 ? host[g - 1].share : g - 1;
     }
+    // same inputs and kernel as the GP in front, whatever the noise, the jitter and the
+    // history (the constraints of a SafeOpt problem: add_new_data_point gives every GP the
+    // same x): the same covariances k(X, x), not the same factor.  Set whether factors
+    // are shared or not; a GP that shares the factor keeps that mark (riding wins)
+    if (host[g].share < 0 && g > 0) {
+      const sgp_gp *a = gps[g - 1], *b = gps[g];
+      if (a != b && a->n == b->n && !a->xhash.empty() && a->xhash.size() == size_t(a->n) &&
+          b->xhash.size() == size_t(b->n) && a->xhash.back() == b->xhash.back() &&
+          memcmp(&a->kern, &b->kern, sizeof(KernDesc)) == 0 &&
+          a->xhost.size() == b->xhost.size() &&
+          memcmp(a->xhost.data(), b->xhost.data(), a->xhost.size() * sizeof(double)) == 0) {
+        const int lead = host[g - 1].share >= 0 ? host[g - 1].share
+                                                : (host[g - 1].share <= -2 ? gp_cov_lead(host[g - 1]) : g - 1);
+        host[g].share = -2 - lead;
+      }
+    }
   }
   return 0;
 }
@@ -280,6 +296,7 @@ void sgp_destroy(sgp_ctx* ctx) {
   if (ctx->stage_tab.p) (void)hipFree(ctx->stage_tab.p);
   if (ctx->pstage_tab.p) (void)hipFree(ctx->pstage_tab.p);
   if (ctx->pair_split.p) (void)hipFree(ctx->pair_split.p);
+  if (ctx->pair_hand.p) (void)hipFree(ctx->pair_hand.p);
   if (ctx->pair_post.p) (void)hipFree(ctx->pair_post.p);
   for (auto e : ctx->prof_events) (void)hipEventDestroy(e);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -2278,7 +2295,7 @@ int sgp_ctx_last_sweep(sgp_ctx* ctx) { return ctx ? ctx->last_sweep : 0; }
 int sgp_ctx_set_sweep(sgp_ctx* ctx, int which) {
   if (!ctx) return -1;
   const int old = ctx->sweep_choice;
-  if (which >= 0 && which < 64) ctx->sweep_choice = which;
+  if (which >= 0 && which < 128) ctx->sweep_choice = which;
   return old;
 }
 

@@ -83,6 +83,15 @@ struct GpDev {
                         // as the GP in front of it in the launch (the multi-output
                         // case): same L^-1, so the paired sweep takes |L^-1 k|^2
                         // from that GP and only forms alpha . k (collect_gps)
+                        // <= -2: a COVARIANCE TWIN of GP -2 - share (gp_cov_lead): same
+                        // training inputs and kernel, but its own noise, jitter or
+                        // history, hence its own L^-1 -- k(X, x) is the leader's, which
+                        // the paired sweep hands down instead of evaluating it again
+                        // (sweep_pair.hip, "hand-down").  Every other reader tests
+                        // share >= 0 only: a twin is a GP with a factor of its own.
+                        // (Test the sign, never share == -1.  The mark lives in this
+                        // field because a field of its own would move `kern` and change
+                        // the stride of gps[g] in every kernel of the library)
   int narrow;           // 1: the last row block has <= 4 real rows and Apack holds
                         // them in the "narrow" form (k_pack): the sweep then needs
                         // one MFMA per k-step for that block instead of four
@@ -102,6 +111,9 @@ struct GpDev {
   double prior;
   KernDesc kern;
 };
+
+// GP whose covariances k(X, x) are bit for bit those of `g` (GpDev::share <= -2), or -1
+inline int gp_cov_lead(const GpDev& g) { return g.share <= -2 ? -2 - g.share : -1; }
 
 // A candidate grid that is a TENSOR grid (linearly_spaced_combinations,
 // safeopt/utilities.py:21-54: global row i has column k equal to
@@ -203,10 +215,12 @@ struct sgp_ctx {
                                          // the stage count
   int pstage_chunk_off[SGP_MAX_GPS + 1] = {0};   // first chunk number of every GP
   DevBuf pair_split;                     // per-lane partial sums of split remainder tiles
+  DevBuf pair_hand;                      // B-operand images a leader hands to its covariance
+                                         // twins: [workgroup][j-block][pair][256]
   DevBuf pair_post;                      // [G][P] mean | var of a swarm (sweep_pair.hip)
   int sweep_partials = 0;     // partials of max l0[S] the last confidence sweep left
   int sweep_choice = 0;       // sgp_ctx_set_sweep: 0 auto, 1 4-wave, 2 paired, 3 auto (mid kernel asked for)
-  int last_sweep = 0;         // kernel of the last posterior sweep (sgp_ctx_last_sweep)
+  int last_sweep = 0;         // kernel of the last posterior sweep (sgp_ctx_last_sweep; + 256: with the hand-down)
   int share_factors = 1;      // sgp_ctx_set_share: GPs with identical (X, kernel, noise)
                               // share the variance contraction (paired sweep)
   // sgp_grid_step_small: its result block lives in host memory the device writes directly

@@ -32,7 +32,10 @@
 //     partial |v|^2 and alpha . k, runs the row epilogue one stage later);
 //   * GPs with the factor of the GP in front of them (the outputs of a multi-
 //     output GP) ride in its stages: their alpha . k comes from the covariances
-//     the leader evaluates anyway (kMaxRide).
+//     the leader evaluates anyway (kMaxRide);
+//   * GPs with the training inputs and kernel of the GP in front but a factor of their own
+//     (covariance twins, gp_cov_lead: the constraints of a SafeOpt problem) receive the
+//     leader's covariances ready made -- the "hand-down", see PW_PUT / PW_GET.
 // The stage sequence comes from a host-built table with ABSOLUTE source
 // addresses (one scalar load per stage, no pointer arithmetic on the device);
 // the training rows and alpha of a j-block are one contiguous block
@@ -109,7 +112,15 @@ enum : uint32_t {
                             // covariances for alpha . k; |L^-1 k|^2 is the leader's
   PW_DUO = 1u << 23,        // the stage has a second j-block (segment B)
   PW_NB_SHIFT = 24,         // active global slots of segment B (6 bits)
-  PW_G_SHIFT = 12           // GP index (3 bits)
+  PW_G_SHIFT = 12,          // GP index (3 bits)
+  // The hand-down (instances with HAND, whole tiles only).  A leader's stages (PUT) also
+  // store every B-operand image they write -- the lane's 16 bytes, at the image's LDS
+  // offset -- to the workgroup's scratch [j-block][pair][256] and form the twins' alpha . k
+  // as they would a rider's; a twin's stages (GET) keep their slots and L^-1 units but have
+  // no training block, no evaluation and no mean: half 0 copies the images back by LDS-DMA,
+  // straight into the B buffers, behind the L^-1 units of its copy plan.
+  PW_PUT = 1u << 30,
+  PW_GET = 1u << 31
 };
 
 // LDS (doubles):  [2][A chunk 64 KB]  [2][2 j-blocks][16 D rows | 16 alpha]  exp table
@@ -146,10 +157,16 @@ struct LayP {
 // (what the LDS of a d <= 4 instance has room for); further followers keep stages
 // without rows (PW_SHARED).
 constexpr int kMaxRide = 2;
+// (hand-down: the twins' reduced alpha . k wait behind the layout for the twin's own last
+// stage, [pair][twin][half][16])
+constexpr int kParkPair = kMaxRide * 2 * 16;
+constexpr int kParkDoubles = kPairs * kParkPair;
 static_assert(sizeof(PStage) == 32, "one aligned scalar load per stage");
 static_assert(LayP<8>::bytes() <= 160 * 1024, "LDS budget of one workgroup per CU");
 static_assert(LayP<1>::kKb2Off + kPairs * LayP<1>::kKbBuf <= LayP<1>::kATile, "second B buffers");
 static_assert(LayP<4, kMaxRide>::bytes() <= 160 * 1024, "LDS budget with riders");
+static_assert(LayP<4, kMaxRide>::bytes() + kParkDoubles * sizeof(double) <= 160 * 1024,
+              "LDS budget with covariance twins");
 
 struct PairParams {
   const GpDev* gps;
@@ -179,6 +196,21 @@ struct PairParams {
   double* split_m;        // [split_count][geff][512]
   int split_partial0;     // first slot of the finish kernel in ConfOut::partial
   SepLaunch sep;          // tensor grid + factor tables (instances with SEP > 0)
+  // hand-down (instances with HAND; behind everything the other instances read).  The
+  // table then holds TWO sequences of nstages entries: the one with PUT / GET stages for
+  // whole tiles, and behind it the plain one for the runs of remainder tiles (a run may
+  // start inside a twin, whose leader never ran in that workgroup).  nride / ride_delta
+  // describe the twins of a PUT leader.
+  char* hand_scr;         // [workgroup][j-block][pair][256 doubles]
+  unsigned hand_wg_bytes; // ... bytes per workgroup
+  int hand_slot[SGP_MAX_GPS];   // twin g: which of its leader's twins it is (0 ..)
+  // pts.base / stride_row / stride_col once more, for load_x of these instances.  Read
+  // from `pts`, the four fields are ONE 32-byte scalar load that lives across the stage
+  // loop; the register allocator spills it, then rematerialises every use after all and
+  // leaves the spill slot in the frame: 36 bytes of scratch no instruction touches, but
+  // which every launch would have to be given (scripts/resource_usage.py).
+  const double* hand_x;
+  int64_t hand_x_row, hand_x_col;
 #ifdef SGP_INSTRUMENT
   int ablate;
 #endif
@@ -477,10 +509,13 @@ __device__ __forceinline__ void row_epilogue(const PairParams& p, RowState& rs,
 // parts (SepLaunch, sweep.hip): a covariance is the product of SEP table entries -- one
 // 16-byte load per axis, lane and stage, requested a stage ahead -- instead of ~20 fp64
 // instructions per value.  (Instantiated with D = 1: the rows themselves are not read.)
-template <int D, bool SINGLE, int H, int R, int SEP>
+// HAND: the instance knows PUT and GET stages (on top of R = kMaxRide; launches without
+// covariance twins never run it).
+template <int D, bool SINGLE, int H, int R, int SEP, bool HAND>
 __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
                                           const int lane, const int wave) {
   typedef LayP<D, R> L;
+  static_assert(!HAND || (R == kMaxRide && SEP == 0 && SINGLE && D <= 4), "hand-down instances");
   // (32 more live registers across the evaluation: instances that would spill for
   // it -- d >= 6, product kernels -- do without)
   // (instances with riders: up to d = 3 -- at d = 4 the fetch spills -- and without the row
@@ -508,16 +543,34 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
   const uint32_t lds_a = lds_addr_of(lds);
   const uint32_t lds_xa = lds_addr_of(lds + L::kXOff);
   const uint32_t voff = uint32_t(lane) * 16u;
+  // hand-down: this pair's image of j-block jb in the workgroup's scratch (formed from the
+  // kernel arguments where it is used: two scalar registers the stage loop does not have),
+  // the parked means
+  auto hand_img = [&](uint32_t jb) {
+    return uint64_t(reinterpret_cast<uintptr_t>(p.hand_scr)) +
+           uint64_t(blockIdx.x) * p.hand_wg_bytes +
+           (jb * uint32_t(kPairs) + uint32_t(pr)) * (L::kKbBuf * 8u);
+  };
+  double* park = lds + L::kTotal + pr * kParkPair;
 
   // candidate rows of the tile being EVALUATED (one stage ahead of the
   // multiplication) and, prefetched, of the tile after it
   auto load_x = [&](int t, double (&xo)[D]) {
     int64_t r = int64_t(t) * kTileRows + pr * 16 + c16;
     r = r < p.pts.N ? r : p.pts.N - 1;
+    if constexpr (HAND) {
+      // (PairParams::hand_x*: the same three values as pts.base / stride_row / stride_col,
+      // from fields of their own -- with `pts` the instance reports 36 bytes of scratch that
+      // nothing touches, see there; scripts/resource_usage.py shows it)
+#pragma unroll
+      for (int k = 0; k < D; ++k)
+        xo[k] = __builtin_nontemporal_load(p.hand_x + r * p.hand_x_row + k * p.hand_x_col);
+    } else {
 #pragma unroll
     for (int k = 0; k < D; ++k)
       xo[k] = __builtin_nontemporal_load(p.pts.base + r * p.pts.stride_row +
                                          k * p.pts.stride_col);
+    }
   };
   // x_raw: raw rows of the tile being evaluated -- until the scaled rows of its
   // LAST GP are formed, from then on already the rows of the next tile (the load
@@ -581,6 +634,7 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
     }
   };
 
+  PStage e1{};       // the stage being evaluated (one ahead of the multiplication)
   // covariances of one stage: this wave's half (training points 8 H .. 8 H + 7 of
   // the j-block) -> the pair's B buffer, [k][q pair][point][2]
   double mean = 0.0;
@@ -650,11 +704,26 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
     // (odd k-rows: the halves of the q pair's 32 doubles swapped -- fetch_ops)
     *reinterpret_cast<double2_t*>(kbw + k4 * kKbRow + H * 32 + ((c16 * 2) ^ ((k4 & 1) * 16))) =
         double2_t{kv[0], kv[1]};
+    if constexpr (HAND) {
+      if (w1 & PW_PUT) {
+        // ... and to the image the twins' stages copy back (a GLOBAL store: a flat one
+        // would count on lgkmcnt as well)
+        typedef __attribute__((address_space(1))) double2_t* gvec_t;
+        const uint64_t img = hand_img(e1.jb() + (J == 0 ? 0u : e1.djb()));
+        const uint32_t at = uint32_t(k4 * kKbRow + H * 32 + ((c16 * 2) ^ ((k4 & 1) * 16))) * 8u;
+        *(gvec_t)(reinterpret_cast<double2_t*>(img + at)) = double2_t{kv[0], kv[1]};
+      }
+    }
+  };
+  // riders whose alpha . k the stages of GP g (stage word w) form
+  auto riders_of = [&](uint32_t w, int g) {
+    if constexpr (HAND) return (w & PW_PUT) ? p.nride[g] : 0;
+    return R > 0 ? p.nride[g] : 0;
   };
   auto evaluate = [&](uint32_t w1, const Rows& r, const double* xa, double* kbw, double* kb2w) {
     if (SEP == 0 && __builtin_expect((w1 & PW_GP_FIRST) != 0, 0)) {
       kf.load_const(&p.gps[int(w1 >> PW_G_SHIFT) & 7].kern);
-      if (R > 0) nr_e = p.nride[int(w1 >> PW_G_SHIFT) & 7];
+      if (R > 0) nr_e = riders_of(w1, int(w1 >> PW_G_SHIFT) & 7);
       if constexpr (kLeanX) {
         double xr[D];
         load_x(tile_e, xr);
@@ -676,7 +745,6 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
       eval_block(w1, std::integral_constant<int, 1>{}, r, xa + L::kXBlk, kb2w);
   };
 
-  PStage e1{};
   uint32_t wcur = 0;
   int si1 = 0;
 
@@ -821,11 +889,19 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
       ssq = ssq_lead;
     else
       ssq_lead = ssq;
-    const double mu = keep_mu + ex[16 + c16];
+    double mu = keep_mu + ex[16 + c16];
     const int g = int(pend_w >> PW_G_SHIFT) & 7;
+    if constexpr (HAND) {
+      // a twin: the two halves' alpha . k as its leader's last stage left them (the sum a
+      // GP's own stages end in: half 1's + half 0's); |L^-1 k|^2 is its own
+      if (pend_w & PW_GET) {
+        const double* pk = park + p.hand_slot[g] * 32;
+        mu = pk[16 + c16] + pk[c16];
+      }
+    }
     const double kdiag = gpc[g].kern.kdiag;
     const double var = fmax(kdiag - ssq, 1e-15);  // GPy clip
-    const int nr = R > 0 ? p.nride[g] : 0;
+    const int nr = (R > 0 && !HAND) ? p.nride[g] : 0;
     // (the tile ends behind the last rider)
     row_epilogue<D>(p, rs, nr > 0 ? pend_w & ~uint32_t(PW_TILE_END) : pend_w, pend_tile,
                     pr, lane, mu, var, qst);
@@ -855,6 +931,8 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
 #pragma unroll 1
   for (int item = 0; item < 2; ++item) {
   int s_lo = 0;                        // first stage of the item
+  // (hand-down: the plain sequence, for the runs of remainder tiles, lies behind the other)
+  const int sbase = (HAND && item == 1) ? nstages : 0;
   if (item == 0) {
     const int whole_end = p.split_parts > 0 ? p.split_tile0 : ntiles;
     if (int(blockIdx.x) >= whole_end) continue;
@@ -874,9 +952,9 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
   // the same bits wherever an item begins).  Only the training block of the first
   // stage has to be in LDS before it.
   par = 0;
-  e1 = load_pstage<(R > 0), (SEP > 0)>(stages, s_lo);
+  e1 = load_pstage<(R > 0), (SEP > 0)>(stages, sbase + s_lo);
   if (wave == 7) {
-    const PStage el = load_pstage<(R > 0), (SEP > 0)>(stages, (s_lo == 0 ? nstages : s_lo) - 1);
+    const PStage el = load_pstage<(R > 0), (SEP > 0)>(stages, sbase + (s_lo == 0 ? nstages : s_lo) - 1);
     // block(s) of the first stage
     xa_dma<D>(el.xa_next, lds_xa + L::kXBuf * 8, lane, voff);
     if (R > 0)
@@ -902,7 +980,7 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
   if (SEP == 0 && !(e1.word & PW_GP_FIRST)) {
     // the item begins inside a GP (a run of chunks of a remainder tile)
     kf.load_const(&p.gps[int(e1.word >> PW_G_SHIFT) & 7].kern);
-    if (R > 0) nr_e = p.nride[int(e1.word >> PW_G_SHIFT) & 7];
+    if (R > 0) nr_e = riders_of(e1.word, int(e1.word >> PW_G_SHIFT) & 7);
     if constexpr (kLeanX) {
       double xr[D];
       load_x(tile_e, xr);
@@ -932,6 +1010,9 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
     constexpr bool kXaHalf0 = R > 0 && D <= 3;
     // (the training blocks of BOTH j-blocks of a merged stage)
     auto xa_prefetch = [&](const PStage& e, uint32_t dst) {
+      if constexpr (HAND) {
+        if (e.xa_next == 0) return;      // (a GET stage has no training block)
+      }
       xa_dma<D>(e.xa_next, dst, lane, voff);
       if (R > 0) rider_dma<D>(p.nride, p.ride_delta, int(e.g_next()), e.xa_next, dst, lane, voff);
       if (e.xb_next != 0) {
@@ -966,7 +1047,7 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
     // letting it start early, the waves of a SIMD then run their VALU bursts
     // together; experiments.txt section 10)
     PStage e2 = e1;
-    if (left > 2) e2 = load_pstage<(R > 0), (SEP > 0)>(stages, si2);
+    if (left > 2) e2 = load_pstage<(R > 0), (SEP > 0)>(stages, sbase + si2);
 
     const double* abuf = lds + par * L::kATile;
     const double* kbr = kbp + par * L::kKbBuf;
@@ -987,7 +1068,7 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
       // alpha . k of the GP that ends here (the evaluation below may already belong
       // to the next one): half 0 hands its share over, half 1 keeps it
       const int g_end = int(wcur >> PW_G_SHIFT) & 7;
-      const int nr = R > 0 ? p.nride[g_end] : 0;
+      const int nr = riders_of(wcur, g_end);
       if (p.split_parts > 0 && tile >= p.split_tile0) {
         // (a run of a remainder tile: per lane, summed by k_pair_split_finish)
         double* sm = p.split_m + (size_t(tile - p.split_tile0) * p.geff + g_end) * 512 +
@@ -1010,7 +1091,10 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
           for (int f = 0; f < R; ++f) {
             if (f < nr) {
               const double mu_f = sum_lane_groups(mean_r[f]);
-              if (H != kFin) {
+              if constexpr (HAND) {
+                // (twins: parked until the twin's own last stage -- finish)
+                if (lane < 16) park[f * 32 + H * 16 + lane] = mu_f;
+              } else if (H != kFin) {
                 if (lane < 16) exch[par * L::kExRow + 16 * (2 + f) + lane] = mu_f;
               } else {
                 keep_mu_r[f] = mu_f;
@@ -1025,7 +1109,11 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
         for (int f = 0; f < R; ++f) mean_r[f] = 0.0;
       }
     }
+    if constexpr (HAND) {
+      if (more && !(wnext & PW_GET)) evaluate(wnext, rows, xa, kbw, kb2w);
+    } else {
     if (more) evaluate(wnext, rows, xa, kbw, kb2w);
+    }
     if constexpr (SEP > 0) {
       // the factors of the stage after the next one (its entry, e2, was requested
       // above: it has arrived under the evaluation); they have the matrix phase to come
@@ -1045,6 +1133,17 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
         xa_prefetch(e1, lds_xa + uint32_t(par) * (L::kXBuf * 8));
     }
     multiply(wcur, abuf, kb2r, ops, plan);
+    if constexpr (HAND && H == 0) {
+      // the B images of a twin's next stage: wave w copies those of pair w, 2 KB per
+      // j-block, behind the L^-1 units (a late return never sits in front of them)
+      if (more && (wnext & PW_GET)) {
+        dma_2k(hand_img(e1.jb()), lds_a + uint32_t(L::kKbOff + pr * (2 * L::kKbBuf) + (par ^ 1) * L::kKbBuf) * 8u,
+               voff);
+        if (wnext & PW_DUO)
+          dma_2k(hand_img(e1.jb() + e1.djb()),
+                 lds_a + uint32_t((par ^ 1) * L::kATile + L::kKb2Off + pr * L::kKbBuf) * 8u, voff);
+      }
+    }
     PGP_STAMP(2);     // matrix phase (operand reads, slots, chunk fold)
 
     if (__builtin_expect((wcur & PW_GP_END) != 0, 0)) {
@@ -1090,7 +1189,7 @@ __device__ __forceinline__ void pair_loop(const PairParams& p, double* lds,
   }
 }
 
-template <int D, bool SINGLE, int R = 0, int SEP = 0>
+template <int D, bool SINGLE, int R = 0, int SEP = 0, bool HAND = false>
 __global__ __launch_bounds__(512, 1) void k_sweep_pair(PairParams p) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   exp_tab_init(lds + LayP<D, R>::kTabOff);   // visible after the first barrier
@@ -1098,9 +1197,9 @@ __global__ __launch_bounds__(512, 1) void k_sweep_pair(PairParams p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave < 4)
-    pair_loop<D, SINGLE, 0, R, SEP>(p, lds, lane, wave);
+    pair_loop<D, SINGLE, 0, R, SEP, HAND>(p, lds, lane, wave);
   else
-    pair_loop<D, SINGLE, 1, R, SEP>(p, lds, lane, wave);
+    pair_loop<D, SINGLE, 1, R, SEP, HAND>(p, lds, lane, wave);
 }
 
 // Remainder tiles that were cut into runs of chunks (PairParams::split_*): the
@@ -1171,18 +1270,29 @@ bool pair_merge_wanted(const sgp_ctx* ctx) {
   return !off && !(ctx->sweep_choice & 32);
 }
 
+//
+// hand (may be null): role of every GP in the hand-down, kHandLead / kHandTwin or 0.  With
+// any role set the table holds a second sequence behind the first (PairParams::hand_scr):
+// first the one with PUT / GET stages, then the plain one.
+enum { kHandLead = 1, kHandTwin = 2 };
 int pair_stage_table(sgp_ctx* ctx, const GpDev* gh, int Geff, int d, bool sep, const bool* rides,
-                     const PStage** dev, int* nstages) {
+                     const int* hand, const PStage** dev, int* nstages) {
   const bool merge = pair_merge_wanted(ctx);
   std::vector<uint64_t> sig(1, uint64_t(Geff));
   sig.push_back(uint64_t(d) | (uint64_t(sep) << 8) | (uint64_t(merge) << 9));
   int last_staged = 0;
   for (int g = 0; g < Geff; ++g)
     if (!rides[g]) last_staged = g;
+  bool any_hand = false;
+  int last_eval = 0;              // last GP whose stages evaluate (hand-down sequence)
+  for (int g = 0; g < Geff; ++g) {
+    any_hand = any_hand || (hand && hand[g] != 0);
+    if (!(hand && hand[g] == kHandTwin)) last_eval = g;
+  }
   for (int g = 0; g < Geff; ++g) {
     sig.push_back(uint64_t(gh[g].nblk));
     sig.push_back(uint64_t(gh[g].narrow) | (uint64_t(gh[g].share >= 0) << 8) |
-                  (uint64_t(rides[g]) << 9));
+                  (uint64_t(rides[g]) << 9) | (uint64_t(hand ? hand[g] : 0) << 10));
     sig.push_back(reinterpret_cast<uint64_t>(gh[g].Apack));
     sig.push_back(reinterpret_cast<uint64_t>(gh[g].XA));
   }
@@ -1259,10 +1369,28 @@ int pair_stage_table(sgp_ctx* ctx, const GpDev* gh, int Geff, int d, bool sep, c
   ctx->pstage_chunk_off[Geff] = int(chunk_start.size());
   chunk_start.push_back(int(tab.size()));
   ctx->pstage_chunk_start = chunk_start;
+  const size_t count = tab.size();
+  if (any_hand) {
+    // the sequence with PUT / GET stages in front of the plain one: a twin's stages lose
+    // their training blocks, and the candidate rows advance with the last GP that evaluates
+    const std::vector<PStage> plain(tab);
+    tab.insert(tab.end(), plain.begin(), plain.end());
+    for (size_t i = 0; i < count; ++i) {
+      const int g = int(gof[i]), gn = int(gof[(i + 1) % count]);
+      tab[i].word &= ~uint32_t(PW_LAST_GP);
+      if (g == last_eval) tab[i].word |= PW_LAST_GP;
+      if (hand[g] == kHandLead) tab[i].word |= PW_PUT;
+      if (hand[g] == kHandTwin) tab[i].word |= PW_GET;
+      if (hand[gn] == kHandTwin) {
+        tab[i].xa_next = 0;
+        tab[i].xb_next = 0;
+      }
+    }
+  }
   SGP_TRY(sgp_reserve(ctx, &ctx->pstage_tab, tab.size() * sizeof(PStage)));
   SGP_TRY(sgp_h2d(ctx, ctx->pstage_tab.p, tab.data(), tab.size() * sizeof(PStage)));
   ctx->pstage_sig = sig;
-  ctx->pstage_count = int(tab.size());
+  ctx->pstage_count = int(count);
   *dev = static_cast<const PStage*>(ctx->pstage_tab.p);
   *nstages = ctx->pstage_count;
   return 0;
@@ -1346,14 +1474,14 @@ PairPlan pair_plan(const sgp_ctx* ctx, int64_t N) {
   return pl;
 }
 
-template <int D, bool SINGLE, int R = 0, int SEP = 0>
+template <int D, bool SINGLE, int R = 0, int SEP = 0, bool HAND = false>
 int launch_pair_v(sgp_ctx* ctx, const PairParams& p, double flops) {
+  constexpr size_t kLds = LayP<D, R>::bytes() + (HAND ? kParkDoubles * sizeof(double) : 0);
   static bool attr_set = false;
   if (!attr_set) {
     SGP_HIP(ctx, hipFuncSetAttribute(
-                     reinterpret_cast<const void*>(&k_sweep_pair<D, SINGLE, R, SEP>),
-                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                     int(LayP<D, R>::bytes())));
+                     reinterpret_cast<const void*>(&k_sweep_pair<D, SINGLE, R, SEP, HAND>),
+                     hipFuncAttributeMaxDynamicSharedMemorySize, int(kLds)));
     attr_set = true;
   }
   const PairPlan pl = pair_plan(ctx, p.pts.N);
@@ -1385,8 +1513,8 @@ int launch_pair_v(sgp_ctx* ctx, const PairParams& p, double flops) {
   if (!stamps_dev) SGP_HIP(ctx, hipMalloc(&stamps_dev, size_t(4096) * 64 * 8));
   pp.stamps = stamps_dev;
 #endif
-  hipLaunchKernelGGL((k_sweep_pair<D, SINGLE, R, SEP>), dim3(nblocks), dim3(512),
-                     (LayP<D, R>::bytes()), ctx->stream, pp);
+  hipLaunchKernelGGL((k_sweep_pair<D, SINGLE, R, SEP, HAND>), dim3(nblocks), dim3(512), kLds,
+                     ctx->stream, pp);
   if (pl.parts > 0)
     hipLaunchKernelGGL(k_pair_split_finish, dim3(pl.count), dim3(512), 0,
                        ctx->stream, pp);
@@ -1417,8 +1545,10 @@ int launch_pair_v(sgp_ctx* ctx, const PairParams& p, double flops) {
 
 // (riders: single-part kernels up to d = 4 -- pair_riders)
 template <int D>
-int launch_pair_d(sgp_ctx* ctx, const PairParams& p, bool single, bool riders, double flops) {
+int launch_pair_d(sgp_ctx* ctx, const PairParams& p, bool single, bool riders, bool hand,
+                  double flops) {
   if constexpr (D <= 4) {
+    if (hand) return launch_pair_v<D, true, kMaxRide, 0, true>(ctx, p, flops);
     if (riders) return launch_pair_v<D, true, kMaxRide>(ctx, p, flops);
   }
   return single ? launch_pair_v<D, true>(ctx, p, flops)
@@ -1441,6 +1571,76 @@ bool pair_sweep_wanted(const sgp_ctx* ctx, const GpDev* gh, int Geff) {
   return np > 256;
 }
 
+// The hand-down groups of a launch (see PW_PUT / PW_GET): consecutive GPs with the training
+// inputs and kernel of one leader (gp_cov_lead) -- a leader and at most kMaxRide twins, a
+// further twin leads the next group.  Single-part kernels up to d = 4, one accumulator chunk
+// (n_pad <= 512), the images of all workgroups within kHandCap; launches with factor tables
+// or riders do not get here.  sgp_ctx_set_sweep(.. | 64) / SGP_PAIR_HAND=0: no groups
+// (same bits; A/B runs, tests).  hand[g]: kHandLead / kHandTwin / 0; fills the twins'
+// nride / ride_delta / hand_slot and the scratch of *p.
+constexpr size_t kHandCap = size_t(128) << 20;     // half the Infinity Cache
+// stages of a GP with one accumulator chunk of nblk row blocks (as pair_stage_table lays them out)
+static int pair_gp_stages(int nblk, bool merge) {
+  int stages = 0;
+  for (int lo = 0, hi = nblk - 1; lo <= hi; ++lo, ++stages)
+    if (merge && lo < hi && (nblk - lo) + (nblk - hi) <= kDuoUnits) --hi;
+  return stages;
+}
+static int pair_hand_groups(sgp_ctx* ctx, const GpDev* gh, int Geff, int d, bool single,
+                            int64_t N, int* hand, PairParams* p, bool* any) {
+  static const bool off = getenv("SGP_PAIR_HAND") && atoi(getenv("SGP_PAIR_HAND")) == 0;
+  for (int g = 0; g < SGP_MAX_GPS; ++g) hand[g] = 0;
+  *any = false;
+  if (off || (ctx->sweep_choice & 64) || !single || d > 4) return 0;
+  for (int g = 0; g < Geff; ++g)
+    if (gh[g].share >= 0) return 0;      // (followers of a shared factor in the launch)
+  int n_pad = 0;
+  int lead = -1, root = -1;       // the running group: its leader, whose covariances they are
+  for (int g = 0; g < Geff; ++g) {
+    const int r = gp_cov_lead(gh[g]);
+    // (at least TWO stages per GP: the parked means are one buffer -- a leader's last stage
+    // writes them, the iteration that multiplies the stage behind a twin's last one reads
+    // them; with one-stage GPs, L T L T .., those are the SAME iteration of the next tile's
+    // leader, half 0 writing while half 1 still reads, with no barrier between them)
+    if (r >= 0 && r < g && lead >= 0 && r == root && gh[g].n_pad <= 512 &&
+        gh[g].nblk == gh[lead].nblk && pair_gp_stages(gh[g].nblk, pair_merge_wanted(ctx)) >= 2) {
+      if (p->nride[lead] < kMaxRide) {
+        hand[g] = kHandTwin;
+        hand[lead] = kHandLead;
+        p->hand_slot[g] = p->nride[lead]++;
+        p->ride_delta[g] = (long long)(reinterpret_cast<intptr_t>(gh[g].XA) -
+                                       reinterpret_cast<intptr_t>(gh[lead].XA));
+        n_pad = std::max(n_pad, gh[g].n_pad);
+        continue;
+      }
+      lead = g;                   // (a further twin: leader of the next group, same root)
+      continue;
+    }
+    lead = g;
+    root = r >= 0 ? r : g;
+  }
+  if (n_pad == 0) return 0;
+  const size_t wg_bytes = size_t(n_pad / kJC) * kPairs * LayP<1>::kKbBuf * sizeof(double);
+  const size_t bytes = wg_bytes * size_t(pair_grid_blocks(ctx->num_cu, N));
+  if (bytes > kHandCap) {
+    for (int g = 0; g < Geff; ++g) {
+      hand[g] = 0;
+      p->nride[g] = 0;
+      p->ride_delta[g] = 0;
+    }
+    return 0;
+  }
+  SGP_TRY(sgp_reserve(ctx, &ctx->pair_hand, bytes));
+  p->hand_scr = static_cast<char*>(ctx->pair_hand.p);
+  p->hand_wg_bytes = unsigned(wg_bytes);
+  p->hand_x = p->pts.base;
+  p->hand_x_row = p->pts.stride_row;
+  p->hand_x_col = p->pts.stride_col;
+  *any = true;
+  ctx->last_sweep |= 256;         // (sgp_ctx_last_sweep: this launch hands down)
+  return 0;
+}
+
 int launch_sweep_pair(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d,
                       int Geff, double flops, const SepLaunch* sep) {
   PairParams p{};
@@ -1460,7 +1660,11 @@ int launch_sweep_pair(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d,
       assign_riders(gh, Geff, d, single, kMaxRide, 4, rides, p.nride, p.ride_delta);
   // (factor tables: the instances without riders; a launch with riders evaluates)
   if (riders) sep = nullptr;
-  SGP_TRY(pair_stage_table(ctx, gh, Geff, d, sep != nullptr, rides, &p.stages, &p.nstages));
+  int hand[SGP_MAX_GPS];
+  bool handing = false;
+  if (!riders && !sep) SGP_TRY(pair_hand_groups(ctx, gh, Geff, d, single, a.pts.N, hand, &p, &handing));
+  SGP_TRY(pair_stage_table(ctx, gh, Geff, d, sep != nullptr, rides, handing ? hand : nullptr,
+                           &p.stages, &p.nstages));
   if (sep) {
     p.sep = *sep;
     switch (sep->naxes) {
@@ -1473,14 +1677,14 @@ int launch_sweep_pair(sgp_ctx* ctx, const SweepArgs& a, const GpDev* gh, int d,
   }
   int rc = -2;
   switch (d) {
-    case 1: rc = launch_pair_d<1>(ctx, p, single, riders, flops); break;
-    case 2: rc = launch_pair_d<2>(ctx, p, single, riders, flops); break;
-    case 3: rc = launch_pair_d<3>(ctx, p, single, riders, flops); break;
-    case 4: rc = launch_pair_d<4>(ctx, p, single, riders, flops); break;
-    case 5: rc = launch_pair_d<5>(ctx, p, single, riders, flops); break;
-    case 6: rc = launch_pair_d<6>(ctx, p, single, riders, flops); break;
-    case 7: rc = launch_pair_d<7>(ctx, p, single, riders, flops); break;
-    case 8: rc = launch_pair_d<8>(ctx, p, single, riders, flops); break;
+    case 1: rc = launch_pair_d<1>(ctx, p, single, riders, handing, flops); break;
+    case 2: rc = launch_pair_d<2>(ctx, p, single, riders, handing, flops); break;
+    case 3: rc = launch_pair_d<3>(ctx, p, single, riders, handing, flops); break;
+    case 4: rc = launch_pair_d<4>(ctx, p, single, riders, handing, flops); break;
+    case 5: rc = launch_pair_d<5>(ctx, p, single, riders, handing, flops); break;
+    case 6: rc = launch_pair_d<6>(ctx, p, single, riders, handing, flops); break;
+    case 7: rc = launch_pair_d<7>(ctx, p, single, riders, handing, flops); break;
+    case 8: rc = launch_pair_d<8>(ctx, p, single, riders, handing, flops); break;
     default:
       sgp_set_error(ctx, "input dimension %d not in 1..%d", d, SGP_MAX_D);
       return -2;
