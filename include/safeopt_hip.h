@@ -82,6 +82,18 @@ int sgp_gp_set_data(sgp_gp* gp, const double* X, const double* Y, int64_t n,
  * applies GPy's jitter), -1 no spare capacity (same remedy).                  */
 int sgp_gp_append(sgp_gp* gp, const double* x, double y, int* info);
 int sgp_gp_pop(sgp_gp* gp);
+/* Forget training row `index` (0 .. n-1, n >= 2), whichever it is: an O(n^2) downdate of
+ * L^-1 and alpha instead of the refit gp.set_XY would cost (the reference has only
+ * remove_last_data_point).  With M = L^-1, c = column index of M, P_ii = |c|^2 and
+ * p = M^T c:  w = -p_{-i} / P_ii,  alpha_new = alpha_{-i} + w alpha_i, and L_new^-1 = M
+ * without column i after the rotations that fold c_k into c_i, k = i+1 .. n-1 (DESIGN.md
+ * 4.4a).  Kernel, noise, jitter and row capacity of the fit stay.  Every sum is formed in a
+ * fixed order: the same inputs give the same bits.  It leaves the record of the removal
+ * {w, alpha_i, P_ii, x_i} for sgp_grid_rank1_remove -- also for index == n-1, unlike
+ * sgp_gp_pop.  info = 0 ok; > 0: P_ii or a rotation is not positive and finite -- the GP
+ * is untouched (refit the reduced data with sgp_gp_set_data).  An index outside 0 .. n-1,
+ * n == 1 and a GP that is not fitted are errors.                                          */
+int sgp_gp_remove(sgp_gp* gp, int64_t index, int* info);
 /* gp.predict_noiseless / gp._raw_predict (gp_opt.py:469, 591, 929, 973, 1117,
  * 1132; utilities.py:203, 282, 355).  Xnew element (r,c) at
  * Xnew[r*stride_row + c*stride_col] (strides in elements: C or F order).
@@ -224,6 +236,16 @@ int sgp_grid_posterior(sgp_grid* grid, sgp_gp* const* gps, int G);
  * O(n) per row instead of the O(n^2) sweep, then Q and S for all GPs from the
  * resident mean/var with the given beta.  out2 as sgp_grid_confidence.        */
 int sgp_grid_rank1_update(sgp_grid* grid, sgp_gp* const* gps, int G,
+                          const int* which, double beta, const double* fmin,
+                          double* out2);
+/* ... and after ONE sgp_gp_remove on the GPs flagged in which[]: with x_i the row that
+ * left and w, alpha_i, P_ii of its record,
+ *   c(x) = k(x,x_i) - k(X_new,x)^T w,  mean -= c alpha_i,
+ *   var = max(var + c^2 P_ii, 1e-15),
+ * then Q and S for all GPs; out2, the deferred form, context columns and shared factors
+ * as sgp_grid_rank1_update.  Each of the two refuses the other's record (and a GP whose
+ * newest change left none).                                                     */
+int sgp_grid_rank1_remove(sgp_grid* grid, sgp_gp* const* gps, int G,
                           const int* which, double beta, const double* fmin,
                           double* out2);
 /* replace Q by host values (N x 2G row-major) and recompute S (tests, and

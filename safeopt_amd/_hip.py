@@ -56,6 +56,7 @@ PROTOTYPES = {
                              c_int_p]),
     "sgp_gp_append": (C.c_int, [vp, c_double_p, C.c_double, c_int_p]),
     "sgp_gp_pop": (C.c_int, [vp]),
+    "sgp_gp_remove": (C.c_int, [vp, C.c_int64, c_int_p]),
     "sgp_gp_predict": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
                                  C.c_int64, c_double_p, c_double_p]),
     "sgp_gp_predict_cov": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
@@ -92,6 +93,8 @@ PROTOTYPES = {
                                       c_double_p, c_double_p]),
     "sgp_grid_posterior": (C.c_int, [vp, vpp, C.c_int]),
     "sgp_grid_rank1_update": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
+                                        c_double_p, c_double_p]),
+    "sgp_grid_rank1_remove": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
                                         c_double_p, c_double_p]),
     "sgp_grid_upload_Q": (C.c_int, [vp, c_double_p, c_double_p, c_double_p]),
     "sgp_grid_maximizers": (C.c_int, [vp, C.c_double, c_double_p]),
@@ -519,9 +522,11 @@ class DeviceGP(object):
         self.n = 0
         self.jitter = 0.0
         # data version: bumped by every change; `appended` = the last change
-        # was a one-row append whose rank-1 record is on the device
+        # was a one-row append whose rank-1 record is on the device, `removed` =
+        # it was the removal of one row (`remove`), likewise
         self.version = 0
         self.appended = False
+        self.removed = False
         self.serial = next(DeviceGP._serials)
 
     def __del__(self):
@@ -545,7 +550,7 @@ class DeviceGP(object):
         self.n = X.shape[0]
         self.jitter = jit.value
         self.version += 1
-        self.appended = False
+        self.appended = self.removed = False
 
     def _hyper(self, variances, inv_ls):
         variances = f64(variances).reshape(-1)
@@ -564,7 +569,7 @@ class DeviceGP(object):
         rc = lib().sgp_gp_set_hyper(self.h, dptr(variances), dptr(inv_ls),
                                     float(noise_var), C.byref(info), C.byref(jit))
         self.version += 1
-        self.appended = False
+        self.appended = self.removed = False
         if rc > 0 or info.value != 0:
             self.n = 0
             raise np.linalg.LinAlgError(
@@ -581,7 +586,7 @@ class DeviceGP(object):
         out = np.empty(2 + P + P * d)
         info = C.c_int(0)
         self.version += 1
-        self.appended = False
+        self.appended = self.removed = False
         self.ctx.check(lib().sgp_gp_lml(self.h, dptr(variances), dptr(inv_ls),
                                         float(noise_var), dptr(out), C.byref(info)))
         self.jitter = 0.0
@@ -599,7 +604,7 @@ class DeviceGP(object):
             return False
         self.n += 1
         self.version += 1
-        self.appended = True
+        self.appended, self.removed = True, False
         return True
 
     def pop(self):
@@ -607,7 +612,20 @@ class DeviceGP(object):
         self.ctx.check(lib().sgp_gp_pop(self.h))
         self.n -= 1
         self.version += 1
-        self.appended = False
+        self.appended = self.removed = False
+
+    def remove(self, index):
+        """Forget observation ``index`` (0 .. n-1), whichever it is, by an O(n^2) downdate
+        of the factor (``sgp_gp_remove``); False = a pivot of the downdate is not positive:
+        the GP is untouched and the caller refits with set_data."""
+        info = C.c_int(0)
+        self.ctx.check(lib().sgp_gp_remove(self.h, int(index), C.byref(info)))
+        if info.value != 0:
+            return False
+        self.n -= 1
+        self.version += 1
+        self.appended, self.removed = False, True
+        return True
 
     def predict(self, Xnew):
         Xnew = np.asarray(Xnew, dtype=np.float64)
@@ -722,6 +740,7 @@ class DeviceGP(object):
         twin.ctx, twin.d, twin.h = self.ctx, self.d, h
         twin.n_parts, twin.n, twin.jitter = self.n_parts, self.n, self.jitter
         twin.version, twin.appended = self.version, self.appended
+        twin.removed = self.removed
         twin.serial = next(DeviceGP._serials)
         return twin
 
@@ -853,6 +872,16 @@ class DeviceGrid(object):
         w = np.ascontiguousarray(which, dtype=np.int32)
         out = np.empty(2)
         self.ctx.check(lib().sgp_grid_rank1_update(
+            self.h, _gp_array(gps), len(gps), w.ctypes.data_as(c_int_p),
+            float(beta), dptr(fmin), None if defer else dptr(out)))
+        return (None, None) if defer else (out[0], bool(out[1]))
+
+    def rank1_remove(self, gps, which, beta, fmin, defer=False):
+        """``rank1_update`` after one ``DeviceGP.remove`` on the GPs of ``which``."""
+        fmin = f64(fmin)
+        w = np.ascontiguousarray(which, dtype=np.int32)
+        out = np.empty(2)
+        self.ctx.check(lib().sgp_grid_rank1_remove(
             self.h, _gp_array(gps), len(gps), w.ctypes.data_as(c_int_p),
             float(beta), dptr(fmin), None if defer else dptr(out)))
         return (None, None) if defer else (out[0], bool(out[1]))

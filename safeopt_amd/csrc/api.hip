@@ -392,6 +392,7 @@ static int rewrite_hyper(sgp_gp* gp, const double* variances, const double* inv_
   gp->noise_var = noise_var;
   ++gp->data_version;
   gp->upd_valid = false;
+  gp->rem_valid = false;
   // (a refit at the current n: the history of appends and removals no longer matters)
   gp->prov = 0x9e3779b97f4a7c15ull ^ uint64_t(gp->n);
   return 0;
@@ -493,6 +494,32 @@ int sgp_gp_pop(sgp_gp* gp) {
   gp->xhost.resize(size_t(gp->n) * gp->kern.d);
   gp->xhash.resize(size_t(gp->n));
   gp->prov = gp->prov * 1099511628211ull + 3;
+  return 0;
+}
+
+int sgp_gp_remove(sgp_gp* gp, int64_t index, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
+  SGP_CHECK(ctx, gp->n > 1, "cannot remove the only training point");
+  SGP_CHECK(ctx, index >= 0 && index < gp->n, "row %lld of %lld training points",
+            (long long)index, (long long)gp->n);
+  *info = -1;
+  const int64_t n0 = gp->n;
+  SGP_TRY(remove_gp(gp, int(index), info));
+  if (gp->n != n0 - 1) return 0;               // pivot not positive: the GP is as it was
+  ++gp->data_version;
+  const size_t d = size_t(gp->kern.d), i = size_t(index);
+  gp->xhost.erase(gp->xhost.begin() + i * d, gp->xhost.begin() + (i + 1) * d);
+  gp->xhash.resize(size_t(gp->n));
+  uint64_t h = i > 0 ? gp->xhash[i - 1] : 14695981039346656037ull;
+  for (size_t r = i; r < size_t(gp->n); ++r) {
+    h = hash_rows(h, gp->xhost.data() + r * d, d);
+    gp->xhash[r] = h;
+  }
+  // (the row that left is part of the history: equal removals keep a shared factor shared)
+  gp->prov = (gp->prov * 1099511628211ull + 5) ^ (uint64_t(index) * 0x9e3779b97f4a7c15ull);
   return 0;
 }
 
@@ -634,6 +661,7 @@ int sgp_gp_clone(sgp_gp* src, sgp_gp** out) {
   gp->xhash = src->xhash;
   gp->prov = src->prov;
   gp->upd_valid = src->upd_valid;
+  gp->rem_valid = src->rem_valid;
   gp->factored = true;
   const int d = src->kern.d, ld0 = src->ld;
   const int ld = std::max(ld0, int((src->n + SGP_MAX_BATCH + 63) / 64) * 64);
@@ -1052,9 +1080,10 @@ int sgp_grid_posterior(sgp_grid* g, sgp_gp* const* gps, int G) {
                            sep_launch(g, gps, host, G, &sl), /*rows_sharded=*/true);
 }
 
-int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
-                          const int* which, double beta, const double* fmin,
-                          double* out2) {
+// sgp_grid_rank1_update / sgp_grid_rank1_remove: the flagged GPs carry the record of an
+// append / of a removal
+static int rank1_refresh(sgp_grid* g, sgp_gp* const* gps, int G, const int* which, double beta,
+                         const double* fmin, double* out2, bool remove) {
   sgp_ctx* ctx = g->ctx;
   GpDev host[SGP_MAX_GPS];
   SGP_TRY(grid_gps(g, gps, G, host));
@@ -1062,9 +1091,14 @@ int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
   for (int i = 0; i < SGP_MAX_GPS; ++i) {
     ra.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
     ra.which[i] = (i < G) ? which[i] : 0;
-    if (i < G && which[i])
-      SGP_CHECK(ctx, gps[i]->upd_valid,
-                "GP %d has no append record for a rank-1 update", i);
+    if (i < G && which[i]) {
+      if (remove)
+        SGP_CHECK(ctx, gps[i]->rem_valid,
+                  "GP %d has no removal record for a rank-1 update", i);
+      else
+        SGP_CHECK(ctx, gps[i]->upd_valid,
+                  "GP %d has no append record for a rank-1 update", i);
+    }
   }
   ra.Q = g->Q;
   ra.mean = g->mean;
@@ -1073,8 +1107,19 @@ int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
   ra.partial = g->partial;
   ra.beta = beta;
   SweepPoints sp{g->pts, g->N, 1, g->N};
-  SGP_TRY(launch_rank1(ctx, g->gpdev, G, g->d, sp, ra));
+  SGP_TRY(launch_rank1(ctx, g->gpdev, G, g->d, sp, ra, remove));
   return finish_safe_partials(g, rank1_num_blocks(g->N), out2);
+}
+
+int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
+                          const int* which, double beta, const double* fmin,
+                          double* out2) {
+  return rank1_refresh(g, gps, G, which, beta, fmin, out2, false);
+}
+
+int sgp_grid_rank1_remove(sgp_grid* g, sgp_gp* const* gps, int G, const int* which,
+                          double beta, const double* fmin, double* out2) {
+  return rank1_refresh(g, gps, G, which, beta, fmin, out2, true);
 }
 
 int sgp_grid_upload_Q(sgp_grid* g, const double* Q, const double* fmin,

@@ -102,6 +102,9 @@ struct GpDev {
   // rank-1 update of the resident posterior: w = Ky_old^-1 k(X_old, x*)
   // (zero padded to n_pad), upd[0] = (y* - mu(x*)) / s2, upd[1] = 1 / s2,
   // upd[2..2+d) = x*
+  // ... or of the last removal (sgp_gp_remove), the same four things for the row x_i that
+  // left, as an append of it to the reduced GP would write them: w = Ky_new^-1 k(X_new, x_i),
+  // upd[0] = alpha_i, upd[1] = (Ky_old^-1)_ii, upd[2..2+d) = x_i
   const double* upd_w;
   const double* upd;
   // dense L^-1 (row pitch ld) and k(x,x) + noise + 1e-8 + jitter: what the
@@ -266,6 +269,8 @@ struct sgp_gp {
                                  // (fit at n, appends, removals): two GPs with equal
                                  // inputs AND equal history have the same bits in L^-1
   bool upd_valid = false;  // dev.upd* describes the step to the current data
+  bool rem_valid = false;  // ... as the record of a REMOVAL (sgp_gp_remove): the row that left,
+                           // in the layout of an append of that row to the reduced GP
   bool factored = true;    // false: sgp_gp_lml met a non-positive pivot -- the data are
                            // resident, the factor is not valid until the next fit
   DevBuf X, Y, Xpad, Xs, XA, alpha, Apack, Linv, Kmat, work, tvec, updw, upd;
@@ -375,6 +380,8 @@ int lml_result_words(const KernDesc& kd);   // 2 + P + P d values and the pivot 
 int launch_lml(sgp_gp* gp, const int* info_dev, double* out_dev);
 int append_gp(sgp_gp* gp, double y, int* info);  // row n already in gp->X
 int pop_gp(sgp_gp* gp);
+// row `index` leaves (0 <= index < n, n >= 2); *info != 0 leaves the GP untouched
+int remove_gp(sgp_gp* gp, int index, int* info);
 int publish_gp(sgp_gp* gp);  // Apack / Xpad / Xs / dev descriptor from Linv
 struct ExpanderOps {      // all arrays on the device; [g] blocks as noted
   const double* xc;       // [m][d] candidates
@@ -547,8 +554,9 @@ struct Rank1Args {
   int which[SGP_MAX_GPS];
 };
 int rank1_num_blocks(int64_t N);
+// remove: the records are removal records (sgp_gp_remove) -- both signs of the update flip
 int launch_rank1(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d,
-                 SweepPoints pts, Rank1Args ra);
+                 SweepPoints pts, Rank1Args ra, bool remove = false);
 
 // batch.hip: one pick of a hallucinated batch (sgp_grid_batch_next).  Every GP carries the
 // append record of the previous pick: var_out = max(var_in - c(x)^2 / s2, 1e-15) per row and

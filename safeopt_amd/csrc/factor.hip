@@ -466,6 +466,7 @@ int factor_gp(sgp_gp* gp, int* info, const int** info_dev_out) {
   double* tv = static_cast<double*>(gp->tvec.p);
   int* info_dev = reinterpret_cast<int*>(tv + ld);
   gp->upd_valid = false;
+  gp->rem_valid = false;
 
   // padded rows of X are never read: n_valid = n turns them into identity
   SGP_TRY(launch_kernel_matrix(ctx, gp->kern, static_cast<double*>(gp->X.p),
@@ -583,6 +584,7 @@ int append_gp(sgp_gp* gp, double y, int* info) {
   gp->n_pad = np_new;
   gp->n_f = (n + 1 + 31) / 32 * 32;
   gp->upd_valid = true;
+  gp->rem_valid = false;
   return publish_gp(gp);
 }
 
@@ -597,9 +599,211 @@ int pop_gp(sgp_gp* gp) {
   gp->n_pad = (n + 15) / 16 * 16;
   gp->n_f = (n + 31) / 32 * 32;
   gp->upd_valid = false;
+  gp->rem_valid = false;
   SGP_TRY(launch_tri_mv(ctx, Li, ld, n, static_cast<double*>(gp->Y.p), 0, 1, tv, 0));
   SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, tv, 0, 1,
                          static_cast<double*>(gp->alpha.p), 0, gp->n_pad));
+  return publish_gp(gp);
+}
+
+// ---- removal of ANY row --------------------------------------------------------------
+// With M = L^-1 and c = column i of M (zero above row i):  P_ii = |c|^2 = (Ky^-1)_ii and
+// p = M^T c = column i of Ky^-1.  The reduced GP follows in closed form:
+//   w = -p_{-i} / P_ii  (= Ky_new^-1 k(X_new, x_i)),   alpha_new = alpha_{-i} + w alpha_i,
+// and L_new^-1 = M with column i deleted after the Givens rotations that fold c_k into c_i,
+// k = i+1 .. n-1 in that order:  gamma_i = c_i, gamma_k^2 = gamma_{k-1}^2 + c_k^2,
+// cs_k = gamma_{k-1} / gamma_k, sn_k = c_k / gamma_k, applied to the rows (i, k).  Row i
+// collects what is thrown away; every row k keeps its zeros and a positive diagonal
+// (cs_k M_kk).  {w, alpha_i, P_ii, x_i} is the record of the removal, in the layout of the
+// append record: what appending x_i to the reduced GP would write (k_rank1<.., true>).
+
+// The scratch of a removal (kSlotStage), in doubles, L = the pitch of L^-1: everything is
+// formed here, and the pivot word read back, before the GP is touched.
+struct RemoveBufs {
+  double *c, *p, *cs, *sn;   // [L] column i of M (zero above i), M^T c, the rotations
+  double *w, *alpha;         // [L + 16] the record's w and alpha_new, zero padded to n_pad
+  double *X, *Y;             // [L d], [L]: the rows behind i, one row up
+  double* rec;               // [2 + SGP_MAX_D] alpha_i | P_ii | x_i
+  int* info;
+};
+inline size_t remove_scratch_bytes(int ld, int d) {
+  return (size_t(ld) * (7 + d) + 32 + 2 + SGP_MAX_D) * sizeof(double) + 64;
+}
+inline RemoveBufs remove_bufs(double* b, int ld, int d) {
+  RemoveBufs r;
+  r.c = b;
+  r.p = r.c + ld;
+  r.cs = r.p + ld;
+  r.sn = r.cs + ld;
+  r.w = r.sn + ld;
+  r.alpha = r.w + ld + 16;
+  r.X = r.alpha + ld + 16;
+  r.Y = r.X + size_t(ld) * d;
+  r.rec = r.Y + ld;
+  r.info = reinterpret_cast<int*>(r.rec + 2 + SGP_MAX_D);
+  return r;
+}
+
+// c, P_ii and the rotation coefficients: one workgroup.  gamma_k^2 is a running sum of
+// squares -- a scan in a fixed order: every thread owns a run of consecutive k, the runs'
+// sums are scanned through the wave and then over the 16 waves.  info: 0, or index + 1
+// when P_ii or a gamma is not positive and finite.
+__global__ __launch_bounds__(1024) void k_remove_coef(const double* Li, int64_t ld, int n,
+                                                      int i, RemoveBufs rb) {
+  __shared__ double sh[1024 / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int k = tid; k < i; k += 1024) rb.c[k] = 0.0;
+  const int m = n - i;                         // entries i .. n-1 of the column
+  const int per = (m + 1023) / 1024;
+  const int e0 = min(tid * per, m), e1 = min(e0 + per, m);
+  double local = 0.0;
+  for (int e = e0; e < e1; ++e) {
+    const double ck = Li[int64_t(i + e) * ld + i];
+    rb.c[i + e] = ck;
+    local = fma(ck, ck, local);
+  }
+  double v = local;                            // inclusive scan of the wave's runs
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  if (lane == 63) sh[wave] = v;
+  double before = __shfl_up(v, 1, 64);         // the runs in front of this one, in the wave
+  if (lane == 0) before = 0.0;
+  __syncthreads();
+  double base = 0.0, total = 0.0;
+  for (int w = 0; w < 1024 / 64; ++w) {
+    if (w < wave) base += sh[w];
+    total += sh[w];
+  }
+  bool bad = false;
+  double s = base + before;                    // gamma_{k-1}^2 in front of the run
+  for (int e = e0; e < e1; ++e) {
+    const double ck = rb.c[i + e];             // (written by this thread)
+    const double s1 = fma(ck, ck, s);
+    if (e > 0) {
+      const double g1 = sqrt(s1);
+      rb.cs[i + e] = sqrt(s) / g1;
+      rb.sn[i + e] = ck / g1;
+    }
+    bad = bad || !(s1 > 0.0) || !isfinite(s1);
+    s = s1;
+  }
+  bad = bad || !(total > 0.0) || !isfinite(total);
+  const int bad_any = __syncthreads_or(bad);
+  if (tid == 0) {
+    rb.rec[1] = total;
+    rb.info[0] = bad_any ? i + 1 : 0;
+  }
+}
+
+// The images of what changes besides L^-1: w and alpha_new (zero behind n - 1, up to the
+// new n_pad), the record, and the rows of X / Y behind i moved one up.
+__global__ void k_remove_stage(const double* alpha, const double* X, const double* Y, int n,
+                               int d, int i, int n_pad_new, RemoveBufs rb) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const double Pii = rb.rec[1];
+  if (e < n_pad_new) {
+    double w = 0.0, a = 0.0;
+    if (e < n - 1) {
+      const int src = e + (e >= i ? 1 : 0);
+      w = -rb.p[src] / Pii;
+      a = fma(w, alpha[i], alpha[src]);
+    }
+    rb.w[e] = w;
+    rb.alpha[e] = a;
+  }
+  if (e >= i && e < n - 1) rb.Y[e] = Y[e + 1];
+  if (e >= i * d && e < (n - 1) * d) rb.X[e] = X[e + d];
+  if (e == 0) rb.rec[0] = alpha[i];
+  if (e < d) rb.rec[2 + e] = X[i * d + e];
+}
+
+// out = M with the rotations applied and row / column i deleted; one thread per column j of
+// M: rho = M[i][j], then rows k = max(i + 1, j) .. n-1 in order (the loads of a row are
+// coalesced over the lanes and do not depend on rho).  `out` is zero where nothing is written.
+__global__ __launch_bounds__(64) void k_remove_rotate(const double* M, double* out, int64_t ld,
+                                                      int n, int i, const double* cs,
+                                                      const double* sn) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n || j == i) return;
+  const int jo = j - (j > i ? 1 : 0);
+  for (int k = j; k < i; ++k) out[int64_t(k) * ld + jo] = M[int64_t(k) * ld + j];
+  double rho = (j < i) ? M[int64_t(i) * ld + j] : 0.0;
+  int k = max(i + 1, j);
+  constexpr int kU = 8;                        // loads in flight per lane
+  for (; k + kU <= n; k += kU) {
+    double mv[kU], c[kU], s[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      mv[u] = M[int64_t(k + u) * ld + j];
+      c[u] = cs[k + u];
+      s[u] = sn[k + u];
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      out[int64_t(k + u - 1) * ld + jo] = fma(c[u], mv[u], -(s[u] * rho));
+      rho = fma(c[u], rho, s[u] * mv[u]);
+    }
+  }
+  for (; k < n; ++k) {
+    const double mv = M[int64_t(k) * ld + j], c = cs[k], s = sn[k];
+    out[int64_t(k - 1) * ld + jo] = fma(c, mv, -(s * rho));
+    rho = fma(c, rho, s * mv);
+  }
+}
+
+// ... and the images copied over the GP, once the pivot word has said yes.
+__global__ void k_remove_commit(RemoveBufs rb, int n, int d, int i, int n_pad_new,
+                                double* alpha, double* updw, double* upd, double* X, double* Y) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n_pad_new) {
+    alpha[e] = rb.alpha[e];
+    updw[e] = rb.w[e];
+  }
+  if (e >= i && e < n - 1) Y[e] = rb.Y[e];
+  if (e >= i * d && e < (n - 1) * d) X[e] = rb.X[e];
+  if (e < 2 + d) upd[e] = rb.rec[e];
+}
+
+int remove_gp(sgp_gp* gp, int index, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  const int n = int(gp->n), ld = gp->ld, d = gp->kern.d, i = index;
+  const size_t mat = size_t(ld) * ld * sizeof(double);
+  // (a clone has no spare matrix before its first refit)
+  SGP_TRY(sgp_reserve(ctx, &gp->work, mat));
+  double* Li = static_cast<double*>(gp->Linv.p);
+  double* out = static_cast<double*>(gp->work.p);
+  double* X = static_cast<double*>(gp->X.p);
+  double* Y = static_cast<double*>(gp->Y.p);
+  double* alpha = static_cast<double*>(gp->alpha.p);
+  double* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, remove_scratch_bytes(ld, d), &buf));
+  const RemoveBufs rb = remove_bufs(buf, ld, d);
+  const int np_new = (n - 1 + 15) / 16 * 16;
+  const int elems = std::max(np_new, std::max((n - 1) * d, 2 + d));
+  hipLaunchKernelGGL(k_remove_coef, dim3(1), dim3(1024), 0, ctx->stream, Li, int64_t(ld), n, i,
+                     rb);
+  SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, rb.c, 0, 1, rb.p, 0, n));
+  hipLaunchKernelGGL(k_remove_stage, dim3((elems + 255) / 256), dim3(256), 0, ctx->stream,
+                     alpha, X, Y, n, d, i, np_new, rb);
+  SGP_HIP(ctx, hipMemsetAsync(out, 0, mat, ctx->stream));
+  hipLaunchKernelGGL(k_remove_rotate, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, Li, out,
+                     int64_t(ld), n, i, rb.cs, rb.sn);
+  SGP_HIP(ctx, hipGetLastError());
+  SGP_TRY(sgp_d2h(ctx, info, rb.info, sizeof(int)));
+  if (*info != 0) return 0;
+  hipLaunchKernelGGL(k_remove_commit, dim3((elems + 255) / 256), dim3(256), 0, ctx->stream, rb,
+                     n, d, i, np_new, alpha, static_cast<double*>(gp->updw.p),
+                     static_cast<double*>(gp->upd.p), X, Y);
+  SGP_HIP(ctx, hipGetLastError());
+  std::swap(gp->Linv, gp->work);
+  gp->n = n - 1;
+  gp->n_pad = np_new;
+  gp->n_f = (n - 1 + 31) / 32 * 32;
+  gp->upd_valid = false;
+  gp->rem_valid = true;
   return publish_gp(gp);
 }
 

@@ -1588,9 +1588,25 @@ __global__ __launch_bounds__(256) void k_expander_list(const GpDev* gps, int G,
 // GP this is n covariance evaluations and n FMAs on the VALU -- no n^2 term.
 // Lane (r, q) = (lane & 15, lane >> 4) handles row r and training points
 // j = q (mod 4); the four partial dot products are folded with two shuffles.
+// kRemove: the record is that of a REMOVAL (sgp_gp_remove) -- the row x_i that left, written
+// as an append of it to the reduced GP would write it -- and the update runs backwards:
+// mean -= c alpha_i, var += c^2 P_ii, with c(x) = k(x, x_i) - k(X_new, x)^T w as before.
 constexpr int kRank1Lds = 6144;   // doubles of staged training data (48 KB)
 
-template <int D>
+// mean / var of a row after the record {u0, u1} of an append (of a removal: kRemove)
+template <bool kRemove>
+__device__ __forceinline__ void rank1_apply(double cx, double u0, double u1, double& mean,
+                                            double& var) {
+  if (kRemove) {
+    mean = fma(-cx, u0, mean);
+    var = fmax(var + cx * cx * u1, 1e-15);
+  } else {
+    mean = fma(cx, u0, mean);
+    var = fmax(var - cx * cx * u1, 1e-15);
+  }
+}
+
+template <int D, bool kRemove>
 __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
                                                SweepPoints pts, Rank1Args ra) {
   __shared__ double tab[kExpTabSize];
@@ -1624,8 +1640,7 @@ __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
     double var = ra.var[int64_t(g) * pts.N + rrow];
     if (ra.which[g] && gps[g].share >= 0 && have_cx) {
       const GpDev& gp = gps[g];
-      mean = fma(cx_keep, gp.upd[0], mean);
-      var = fmax(var - cx_keep * cx_keep * gp.upd[1], 1e-15);
+      rank1_apply<kRemove>(cx_keep, gp.upd[0], gp.upd[1], mean, var);
       if (writer) {
         ra.mean[int64_t(g) * pts.N + row] = mean;
         ra.var[int64_t(g) * pts.N + row] = var;
@@ -1662,8 +1677,7 @@ __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
       const double cx = kf.raw(x, gp.upd + 2, tab) - dot;
       cx_keep = cx;
       have_cx = true;
-      mean = fma(cx, gp.upd[0], mean);
-      var = fmax(var - cx * cx * gp.upd[1], 1e-15);
+      rank1_apply<kRemove>(cx, gp.upd[0], gp.upd[1], mean, var);
       if (writer) {
         ra.mean[int64_t(g) * pts.N + row] = mean;
         ra.var[int64_t(g) * pts.N + row] = var;
@@ -2249,13 +2263,17 @@ int launch_verify_axes(sgp_grid* g, int* mismatch_dev) {
 int rank1_num_blocks(int64_t N) { return int((N + 63) / 64); }
 
 int launch_rank1(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d,
-                 SweepPoints pts, Rank1Args ra) {
+                 SweepPoints pts, Rank1Args ra, bool remove) {
   if (pts.N <= 0) return 0;
   const int nblocks = rank1_num_blocks(pts.N);
 #define R1_CASE(DD)                                                           \
   case DD:                                                                    \
-    hipLaunchKernelGGL(k_rank1<DD>, dim3(nblocks), dim3(256), 0, ctx->stream, \
-                       gps_dev, G, pts, ra);                                  \
+    if (remove)                                                               \
+      hipLaunchKernelGGL((k_rank1<DD, true>), dim3(nblocks), dim3(256), 0,    \
+                         ctx->stream, gps_dev, G, pts, ra);                   \
+    else                                                                      \
+      hipLaunchKernelGGL((k_rank1<DD, false>), dim3(nblocks), dim3(256), 0,   \
+                         ctx->stream, gps_dev, G, pts, ra);                   \
     break;
   switch (d) {
     R1_CASE(1) R1_CASE(2) R1_CASE(3) R1_CASE(4)

@@ -70,7 +70,8 @@ class GaussianProcessOptimization(object):
     Same constructor, attributes and methods as the base class of the
     reference (``gp_opt.py:30-278``): ``gps`` / ``gp``, ``fmin`` (one per GP),
     ``beta`` (always callable), ``scaling``, ``x`` / ``y`` / ``data`` / ``t``,
-    ``add_new_data_point`` / ``remove_last_data_point``.
+    ``add_new_data_point`` / ``remove_last_data_point``; ``remove_data_point`` forgets
+    any measurement (not in the reference).
     """
 
     def __init__(self, gp, fmin, beta=2, num_contexts=0, threshold=0,
@@ -161,6 +162,31 @@ class GaussianProcessOptimization(object):
             if not np.isnan(value):
                 self._remove_last_data_point(gp)
         self._x, self._y = self._x[:-1, :], self._y[:-1, :]
+
+    def remove_data_point(self, index):
+        """Forget measurement ``index`` of the log (``0 <= index < t``), whichever it is: a
+        faulty reading, the oldest one of a sliding window.  Every GP that observed it drops
+        it -- its row there is the number of measurements in front of ``index`` that the GP
+        observed -- by an O(n^2) downdate of its factor (``GPRegression.remove_data``), and
+        the next ``optimize()`` of a ``SafeOpt`` corrects the resident posterior in closed
+        form instead of sweeping the grid again.  ``IndexError`` for an index outside the
+        log, ``ValueError`` when a GP would be left without data; nothing has changed then.
+        On N ranks nothing is different: the GPs are replicated, every rank makes the same
+        call, and the correction of the posterior is local to the rows of a rank."""
+        if isinstance(index, bool) or index != int(index) or not 0 <= index < self.t:
+            raise IndexError("measurement %r of %d" % (index, self.t))
+        index = int(index)
+        seen = ~np.isnan(self._y[index])
+        rows = [int(np.count_nonzero(~np.isnan(self._y[:index, i])))
+                for i in range(len(self.gps))]
+        for i, gp in enumerate(self.gps):
+            if seen[i] and gp.X.shape[0] < 2:
+                raise ValueError("GP %d would be left without data" % i)
+        for i, gp in enumerate(self.gps):
+            if seen[i]:
+                gp.remove_data(rows[i])
+        self._x = np.delete(self._x, index, axis=0)
+        self._y = np.delete(self._y, index, axis=0)
 
 
 #: Hook of the CPU test-suite (tests/_oracle_backend.py): a callable ``(gps, rows of
@@ -279,17 +305,22 @@ class _HipGridBackend(object):
         tags = self._tags(devs)
         which = [0] * len(devs)
         rank1 = self.incremental and self._rank1_streak < self.refresh_every
+        kinds = set()                            # of the stale GPs' one-row changes
         for i, dv in enumerate(devs):
             if self._seen[i] == tags[i]:
                 continue                                  # up to date
-            if (rank1 and dv.appended and self._seen[i] is not None
+            removed = getattr(dv, 'removed', False)
+            if (rank1 and (dv.appended or removed) and self._seen[i] is not None
                     and self._seen[i] == (dv.serial, dv.version - 1)):
-                which[i] = 1                              # one append behind
+                which[i] = 1                              # one append / one removal behind
+                kinds.add(removed)
             else:
                 rank1 = False
+        rank1 = rank1 and len(kinds) == 1        # (appends and removals mixed: a sweep)
         self._seen = [None] * len(devs)          # unknown until the call is through
         if rank1 and any(which):
-            out = self.grid.rank1_update(devs, which, beta, fmin, defer)
+            refresh = self.grid.rank1_remove if kinds.pop() else self.grid.rank1_update
+            out = refresh(devs, which, beta, fmin, defer)
             self._rank1_streak += 1
         else:
             out = self.grid.confidence(devs, beta, fmin, defer)

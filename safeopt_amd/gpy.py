@@ -248,6 +248,25 @@ class GPRegression(object):
         dev.set_data(X, Y[:, 0])
         self._dev_fitted = True
 
+    def remove_data(self, index):
+        """Forget observation ``index`` (0 .. n-1), whichever it is: an O(n^2) downdate
+        of the factor on the device (``sgp_gp_remove``) instead of the refit ``set_XY``
+        with the reduced arrays costs -- which is what happens with ``incremental =
+        False``, or when a pivot of the downdate is not positive."""
+        n = self.X.shape[0]
+        if not -n <= index < n:
+            raise IndexError("observation %d of %d" % (index, n))
+        if n < 2:
+            raise ValueError("cannot remove the only observation")
+        index = int(index) % n
+        X, Y = np.delete(self.X, index, axis=0), np.delete(self.Y, index, axis=0)
+        dev = self._device_gp()
+        if (self._dev_fitted and dev.n == n and self.incremental
+                and dev.remove(index)):
+            self.X, self.Y = X, Y
+            return
+        self.set_XY(X, Y)
+
     def _fitted(self):
         """Device GP, fitted.  Hot path: a comparison of the hyper-parameter bytes
         when nothing changed; an edited kernel parameter or ``noise_var`` refits the
