@@ -504,13 +504,36 @@ int sgp_grid_paths_comm(sgp_grid* grid, sgp_gp* gp, const double* Omega, const d
  * over the rows that are not among picked[n_picked] (GLOBAL rows, n_picked <= SGP_MAX_BATCH);
  * the lowest global row wins among equal values; value = -inf, gidx = -1 when no row is
  * eligible (var_h is downdated all the same).  Q, S, M, G, mean and var are only read.  One
- * launch of the row kernel, a small final kernel, one read-back.  One rank.  var_h (G,N) is
- * a buffer of the grid, allocated by the first call: sgp_grid_download(SGP_VAR_H).        */
+ * launch of the row kernel, a small final kernel, one read-back.  The pick of the SHARD the
+ * grid holds: the call never communicates, whatever communicator the context has (the pick
+ * over all ranks: sgp_grid_batch_next_comm).  var_h (G,N) is a buffer of the grid, allocated
+ * by the first call: sgp_grid_download(SGP_VAR_H).                                        */
 int sgp_grid_batch_next(sgp_grid* grid, sgp_gp* const* gps, int G, int first, int mode,
                         double beta, const double* scaling, const int64_t* picked,
                         int n_picked, double* value, int64_t* gidx);
+/* sgp_grid_batch_next on a grid whose context has a communicator (sgp_comm_init or
+ * sgp_comm_init_host): one pick of a batch over the shards of all ranks.  Every rank runs the
+ * row kernel and the final kernel of sgp_grid_batch_next over its resident rows; its record
+ * {value, GLOBAL row, stop} is all-gathered -- ONE collective per pick, in stream on RCCL,
+ * through the host transport otherwise -- and one one-wave kernel merges the world records:
+ * the largest value, the lowest global row among equal values; a shard without an eligible
+ * row (-inf / -1) never wins against one with a row, and no eligible row on any shard gives
+ * -inf / -1.  *stop_any = the maximum of the ranks' stop words.  Every rank returns the same
+ * (value, gidx, stop_any) after ONE read-back of the merged record.
+ * stop != 0: this rank takes no part in the pick (the bordered append of its clones met a
+ * non-positive pivot) but still makes the call -- a collective, every rank must arrive: no
+ * row kernel runs, var_h stays as it was, the clones' append records are not looked at, and
+ * the rank contributes {-inf, -1, 1}.  The ranks end the batch together on stop_any.
+ * picked[] are global rows, the same on every rank.  Everything else -- modes, first, the
+ * refusals (no append record, another mode, n_picked > SGP_MAX_BATCH, first = 0 before a
+ * downdate) -- as sgp_grid_batch_next; without a communicator (one rank) it equals
+ * sgp_grid_batch_next, with *stop_any = stop.                                            */
+int sgp_grid_batch_next_comm(sgp_grid* grid, sgp_gp* const* gps, int G, int first, int mode,
+                             double beta, const double* scaling, const int64_t* picked,
+                             int n_picked, int stop, double* value, int64_t* gidx,
+                             int* stop_any);
 /* copy a resident array to the host: Q (N,2G) f64 | S/M/G (N) u8 |
- * mean/var/var_h (G,N) f64 (var_h: after a sgp_grid_batch_next)              */
+ * mean/var/var_h (G,N) f64 (var_h: after a sgp_grid_batch_next[_comm])       */
 /* S / M / G of the shard from the host: the reference's arrays are mutated in place
  * (safeopt/gp_opt.py:481, 505-506, 511, 615) and user code may write into them; the next
  * arg-max (get_new_query_point, gp_opt.py:635-649) reads what was uploaded.            */
@@ -619,8 +642,9 @@ int sgp_swarm_run_path(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
  * everything else as for sgp_swarm_run.  Like a path run it ALWAYS takes the general
  * launches -- move, fitness (downdate, posterior, shaping), personal bests, global best --
  * never the one-workgroup step of a small swarm: with rand != NULL the run is bit-identical
- * to the host loop over sgp_swarm_fitness_hall.  The whole swarm in one call.  The refusals
- * of sgp_swarm_fitness_hall; P <= 0 returns 0 and writes nothing.               */
+ * to the host loop over sgp_swarm_fitness_hall.  The whole swarm in one call (a rank's
+ * block: sgp_swarm_run_hall_shard).  The refusals of sgp_swarm_fitness_hall; P <= 0 returns 0
+ * and writes nothing.                                                           */
 int sgp_swarm_run_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
                        int swarm_type, double beta, const double* fmin, const double* scaling,
                        double best_lower_bound, int64_t P, double* positions,
@@ -663,6 +687,22 @@ int sgp_swarm_run_path_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double bet
                              int iters, double inertia0, double step, const double* rand,
                              uint64_t seed, const double* Omega, const double* phase, int m,
                              const double* w, const double* v, int64_t p0, int64_t P_total);
+
+/* sgp_swarm_run_hall on a rank's block [p0, p0 + P) of a hallucinated swarm of P_total: the
+ * block, the merge of the global best after init and after every iteration, the Philox
+ * indexing and the layout of rand are those of sgp_swarm_run_shard; the posterior kernel
+ * follows P_total; every rank passes clones with the same pending picks.  The downdate is
+ * per particle (sgp_swarm_fitness_hall), so a block computes the bits the whole swarm
+ * computes for its particles.  The refusals of sgp_swarm_run_hall.  p0 = 0, P = P_total is
+ * sgp_swarm_run_hall; P < P_total needs a communicator on ctx, and P >= 1 on every rank.  */
+int sgp_swarm_run_hall_shard(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                             int swarm_type, double beta, const double* fmin,
+                             const double* scaling, double best_lower_bound, int64_t P,
+                             double* positions, double* velocities, double* best_positions,
+                             double* best_values, double* global_best,
+                             const double* velocity_scale, const double* bounds, int init,
+                             int iters, double inertia0, double step, const double* rand,
+                             uint64_t seed, int64_t p0, int64_t P_total);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------
  * The only cross-rank traffic of the path is a handful of scalars per

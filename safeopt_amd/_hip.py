@@ -79,6 +79,9 @@ PROTOTYPES = {
     "sgp_gp_clone": (C.c_int, [vp, vpp]),
     "sgp_grid_batch_next": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_int, C.c_double,
                                       c_double_p, c_i64_p, C.c_int, c_double_p, c_i64_p]),
+    "sgp_grid_batch_next_comm": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_int, C.c_double,
+                                           c_double_p, c_i64_p, C.c_int, C.c_int, c_double_p,
+                                           c_i64_p, c_int_p]),
     "sgp_kern_K": (C.c_int, [vp, C.c_int, C.c_int, c_int_p, c_double_p,
                              c_double_p, c_double_p, C.c_int64, c_double_p,
                              C.c_int64, c_double_p]),
@@ -189,6 +192,12 @@ PROTOTYPES = {
                                      c_double_p, c_double_p, c_double_p, C.c_int,
                                      C.c_int, C.c_double, C.c_double, c_double_p,
                                      C.c_uint64]),
+    "sgp_swarm_run_hall_shard": (C.c_int, [vp, vpp, vpp, C.c_int, C.c_int, C.c_double,
+                                           c_double_p, c_double_p, C.c_double, C.c_int64,
+                                           c_double_p, c_double_p, c_double_p, c_double_p,
+                                           c_double_p, c_double_p, c_double_p, C.c_int,
+                                           C.c_int, C.c_double, C.c_double, c_double_p,
+                                           C.c_uint64, C.c_int64, C.c_int64]),
     "sgp_swarm_run_path": (C.c_int, [vp, vpp, C.c_int, C.c_double,
                                      c_double_p, c_double_p, C.c_int64,
                                      c_double_p, c_double_p, c_double_p, c_double_p,
@@ -1226,6 +1235,22 @@ class DeviceGrid(object):
             C.byref(i)))
         return v.value, i.value
 
+    def batch_next_comm(self, gps, first, mode, beta, scaling, picked, stop=False):
+        """``batch_next`` over the shards of all ranks of the context's communicator
+        (``sgp_grid_batch_next_comm``): ``(value, global row, stop_any)``, the same on every
+        rank -- a collective, every rank calls it.  ``stop``: this rank takes no part in the
+        pick (its append failed) and only reports that; ``stop_any``: some rank did."""
+        scaling = f64(scaling)
+        picked = np.ascontiguousarray(picked, dtype=np.int64).reshape(-1)
+        v = C.c_double(0)
+        i = C.c_int64(0)
+        any_stop = C.c_int(0)
+        self.ctx.check(lib().sgp_grid_batch_next_comm(
+            self.h, _gp_array(gps), len(gps), int(bool(first)), int(mode), float(beta),
+            dptr(scaling), picked.ctypes.data_as(c_i64_p), int(picked.size), int(bool(stop)),
+            C.byref(v), C.byref(i), C.byref(any_stop)))
+        return v.value, i.value, bool(any_stop.value)
+
     def paths(self, gp, Omega, phase, W, V, mask=False, values=False, best=True, comm=False):
         """Sample paths of ``gp`` over the resident rows (``sgp_grid_paths``): ``(values (N, S)
         or None, best value (S), its global row (S))`` -- the arg-max over all rows, or over
@@ -1326,13 +1351,14 @@ def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=Non
     velocity_scale, bounds)`` -- the first five updated in place -- and ``schedule = (init,
     iters, inertia0, step, rand, seed)``, the structs of the C side.  ``path`` (a Thompson
     swarm; ``swarm_type`` and the best lower bound are not used), ``clones`` (a hallucinated
-    swarm) and ``shard = (p0, P_total)`` pick the entry point."""
+    swarm) and ``shard = (p0, P_total)`` pick the entry point (``sgp_swarm_run[_hall|_path]
+    [_shard]``)."""
     beta, fmin, scaling, best_lower_bound = fit
     init, iters, inertia0, step, rand, seed = schedule
     P = state[0].shape[0]
-    if clones is not None and (path is not None or shard is not None):
-        raise NotImplementedError("a hallucinated swarm is a whole maximizers or expanders "
-                                  "swarm on one rank")
+    if clones is not None and path is not None:
+        raise NotImplementedError("a hallucinated swarm is a maximizers or an expanders "
+                                  "swarm, not a Thompson swarm")
     name, head, tail = _swarm_call(ctx, "sgp_swarm_run", gps, swarm_type, path, clones)
     for a in state[:5]:
         assert a.dtype == np.float64 and a.flags.c_contiguous
@@ -1430,10 +1456,15 @@ def swarm_fitness_hall(ctx, gps, clones, swarm_type, particles, beta, fmin, scal
 
 def swarm_run_hall(ctx, gps, clones, swarm_type, beta, fmin, scaling, best_lower_bound,
                    positions, velocities, best_positions, best_values, global_best,
-                   velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0):
+                   velocity_scale, bounds, init, iters, inertia0, step, rand, seed=0,
+                   shard=None):
     """Whole PSO run of a hallucinated swarm on the device (``sgp_swarm_run_hall``); the state
-    arrays are updated in place, ``clones`` as for :func:`swarm_fitness_hall`."""
+    arrays are updated in place, ``clones`` as for :func:`swarm_fitness_hall`.
+
+    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
+    ``P_total`` sharded over the ranks of ``ctx``'s communicator
+    (``sgp_swarm_run_hall_shard``), as for :func:`swarm_run`."""
     _swarm_run(ctx, gps, swarm_type, (beta, fmin, scaling, best_lower_bound),
                (positions, velocities, best_positions, best_values, global_best,
                 velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
-               clones=clones)
+               clones=clones, shard=shard)

@@ -1272,19 +1272,25 @@ int sgp_grid_argmax(sgp_grid* g, int mode, const double* scaling, double* value,
 
 // One pick of a hallucinated batch: csrc/batch.hip.  The GPs are clones that carry the append
 // record of the pending pick; nothing the real step left on the grid is written.
-int sgp_grid_batch_next(sgp_grid* g, sgp_gp* const* gps, int G, int first, int mode,
-                        double beta, const double* scaling, const int64_t* picked,
-                        int n_picked, double* value, int64_t* gidx) {
-  sgp_ctx* ctx = g->ctx;
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(grid_gps(g, gps, G, host));
+// batch_checks: what every entry refuses, whether or not its rank takes part in the pick.
+static int batch_checks(sgp_ctx* ctx, int mode, int n_picked) {
   SGP_CHECK(ctx, mode == SGP_ARGMAX_MG_WIDTH || mode == SGP_ARGMAX_UCB,
             "sgp_grid_batch_next: mode %d is not SGP_ARGMAX_MG_WIDTH / SGP_ARGMAX_UCB", mode);
   SGP_CHECK(ctx, n_picked >= 0 && n_picked <= SGP_MAX_BATCH,
             "sgp_grid_batch_next: %d rows picked before (SGP_MAX_BATCH = %d)", n_picked,
             SGP_MAX_BATCH);
-  SGP_CHECK(ctx, ctx->world <= 1, "sgp_grid_batch_next runs on one rank (this is rank %d of %d)",
-            ctx->rank, ctx->world);
+  return 0;
+}
+
+// The shard's pick, enqueued: the row kernel and k_batch_final leave {value, global row} in
+// bs->res_v / res_i.  extra: bytes of scratch the caller wants behind the pick's.
+static int batch_enqueue(sgp_grid* g, sgp_gp* const* gps, int G, int first, int mode,
+                         double beta, const double* scaling, const int64_t* picked,
+                         int n_picked, size_t extra, BatchScratch* bs) {
+  sgp_ctx* ctx = g->ctx;
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
+  SGP_TRY(batch_checks(ctx, mode, n_picked));
   for (int i = 0; i < G; ++i)
     SGP_CHECK(ctx, gps[i]->upd_valid, "GP %d has no append record for a hallucinated downdate",
               i);
@@ -1297,8 +1303,8 @@ int sgp_grid_batch_next(sgp_grid* g, sgp_gp* const* gps, int G, int first, int m
   }
   const int nb = batch_num_blocks(g->N);
   void* scr;
-  SGP_TRY(sgp_scratch(ctx, kSlotPartials, batch_scratch_bytes(nb), &scr));
-  const BatchScratch bs = batch_scratch(scr, nb);
+  SGP_TRY(sgp_scratch(ctx, kSlotPartials, batch_scratch_bytes(nb) + extra, &scr));
+  *bs = batch_scratch(scr, nb);
   BatchArgs ba{};
   ba.mean = g->mean;
   ba.var_in = first ? g->var : g->var_h;
@@ -1312,14 +1318,71 @@ int sgp_grid_batch_next(sgp_grid* g, sgp_gp* const* gps, int G, int first, int m
   ba.goff = g->goff;
   ba.n_picked = n_picked;
   for (int k = 0; k < n_picked; ++k) ba.picked[k] = picked[k];
-  ba.part_v = bs.part_v;
-  ba.part_i = bs.part_i;
+  ba.part_v = bs->part_v;
+  ba.part_i = bs->part_i;
   SweepPoints sp{g->pts, g->N, 1, g->N};
-  SGP_TRY(launch_batch_pick(ctx, g->gpdev, G, g->d, sp, ba, bs.res_v, bs.res_i));
+  return launch_batch_pick(ctx, g->gpdev, G, g->d, sp, ba, bs->res_v, bs->res_i);
+}
+
+int sgp_grid_batch_next(sgp_grid* g, sgp_gp* const* gps, int G, int first, int mode,
+                        double beta, const double* scaling, const int64_t* picked,
+                        int n_picked, double* value, int64_t* gidx) {
+  sgp_ctx* ctx = g->ctx;
+  BatchScratch bs;
+  SGP_TRY(batch_enqueue(g, gps, G, first, mode, beta, scaling, picked, n_picked, 0, &bs));
   char res[16];
   SGP_TRY(sgp_d2h(ctx, res, bs.res_v, 16));
   memcpy(value, res, 8);
   memcpy(gidx, res + 8, 8);
+  return 0;
+}
+
+// The pick over the shards of all ranks: this rank's record {value, global row, stop} behind
+// its own pick (or {-inf, -1, 1} without one), ONE all-gather, k_batch_merge, ONE read-back.
+int sgp_grid_batch_next_comm(sgp_grid* g, sgp_gp* const* gps, int G, int first, int mode,
+                             double beta, const double* scaling, const int64_t* picked,
+                             int n_picked, int stop, double* value, int64_t* gidx,
+                             int* stop_any) {
+  sgp_ctx* ctx = g->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  bool comm;
+  SGP_TRY(comm_or_single(ctx, &comm));
+  stop = stop != 0;
+  if (!comm) {
+    *stop_any = stop;
+    if (!stop)
+      return sgp_grid_batch_next(g, gps, G, first, mode, beta, scaling, picked, n_picked,
+                                 value, gidx);
+    SGP_TRY(batch_checks(ctx, mode, n_picked));
+    *value = -INFINITY;
+    *gidx = -1;
+    return 0;
+  }
+  const int world = ctx->world;
+  const int nb = batch_num_blocks(g->N);
+  const size_t extra = batch_comm_scratch_bytes(nb, world) - batch_scratch_bytes(nb);
+  BatchScratch bs;
+  if (stop) {
+    // (no row kernel: var_h stays as it was; the call is still made -- the other ranks wait
+    // in the all-gather)
+    SGP_TRY(batch_checks(ctx, mode, n_picked));
+    void* scr;
+    SGP_TRY(sgp_scratch(ctx, kSlotPartials, batch_scratch_bytes(nb) + extra, &scr));
+    bs = batch_scratch(scr, nb);
+  } else {
+    SGP_TRY(batch_enqueue(g, gps, G, first, mode, beta, scaling, picked, n_picked, extra, &bs));
+  }
+  const BatchCommScratch cs = batch_comm_scratch(bs, world);
+  SGP_TRY(launch_batch_stop(ctx, cs.rec, stop));
+  SGP_TRY(coll_allgather(ctx, cs.rec, cs.recs, kBatchRecBytes));
+  SGP_TRY(launch_batch_merge(ctx, cs.recs, world, cs.merged));
+  char res[kBatchRecBytes];
+  SGP_TRY(sgp_d2h(ctx, res, cs.merged, kBatchRecBytes));
+  int64_t any;
+  memcpy(value, res, 8);
+  memcpy(gidx, res + 8, 8);
+  memcpy(&any, res + 16, 8);
+  *stop_any = any != 0;
   return 0;
 }
 

@@ -126,6 +126,49 @@ __global__ __launch_bounds__(256) void k_batch_final(const double* in_v, const i
   }
 }
 
+// The record of a rank that takes no part in a pick (`stop`: its bordered append met a
+// non-positive pivot) -- {-inf, -1, 1} --, or the stop word 0 behind the pair k_batch_final
+// leaves.  rec: value | row | stop, 8 bytes each.
+__global__ void k_batch_stop(double* rec, int stop) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int64_t* w = reinterpret_cast<int64_t*>(rec);
+  if (stop) {
+    rec[0] = -INFINITY;
+    w[1] = -1;
+  }
+  w[2] = stop ? 1 : 0;
+}
+
+// The ranks' records of one pick (value | global row | stop, gathered in rank order) merged
+// by ONE wave in the order of before_first: the largest value, the lowest global row among
+// equal values, a record without a row (-1) never in front of one with a row; out[2] = the
+// maximum of the stop words.  No row on any rank: -inf / -1.
+__global__ __launch_bounds__(64) void k_batch_merge(const double* recs, int world, double* out) {
+  const int lane = threadIdx.x;
+  const int64_t* w = reinterpret_cast<const int64_t*>(recs);
+  Pair best{-INFINITY, -1};
+  int64_t stop = 0;
+  for (int r = lane; r < world; r += 64) {
+    const Pair p{recs[3 * r], w[3 * r + 1]};
+    if (before_first(p, best)) best = p;
+    stop = w[3 * r + 2] > stop ? w[3 * r + 2] : stop;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    Pair q;
+    q.v = __shfl_xor(best.v, o, 64);
+    q.i = __shfl_xor(best.i, o, 64);
+    if (before_first(q, best)) best = q;
+    const int64_t s = __shfl_xor(stop, o, 64);
+    stop = s > stop ? s : stop;
+  }
+  if (lane == 0) {
+    out[0] = best.i >= 0 ? best.v : -INFINITY;
+    reinterpret_cast<int64_t*>(out)[1] = best.i;
+    reinterpret_cast<int64_t*>(out)[2] = stop;
+  }
+}
+
 }  // namespace
 
 int batch_num_blocks(int64_t N) { return int((N + 63) / 64); }
@@ -149,6 +192,18 @@ int launch_batch_pick(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d, SweepPoi
   SGP_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_batch_final, dim3(1), dim3(256), 0, ctx->stream, ba.part_v, ba.part_i,
                      nblocks, res_v, res_i);
+  SGP_HIP(ctx, hipGetLastError());
+  return 0;
+}
+
+int launch_batch_stop(sgp_ctx* ctx, double* rec, int stop) {
+  hipLaunchKernelGGL(k_batch_stop, dim3(1), dim3(64), 0, ctx->stream, rec, stop);
+  SGP_HIP(ctx, hipGetLastError());
+  return 0;
+}
+
+int launch_batch_merge(sgp_ctx* ctx, const double* recs, int world, double* out) {
+  hipLaunchKernelGGL(k_batch_merge, dim3(1), dim3(64), 0, ctx->stream, recs, world, out);
   SGP_HIP(ctx, hipGetLastError());
   return 0;
 }

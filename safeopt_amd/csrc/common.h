@@ -597,6 +597,27 @@ inline BatchScratch batch_scratch(void* base, int nb) {
 // the downdate and the per-workgroup pairs, then the final pair into (res_v, res_i)
 int launch_batch_pick(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d, SweepPoints pts,
                       BatchArgs ba, double* res_v, int64_t* res_i);
+// A pick over the ranks (sgp_grid_batch_next_comm): behind the scratch of the shard's pick,
+//   stop | records[world][3] | merged[3]
+// (value, res_i) and `stop` are this rank's record {value, global row, stop}, 8 bytes each;
+// the records are gathered in rank order and merged into {value, row, stop_any}.
+constexpr size_t kBatchRecBytes = 24;
+inline size_t batch_comm_scratch_bytes(int nb, int world) {
+  return batch_scratch_bytes(nb) + 8 + (size_t(world) + 1) * kBatchRecBytes;
+}
+struct BatchCommScratch {
+  double* rec;      // = BatchScratch::res_v
+  double* recs;
+  double* merged;
+};
+inline BatchCommScratch batch_comm_scratch(const BatchScratch& bs, int world) {
+  double* rec = bs.res_v;
+  return BatchCommScratch{rec, rec + 3, rec + 3 + 3 * size_t(world)};
+}
+// rec[2] = stop; with stop also rec[0..1] = {-inf, -1} (the rank runs no row kernel)
+int launch_batch_stop(sgp_ctx* ctx, double* rec, int stop);
+// k_batch_merge: one wave over the world records, before_first's order, the maximum stop
+int launch_batch_merge(sgp_ctx* ctx, const double* recs, int world, double* out);
 
 // sweep_tiny.hip: do the GPs of a launch go through the VALU kernel (every one with at most
 // 48 observations)?
@@ -865,7 +886,8 @@ static_assert(swarm_fit_layout_ok(1, 1, 1, false) && swarm_fit_layout_ok(1, 1, 1
               "SwarmFitLayout: a region is misaligned or overlaps its neighbour");
 static_assert(swarm_run_layout_ok(1, 1, 1, 0, false) && swarm_run_layout_ok(1, 1, 1, 0, true) &&
                   swarm_run_layout_ok(65, 3, SGP_MAX_GPS, 0, true) &&
-                  swarm_run_layout_ok(33, 3, 2, 4, false),
+                  swarm_run_layout_ok(33, 3, 2, 4, false) &&
+                  swarm_run_layout_ok(33, 3, 2, 4, true),
               "SwarmRunLayout: a region is misaligned or overlaps its neighbour");
 // The swarm kernels take the rank's block of particles [p0, p0 + P) of a swarm of P_total:
 // e0 / e2 are the global element indices of the block's first r1 / r2 number on the

@@ -1,6 +1,6 @@
 // The swarm entry points of the C ABI (include/safeopt_hip.h): host-side launch sequences
 // around the kernels of swarm.hip, paths.hip, swarm_batch.hip and the posterior sweeps.
-// Eight exported fitness / run functions fill SwarmSpec / SwarmState / PsoSchedule
+// Nine exported fitness / run functions fill SwarmSpec / SwarmState / PsoSchedule
 // (common.h) and share ONE fitness routine and ONE run routine.
 #include <string.h>
 
@@ -98,8 +98,9 @@ static int path_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, int m) {
 //   sgp_swarm_fitness_path  "no GP", path, return 0 if P <= 0, GPs
 //   sgp_swarm_run[_shard]   type, "no GP", "bad swarm size", "bad block", "needs a
 //                           communicator", GPs
-//   sgp_swarm_run_hall      "no clones"; P <= 0: clones, return; else type, "no GP", "bad
-//                           swarm size" (iterations), "bad block", communicator, clones, GPs
+//   sgp_swarm_run_hall[_shard]  "no clones"; P <= 0 and P_total <= 0: clones, return; else
+//                           type, "no GP", "bad swarm size", "bad block", communicator,
+//                           clones, GPs (an empty block of a sharded swarm: "bad swarm size")
 //   sgp_swarm_run_path[_shard]  "no GP", path, return 0 if P <= 0 and P_total <= 0, then as
 //                           sgp_swarm_run_shard (an empty block of a sharded swarm is the
 //                           "bad swarm size" error, not a silent return: the other ranks
@@ -404,16 +405,30 @@ int sgp_swarm_run_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, 
                        double* global_best, const double* velocity_scale,
                        const double* bounds, int init, int iters, double inertia0,
                        double step_size, const double* rand, uint64_t seed) {
+  return sgp_swarm_run_hall_shard(ctx, gps, clones, G, swarm_type, beta, fmin, scaling,
+                                  best_lower_bound, P, positions, velocities, best_positions,
+                                  best_values, global_best, velocity_scale, bounds, init, iters,
+                                  inertia0, step_size, rand, seed, 0, P);
+}
+
+int sgp_swarm_run_hall_shard(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clones, int G,
+                             int swarm_type, double beta, const double* fmin,
+                             const double* scaling, double best_lower_bound, int64_t P,
+                             double* positions, double* velocities, double* best_positions,
+                             double* best_values, double* global_best,
+                             const double* velocity_scale, const double* bounds, int init,
+                             int iters, double inertia0, double step_size, const double* rand,
+                             uint64_t seed, int64_t p0, int64_t P_total) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, clones != nullptr, "no clones");
-  if (P <= 0) {
+  if (P <= 0 && P_total <= 0) {
     GpDev chost[SGP_MAX_GPS];
     int b;
     return hall_clones(ctx, gps, clones, G, swarm_type, chost, &b);
   }
   const SwarmSpec s{gps, G, swarm_type, beta, fmin, scaling, best_lower_bound, nullptr, clones};
   const SwarmState st{positions, velocities, best_positions, best_values, global_best,
-                      velocity_scale, bounds, P, 0, P};
+                      velocity_scale, bounds, P, p0, P_total};
   return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});
 }
 

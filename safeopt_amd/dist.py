@@ -23,7 +23,8 @@ import time
 import numpy as np
 
 __all__ = ["shard_range", "allgather_rows", "LocalComm", "RcclComm", "SocketComm", "init_from_env",
-           "merge_topk", "merge_argmax", "merge_path_records", "check_same_paths",
+           "merge_topk", "merge_argmax", "merge_path_records", "merge_batch_records",
+           "gather_shard_columns", "check_same_paths",
            "launch_check"]
 
 
@@ -55,6 +56,15 @@ def allgather_rows(comm, part, counts=None, count_dtype=np.int64):
     buf[:part.shape[0]] = part
     allp = comm.allgather(buf)
     return np.concatenate([allp[r][:c] for r, c in enumerate(counts)])
+
+
+def gather_shard_columns(comm, part, N):
+    """``(G, N)`` on every rank from the ranks' ``(G, N_local)`` blocks of the columns
+    ``shard_range(N, rank, world)``, in global column order: one ``allgather_rows`` per row
+    of ``part`` (per GP, for the resident per-row arrays of a sharded grid)."""
+    part = np.asarray(part)
+    counts = [hi - lo for lo, hi in (shard_range(N, r, comm.world) for r in range(comm.world))]
+    return np.stack([allgather_rows(comm, row, counts) for row in part])
 
 
 def _digest48(arrays):
@@ -502,3 +512,14 @@ def merge_path_records(values, idxs):
     for s in range(S):
         bv[s], bi[s] = merge_argmax(values[:, s], idxs[:, s])
     return bv, bi
+
+
+def merge_batch_records(records):
+    """One pick of a sharded hallucinated batch from the ranks' records ``(world, 3)``:
+    ``{value, global row, stop}`` per rank (the host form of ``k_batch_merge``).  Value and
+    row merge as in :func:`merge_argmax` -- a rank without an eligible row (row -1) never
+    wins, none on any rank gives ``(-inf, -1)`` --, and any rank's ``stop`` stops all.
+    Returns ``(value, global row, stop_any)``."""
+    records = np.asarray(records, dtype=np.float64).reshape(-1, 3)
+    v, i = merge_argmax(records[:, 0], records[:, 1].astype(np.int64))
+    return v, i, bool(np.any(records[:, 2] != 0))

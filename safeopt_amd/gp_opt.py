@@ -31,8 +31,9 @@ import weakref
 import numpy as np
 
 from . import _hip
-from .dist import (LocalComm, allgather_rows, check_same_paths, merge_argmax,
-                   merge_path_records, merge_topk, shard_range)
+from .dist import (LocalComm, allgather_rows, check_same_paths, gather_shard_columns,
+                   merge_argmax, merge_batch_records, merge_path_records, merge_topk,
+                   shard_range)
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
 
 __all__ = ['SafeOpt', 'SafeOptSwarm']
@@ -458,16 +459,24 @@ class _HipGridBackend(object):
     def download(self, what):
         return self.grid.download(what)
 
-    def batch(self, inputs, row0, size, mode, beta, scaling, want_var=False):
+    def batch(self, inputs, row0, size, mode, beta, scaling, want_var=False, comm=None):
         """The rows of a batch by hallucinated observations behind the pick ``row0`` of the
         real step (``SafeOpt.optimize_batch`` has the definition): private clones of the GPs,
         and per further pick one append of the pick before to every clone -- with ``y = 0``:
         only the variance is read -- and one ``sgp_grid_batch_next``.  ``inputs``: the rows
-        of the grid on the host (global row -> x).  Returns ``(rows, downdates, var_h)``:
-        the global rows picked, how many of them the hallucinated variances ``var_h``
-        ``(G, N)`` account for (None without ``want_var``).  The user's GPs and the resident
-        posterior, intervals and sets are only read; the clones are released on every way
-        out."""
+        of the WHOLE grid on the host (global row -> x).  Returns ``(rows, downdates,
+        var_h)``: the global rows picked, how many of them the hallucinated variances
+        ``var_h`` ``(G, N)`` account for (None without ``want_var``).  The user's GPs and the
+        resident posterior, intervals and sets are only read; the clones are released on
+        every way out.
+
+        ``comm`` with ``world > 1`` (every rank makes the call): the grid is this rank's
+        shard, every rank clones its own GPs and appends the same rows, and a pick is the
+        best record ``{value, global row, stop}`` of all ranks -- ``_pick_over_ranks``: one
+        collective per pick.  A rank whose append fails still takes part, with ``stop``:
+        all ranks end the batch together.  ``var_h`` is gathered over the ranks in global
+        row order."""
+        world = 1 if comm is None else comm.world
         devs = self._dev()
         if not self.posterior_is_current():
             # (intervals assigned by hand, or data added since the last sweep: the downdates
@@ -480,13 +489,23 @@ class _HipGridBackend(object):
                     for dv in devs:
                         clones.append(dv.clone())
                 x = np.asarray(inputs[rows[-1]], dtype=float)
-                if not all([c.append(x, 0.0) for c in clones]):
+                ok = all([c.append(x, 0.0) for c in clones])
+                if not ok:
                     logging.getLogger(__name__).info(
                         "optimize_batch: pick %d (row %d) is determined to rounding by the "
                         "picks before it (non-positive pivot of the bordered append): the "
                         "batch ends with %d points", b - 1, rows[-1], len(rows))
-                    break
-                _v, i = self.grid.batch_next(clones, downdates == 0, mode, beta, scaling, rows)
+                    if world == 1:
+                        break
+                if world == 1:
+                    _v, i = self.grid.batch_next(clones, downdates == 0, mode, beta, scaling,
+                                                 rows)
+                else:
+                    i, stop = self._pick_over_ranks(comm, clones, not ok, downdates == 0, mode,
+                                                    beta, scaling, rows)
+                    if stop:
+                        downdates += int(ok)         # (this rank's var_h took the downdate)
+                        break
                 downdates += 1
                 if i < 0:
                     break
@@ -494,10 +513,28 @@ class _HipGridBackend(object):
             var_h = None
             if want_var:
                 var_h = self.grid.download(_hip.VAR_H if downdates else _hip.VAR)
+                if world > 1:
+                    var_h = gather_shard_columns(comm, var_h, inputs.shape[0])
         finally:
             for c in clones:
                 c.destroy()
         return np.asarray(rows, dtype=np.int64), downdates, var_h
+
+    def _pick_over_ranks(self, comm, clones, stop, first, mode, beta, scaling, rows):
+        """One pick of a sharded batch, ``(global row, stop_any)``, the same on every rank.
+        With an in-stream communicator ``sgp_grid_batch_next_comm``: the records are gathered
+        and merged in the grid's stream, one device round trip.  Otherwise the shard's pick
+        (``sgp_grid_batch_next``, none for a rank that stops), one ``allgather`` of the
+        records and ``dist.merge_batch_records``: the same bits."""
+        if getattr(comm, 'in_stream', False):
+            _v, i, stop_any = self.grid.batch_next_comm(clones, first, mode, beta, scaling,
+                                                        rows, stop=stop)
+            return i, stop_any
+        v, i = (-np.inf, -1) if stop else self.grid.batch_next(clones, first, mode, beta,
+                                                               scaling, rows)
+        rec = comm.allgather(np.array([v, float(i), float(stop)]))       # (rows < 2^53)
+        _v, i, stop_any = merge_batch_records(rec)
+        return i, stop_any
 
     def paths(self, pp, mask, values, comm=False):
         """Sample paths ``pp`` (of one of this backend's GPs) over the resident rows; ``comm``:
@@ -1421,25 +1458,42 @@ class SafeOpt(GaussianProcessOptimization):
         Returns ``X (k, d_parameters)``, context columns stripped as ``optimize()`` strips
         them; with ``return_state=True`` ``(X, rows (k,) int64, var_h (G, N))``: the global
         rows picked and the hallucinated variances after the last downdate (tests, plots).
-        ``size`` above ``SGP_MAX_BATCH`` (64) raises ``ValueError``; more than one rank raises
-        ``NotImplementedError`` before anything runs."""
+        ``size`` above ``SGP_MAX_BATCH`` (64) raises ``ValueError``.
+
+        N ranks (SPMD, as ``optimize()``: the same data and the same call on every rank):
+        every rank clones its own device GPs, appends the same picks to them and downdates
+        the variances of its shard; a pick is the best row of all shards -- one collective of
+        one record ``{value, global row, stop}`` per rank and pick: gathered and merged in
+        the grid's stream with an in-stream communicator (``sgp_grid_batch_next_comm``, one
+        device round trip per pick), else by one ``allgather`` and
+        ``dist.merge_batch_records``.  Both give the bits of the one-rank run, on every rank:
+        ``X``, ``rows`` (global) and ``var_h`` (gathered, ``(G, N)`` in global row order).
+        The batch ends early on every rank at once: no eligible row on any shard, or a
+        non-positive pivot on any rank (``stop``; that rank still takes part in the
+        collective).  A communicator of several ranks without a device context
+        (``comm.ctx``) cannot run the clones' appends next to its grid: there
+        ``optimize_batch`` runs on one rank only and raises ``NotImplementedError`` before
+        anything runs."""
         size = int(size)
         if size < 1 or size > _hip.MAX_BATCH:
             raise ValueError("size must be in 1 .. SGP_MAX_BATCH = %d, got %d"
                              % (_hip.MAX_BATCH, size))
-        if self._comm.world > 1:
-            raise NotImplementedError("optimize_batch runs on one rank (this communicator has "
-                                      "%d)" % self._comm.world)
+        world = self._comm.world
+        if world > 1 and getattr(self._comm, 'ctx', None) is None:
+            raise NotImplementedError(
+                "optimize_batch runs on one rank unless the communicator carries a device "
+                "context (this communicator of %d ranks has no ctx)" % world)
         if not hasattr(self._backend, 'batch'):
             raise NotImplementedError("this grid backend hallucinates no observations")
         x0 = self.optimize(context=context, ucb=ucb)
         mode = _hip.ARGMAX_UCB if ucb else _hip.ARGMAX_MG_WIDTH
         cached = self._argmax_cache
-        # (the row of x_0: the arg-max optimize() took -- its cache, or the same pass again)
+        # (the row of x_0: the arg-max optimize() took -- its cache, or the same pass again,
+        # merged over the ranks)
         row0 = cached[1] if (not ucb and cached is not None) else self._global_argmax(mode)[1]
         rows, _downdates, var_h = self._backend.batch(
             self.inputs, row0, size, mode, self.beta(self.t), self.scaling,
-            want_var=return_state)
+            want_var=return_state, **({'comm': self._comm} if world > 1 else {}))
         X = self.inputs[rows, :self.inputs.shape[1] - self.num_contexts]
         X[0] = x0
         return (X, rows, var_h) if return_state else X
@@ -1792,8 +1846,18 @@ class SafeOptSwarm(GaussianProcessOptimization):
         Returns ``X (k, d)``, ``1 <= k <= size``; with ``return_state=True`` ``(X, sd_h (k,
         G))``: the hallucinated standard deviation of every GP at every pick when it was
         picked (row 0: the real ones).  ``size`` outside ``1 .. SGP_MAX_BATCH`` (64) raises
-        ``ValueError``; more than one rank raises ``NotImplementedError`` before anything
-        runs or is drawn.
+        ``ValueError``.
+
+        N ranks (SPMD, as ``optimize()``: the same data, seed and call on every rank): the
+        hallucinated swarms are split over the ranks by particle like every other swarm
+        (``sgp_swarm_run_hall_shard``: the global best merged on the device after every
+        iteration, the personal bests gathered after a run); every rank clones its own
+        device GPs and appends the same picks.  The start draws, the ``'safe_set'`` recheck
+        of the gathered personal bests, ``swarm_batch_choice`` and the predictions on the
+        clones stay replicated, so every rank returns the bits of the one-rank run and
+        NumPy's generator ends where the one-rank run leaves it.  Several ranks whose
+        communicator carries no device context (``comm.ctx``): ``optimize_batch`` runs on one
+        rank only there and raises ``NotImplementedError`` before anything runs or is drawn.
 
         NumPy's global generator is consumed in this order:
 
@@ -1807,15 +1871,16 @@ class SafeOptSwarm(GaussianProcessOptimization):
            numbers as ``rand(swarm_size d)`` and ``rand(2 swarm_size d max_iters)``, one C
            call each; ``'device-rng'``: nothing.
 
-        Out of scope: N ranks; growing ``S`` from hallucinated runs; all picks or both
-        swarms in one launch."""
+        Out of scope: growing ``S`` from hallucinated runs; all picks or both swarms in one
+        launch."""
         size = int(size)
         if size < 1 or size > _hip.MAX_BATCH:
             raise ValueError("size must be in 1 .. SGP_MAX_BATCH = %d, got %d"
                              % (_hip.MAX_BATCH, size))
-        if self._comm.world > 1:
-            raise NotImplementedError("optimize_batch runs on one rank (this communicator has "
-                                      "%d)" % self._comm.world)
+        if self._comm.world > 1 and getattr(self._comm, 'ctx', None) is None:
+            raise NotImplementedError(
+                "optimize_batch runs on one rank unless the communicator carries a device "
+                "context (this communicator of %d ranks has no ctx)" % self._comm.world)
         x0 = np.array(self.optimize(ucb=ucb), dtype=float)
         sd0 = np.sqrt([gp.predict_noiseless(x0[None, :])[1].item() for gp in self.gps])
         iters = int(max_iters or self.max_iters)
@@ -1824,7 +1889,7 @@ class SafeOptSwarm(GaussianProcessOptimization):
         if size > 1 and isinstance(self.swarms['maximizers'], DeviceSwarmOptimization):
             swarms = {t: DeviceSwarmOptimization(
                 self.swarm_size, self.optimal_velocities, self, t, bounds=self.bounds,
-                rng=self.swarms['maximizers']._rng) for t in types}
+                rng=self.swarms['maximizers']._rng, comm=self._comm) for t in types}
 
         def candidate(swarm_type, clones):
             pick = self._side_swarm_pick(

@@ -151,7 +151,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
     ``set_clones(clones)`` on a ``'maximizers'`` or ``'expanders'`` swarm: a hallucinated
     swarm of ``SafeOptSwarm.optimize_batch`` -- the width term of the fitness comes from the
     clones of the owner's GPs, which carry the pending picks (``sgp_swarm_fitness_hall`` /
-    ``sgp_swarm_run_hall``); one rank only.
+    ``sgp_swarm_run_hall``); with ``comm`` it is sharded like every other swarm
+    (``sgp_swarm_run_hall_shard``), every rank holding clones with the same pending picks.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
@@ -199,9 +200,6 @@ class DeviceSwarmOptimization(SwarmOptimization):
             if self._type not in ('maximizers', 'expanders'):
                 raise ValueError("only a 'maximizers' or an 'expanders' swarm takes clones, "
                                  "this is %r" % (self._type,))
-            if self._comm.world > 1:
-                raise NotImplementedError("a hallucinated swarm runs on one rank (this "
-                                          "communicator has %d)" % self._comm.world)
             clones = list(clones)
         self._clones = clones
 
