@@ -130,6 +130,35 @@ int sgp_gp_set_hyper(sgp_gp* gp, const double* variances, const double* inv_ls,
  * data returns the same bits.  On success the GP is fitted at theta.               */
 int sgp_gp_lml(sgp_gp* gp, const double* variances, const double* inv_ls,
                double noise_var, double* out, int* info);
+/* Leave-one-out predictions of a fitted GP (Rasmussen & Williams 5.4.2), every observation
+ * predicted from all the others, in closed form from the resident L^-1 and alpha -- O(n^2)
+ * for all n together, whatever appends and removals led to the factor:
+ *   P_ii = (Ky^-1)_ii = sum_{k >= i} (L^-1)_ki^2
+ *   mean[i] = y_i - alpha_i / P_ii
+ *   var[i]  = 1 / P_ii      (of the NOISY y_i: noise_var + 1e-8 + jitter included)
+ *   *sum_log_pred = sum_i [ -1/2 log var[i] - 1/2 (y_i - mean[i])^2 / var[i] - 1/2 log 2 pi ]
+ * n = 1 gives the prior: mean 0, var Ky_11.  *info = 0, or i + 1 for the first P_ii that
+ * is not positive and finite -- nothing is written then.  Deterministic: the column sums
+ * are formed in a fixed order.  A GP that is not fitted is an error.                     */
+int sgp_gp_loo(sgp_gp* gp, double* mean, double* var, double* sum_log_pred, int* info);
+/* The leave-one-out log pseudo-likelihood L_LOO (= *sum_log_pred of sgp_gp_loo) and its
+ * gradient at a full set of hyper-parameters: arguments, result block, jitter = 0 and the
+ * contract of sgp_gp_lml -- the data are factorised at theta; *info = the first non-positive
+ * pivot (or the first P_ii that is not positive and finite) leaves the GP unfitted with its
+ * data resident, otherwise the GP is fitted at theta:
+ *   out[0]                L_LOO
+ *   out[1]                d/d noise_var
+ *   out[2 .. 2+P)         d/d variance[p]
+ *   out[2+P .. 2+P+P*d)   d/d inv_ls[p*d + a]   (0 for a column the part does not use)
+ * The gradient is sum_ij G_ij dKy_ij/dtheta (R&W eq. 5.13 rearranged), with
+ *   a_i = alpha_i / P_ii,   b_i = 1/2 (1 + alpha_i^2 / P_ii) / P_ii,   u = Ky^-1 a,
+ *   G = 1/2 (u alpha^T + alpha u^T) - C^T C,   C = diag(sqrt(b)) Ky^-1,
+ * and dKy/dtheta as for sgp_gp_lml.  Deterministic.  Device memory: C, n x n doubles (n
+ * rounded up to 64 in one direction), in scratch of the CONTEXT: it grows to the largest n
+ * asked for and stays allocated after the call, until sgp_destroy -- 33 MB once n = 2000
+ * has been evaluated, 2.1 GB at the 16384 observations a GP can hold.                      */
+int sgp_gp_loo_lml(sgp_gp* gp, const double* variances, const double* inv_ls,
+                   double noise_var, double* out, int* info);
 /* gp.predict_noiseless(Xnew, full_cov=True) (GPy: Posterior._raw_predict): mean (N), cov
  * (N x N row-major, exactly symmetric).  cov = k(X*,X*) - V^T V, V = L^-1 k(X,X*); its
  * diagonal is NOT clipped (GPy clips only the full_cov=False variance).  Strides as

@@ -54,6 +54,9 @@ PROTOTYPES = {
                                    c_int_p, c_double_p]),
     "sgp_gp_lml": (C.c_int, [vp, c_double_p, c_double_p, C.c_double, c_double_p,
                              c_int_p]),
+    "sgp_gp_loo": (C.c_int, [vp, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "sgp_gp_loo_lml": (C.c_int, [vp, c_double_p, c_double_p, C.c_double, c_double_p,
+                                 c_int_p]),
     "sgp_gp_append": (C.c_int, [vp, c_double_p, C.c_double, c_int_p]),
     "sgp_gp_pop": (C.c_int, [vp]),
     "sgp_gp_remove": (C.c_int, [vp, C.c_int64, c_int_p]),
@@ -601,6 +604,36 @@ class DeviceGP(object):
         self.jitter = 0.0
         return (float(out[0]), float(out[1]), out[2:2 + P].copy(),
                 out[2 + P:].reshape(P, d).copy(), int(info.value))
+
+    def loo_lml(self, variances, inv_ls, noise_var):
+        """``(L_LOO, d/d noise_var, d/d variance[P], d/d inv_ls[P, d], info)``: the
+        leave-one-out log pseudo-likelihood and its gradient at theta, the 5-tuple and the
+        contract of ``lml`` (``sgp_gp_loo_lml``)."""
+        variances, inv_ls = self._hyper(variances, inv_ls)
+        P, d = self.n_parts, self.d
+        out = np.empty(2 + P + P * d)
+        info = C.c_int(0)
+        self.version += 1
+        self.appended = self.removed = False
+        self.ctx.check(lib().sgp_gp_loo_lml(self.h, dptr(variances), dptr(inv_ls),
+                                            float(noise_var), dptr(out), C.byref(info)))
+        self.jitter = 0.0
+        return (float(out[0]), float(out[1]), out[2:2 + P].copy(),
+                out[2 + P:].reshape(P, d).copy(), int(info.value))
+
+    def loo(self):
+        """``(mean, var, sum_log_pred)``: every observation predicted from all the others
+        (``(n,)`` each; ``var`` is that of the noisy observation) and the sum of their log
+        predictive densities, from the factor as it stands (``sgp_gp_loo``).
+        ``LinAlgError`` when a ``(Ky^-1)_ii`` is not positive and finite."""
+        mean, var = np.empty(self.n), np.empty(self.n)
+        total, info = C.c_double(0), C.c_int(0)
+        self.ctx.check(lib().sgp_gp_loo(self.h, dptr(mean), dptr(var), C.byref(total),
+                                        C.byref(info)))
+        if info.value != 0:
+            raise np.linalg.LinAlgError("(Ky^-1)_ii of observation %d is not positive"
+                                        % (info.value - 1))
+        return mean, var, float(total.value)
 
     def append(self, x, y):
         """One more observation by a bordered update; False = not possible

@@ -458,6 +458,47 @@ int sgp_gp_lml(sgp_gp* gp, const double* variances, const double* inv_ls, double
   return 0;
 }
 
+int sgp_gp_loo_lml(sgp_gp* gp, const double* variances, const double* inv_ls, double noise_var,
+                   double* out, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_TRY(rewrite_hyper(gp, variances, inv_ls, noise_var));
+  gp->jitter = 0.0;
+  gp->factored = false;          // until the info word says otherwise
+  const int words = lml_result_words(gp->kern);
+  double* res;
+  SGP_TRY(sgp_scratch(ctx, kSlotResult, size_t(words) * sizeof(double), &res));
+  const int* info_dev = nullptr;
+  int unused = 0;
+  SGP_TRY(factor_gp(gp, &unused, &info_dev));
+  SGP_TRY(launch_loo_lml(gp, info_dev, res));
+  double host[3 + SGP_MAX_PARTS + SGP_MAX_PARTS * SGP_MAX_D];
+  SGP_TRY(sgp_d2h(ctx, host, res, size_t(words) * sizeof(double)));
+  *info = int(host[words - 1]);
+  gp->factored = *info == 0;
+  memcpy(out, host, size_t(words - 1) * sizeof(double));
+  return 0;
+}
+
+int sgp_gp_loo(sgp_gp* gp, double* mean, double* var, double* sum_log_pred, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
+  const double* dev = nullptr;
+  int np = 0;
+  SGP_TRY(launch_loo(gp, &dev, &np));
+  std::vector<double> host(size_t(2) * np + 2);
+  SGP_TRY(sgp_d2h(ctx, host.data(), dev, host.size() * sizeof(double)));
+  *info = int(host[size_t(2) * np + 1]);
+  if (*info != 0) return 0;
+  const size_t n = size_t(gp->n);
+  memcpy(mean, host.data(), n * sizeof(double));
+  memcpy(var, host.data() + np, n * sizeof(double));
+  *sum_log_pred = host[size_t(2) * np];
+  return 0;
+}
+
 int sgp_gp_append(sgp_gp* gp, const double* x, double y, int* info) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));

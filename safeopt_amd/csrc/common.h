@@ -179,6 +179,10 @@ enum ScratchSlot : int {
   kSlotPathB = 19,      // ... [amp W ; V], zero padded
   kSlotPathOut = 20,    // ... path values (rows x S); path_weights' U | E | T | V
   kSlotPathPart = 21,   // ... per-workgroup (value, row) partials of the arg-max, the result
+  kSlotLooVec = 22,     // hyper.hip: the vectors of a leave-one-out call (LooVec)
+  kSlotLooC = 23,       // ... C = diag(sqrt(b)) Ky^-1 of sgp_gp_loo_lml (n x n: like every slot
+                        // it stays at its largest size until sgp_destroy, 2.1 GB after one
+                        // call at kMaxObservations)
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }
@@ -271,7 +275,7 @@ struct sgp_gp {
   bool upd_valid = false;  // dev.upd* describes the step to the current data
   bool rem_valid = false;  // ... as the record of a REMOVAL (sgp_gp_remove): the row that left,
                            // in the layout of an append of that row to the reduced GP
-  bool factored = true;    // false: sgp_gp_lml met a non-positive pivot -- the data are
+  bool factored = true;    // false: sgp_gp_lml / sgp_gp_loo_lml met a non-positive pivot: the data are
                            // resident, the factor is not valid until the next fit
   DevBuf X, Y, Xpad, Xs, XA, alpha, Apack, Linv, Kmat, work, tvec, updw, upd;
   GpDev dev;      // filled by set_data
@@ -369,6 +373,12 @@ int joint_predict_cov(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_
 int joint_posterior_draw(sgp_gp* gp, const double* Xnew, int64_t N, int64_t stride_row,
                          int64_t stride_col, const double* Z, int S, double* out, double* mean,
                          int* chol_info, double* jitter_used);
+// T[c][i] = sum_{j <= i} Li[i][j] V[c][j]  and  W[c][j] = sum_{i >= j} Li[i][j] T[c][i]
+// (0 for n <= j < n_out): the triangular mat-vecs behind alpha, m <= 16 right-hand sides
+int tri_mv_dense(sgp_ctx* ctx, const double* Li, int64_t ld, int n, const double* V,
+                 int64_t ldv, int m, double* T, int64_t ldo);
+int tri_mtv_dense(sgp_ctx* ctx, const double* Li, int64_t ld, int n, const double* T,
+                  int64_t ldt, int m, double* W, int64_t ldo, int n_out);
 int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
                          int64_t n1, const double* X2, int64_t n2, double* out,
                          int64_t ld, int symmetric_diag, double diag_add,
@@ -378,6 +388,11 @@ int factor_gp(sgp_gp* gp, int* info, const int** info_dev_out = nullptr);
 // hyper.hip: log marginal likelihood and gradient of a GP factor_gp has just factorised
 int lml_result_words(const KernDesc& kd);   // 2 + P + P d values and the pivot word
 int launch_lml(sgp_gp* gp, const int* info_dev, double* out_dev);
+// ... the leave-one-out objective and gradient in the same block, likewise
+int launch_loo_lml(sgp_gp* gp, const int* info_dev, double* out_dev);
+// leave-one-out predictions from the factor as it stands: *out_dev = [mean | var] (*np doubles
+// each, n rounded up to 64) | sum of the log predictive densities | info (as a double)
+int launch_loo(sgp_gp* gp, const double** out_dev, int* np);
 int append_gp(sgp_gp* gp, double y, int* info);  // row n already in gp->X
 int pop_gp(sgp_gp* gp);
 // row `index` leaves (0 <= index < n, n >= 2); *info != 0 leaves the GP untouched

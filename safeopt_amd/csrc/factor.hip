@@ -369,6 +369,16 @@ int gemm_dense(sgp_ctx* ctx, bool transB, int m, int n, int k, double alpha, con
   return gemm(ctx, transB, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
 }
 
+int tri_mv_dense(sgp_ctx* ctx, const double* Li, int64_t ld, int n, const double* V,
+                 int64_t ldv, int m, double* T, int64_t ldo) {
+  return launch_tri_mv(ctx, Li, ld, n, V, ldv, m, T, ldo);
+}
+
+int tri_mtv_dense(sgp_ctx* ctx, const double* Li, int64_t ld, int n, const double* T,
+                  int64_t ldt, int m, double* W, int64_t ldo, int n_out) {
+  return launch_tri_mtv(ctx, Li, ld, n, T, ldt, m, W, ldo, n_out);
+}
+
 int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
                          int64_t n1, const double* X2, int64_t n2, double* out,
                          int64_t ld, int symmetric_diag, double diag_add,

@@ -189,6 +189,28 @@ class GaussianProcessOptimization(object):
         self._x = np.delete(self._x, index, axis=0)
         self._y = np.delete(self._y, index, axis=0)
 
+    def loo_residuals(self):
+        """Standardised leave-one-out residuals of the log, ``(t, n_gps)``: column ``g`` holds
+        GP ``g``'s ``z = (y - mean_-i) / sqrt(var_-i)`` of every measurement it observed
+        (``GPRegression.loo_residuals``, O(n^2) per GP from its resident factor), ``nan``
+        where it did not.  Changes nothing in the optimiser."""
+        out = np.full(self._y.shape, np.nan)
+        for g, gp in enumerate(self.gps):
+            seen = ~np.isnan(self._y[:, g])
+            out[seen, g] = gp.loo_residuals()[:, 0]
+        return out
+
+    def suspect_data_points(self, threshold=3.0):
+        """Indices of the measurements that the other measurements do not explain:
+        ``max_g |z| > threshold`` over the GPs' leave-one-out residuals, the largest first
+        (ties by index).  Each can be passed straight to ``remove_data_point``.  Changes
+        nothing in the optimiser."""
+        z = np.abs(np.asarray(self.loo_residuals(), dtype=float))
+        z = z.reshape(z.shape[0], -1)
+        worst = np.max(np.where(np.isnan(z), -np.inf, z), axis=1) if z.size else np.zeros(0)
+        order = np.lexsort((np.arange(worst.size), -worst))
+        return [int(i) for i in order if worst[i] > threshold]
+
 
 #: Hook of the CPU test-suite (tests/_oracle_backend.py): a callable ``(gps, rows of
 #: this rank, global offset) -> backend`` that stands in for ``_HipGridBackend`` so the

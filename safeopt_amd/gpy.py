@@ -281,13 +281,14 @@ class GPRegression(object):
         return dev
 
     # -- fitting the hyper-parameters
-    def _evaluate(self, variances, inv_ls, noise_var):
+    def _evaluate(self, variances, inv_ls, noise_var, loo=False):
         """One device call: likelihood and gradient at theta; the device GP is left
-        fitted there (or unfitted, data resident, when theta is infeasible)."""
+        fitted there (or unfitted, data resident, when theta is infeasible).  ``loo``: the
+        leave-one-out log pseudo-likelihood instead of the marginal likelihood."""
         dev = self._dev
         if dev is None or dev.n != self.X.shape[0]:
             dev = self._fitted()
-        out = dev.lml(variances, inv_ls, noise_var)
+        out = (dev.loo_lml if loo else dev.lml)(variances, inv_ls, noise_var)
         self._dev_fitted = out[4] == 0
         self._dev_key = (self.input_dim, self._dev_key[1], np.asarray(variances).tobytes(),
                          np.asarray(inv_ls).tobytes(), float(noise_var))
@@ -315,20 +316,63 @@ class GPRegression(object):
     def objective_function(self):
         return -self.log_likelihood()
 
-    def optimize(self, optimizer='lbfgsb', max_iters=1000, messages=False, fixed=()):
+    # -- leave-one-out cross-validation (Rasmussen & Williams 5.4.2)
+    def _evaluate_loo(self, variances, inv_ls, noise_var):
+        return self._evaluate(variances, inv_ls, noise_var, loo=True)
+
+    def _evaluator(self, objective):
+        """The evaluate callback of ``optimize(objective=...)``; checked before any device
+        use."""
+        if objective == 'lml':
+            return self._evaluate
+        if objective == 'loo':
+            return self._evaluate_loo
+        raise ValueError("objective %r: 'lml' (marginal likelihood) or 'loo' (leave-one-out "
+                         "log pseudo-likelihood)" % (objective,))
+
+    def loo(self):
+        """Leave-one-out predictions ``(mean, var)``, ``(n, 1)`` each: every observation
+        predicted from all the others at the current hyper-parameters, ``var`` the
+        predictive variance of the noisy observation.  Closed form from the resident
+        factor, O(n^2) for all of them together (``sgp_gp_loo``)."""
+        mean, var, _ = self._fitted().loo()
+        return mean[:, None], var[:, None]
+
+    def loo_residuals(self):
+        """Standardised leave-one-out residuals ``z = (y - mean) / sqrt(var)``, ``(n, 1)``:
+        about N(0, 1) each when the model explains the data; a faulty reading stands out."""
+        mean, var = self.loo()
+        return (self.Y - mean) / np.sqrt(var)
+
+    def log_pseudo_likelihood(self):
+        """The leave-one-out log pseudo-likelihood ``L_LOO = sum_i log p(y_i | X, y_-i,
+        theta)`` at the current hyper-parameters."""
+        self._fitted()
+        desc = self.kern._desc(self.input_dim)
+        ll, _, _, _, info = self._evaluate_loo(desc[2], desc[3], self.noise_var)
+        self._settle()
+        if info != 0:
+            raise np.linalg.LinAlgError("not positive definite (pivot %d)" % info)
+        return ll
+
+    def optimize(self, optimizer='lbfgsb', max_iters=1000, messages=False, fixed=(),
+                 objective='lml'):
         """Maximise the marginal likelihood over the hyper-parameters (L-BFGS-B on the
         softplus-transformed values, GPy's defaults); every evaluation is one device
         call.  ``fixed``: names to leave alone (``'noise_var'``, ``'<part>.variance'``,
         ``'<part>.lengthscale'``; ``'variance'`` / ``'lengthscale'`` for a single
         kernel).  The fitted values are written in place into ``kern`` / ``noise_var``
         and the model is fitted at them.  Returns an object with ``f_opt``, ``x_opt``,
-        ``funct_eval``, ``status``."""
+        ``funct_eval``, ``status``.  ``objective='loo'`` maximises the leave-one-out log
+        pseudo-likelihood instead (``f_opt = -L_LOO``): more robust than the marginal
+        likelihood when the kernel family does not fit the data."""
+        evaluate = self._evaluator(objective)
         if optimizer not in ('lbfgsb', 'lbfgs', None):
             raise NotImplementedError("optimizer %r (only 'lbfgsb')" % (optimizer,))
         self._fitted()
         params = _hyper.Parameters(self.kern, self.noise_var, self.input_dim, fixed)
         try:
-            res = _hyper.optimize(params, self._evaluate, max_iters=max_iters,
+            res = _hyper.optimize(params, evaluate, max_iters=max_iters,
                                   messages=messages)
         finally:
             self.noise_var = params.noise_var
@@ -338,14 +382,15 @@ class GPRegression(object):
     def optimize_restarts(self, num_restarts=10, robust=True, **kwargs):
         """``optimize`` from the current values and from ``num_restarts - 1`` random
         starts (``N(0, 1)`` per transformed parameter, NumPy's global generator);
-        keeps the best."""
+        keeps the best.  ``objective`` as in ``optimize``."""
         fixed = kwargs.pop('fixed', ())
+        evaluate = self._evaluator(kwargs.pop('objective', 'lml'))
         if kwargs.pop('optimizer', 'lbfgsb') not in ('lbfgsb', 'lbfgs', None):
             raise NotImplementedError("only 'lbfgsb'")
         self._fitted()
         params = _hyper.Parameters(self.kern, self.noise_var, self.input_dim, fixed)
         try:
-            res = _hyper.optimize_restarts(params, self._evaluate, num_restarts=num_restarts,
+            res = _hyper.optimize_restarts(params, evaluate, num_restarts=num_restarts,
                                            robust=robust, **kwargs)
         finally:
             self.noise_var = params.noise_var

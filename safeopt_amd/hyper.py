@@ -9,8 +9,10 @@ vector ``x``, kept positive the way GPy does by default: ``theta = log(1 + exp(x
         -> (log_likelihood, d/d noise_var, d/d variances[P], d/d inv_ls[P, d], info)
 
 in the device descriptor's layout (``kern._desc``); ``info != 0`` or a non-finite value
-marks an infeasible point.  The product only ever passes ``_hip.DeviceGP.lml``; the seam
-is what the tests drive with a NumPy likelihood.
+marks an infeasible point.  The product only ever passes ``_hip.DeviceGP.lml`` or, for
+``optimize(objective='loo')``, ``_hip.DeviceGP.loo_lml`` (the leave-one-out log
+pseudo-likelihood in the same layout); the seam is what the tests drive with a NumPy
+likelihood.
 """
 from __future__ import annotations
 
