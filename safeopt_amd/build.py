@@ -17,20 +17,25 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(PKG, "libsafeopt_hip.so")
-SOURCES = ["api.hip", "batch.hip", "sweep.hip", "sweep_pair.hip", "sweep_mid.hip", "sweep_tiny.hip",
-           "step_small.hip",
+SOURCES = ["api.hip", "expander_api.hip", "batch.hip", "sweep.hip", "expander.hip", "sweep_pair.hip",
+           "sweep_mid.hip", "sweep_tiny.hip", "step_small.hip",
            "factor.hip", "hyper.hip", "joint.hip", "paths.hip", "sets.hip", "swarm.hip",
            "swarm_api.hip", "swarm_batch.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "kern_eval.h", "fitness.h",
                                             "small_path.h", "sweep_shared.h",
                                             "sweep_slots.h", "set_order.h",
-                                            "tiny_row.h", "sets_front.h")] + \
+                                            "tiny_row.h", "sets_front.h",
+                                            "expander_layout.h")] + \
           [os.path.join(REPO, "include", "safeopt_hip.h")]
 BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
         "-I", os.path.join(REPO, "include"), "-I", CSRC, "-Wall",
         "-Wno-unused-function"]
 # sweep.hip: the accumulators of the 4-wave sweep live in hand-assigned AccVGPRs
 # (csrc/sweep_slots.h); the compiler must not park spilled VGPRs there.
+# expander.hip (the expander and rank-1 kernels, out of sweep.hip, and the operand kernels,
+# out of factor.hip) takes no extra flags: none of its kernels spills, so with sweep.hip's
+# flags or without them every one of them is the same instruction stream as before the
+# split (profiles/expander_split/isa_diff.txt), and it holds no inline asm to warn about.
 EXTRA = {"sets.hip": ["-ffp-contract=off"], "swarm.hip": ["-ffp-contract=off"],
          "swarm_batch.hip": ["-ffp-contract=off"],
          "sweep.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-Wno-inline-asm"]}

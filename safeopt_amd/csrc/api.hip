@@ -14,6 +14,7 @@
 #include <chrono>
 
 #include "common.h"
+#include "expander_layout.h"
 #include "sets_front.h"
 #include "small_path.h"
 
@@ -1064,8 +1065,8 @@ static int stage_gpdev(sgp_grid* g, const GpDev* host, int G) {
 }
 
 // The preamble of the grid entry points that take GPs: the device, the G the grid was made
-// for, the GPs' descriptors in `host` and, staged, in g->gpdev.
-static int grid_gps(sgp_grid* g, sgp_gp* const* gps, int G, GpDev* host) {
+// for, the GPs' descriptors in `host` and, staged, in g->gpdev.  (declared in expander_layout.h)
+int grid_gps(sgp_grid* g, sgp_gp* const* gps, int G, GpDev* host) {
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
@@ -1456,450 +1457,6 @@ int sgp_grid_download(sgp_grid* g, int what, void* out) {
   return -2;
 }
 
-// The operands of an expander test of up to SGP_TOPK candidates (kept slot: staged by the
-// caller, on the device or from the host, then built by enqueue_expander).
-struct ExpanderBufs {   // device layout: xc | resid[G][16] | delta | inv_s2 | tn2 | flags | W
-  double *xc, *resid, *delta, *inv_s2, *tn2, *W;
-  int32_t* flags;
-  size_t bx, bv, bf;
-  int64_t wstride;
-};
-
-// doubles between consecutive GPs of a W operand block: the largest factor's n_pad / 4 k-steps
-static int64_t w_stride(const GpDev* host, int G) {
-  int np_max = 0;
-  for (int i = 0; i < G; ++i) np_max = host[i].n_pad > np_max ? host[i].n_pad : np_max;
-  return int64_t(np_max / 4) * 64;
-}
-
-static int expander_bufs(sgp_grid* g, const GpDev* host, int G, ExpanderBufs* b) {
-  b->wstride = w_stride(host, G);
-  b->bx = size_t(SGP_TOPK) * g->d * 8;
-  b->bv = size_t(G) * 16 * 8;
-  b->bf = size_t(SGP_TOPK) * G * 4 + 64;
-  const size_t total = b->bx + 4 * b->bv + b->bf + size_t(G) * b->wstride * 8;
-  char* buf;
-  SGP_TRY(sgp_scratch(g->ctx, kSlotOperands, total, &buf));
-  b->xc = reinterpret_cast<double*>(buf);
-  b->resid = reinterpret_cast<double*>(buf + b->bx);
-  b->delta = reinterpret_cast<double*>(buf + b->bx + b->bv);
-  b->inv_s2 = reinterpret_cast<double*>(buf + b->bx + 2 * b->bv);
-  b->tn2 = reinterpret_cast<double*>(buf + b->bx + 3 * b->bv);
-  b->flags = reinterpret_cast<int32_t*>(buf + b->bx + 4 * b->bv);
-  b->W = reinterpret_cast<double*>(buf + b->bx + 4 * b->bv + b->bf);
-  return 0;
-}
-
-// fmin of every GP slot and the GPs with a constraint, for the operands and the scan
-static void fill_fmin_active(const double* fmin, int G, ExpanderArgs* ea, ExpanderOps* ops) {
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    ea->fmin[i] = (i < G) ? fmin[i] : -INFINITY;
-    ea->active[i] = (i < G) && (fmin[i] != -INFINITY);
-    ops->active[i] = ea->active[i];
-  }
-}
-
-// Enqueue the expander test of m <= SGP_TOPK candidates (operands + scan) on the GPs `host`,
-// staged in g->gpdev; the flags stay on the device (eb.flags).  xc == nullptr: eb already
-// holds the candidates and zeroed flags (launch_stage_batch, the front fold, k_merge_front);
-// else they come from the host arrays xc / mu_c / u_c.
-static int enqueue_expander(sgp_grid* g, const GpDev* host, const ExpanderBufs& eb,
-                            double beta, const double* fmin, int m, const double* xc,
-                            const double* mu_c, const double* u_c, double near_frac,
-                            const FrontArgs* fold = nullptr) {
-  sgp_ctx* ctx = g->ctx;
-  const int d = g->d, G = g->G;
-  SGP_CHECK(ctx, m >= 1 && m <= SGP_TOPK, "m = %d not in 1..%d", m, SGP_TOPK);
-  if (xc) {
-    // pinned staging block: xc | resid (descriptors have their own slot); previous users of
-    // this block have completed (every call that writes it syncs before returning)
-    const size_t hb = eb.bx + eb.bv + sizeof(GpDev) * SGP_MAX_GPS;
-    SGP_CHECK(ctx, hb <= ctx->pinned_cap / 2, "staging buffer too small");
-    char* stage = static_cast<char*>(ctx->pinned) + ctx->pinned_cap / 2;
-    memset(stage, 0, eb.bx + eb.bv);
-    memcpy(stage, xc, size_t(m) * d * 8);
-    double* resid = reinterpret_cast<double*>(stage + eb.bx);
-    for (int c = 0; c < m; ++c)
-      for (int i = 0; i < G; ++i)
-        resid[size_t(i) * 16 + c] = u_c[c * G + i] - mu_c[c * G + i];
-    SGP_HIP(ctx, hipMemcpyAsync(eb.xc, stage, eb.bx + eb.bv, hipMemcpyHostToDevice,
-                                ctx->stream));
-    SGP_HIP(ctx, hipMemsetAsync(eb.flags, 0, eb.bf, ctx->stream));
-  }
-  ExpanderArgs ea{};
-  ExpanderOps ops{};
-  fill_fmin_active(fmin, G, &ea, &ops);
-  ops.xc = eb.xc;
-  ops.resid = eb.resid;
-  ops.Wpack = eb.W;
-  ops.delta = eb.delta;
-  ops.inv_s2 = eb.inv_s2;
-  ops.tn2 = eb.tn2;
-  ops.wstride = eb.wstride;
-  ops.m = m;
-  SGP_TRY(expander_operands_all(ctx, g->gpdev, host, G, d, ops, fold));
-  ea.Wpack = eb.W;
-  ea.xc = eb.xc;
-  ea.delta = eb.delta;
-  ea.inv_s2 = eb.inv_s2;
-  ea.tn2 = eb.tn2;
-  ea.m = m;
-  ea.beta = beta;
-  ea.S = g->S;
-  ea.mean = g->mean;
-  ea.var = g->var;
-  ea.flags = eb.flags;
-  ea.wstride = eb.wstride;
-  ea.near_frac = near_frac;
-  // single candidate: pre-filter + listed contraction; the group counter sits
-  // in the slack behind the flags (zeroed with them), the list in scratch
-  ea.count = reinterpret_cast<int*>(reinterpret_cast<char*>(eb.flags) +
-                                    size_t(SGP_TOPK) * G * 4 + 32);
-  if (m == 1) SGP_TRY(sgp_scratch(ctx, kSlotList, (size_t(g->N) + 64) * sizeof(int), &ea.list));
-  SweepPoints sp{g->pts, g->N, 1, g->N};
-  return launch_expander_check(ctx, g->gpdev, host, G, d, sp, ea);
-}
-
-int sgp_grid_expander_check(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
-                            const double* fmin, int m, const double* xc,
-                            const double* mu_c, const double* u_c,
-                            double near_frac, int32_t* flags) {
-  sgp_ctx* ctx = g->ctx;
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(grid_gps(g, gps, G, host));
-  ExpanderBufs eb;
-  SGP_TRY(expander_bufs(g, host, G, &eb));
-  SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, m, xc, mu_c, u_c, near_frac));
-  std::vector<int32_t> fl(size_t(SGP_TOPK) * G);
-  SGP_TRY(sgp_d2h(ctx, fl.data(), eb.flags, fl.size() * 4));
-  memcpy(flags, fl.data(), size_t(m) * G * 4);
-  return 0;
-}
-
-// One pass of the expander loop (gp_opt.py:557-612) over the next k candidates in visiting
-// order with ONE stream synchronisation: top-k behind the cut -> their rows staged on the
-// device as the operands of the test -> the exact scan over the unsafe rows -> widths,
-// global indices, count and flags in one read-back.  (The step-by-step entry points --
-// sgp_grid_topk, _gather_rows, _expander_check -- need a host round trip each; a grid
-// without expanders, the usual state of a converged run, visits ALL its candidates every
-// iteration.)  One rank: on N ranks the candidates of the shards are merged on the host.
-int sgp_grid_expander_batch(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
-                            const double* fmin, int mode, double cut_w, int64_t cut_idx,
-                            int k, double* w_out, int64_t* gidx_out, int* n_out,
-                            int32_t* flags) {
-  sgp_ctx* ctx = g->ctx;
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(grid_gps(g, gps, G, host));
-  SGP_CHECK(ctx, k >= 1 && k <= SGP_TOPK, "k = %d not in 1..%d", k, SGP_TOPK);
-  char* res;
-  SGP_TRY(sgp_scratch(ctx, kSlotResult, 2048, &res));
-  double* wd = reinterpret_cast<double*>(res);
-  int64_t* id = reinterpret_cast<int64_t*>(res + 512);
-  int* nd = reinterpret_cast<int*>(res + 1024);
-  if (mode == 1) cut_w = (cut_idx < 0) ? INFINITY : -double(cut_idx);
-  SGP_TRY(launch_topk(g, mode, cut_w, cut_idx, k, wd, id, nd));
-  ExpanderBufs eb;
-  SGP_TRY(expander_bufs(g, host, G, &eb));
-  SGP_TRY(launch_stage_batch(g, id, nd, k, eb.xc, int((eb.bx + eb.bv) / 8), eb.flags,
-                             int(eb.bf / 4)));
-  SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, k, nullptr, nullptr, nullptr, 0.0));
-  // flags behind the top-k block of the scratch: one read-back for both
-  SGP_HIP(ctx, hipMemcpyAsync(res + 1032, eb.flags, size_t(SGP_TOPK) * G * 4,
-                              hipMemcpyDeviceToDevice, ctx->stream));
-  char hbuf[2048];
-  const size_t span = 1032 + size_t(SGP_TOPK) * G * 4;
-  SGP_TRY(sgp_d2h(ctx, hbuf, res, span));
-  memcpy(w_out, hbuf, size_t(k) * sizeof(double));
-  memcpy(gidx_out, hbuf + 512, size_t(k) * sizeof(int64_t));
-  memcpy(n_out, hbuf + 1024, sizeof(int));
-  memcpy(flags, hbuf + 1032, size_t(k) * G * 4);
-  return 0;
-}
-
-// The scratch of a big pass (kept slot): the listed candidates (local rows) | the key
-// histogram | the selection | per-chunk counts of the listing
-struct PassScratch {
-  int* list;        // [N]
-  unsigned* hist;   // [kPassBins]
-  PassSel* sel;
-  int* counts;      // [N / 256 + 2]
-};
-
-static int pass_scratch(sgp_grid* g, PassScratch* ps) {
-  const size_t nl = (size_t(g->N) * 4 + 63) & ~size_t(63);
-  const size_t nh = kPassBins * sizeof(unsigned);
-  static_assert(sizeof(PassSel) <= 256, "PassSel has 256 bytes");
-  char* sb;
-  SGP_TRY(sgp_scratch(g->ctx, kSlotPass, nl + nh + 256 + (size_t(g->N) / 256 + 2) * 4, &sb));
-  ps->list = reinterpret_cast<int*>(sb);
-  ps->hist = reinterpret_cast<unsigned*>(sb + nl);
-  ps->sel = reinterpret_cast<PassSel*>(sb + nl + nh);
-  ps->counts = reinterpret_cast<int*>(sb + nl + nh + 256);
-  return 0;
-}
-
-// The expander test of m listed candidates in one scan of the unsafe rows (k_expander_many):
-// the operand / W / flag blocks of the kept slots, the operands of every active GP (staged
-// GPs `host`), the scan.  The candidates are the first m of the device list of a pass
-// (list) or come from the host: xc [m][d], resid [m][G] = u_g - mu_g at the candidate.
-// *flags_dev: [m][G] flags, then 64 bytes of slack.
-static int expander_many_test(sgp_grid* g, const GpDev* host, double beta, const double* fmin,
-                              int m, const int* list, const double* xc, const double* resid,
-                              int32_t** flags_dev) {
-  sgp_ctx* ctx = g->ctx;
-  const int d = g->d, G = g->G;
-  const int64_t wstride = w_stride(host, G);
-  const size_t ngroups = (size_t(m) + 15) / 16;
-  const size_t nxc = ngroups * 16 * d, nv = ngroups * G * 16;
-  // xc | resid[group][g][16] | delta | inv_s2 | tn2 | stn | svc | agg | box | sagg | sbox
-  double* ob;
-  double* Wp;
-  int32_t* dfl;
-  SGP_TRY(sgp_scratch(ctx, kSlotManyOps,
-                      (nxc + 7 * nv + ngroups * 2 * d + 8 + (ngroups / 8 + 1) * (4 * G + 2 * d)) * 8,
-                      &ob));
-  SGP_TRY(sgp_scratch(ctx, kSlotManyW, ngroups * G * size_t(wstride) * 8, &Wp));
-  SGP_TRY(sgp_scratch(ctx, kSlotManyFlags, ngroups * 16 * G * 4 + 64, &dfl));
-  double *dxc = ob, *dres = ob + nxc, *ddel = dres + nv, *dis2 = ddel + nv, *dtn2 = dis2 + nv;
-  if (list) {
-    SGP_HIP(ctx, hipMemsetAsync(ob, 0, (nxc + nv) * 8, ctx->stream));
-    SGP_TRY(launch_pass_stage(g, list, m, dxc, dres));
-  } else {
-    std::vector<double> st(nxc + nv, 0.0);
-    memcpy(st.data(), xc, size_t(m) * d * 8);
-    for (int c = 0; c < m; ++c)
-      for (int i = 0; i < G; ++i)
-        st[nxc + (size_t(c >> 4) * G + i) * 16 + (c & 15)] = resid[size_t(c) * G + i];
-    SGP_TRY(sgp_h2d(ctx, ob, st.data(), st.size() * 8));
-  }
-  SGP_HIP(ctx, hipMemsetAsync(dfl, 0, ngroups * 16 * G * 4, ctx->stream));
-  ExpanderArgs ea{};
-  ExpanderOps ops{};
-  fill_fmin_active(fmin, G, &ea, &ops);
-  ops.xc = dxc;
-  ops.resid = dres;
-  ops.Wpack = Wp;
-  ops.delta = ddel;
-  ops.inv_s2 = dis2;
-  ops.tn2 = dtn2;
-  ops.wstride = wstride;
-  ops.m = m;
-  ops.Gs = G;
-  SGP_TRY(expander_operands_all(ctx, g->gpdev, host, G, d, ops, nullptr));
-  ea.Wpack = Wp;
-  ea.xc = dxc;
-  ea.delta = ddel;
-  ea.inv_s2 = dis2;
-  ea.tn2 = dtn2;
-  ea.stn = dtn2 + nv;
-  ea.svc = dtn2 + 2 * nv;
-  ea.agg = dtn2 + 3 * nv;          // (ngroups G 4 <= nv)
-  ea.box = dtn2 + 4 * nv;
-  ea.sagg = ea.box + ngroups * 2 * d + 8;
-  ea.sbox = ea.sagg + (ngroups / 8 + 1) * 4 * G;
-  ea.m = m;
-  ea.beta = beta;
-  ea.S = g->S;
-  ea.mean = g->mean;
-  ea.var = g->var;
-  ea.flags = dfl;
-  ea.wstride = wstride;
-  ea.near_frac = 0.0;
-  SweepPoints sp{g->pts, g->N, 1, g->N};
-  SGP_TRY(launch_expander_many(ctx, g->gpdev, G, d, sp, ea));
-  *flags_dev = dfl;
-  return 0;
-}
-
-// The work and flag blocks of the Lipschitz test of m candidates (launch_lipschitz_many);
-// *flags: [m][G], then 64 bytes of slack.
-static int lipschitz_bufs(sgp_grid* g, int m, double** work, int32_t** flags) {
-  const int d = g->d, G = g->G;
-  const size_t ngroups = (size_t(m) + 15) / 16;
-  SGP_TRY(sgp_scratch(g->ctx, kSlotManyOps, (size_t(m) * (d + G) + ngroups * (2 * d + 1) + 8) * 8,
-                      work));
-  return sgp_scratch(g->ctx, kSlotManyFlags, size_t(m) * G * 4 + 64, flags);
-}
-
-// the 8-byte aligned slack behind `bytes` of flags
-static double* behind_flags(int32_t* flags, size_t bytes) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(flags) + bytes;
-  return reinterpret_cast<double*>((p + 7) & ~uintptr_t(7));
-}
-
-// A pass of the expander loop over MANY candidates (gp_opt.py:557-612 where the loop has to
-// go far: no expander among the first candidates -- or none at all, the state of a converged
-// run -- and full_sets, which visits every safe row).  The next ~`want` candidates behind
-// the cut (visiting order: key descending -- the width, or minus the row index in full_sets
-// mode -- then index descending), chosen by a histogram of the keys instead of a sort, are
-// ALL tested in one scan of the unsafe rows (k_expander_many); two stream synchronisations
-// (the size of the pass, its result) whatever the number of candidates.
-//   mode 0: out6 = { candidates tested, expanders among them, key and global row of the
-//           FIRST expander in visiting order (nothing is marked: the caller settles exact
-//           ties and marks), key below which the candidates are still untested (-inf: none
-//           left), 0 }
-//   mode 1: every expander of the pass is marked in G; out6[2..3] unused.
-// key_lo / key_hi: range of the keys still behind the cut (histogram range; mode 0:
-// 0 .. the width of the cut).  One rank.
-//
-// The selection of such a pass: *count candidates listed in ps, out6[0] / out6[4] set.
-static int pass_select(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, double key_lo,
-                       double key_hi, int want, double* out6, PassScratch* ps, int* count) {
-  sgp_ctx* ctx = g->ctx;
-  SGP_CHECK(ctx, want >= 1, "want = %d", want);
-  SGP_CHECK(ctx, key_hi > key_lo, "empty key range %g .. %g", key_lo, key_hi);
-  SGP_CHECK(ctx, g->N < (int64_t(1) << 31), "%lld rows", (long long)g->N);
-  for (int i = 0; i < 6; ++i) out6[i] = 0.0;
-  SGP_TRY(pass_scratch(g, ps));
-  SGP_TRY(launch_pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, ps->sel, ps->list,
-                             ps->hist, ps->counts));
-  PassSel hs;
-  SGP_TRY(sgp_d2h(ctx, &hs, ps->sel, sizeof(hs)));
-  *count = hs.count;
-  out6[0] = double(hs.count);
-  out6[4] = hs.count == 0 ? -INFINITY : hs.thr;
-  return 0;
-}
-
-// the result of a pass and, behind it in the same read-back, the arg-max of the step
-// (gp_opt.py:631-641 over M | G) for the case that the pass ends the loop without a hit
-static int pass_result_and_argmax(sgp_grid* g, const int* list, int count, int32_t* dfl,
-                                  size_t flag_bytes, const double* fmin, int mode,
-                                  const double* scaling, double* out6) {
-  sgp_ctx* ctx = g->ctx;
-  double* res = behind_flags(dfl, flag_bytes);
-  SGP_TRY(launch_pass_result(g, list, count, dfl, fmin, mode, res));
-  const bool spec = scaling != nullptr && mode == 0;
-  if (spec)
-    SGP_TRY(launch_argmax(g, SGP_ARGMAX_MG_WIDTH, scaling, res + 3,
-                          reinterpret_cast<int64_t*>(res + 4)));
-  double hr[5];
-  SGP_TRY(sgp_d2h(ctx, hr, res, sizeof(hr)));
-  out6[1] = hr[0];
-  out6[2] = hr[1];
-  int64_t bi;
-  memcpy(&bi, &hr[2], 8);
-  out6[3] = double(bi);
-  int64_t ai = -1;
-  if (spec) memcpy(&ai, &hr[4], 8);
-  out6[5] = double(ai);
-  return 0;
-}
-
-int sgp_grid_expander_pass(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
-                           const double* fmin, int mode, double cut_w, int64_t cut_idx,
-                           double key_lo, double key_hi, int want, const double* scaling,
-                           double* out6) {
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(grid_gps(g, gps, G, host));
-  PassScratch ps;
-  int count = 0;
-  SGP_TRY(pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, out6, &ps, &count));
-  if (count == 0) return 0;
-  int32_t* dfl;
-  SGP_TRY(expander_many_test(g, host, beta, fmin, count, ps.list, nullptr, nullptr, &dfl));
-  return pass_result_and_argmax(g, ps.list, count, dfl, (size_t(count) + 15) / 16 * 16 * G * 4,
-                                fmin, mode, scaling, out6);
-}
-
-// The same pass with Lipschitz certificates (gp_opt.py:558-576 instead of :577-606): selection
-// as above, then the distance test of ALL listed candidates in one scan (k_lip_*).  out6 as
-// sgp_grid_expander_pass.  One rank.
-int sgp_grid_lipschitz_pass(sgp_grid* g, int G, const double* fmin, const double* lipschitz,
-                            int mode, double cut_w, int64_t cut_idx, double key_lo,
-                            double key_hi, int want, const double* scaling, double* out6) {
-  sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  PassScratch ps;
-  int count = 0;
-  SGP_TRY(pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, out6, &ps, &count));
-  if (count == 0) return 0;
-  double* work;
-  int32_t* dfl;
-  SGP_TRY(lipschitz_bufs(g, count, &work, &dfl));
-  SGP_TRY(launch_lipschitz_many(g, G, fmin, lipschitz, ps.list, count, nullptr, nullptr, work, dfl));
-  return pass_result_and_argmax(g, ps.list, count, dfl, size_t(count) * G * 4, fmin, mode,
-                                scaling, out6);
-}
-
-// ---- the same pass on N ranks, in three calls with the ranks' agreement in between ----------
-// (SafeOpt._visit_in_big_passes_nrank): every rank's histogram of the keys behind the cut
-// (the ranks sum them and pick ONE threshold), every rank's candidates above it with what the
-// other ranks need of them (the ranks gather them: the same list everywhere), and the test of
-// ALL those candidates against this rank's unsafe rows (the ranks OR the flags).
-int sgp_grid_pass_hist(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, double key_lo,
-                       double key_hi, uint32_t* hist) {
-  sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, key_hi > key_lo, "empty key range %g .. %g", key_lo, key_hi);
-  PassScratch ps;
-  SGP_TRY(pass_scratch(g, &ps));
-  SGP_TRY(launch_pass_hist(g, mode, cut_w, cut_idx, key_lo, key_hi, ps.hist));
-  return sgp_d2h(ctx, hist, ps.hist, kPassBins * sizeof(uint32_t));
-}
-
-int sgp_grid_pass_list(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, double thr, int cap,
-                       int* count, int64_t* gidx, double* key, double* x, double* resid) {
-  sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, g->N < (int64_t(1) << 31), "%lld rows", (long long)g->N);
-  PassScratch ps;
-  SGP_TRY(pass_scratch(g, &ps));
-  PassSel hs = {thr, 0, 0};
-  SGP_TRY(sgp_h2d(ctx, ps.sel, &hs, sizeof(hs)));
-  const int upper = mode & 2;            // resid = u_i (Lipschitz certificates) instead of u_i - mu_i
-  mode &= 1;
-  SGP_TRY(launch_pass_list(g, mode, cut_w, cut_idx, ps.sel, ps.list, ps.counts));
-  SGP_TRY(sgp_d2h(ctx, &hs, ps.sel, sizeof(hs)));
-  *count = hs.count;
-  if (hs.count == 0) return 0;
-  SGP_CHECK(ctx, hs.count <= cap, "%d candidates above the threshold, room for %d", hs.count, cap);
-  const int d = g->d, G = g->G;
-  const size_t per = 2 + size_t(d) + size_t(G);
-  double* ob;
-  SGP_TRY(sgp_scratch(ctx, kSlotManyOps, size_t(hs.count) * per * 8, &ob));
-  int64_t* dg = reinterpret_cast<int64_t*>(ob);
-  double *dk = ob + hs.count, *dx = dk + hs.count, *dr = dx + size_t(hs.count) * d;
-  SGP_TRY(launch_pass_gather(g, ps.list, hs.count, mode | upper, dg, dk, dx, dr));
-  std::vector<double> host(size_t(hs.count) * per);
-  SGP_TRY(sgp_d2h(ctx, host.data(), ob, host.size() * 8));
-  memcpy(gidx, host.data(), size_t(hs.count) * 8);
-  memcpy(key, host.data() + hs.count, size_t(hs.count) * 8);
-  memcpy(x, host.data() + 2 * size_t(hs.count), size_t(hs.count) * d * 8);
-  memcpy(resid, host.data() + size_t(hs.count) * (2 + d), size_t(hs.count) * G * 8);
-  return 0;
-}
-
-// xc [K][d], resid [K][G] (u_g - mu_g at the candidate): flags[c * G + i] != 0 when candidate c
-// lifts one of THIS shard's unsafe rows above fmin_i.
-int sgp_grid_pass_test(sgp_grid* g, sgp_gp* const* gps, int G, double beta, const double* fmin,
-                       int K, const double* xc, const double* resid, int32_t* flags) {
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(grid_gps(g, gps, G, host));
-  if (K <= 0) return 0;
-  int32_t* dfl;
-  SGP_TRY(expander_many_test(g, host, beta, fmin, K, nullptr, xc, resid, &dfl));
-  return sgp_d2h(g->ctx, flags, dfl, size_t(K) * G * 4);
-}
-
-// ... and with Lipschitz certificates: the distance test of ALL K gathered candidates (rows xc
-// [K][d], upper bounds uc [K][G]: sgp_grid_pass_list with mode | 2) against this shard's unsafe
-// rows; flags[c * G + i] != 0: some unsafe row of the shard is in reach of candidate c for every
-// GP with a constraint (one flag per candidate, see k_lip_items) -- the ranks OR them.
-int sgp_grid_pass_lipschitz_test(sgp_grid* g, int G, const double* fmin, const double* lipschitz,
-                                 int K, const double* xc, const double* uc, int32_t* flags) {
-  sgp_ctx* ctx = g->ctx;
-  SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
-  if (K <= 0) return 0;
-  double* work;
-  int32_t* dfl;
-  SGP_TRY(lipschitz_bufs(g, K, &work, &dfl));
-  SGP_TRY(launch_lipschitz_many(g, G, fmin, lipschitz, nullptr, K, xc, uc, work, dfl));
-  return sgp_d2h(ctx, flags, dfl, size_t(K) * G * 4);
-}
-
 // The ABI's outputs of a step (null: not asked for) ...
 struct StepOut {
   double* out5;
@@ -2114,17 +1671,16 @@ int sgp_grid_sets_back(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
   SGP_TRY(expander_bufs(g, host, G, &eb));
   SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, 1, xc, mu_c, u_c, near_frac));
   if (mark) SGP_TRY(launch_mark_if(g, li, eb.flags, fmin));
-  // results right behind the flags block: value (f64) | index (i64)
-  double* res = behind_flags(eb.flags, size_t(SGP_TOPK) * G * 4);
+  // results in the tail behind the flags: value (f64) | index (i64), one read-back for both
+  double* res = eb.tail->res;
   SGP_TRY(launch_argmax(g, SGP_ARGMAX_MG_WIDTH, scaling, res,
                         reinterpret_cast<int64_t*>(res + 1)));
-  const size_t span = size_t(reinterpret_cast<char*>(res + 2) -
-                             reinterpret_cast<char*>(eb.flags));
-  std::vector<char> hb(span);
-  SGP_TRY(sgp_d2h(ctx, hb.data(), eb.flags, span));
+  const size_t at = eb.l.tail - eb.l.flags;
+  std::vector<char> hb(at + 16);
+  SGP_TRY(sgp_d2h(ctx, hb.data(), eb.flags, hb.size()));
   memcpy(flags, hb.data(), size_t(G) * 4);
-  memcpy(value, hb.data() + (span - 16), 8);
-  memcpy(gidx, hb.data() + (span - 8), 8);
+  memcpy(value, hb.data() + at, 8);
+  memcpy(gidx, hb.data() + at + 8, 8);
   return 0;
 }
 
@@ -2179,7 +1735,7 @@ int sgp_grid_sets_fused(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
   SGP_TRY(launch_sets_front_fused(
       g, max_l, pending ? g->partial : nullptr, g->l0_pending,
       (resident && !pending) ? g->scal : nullptr, scaling, thr_beta, res,
-      dres + res_max_l(d, G), eb.xc, int((eb.bx + eb.bv) / 8), eb.flags, int(eb.bf / 4),
+      dres + res_max_l(d, G), eb.xc, int(eb.l.staged / 8), eb.flags, int(eb.l.zeroed / 4),
       mapped ? &fold : nullptr));
   fold.res_host = dres;
   g->l0_pending = 0;
@@ -2270,82 +1826,6 @@ int sgp_grid_step_small(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
   return 0;
 }
 
-// Every candidate of a small grid at once (step_small.hip: k_cand_ops, k_cand_scan):
-// flags[c * G + i] != 0 when candidate gidx[c] lifts an unsafe row above fmin_i after the
-// rank-1 update by (x_c, u_i(x_c)) -- the test of gp_opt.py:579-606 for m candidates in
-// two launches and one round trip.  Grids of at most kStepSmallRows rows, GPs with at most 48
-// observations (sgp_grid_step_small_ok).
-int sgp_grid_expanders_small(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
-                             const double* fmin, const int64_t* gidx, int m, int32_t* flags) {
-  sgp_ctx* ctx = g->ctx;
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(grid_gps(g, gps, G, host));
-  if (m <= 0) return 0;
-  SGP_CHECK(ctx, step_small_eligible(ctx, host, G, g->N),
-            "sgp_grid_expanders_small: %lld rows / a GP with more than 48 observations",
-            (long long)g->N);
-  for (int c = 0; c < m; ++c)
-    SGP_CHECK(ctx, gidx[c] >= g->goff && gidx[c] < g->goff + g->N,
-              "candidate %lld is not a row of this grid", (long long)gidx[c]);
-  const size_t nops = cand_ops_doubles(m, G);
-  char* buf;
-  SGP_TRY(sgp_scratch(ctx, kSlotOperands, nops * 8 + size_t(m) * 8 + size_t(m) * G * 4, &buf));
-  double* ops = reinterpret_cast<double*>(buf);
-  int64_t* cl = reinterpret_cast<int64_t*>(buf + nops * 8);
-  int32_t* dfl = reinterpret_cast<int32_t*>(buf + nops * 8 + size_t(m) * 8);
-  SGP_TRY(sgp_h2d(ctx, cl, gidx, size_t(m) * 8));
-  SGP_HIP(ctx, hipMemsetAsync(dfl, 0, size_t(m) * G * 4, ctx->stream));
-  SGP_TRY(launch_cand_all(g, g->gpdev, host, G, beta, fmin, cl, m, ops, dfl));
-  return sgp_d2h(ctx, flags, dfl, size_t(m) * G * 4);
-}
-
-// ... of EVERY candidate of the grid, listed on the device in row order: global rows, widths and
-// flags come back in ONE read-back (the candidate mask and the widths do not travel first).
-// *count > cap: nothing else is valid (the caller takes the two-step path).
-int sgp_grid_expanders_small_all(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
-                                 const double* fmin, int cap, int* count, int64_t* gidx,
-                                 double* width, int32_t* flags) {
-  sgp_ctx* ctx = g->ctx;
-  *count = 0;
-  GpDev host[SGP_MAX_GPS];
-  SGP_TRY(grid_gps(g, gps, G, host));
-  SGP_CHECK(ctx, cap >= 1, "cap = %d", cap);
-  SGP_CHECK(ctx, step_small_eligible(ctx, host, G, g->N),
-            "sgp_grid_expanders_small_all: %lld rows / a GP with more than 48 observations",
-            (long long)g->N);
-  if (cap > g->N) cap = int(g->N);
-  // the list: every candidate, row order (the selection of the big passes with no threshold)
-  PassScratch ps;
-  SGP_TRY(pass_scratch(g, &ps));
-  PassSel hs = {-INFINITY, 0, 0};
-  SGP_TRY(sgp_h2d(ctx, ps.sel, &hs, sizeof(hs)));
-  SGP_TRY(launch_pass_list(g, 0, INFINITY, -1, ps.sel, ps.list, ps.counts));
-  const int* count_dev = &ps.sel->count;
-  // [count | rows | widths | flags] for the read-back, the operands behind them
-  const size_t bh = 8, bc = size_t(cap) * 8, bw = size_t(cap) * 8,
-               bf = (size_t(cap) * G * 4 + 7) & ~size_t(7);
-  const size_t nops = cand_ops_doubles(cap, G);
-  char* buf;
-  SGP_TRY(sgp_scratch(ctx, kSlotOperands, bh + bc + bw + bf + nops * 8, &buf));
-  int64_t* hdr = reinterpret_cast<int64_t*>(buf);
-  int64_t* cl = reinterpret_cast<int64_t*>(buf + bh);
-  double* dw = reinterpret_cast<double*>(buf + bh + bc);
-  int32_t* dfl = reinterpret_cast<int32_t*>(buf + bh + bc + bw);
-  double* ops = reinterpret_cast<double*>(buf + bh + bc + bw + bf);
-  SGP_TRY(launch_small_pack(g, ps.list, count_dev, cap, hdr, cl, dw, dfl));
-  SGP_TRY(launch_cand_all(g, g->gpdev, host, G, beta, fmin, cl, cap, ops, dfl, count_dev));
-  std::vector<char> hb(bh + bc + bw + bf);
-  SGP_TRY(sgp_d2h(ctx, hb.data(), buf, hb.size()));
-  int64_t n64;
-  memcpy(&n64, hb.data(), 8);
-  *count = int(n64);
-  if (n64 > cap) return 0;
-  memcpy(gidx, hb.data() + bh, size_t(n64) * 8);
-  memcpy(width, hb.data() + bh + bc, size_t(n64) * 8);
-  memcpy(flags, hb.data() + bh + bc + bw, size_t(n64) * G * 4);
-  return 0;
-}
-
 // 1 when sgp_grid_step_small serves this grid with these GPs (at most kStepSmallRows rows, every GP
 // with at most 48 observations, sweep kernel not forced), else 0
 int sgp_grid_step_small_ok(sgp_grid* g, sgp_gp* const* gps, int G) {
@@ -2406,7 +1886,7 @@ int sgp_grid_sets_fused_comm(sgp_grid* g, sgp_gp* const* gps, int G, double beta
     blocks = all;
   }
   SGP_TRY(launch_merge_front(g, blocks, world, int(nfront), res, eb.xc,
-                             int((eb.bx + eb.bv) / 8), eb.flags, int(eb.bf / 4)));
+                             int(eb.l.staged / 8), eb.flags, int(eb.l.zeroed / 4)));
   // ---- probe scan over this shard, flags over all shards
   SGP_TRY(enqueue_expander(g, host, eb, beta, fmin, 1, nullptr, nullptr, nullptr, near_frac));
   if (comm) SGP_TRY(coll_allreduce_max_i32(ctx, eb.flags, size_t(G)));

@@ -9,7 +9,7 @@
 // under SafeOpt's rule on the rows of the mask that are not picked yet, and the best
 // (value, global row) pair of the workgroup; a small kernel reduces the pairs.
 //
-// The layout is k_rank1's (sweep.hip), which does the same per-row work on the resident
+// The layout is k_rank1's (expander.hip), which does the same per-row work on the resident
 // arrays: 64 rows per workgroup, lane (r, q) = (lane & 15, lane >> 4) handles row r and the
 // training points j = q (mod 4), two shuffles fold the four partial dot products; n
 // covariance evaluations and n FMAs per row and GP on the fp64 VALU, no n^2 term.

@@ -108,7 +108,7 @@ struct GpDev {
   const double* upd_w;
   const double* upd;
   // dense L^-1 (row pitch ld) and k(x,x) + noise + 1e-8 + jitter: what the
-  // operands of the rank-1 expander test are built from (factor.hip, k_expw)
+  // operands of the rank-1 expander test are built from (expander.hip, k_expw_mm)
   const double* Linv;
   int64_t ld;
   double prior;
@@ -143,33 +143,39 @@ struct SepLaunch {
 // entry point sizes and fills them, and a callee asks for them again with the same size
 // to find the contents in place (SGP_POISON=2 leaves them alone).
 enum ScratchSlot : int {
+  // (the blocks of the expander test -- slots 0, 7 .. 12 and expander_batch's part of slot 1 --
+  // are laid out in expander_layout.h)
   kSlotList = 0,        // the rows the pre-filter of ONE candidate lists (enqueue_expander)
   kSlotResult = 1,      // small result blocks the entry points read back: maximizers,
-                        // candidates, topk, argmax, expander_batch, sets_front[_comm],
-                        // sets_fused[_comm]
+                        // candidates, topk, argmax, expander_batch (BatchReadLayout),
+                        // sets_front[_comm], sets_fused[_comm]
   kSlotPartials = 2,    // per-workgroup partials of the sets.hip launchers (candidates, topk,
                         // argmax[_marked], the fused front, read by its fold); set_axes'
                         // mismatch count; fitness_small's mean | var; a batch pick's pairs
                         // and result (BatchScratch)
   kSlotStage = 3,       // host rows staged for a launch: gp_predict, kern_K, grid_create,
                         // swarm_fitness, swarm_run's random numbers (swarm_api.hip);
-                        // factor.hip: append_gp, expander_operands_all
+                        // factor.hip: append_gp; expander.hip: expander_operands_all
   kSlotWork = 4,        // gp_predict's points, kern_K's matrix; swarm_api.hip: the block of a
                         // fitness call (SwarmFitLayout), a run (SwarmRunLayout), swarm_grow
                         // (GrowLayout)
   kSlotGpDev = 5,       // gp_predict's GP descriptor
   kSlotSmall = 6,       // small_reserve (few-points path), upload_local_idx,
                         // comm_allreduce_max, comm_allgather
-  kSlotOperands = 7,    // kept: operands of <= SGP_TOPK candidates (expander_bufs: staged by
-                        // expander_batch / sets_fused[_comm], asked for again by
-                        // enqueue_expander); gather_rows, lipschitz_check, expanders_small[_all]
-  kSlotPass = 8,        // kept: the scratch of a big pass (PassScratch: list | histogram |
+  kSlotOperands = 7,    // kept: operands of <= SGP_TOPK candidates (ExpanderLayout, expander_bufs:
+                        // staged by expander_batch / sets_fused[_comm], asked for again by
+                        // enqueue_expander); expanders_small[_all] (SmallLayout); gather_rows,
+                        // lipschitz_check
+  kSlotPass = 8,        // kept: the scratch of a big pass (PassLayout: list | histogram |
                         // PassSel | counts), the selection carried from pass_list on
-  kSlotManyOps = 9,     // kept: operands of m listed candidates (expander_many_test), the
-                        // Lipschitz work block, pass_list's gathered rows
-  kSlotManyW = 10,      // kept: their W operands
-  kSlotManyFlags = 11,  // kept: their flags, the pass result behind them
-  kSlotHot = 12,        // launch_expander_many / launch_lipschitz_many: the hot waves and rows
+  kSlotManyOps = 9,     // kept: operands of m listed candidates (ManyLayout, expander_many_test),
+                        // the Lipschitz work block (LipLayout), pass_list's gathered rows
+                        // (PassListLayout)
+  kSlotManyW = 10,      // kept: their W operands (ManyLayout::w_bytes)
+  kSlotManyFlags = 11,  // kept: their flags, the pass result in the tail behind them
+                        // (FlagsLayout, FlagTail)
+  kSlotHot = 12,        // launch_expander_many (HotLayout) / launch_lipschitz_many
+                        // (LipHotLayout): the hot waves and rows
   kSlotJointA = 13,     // joint.hip: Sigma (N_pad x N_pad), the Cholesky factor in its lower part
   kSlotJointLi = 14,    // ... the inverse factor the recursion forms along the way
   kSlotJointT = 15,     // ... and its workspace
@@ -398,6 +404,9 @@ int pop_gp(sgp_gp* gp);
 // row `index` leaves (0 <= index < n, n >= 2); *info != 0 leaves the GP untouched
 int remove_gp(sgp_gp* gp, int index, int* info);
 int publish_gp(sgp_gp* gp);  // Apack / Xpad / Xs / dev descriptor from Linv
+// right-hand sides of a triangular product, candidates of a group of the expander test
+constexpr int kMaxRhs = 16;
+// expander.hip
 struct ExpanderOps {      // all arrays on the device; [g] blocks as noted
   const double* xc;       // [m][d] candidates
   const double* resid;    // [G][16]  u_c - mu_c
@@ -551,11 +560,12 @@ struct ExpanderArgs {
   int* wlist;            // (count, [G][N / 16] segments, masks of their listed rows); count /
   unsigned* wmask;       // list: the rows that pass the pair test of some candidate, [G][N]
 };
+// expander.hip
 int launch_expander_check(sgp_ctx* ctx, const GpDev* gps_dev,
                           const GpDev* gps_host, int G, int d, SweepPoints pts,
                           ExpanderArgs ea);
 // ea.m candidates in groups of 16, every per-candidate array [group][G][...] (flags
-// [candidate][G]): sweep.hip, k_expander_many
+// [candidate][G]): expander.hip, k_expander_many
 int launch_expander_many(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d, SweepPoints pts,
                          ExpanderArgs ea);
 struct Rank1Args {
@@ -705,8 +715,8 @@ int launch_pass_gather(sgp_grid* g, const int* list_dev, int count, int mode, in
                        double* key, double* x, double* resid);
 int launch_pass_stage(sgp_grid* g, const int* list_dev, int count, double* xc, double* resid);
 // the Lipschitz test of many candidates (sets.hip: k_lip_*): rows and upper bounds staged from
-// list_dev (local rows) or copied from the host arrays; work: (count (d + G) + groups (2 d + 1))
-// doubles on the device
+// list_dev (local rows) or copied from the host arrays; work: the block of LipLayout
+// (expander_layout.h) on the device
 int launch_lipschitz_many(sgp_grid* g, int G, const double* fmin, const double* lipschitz,
                           const int* list_dev, int count, const double* xc_in, const double* uc_in,
                           double* work, int32_t* flags_dev);

@@ -6,6 +6,8 @@
 // n <= a few thousand, so n^3/3 <= ~3 GFLOP: a recursive blocked algorithm
 // (32x32 leaves in LDS + one tiled fp64 GEMM kernel) is launch-bound, not
 // flop-bound, and runs replicated on every GPU (no communication).
+// Also here: the one-row updates behind sgp_gp_append / _pop / _remove and the posterior of
+// a FEW points (small_path.h).  (The operands of the expander test: expander.hip.)
 //
 //   factor(A[0:s]):  s == 32 -> leaf (potf2 + triangular inverse in LDS)
 //     else split h:  factor(A11); L21 = A21 Linv11^T; A22 -= L21 L21^T;
@@ -253,8 +255,7 @@ __global__ void k_pack(const double* Li, int64_t ld, int n, int nblk,
 // Lower-triangular products with up to 16 right-hand sides, V and the results
 // stored one vector per row (pitch ldv / ldo).  Both read L^-1 exactly once,
 // coalesced along its rows, in a fixed summation order (every rank of a
-// multi-GPU run computes bit-identical operands).
-constexpr int kMaxRhs = 16;
+// multi-GPU run computes bit-identical operands).  (kMaxRhs: common.h)
 
 // T[c][i] = sum_{j <= i} Li[i][j] V[c][j]: one wave per row i.
 __global__ __launch_bounds__(256) void k_tri_mv(const double* Li, int64_t ld,
@@ -934,347 +935,6 @@ __global__ __launch_bounds__(256) void k_small_post(const GpDev* gps, SmallBufs 
     mean[int64_t(g) * P + p] = sb.mtmp[g * sb.passes * 16 + p];
     var[int64_t(g) * P + p] = fmax(gp.kern.kdiag - tot, 1e-15);      // GPy clip
   }
-}
-
-// ---- operands of the rank-1 expander test, all GPs per launch ----------------------
-// For candidate c and GP g:  k_c = k(X, x_c),  t = L^-1 k_c,  w = L^-T t = Ky^-1 k_c
-// (packed as an MFMA A operand: cand x j),  s2 = prior - |t|^2,  delta = resid / s2.
-namespace {
-struct ExpGpSel {
-  int active[SGP_MAX_GPS];
-};
-
-// 2 .. thousands of candidates (sgp_grid_expander_batch, sgp_grid_expander_pass) in groups of
-// 16; every per-candidate array is laid out [group][GP slot][...] (ExpanderOps::Gs slots), the
-// group's candidate count is what is left of `m` behind the groups in front.  The two
-// triangular products are matrix products of 16-candidate panels on v_mfma_f64_16x16x4_f64:
-// per (group, GP) the panels Kc and T are [j][16 candidates] -- 64 consecutive doubles are a
-// B operand (k_expt_mm: lane 16 k + c <- [4 s + k][c]) or an A operand (k_expw_mm) as they lie.
-constexpr int kOpGroups = 2;       // groups of a wave: one operand of L^-1 feeds that many products
-
-// Kc[group][g][j][c] = k(x_c, X_j); zero for j >= n (the padding meets zeros of L^-1) and c >= m
-template <int D>
-__global__ __launch_bounds__(256) void k_expk(const GpDev* gps, ExpGpSel sel,
-                                              const double* xc, int m, double* Kc,
-                                              int64_t ldk, int Gs) {
-  const int g = blockIdx.y;
-  if (!sel.active[g]) return;
-  const int z = blockIdx.z;
-  xc += int64_t(z) * kMaxRhs * D;
-  m = min(kMaxRhs, m - kMaxRhs * z);
-  const GpDev& gp = gps[g];
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= gp.n_pad) return;
-  double* out = Kc + ((int64_t(z) * Gs + g) * ldk + j) * kMaxRhs;
-  double xj[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) xj[k] = gp.Xpad[int64_t(j) * D + k];
-  for (int c = 0; c < kMaxRhs; ++c)
-    out[c] = (j < gp.n && c < m) ? kern_eval<D>(gp.kern, xc + c * D, xj) : 0.0;
-}
-
-// T[group][g][i][c] = sum_{j <= i} Li[i][j] Kc[..][j][c]: a wave per (row block of 16, kOpGroups
-// groups); A = the packed L^-1 of the sweeps (GpDev::Apack: zero above the diagonal and in the
-// padding), B = the panel.  D: column (candidate) = lane & 15, rows (lane >> 4) + 4 r.
-__global__ __launch_bounds__(256) void k_expt_mm(const GpDev* gps, ExpGpSel sel,
-                                                 const double* Kc, double* Tt,
-                                                 int64_t ldk, int Gs, int ngroups) {
-  const int g = blockIdx.y;
-  if (!sel.active[g]) return;
-  const GpDev& gp = gps[g];
-  const int b = blockIdx.x;
-  if (b >= gp.nblk) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int z0 = (blockIdx.z * 4 + wave) * kOpGroups;
-  if (z0 >= ngroups) return;
-  const int nsteps = gp.n_pad >> 2;
-  const double* A = gp.Apack + int64_t(b) * nsteps * 64 + lane;
-  // narrow packing of the last row block (k_pack): its rows 4..15 repeat rows 0..3
-  const bool dup = b == gp.nblk - 1 && gp.narrow && (lane & 15) >= 4;
-  const double* B[kOpGroups];
-#pragma unroll
-  for (int q = 0; q < kOpGroups; ++q)
-    B[q] = Kc + (int64_t(min(z0 + q, ngroups - 1)) * Gs + g) * ldk * kMaxRhs + lane;
-  double4_t acc[kOpGroups];
-#pragma unroll
-  for (int q = 0; q < kOpGroups; ++q) acc[q] = double4_t{0.0, 0.0, 0.0, 0.0};
-  const int send = (b + 1) * 4;                 // up to the diagonal block
-  constexpr int kInFlight = 4;
-#pragma unroll 1
-  for (int s = 0; s < send; s += kInFlight) {   // (send is a multiple of 4)
-    double av[kInFlight], bv[kOpGroups][kInFlight];
-#pragma unroll
-    for (int i = 0; i < kInFlight; ++i) {
-      av[i] = A[(s + i) * 64];
-#pragma unroll
-      for (int q = 0; q < kOpGroups; ++q) bv[q][i] = B[q][(s + i) * 64];
-    }
-#pragma unroll
-    for (int i = 0; i < kInFlight; ++i) {
-      const double a = dup ? 0.0 : av[i];
-#pragma unroll
-      for (int q = 0; q < kOpGroups; ++q)
-        acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[q][i], acc[q], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < kOpGroups; ++q) {
-    if (z0 + q < ngroups) {
-      double* T = Tt + (int64_t(z0 + q) * Gs + g) * ldk * kMaxRhs;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        T[(16 * b + (lane >> 4) + 4 * r) * kMaxRhs + (lane & 15)] = acc[q][r];
-    }
-  }
-}
-
-// W[c][j] = sum_{i >= j} Li[i][j] T[..][i][c] straight into the packed operand
-// (Wpack[(j / 4) * 64 + (j % 4) * 16 + c], zero for j >= n and c >= m): a wave per (column block
-// of 16, kOpGroups groups); A = the panel, B = rows of the dense L^-1 (16 consecutive columns).
-// D: column j = lane & 15, rows (candidates) (lane >> 4) + 4 r.  The wave of column block 0 walks
-// over every row: it also leaves s2 / delta / |t|^2 of its candidates.
-__global__ __launch_bounds__(256) void k_expw_mm(const GpDev* gps, ExpGpSel sel,
-                                                 const double* Tt, int64_t ldk, ExpanderOps ops,
-                                                 int ngroups) {
-  const int g = blockIdx.y;
-  if (!sel.active[g]) return;
-  const GpDev& gp = gps[g];
-  const int jb = blockIdx.x;
-  if (jb >= gp.nblk) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int z0 = (blockIdx.z * 4 + wave) * kOpGroups;
-  if (z0 >= ngroups) return;
-  const int n = gp.n;
-  const int j = 16 * jb + (lane & 15);
-  const double* A[kOpGroups];
-#pragma unroll
-  for (int q = 0; q < kOpGroups; ++q)
-    A[q] = Tt + (int64_t(min(z0 + q, ngroups - 1)) * ops.Gs + g) * ldk * kMaxRhs + lane;
-  const double* Bp = gp.Linv + int64_t(lane >> 4) * gp.ld + min(j, n - 1);
-  double4_t acc[kOpGroups];
-  double ss[kOpGroups];
-#pragma unroll
-  for (int q = 0; q < kOpGroups; ++q) {
-    acc[q] = double4_t{0.0, 0.0, 0.0, 0.0};
-    ss[q] = 0.0;
-  }
-  const int send = (n + 3) >> 2;
-  constexpr int kInFlight = 4;
-#pragma unroll 1
-  for (int s = 4 * jb; s < send; s += kInFlight) {
-    double av[kOpGroups][kInFlight], bv[kInFlight];
-#pragma unroll
-    for (int i = 0; i < kInFlight; ++i) {
-      const int row = 4 * (s + i) + (lane >> 4);
-      bv[i] = Bp[int64_t(min(4 * (s + i), n - 1 - (lane >> 4))) * gp.ld];
-      bv[i] = (row < n && row >= j && j < n) ? bv[i] : 0.0;
-      // (rows >= n of the panel are zero: k_expt_mm, the padding of Apack)
-#pragma unroll
-      for (int q = 0; q < kOpGroups; ++q) av[q][i] = A[q][min(s + i, (gp.n_pad >> 2) - 1) * 64];
-    }
-#pragma unroll
-    for (int i = 0; i < kInFlight; ++i) {
-#pragma unroll
-      for (int q = 0; q < kOpGroups; ++q) {
-        acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q][i], bv[i], acc[q], 0, 0, 0);
-        ss[q] = (s + i < send) ? fma(av[q][i], av[q][i], ss[q]) : ss[q];
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < kOpGroups; ++q) {
-    const int z = z0 + q;
-    if (z >= ngroups) break;
-    const int m = min(kMaxRhs, ops.m - kMaxRhs * z);
-    if (j < gp.n_pad) {
-      double* Wp = ops.Wpack + (int64_t(z) * ops.Gs + g) * ops.wstride;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = (lane >> 4) + 4 * r;
-        Wp[(j >> 2) * 64 + (j & 3) * 16 + c] = (j < n && c < m) ? acc[q][r] : 0.0;
-      }
-    }
-    if (jb == 0) {
-      double t2 = ss[q];
-      t2 += __shfl_xor(t2, 16, 64);
-      t2 += __shfl_xor(t2, 32, 64);
-      const int c = lane;
-      if (c < m) {
-        const int64_t o = (int64_t(z) * ops.Gs + g) * 16 + c;
-        const double s2 = gp.prior - t2;
-        ops.inv_s2[o] = 1.0 / s2;
-        ops.delta[o] = ops.resid[o] / s2;
-        ops.tn2[o] = t2;
-      }
-    }
-  }
-}
-
-// One candidate (the fused single-GPU step and the probe of the first candidate):
-// T[g][0][i] with k_c evaluated where it is needed -- lane l of the wave that owns
-// row i evaluates k(x_c, X_j) for its j = l, l + 64, ... <= i -- instead of a
-// separate launch that writes k_c out first.
-template <int D>
-__global__ __launch_bounds__(256) void k_expkt(const GpDev* gps, ExpGpSel sel,
-                                               const double* xc, double* Tt,
-                                               int64_t ldk, FrontArgs fa, int g_writer) {
-  const int g = blockIdx.y;
-  if (!sel.active[g]) return;
-  const GpDev& gp = gps[g];
-  const int lane = threadIdx.x & 63;
-  double x[D];
-  if (fa.nb > 0) {
-    // one-rank chain: the candidate is not staged yet -- the last step of the front half
-    // runs here (sets_front.h); one workgroup leaves the result block and the staged
-    // operand for the kernels behind this one
-    const int64_t top = front_final_fold(fa, blockIdx.x == 0 && g == g_writer);
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-      x[k] = top >= 0 ? fa.pts[int64_t(k) * fa.N + (top - fa.goff)] : 0.0;
-  } else {
-#pragma unroll
-    for (int k = 0; k < D; ++k) x[k] = xc[k];
-  }
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= gp.n) return;
-  const double* row = gp.Linv + int64_t(i) * gp.ld;
-  double acc = 0.0;
-  for (int j = lane; j <= i; j += 64) {
-    double xj[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) xj[k] = gp.Xpad[int64_t(j) * D + k];
-    acc = fma(row[j], kern_eval<D>(gp.kern, x, xj), acc);
-  }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (lane == 0) Tt[int64_t(g) * kMaxRhs * ldk + i] = acc;
-}
-
-// ... and W[0][j] for it: 64 columns per workgroup, the 16 waves split the rows
-// i >= j0 (four loads in flight per lane), one fold through LDS.
-__global__ __launch_bounds__(1024) void k_expw1(const GpDev* gps, ExpGpSel sel,
-                                                const double* Tt, int64_t ldk,
-                                                ExpanderOps ops) {
-  __shared__ double sh[16][64];
-  const int g = blockIdx.y;
-  if (!sel.active[g]) return;
-  const GpDev& gp = gps[g];
-  const int n = gp.n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j0 = blockIdx.x * 64, j = j0 + lane;
-  if (j0 >= gp.n_pad) return;
-  const double* T = Tt + int64_t(g) * kMaxRhs * ldk;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  if (j < n) {
-    const double* col = gp.Linv + j;
-    int i = j0 + wave;
-    for (; i + 48 < n; i += 64) {
-      const double l0 = (i >= j) ? col[int64_t(i) * gp.ld] : 0.0;
-      const double l1 = (i + 16 >= j) ? col[int64_t(i + 16) * gp.ld] : 0.0;
-      const double l2 = (i + 32 >= j) ? col[int64_t(i + 32) * gp.ld] : 0.0;
-      const double l3 = (i + 48 >= j) ? col[int64_t(i + 48) * gp.ld] : 0.0;
-      a0 = fma(l0, T[i], a0);
-      a1 = fma(l1, T[i + 16], a1);
-      a2 = fma(l2, T[i + 32], a2);
-      a3 = fma(l3, T[i + 48], a3);
-    }
-    for (; i < n; i += 16)
-      if (i >= j) a0 = fma(col[int64_t(i) * gp.ld], T[i], a0);
-  }
-  sh[wave][lane] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (wave == 0 && j < gp.n_pad) {
-    double tot = 0.0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) tot += sh[w][lane];
-    double* Wp = ops.Wpack + int64_t(g) * ops.wstride + (j >> 2) * 64 + (j & 3) * 16;
-    Wp[0] = (j < n) ? tot : 0.0;
-#pragma unroll
-    for (int c = 1; c < kMaxRhs; ++c) Wp[c] = 0.0;
-  }
-  if (blockIdx.x == 0 && wave == 1) {
-    double s = 0.0;
-    for (int i = lane; i < n; i += 64) s = fma(T[i], T[i], s);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) {
-      const double s2 = gp.prior - s;
-      ops.inv_s2[g * 16] = 1.0 / s2;
-      ops.delta[g * 16] = ops.resid[g * 16] / s2;
-      ops.tn2[g * 16] = s;
-    }
-  }
-}
-
-}  // namespace
-
-int expander_operands_all(sgp_ctx* ctx, const GpDev* gps_dev, const GpDev* gps_host,
-                          int G, int d, const ExpanderOps& ops, const FrontArgs* fold) {
-  int n_max = 0, np_max = 0, g_writer = -1;
-  ExpGpSel sel{};
-  FrontArgs fa{};
-  if (fold) fa = *fold;
-  for (int g = 0; g < G; ++g) {
-    sel.active[g] = ops.active[g];
-    if (!ops.active[g]) continue;
-    if (g_writer < 0) g_writer = g;
-    n_max = std::max(n_max, gps_host[g].n);
-    np_max = std::max(np_max, gps_host[g].n_pad);
-  }
-  if (n_max == 0) {
-    // no GP with a constraint: nothing evaluates the candidate, the fold has no host
-    if (fold) return launch_front_final(ctx, *fold);
-    return 0;
-  }
-  SGP_CHECK(ctx, !fold || ops.m == 1, "the front fold goes with one candidate");
-  const int64_t ldk = (np_max + 31) / 32 * 32;
-  const int ngroups = (ops.m + kMaxRhs - 1) / kMaxRhs;
-  SGP_CHECK(ctx, ngroups == 1 || ops.Gs == G, "ExpanderOps::Gs = %d for %d GPs", ops.Gs, G);
-  double* buf;
-  SGP_TRY(sgp_scratch(ctx, kSlotStage, size_t(2) * ngroups * G * kMaxRhs * ldk * sizeof(double),
-                      &buf));
-  double* Kc = buf;
-  double* Tt = buf + size_t(ngroups) * G * kMaxRhs * ldk;
-  if (ops.m == 1) {
-#define EXPKT_CASE(DD)                                                        \
-  case DD:                                                                    \
-    hipLaunchKernelGGL(k_expkt<DD>, dim3((n_max + 3) / 4, G), dim3(256), 0,   \
-                       ctx->stream, gps_dev, sel, ops.xc, Tt, ldk, fa,        \
-                       g_writer);                                             \
-    break;
-    switch (d) {
-      EXPKT_CASE(1) EXPKT_CASE(2) EXPKT_CASE(3) EXPKT_CASE(4)
-      EXPKT_CASE(5) EXPKT_CASE(6) EXPKT_CASE(7) EXPKT_CASE(8)
-      default:
-        sgp_set_error(ctx, "input dimension %d not in 1..%d", d, SGP_MAX_D);
-        return -2;
-    }
-#undef EXPKT_CASE
-    hipLaunchKernelGGL(k_expw1, dim3((np_max + 63) / 64, G), dim3(1024), 0,
-                       ctx->stream, gps_dev, sel, Tt, ldk, ops);
-    SGP_HIP(ctx, hipGetLastError());
-    return 0;
-  }
-#define EXPK_CASE(DD)                                                         \
-  case DD:                                                                    \
-    hipLaunchKernelGGL(k_expk<DD>, dim3((np_max + 255) / 256, G, ngroups), dim3(256), 0,\
-                       ctx->stream, gps_dev, sel, ops.xc, ops.m, Kc, ldk, G); \
-    break;
-  switch (d) {
-    EXPK_CASE(1) EXPK_CASE(2) EXPK_CASE(3) EXPK_CASE(4)
-    EXPK_CASE(5) EXPK_CASE(6) EXPK_CASE(7) EXPK_CASE(8)
-    default:
-      sgp_set_error(ctx, "input dimension %d not in 1..%d", d, SGP_MAX_D);
-      return -2;
-  }
-#undef EXPK_CASE
-  const int zblocks = (ngroups + 4 * kOpGroups - 1) / (4 * kOpGroups);
-  hipLaunchKernelGGL(k_expt_mm, dim3(np_max / 16, G, zblocks), dim3(256), 0, ctx->stream,
-                     gps_dev, sel, Kc, Tt, ldk, G, ngroups);
-  hipLaunchKernelGGL(k_expw_mm, dim3(np_max / 16, G, zblocks), dim3(256), 0, ctx->stream,
-                     gps_dev, sel, Tt, ldk, ops, ngroups);
-  SGP_HIP(ctx, hipGetLastError());
-  return 0;
 }
 
 bool small_path_pays(const sgp_gp* gp, int64_t P) {

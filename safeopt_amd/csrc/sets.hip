@@ -5,6 +5,7 @@
 // both candidate filters, >= for the expander tests) and NumPy's IEEE
 // expression order; this file is compiled with -ffp-contract=off so the masks
 // are bit-exact with the NumPy restatement for identical Q.
+#include "expander_layout.h"
 #include "kern_eval.h"
 #include "set_order.h"
 #include "sets_front.h"
@@ -1344,10 +1345,8 @@ int launch_lipschitz_many(sgp_grid* g, int G, const double* fmin, const double* 
   sgp_ctx* ctx = g->ctx;
   const int d = g->d;
   const int ngroups = (count + 15) / 16;
-  double* xc = work;
-  double* uc = xc + size_t(count) * d;
-  double* box = uc + size_t(count) * G;
-  double* rad = box + size_t(ngroups) * 2 * d;
+  const LipBufs lb = lip_bufs(work, lip_layout(count, d, G));
+  double *xc = lb.xc, *uc = lb.uc, *box = lb.box, *rad = lb.rad;
   if (list_dev) {
     hipLaunchKernelGGL(k_lip_stage, dim3((count + T - 1) / T), dim3(T), 0, ctx->stream, list_dev,
                        count, g->pts, g->Q, g->N, d, G, xc, uc);
@@ -1355,10 +1354,11 @@ int launch_lipschitz_many(sgp_grid* g, int G, const double* fmin, const double* 
     SGP_HIP(ctx, hipMemcpyAsync(xc, xc_in, size_t(count) * d * 8, hipMemcpyHostToDevice, ctx->stream));
     SGP_HIP(ctx, hipMemcpyAsync(uc, uc_in, size_t(count) * G * 8, hipMemcpyHostToDevice, ctx->stream));
   }
-  const size_t nw = size_t((g->N + 15) >> 4);
-  int* hot;
-  SGP_TRY(sgp_scratch(ctx, kSlotHot, (64 + nw) * sizeof(int), &hot));
-  SGP_HIP(ctx, hipMemsetAsync(hot, 0, 64 * sizeof(int), ctx->stream));
+  const size_t nw = hot_segments(g->N);
+  const LipHotLayout hl = lip_hot_layout(g->N);
+  char* hot;
+  SGP_TRY(sgp_scratch(ctx, kSlotHot, hl.bytes, &hot));
+  SGP_HIP(ctx, hipMemsetAsync(hot, 0, kHotHead * sizeof(int), ctx->stream));
   SGP_HIP(ctx, hipMemsetAsync(flags_dev, 0, size_t(count) * G * 4, ctx->stream));
   LipPass a{};
   a.pts = g->pts;
@@ -1375,8 +1375,8 @@ int launch_lipschitz_many(sgp_grid* g, int G, const double* fmin, const double* 
   a.box = box;
   a.rad = rad;
   a.flags = flags_dev;
-  a.wcount = hot;
-  a.wlist = hot + 64;
+  a.wcount = reinterpret_cast<int*>(hot + hl.wcount);
+  a.wlist = reinterpret_cast<int*>(hot + hl.wlist);
   hipLaunchKernelGGL(k_lip_agg, dim3((ngroups + T - 1) / T), dim3(T), 0, ctx->stream, count, d, G,
                      a.fmin, a.lips, xc, uc, box, rad, ngroups);
   hipLaunchKernelGGL(k_lip_scan, dim3(unsigned((nw + T / 64 - 1) / (T / 64))), dim3(T), 0,

@@ -3,7 +3,7 @@
 // (visiting order of safeopt/gp_opt.py:542-552), the totals, and the candidate staged
 // as the operand of the expander test.  A device function, so that it runs either as
 // a launch of its own (k_front_final: N ranks, no active constraint) or at the top of
-// the FIRST kernel that needs its result (factor.hip:k_expkt, one rank): every
+// the FIRST kernel that needs its result (expander.hip:k_expkt, one rank): every
 // workgroup of that kernel finds the first candidate for itself from the <= 1024
 // partial results (28 KB, L2 hits), one of them writes the result block -- a launch
 // and its gap less in the chain, no atomics, no fences.

@@ -17,7 +17,7 @@
 //      number of candidates tied with it             gp_opt.py:519-552
 //   E  rank-1 expander test of that candidate over ALL unsafe rows (exact, no probe):
 //      t = L^-1 k_c, w = L^-T t, s^2, c(x) = k(x, x_c) - w . k(X, x), l_2(x) >= fmin
-//      (sweep.hip:k_expander_list, factor.hip:k_expkt / k_expw1 -- the same summation
+//      (expander.hip: k_expander_list, k_expkt / k_expw1 -- the same summation
 //      orders, so the flags are those of the large-grid path)      gp_opt.py:579-606
 //   F  G mark when every active GP certified it, arg-max over M | G   gp_opt.py:611-649
 // and one result block (sets_front.h) comes back.  Everything the
@@ -36,7 +36,7 @@ namespace {
 // each: a row's 48 covariances and the four FMA chains of tiny_row_gp need up to ~190.
 // (1024 threads with 128 registers for n <= 24 spill 64-320 B and were no faster: the step
 // is a chain of latencies, not of issue slots -- profiles/r05/experiments.txt.)
-constexpr int kExpwWaves = 16;    // row groups of k_expw1 (factor.hip), whose order is kept
+constexpr int kExpwWaves = 16;    // row groups of k_expw1 (expander.hip), whose order is kept
 constexpr int kStepNP = 48;       // observations per GP, at most (tiny_row)
 
 struct StepParams {
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(TH) void k_step_small(StepParams p) {
         const double var2 = fmax(var - cx * cx * inv_s2, 1e-15);
         return mu2 - p.conf.beta * sqrt(var2) >= p.conf.fmin[g];
       };
-      // Pre-filter (k_expander_filter, sweep.hip): |c(x)| <= |k(x, x_c)| + |L^-1 k_x| |t| with
+      // Pre-filter (k_expander_filter, expander.hip): |c(x)| <= |k(x, x_c)| + |L^-1 k_x| |t| with
       // |L^-1 k_x|^2 = k(x,x) - var(x) resident -- ONE covariance per unsafe row instead of
       // n decides for the rows that cannot be lifted to fmin whatever c(x) is; the others
       // (a few per cent) go on a list in LDS and get the exact n-term dot product below.

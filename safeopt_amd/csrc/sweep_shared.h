@@ -1,5 +1,6 @@
-// Shared by the two posterior-sweep translation units (sweep.hip: the 4-wave
-// kernel for small factors; sweep_pair.hip: the paired-wave kernel).
+// Shared by the posterior-sweep translation units (sweep.hip: the 4-wave kernel for small
+// factors; sweep_pair.hip: the paired-wave kernel; sweep_mid.hip) and the
+// expander / rank-1 kernels (expander.hip).
 #pragma once
 
 #include <stdlib.h>
@@ -39,6 +40,9 @@ struct SweepTimer {
     return 0;
   }
 };
+
+// a pointer into global memory, for loads the compiler must not take as flat
+typedef const __attribute__((address_space(1))) double* gptr_t;
 
 // (operand maps of v_mfma_f64_4x4x4_4b_f64: sweep.hip, "matrix part")
 // Covariance values of a stage -> B operands.  Lane (k, c) = (l >> 4, l & 15)

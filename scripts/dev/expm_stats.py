@@ -1,5 +1,6 @@
-"""Counters of k_expander_many (a library built with -DEXPM_STATS: scripts/dev/build_variant.sh
-stats "-DEXPM_STATS"; SAFEOPT_HIP_LIB=scripts/dev/ab/stats.so) on the converged states of
+"""Counters of k_expander_many (a library whose expander.hip is built with -DEXPM_STATS:
+scripts/dev/build_variant.sh stats "-DEXPM_STATS" expander;
+SAFEOPT_HIP_LIB=scripts/dev/ab/stats.so) on the converged states of
 bench.py: how many blocks each test lets through and how full the contracted blocks are.
 
     SAFEOPT_HIP_LIB=scripts/dev/ab/stats.so python scripts/dev/expm_stats.py

@@ -47,8 +47,8 @@ def usage(src):
 
 def main():
     files = sys.argv[1:] or [os.path.join(CSRC, f) for f in
-                             ("sweep.hip", "sweep_pair.hip", "sweep_tiny.hip", "sets.hip", "swarm.hip",
-                              "factor.hip")]
+                             ("sweep.hip", "expander.hip", "sweep_pair.hip", "sweep_tiny.hip", "sets.hip",
+                              "swarm.hip", "factor.hip")]
     print("%-88s %5s %5s %5s %8s %5s %8s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch",
                                             "occ", "LDS"))
     for f in files:

@@ -1,5 +1,5 @@
 """GPU parity of the incremental path -- ``sgp_gp_append`` / ``sgp_gp_pop`` (factor.hip) and the
-closed-form refresh of the resident posterior, ``sgp_grid_rank1_update`` (k_rank1, sweep.hip) --
+closed-form refresh of the resident posterior, ``sgp_grid_rank1_update`` (k_rank1, expander.hip) --
 against a long-double GP (tests/_incremental_ref.py), through the C ABI.
 
 Every BO step but each 16th rests on these kernels.  The cases vary what selects code paths:

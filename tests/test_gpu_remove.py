@@ -1,5 +1,5 @@
 """GPU parity of the removal of any observation -- ``sgp_gp_remove`` (factor.hip: the downdate
-of L^-1 and alpha) and ``sgp_grid_rank1_remove`` (k_rank1<.., true>, sweep.hip: the resident
+of L^-1 and alpha) and ``sgp_grid_rank1_remove`` (k_rank1<.., true>, expander.hip: the resident
 posterior corrected in closed form) -- against long-double refits of the reduced data
 (tests/_remove_ref.py), through the C ABI and through SafeOpt.
 
