@@ -36,6 +36,7 @@ extern "C" {
 #define SGP_MAX_PATHS 64   /* sample paths of one call                         */
 #define SGP_MAX_FEATURES 16384 /* random Fourier features of a sample path     */
 #define SGP_MAX_BATCH 64   /* query points of one hallucinated batch           */
+#define SGP_MAX_MES 64     /* maxima of one max-value entropy search (= SGP_MAX_PATHS) */
 
 /* kernel kinds: GPy.kern.RBF / Matern32 / Matern52 (Stationary.K_of_r)        */
 enum { SGP_RBF = 0, SGP_MATERN32 = 1, SGP_MATERN52 = 2 };
@@ -518,6 +519,50 @@ int sgp_grid_paths(sgp_grid* grid, sgp_gp* gp, const double* Omega, const double
 int sgp_grid_paths_comm(sgp_grid* grid, sgp_gp* gp, const double* Omega, const double* phase,
                         int m, const double* W, const double* V, int S, int mask,
                         double* values, double* best_val, int64_t* best_idx);
+/* Max-value entropy search (Wang & Jegelka 2017).  With K maxima ystar[K] of the objective
+ * (the per-path maxima of sgp_grid_paths over the safe set) and a floor m,
+ *   sigma = sqrt(max(var, 1e-15)),  y_k = max(ystar[k], m),  gamma_k = (y_k - mean) / sigma,
+ *   alpha = (1 / K) sum_k term(gamma_k),  term(g) = g phi(g) / (2 Phi(g)) - ln Phi(g),
+ * the terms added in the order of k.  term is evaluated through one scaled complementary
+ * error function (csrc/mes.hip: mes_term): finite over the whole range, 0 exactly from
+ * gamma = 38.6 on, +inf included.  A row's alpha depends on (mean, var, ystar, m) alone: the
+ * same bits from sgp_mes_eval and from sgp_grid_mes, whatever N, the row's position or the
+ * rank.  1 <= K <= SGP_MAX_MES and every ystar[k] finite, or the call fails with nothing
+ * launched.
+ *
+ * sgp_mes_eval: alpha at N arbitrary points from HOST arrays mean[N], var[N] -> out[N];
+ * floor may be +-inf (-inf: no floor), not NaN.  N <= 0 returns 0 and writes nothing.       */
+enum { SGP_MES_ALL = 0, SGP_MES_S = 1, SGP_MES_MG = 2 };          /* candidate rows            */
+enum { SGP_MES_FLOOR_NONE = 0, SGP_MES_FLOOR_MEAN = 1, SGP_MES_FLOOR_VALUE = 2 };
+int sgp_mes_eval(sgp_ctx* ctx, const double* mean, const double* var, int64_t N,
+                 const double* ystar, int K, double floor, double* out);
+/* alpha over the grid's RESIDENT posterior of GP 0 -- a pass that sweeps it
+ * (sgp_grid_confidence, sgp_grid_posterior, sgp_grid_step_small) must have run on the rows as
+ * they are (sgp_grid_set_context voids it), else the call fails; the call takes no GPs, so
+ * that the pass saw their current data is the caller's business (SafeOpt tracks it) -- and
+ * its arg-max over the candidate
+ * rows: every row (rows = SGP_MES_ALL), the rows of S (SGP_MES_S) or of M | G as they stand on
+ * the device (SGP_MES_MG); value and gidx = GLOBAL row (global_offset + local row), the lowest
+ * row among equal values, -inf / -1 when no row qualifies.  alpha (N_local) may be NULL.
+ * The floor: none (SGP_MES_FLOOR_NONE), floor_value (SGP_MES_FLOOR_VALUE, +-inf allowed), or
+ * the maximum of the mean of GP 0 over the rows of S -- over all rows with SGP_MES_ALL, over S
+ * with SGP_MES_MG too -- (SGP_MES_FLOOR_MEAN; -inf when S is empty): reduced on the device
+ * and read from device memory by the row pass, no host round trip in between.  floor_used
+ * returns the floor applied.  One read-back of {value, gidx, floor}, one more of alpha when
+ * asked for.  Q, S, M, G, mean and var are only read.                                        */
+int sgp_grid_mes(sgp_grid* grid, const double* ystar, int K, int rows, int floor_mode,
+                 double floor_value, double* alpha, double* value, int64_t* gidx,
+                 double* floor_used);
+/* sgp_grid_mes over the shards of all ranks of the context's communicator (sgp_comm_init or
+ * sgp_comm_init_host): the floor of SGP_MES_FLOOR_MEAN is all-reduced (max), the ranks' records
+ * {value, GLOBAL row} are all-gathered and merged on the device -- the largest value, the
+ * lowest global row among equals, a shard without a candidate never wins -- all in the grid's
+ * stream (through the host transport otherwise), then ONE read-back.  Every rank returns the
+ * same value, gidx and floor_used; alpha stays the rank's N_local rows.  A collective: every
+ * rank calls it with the same ystar.  Without a communicator it equals sgp_grid_mes.         */
+int sgp_grid_mes_comm(sgp_grid* grid, const double* ystar, int K, int rows, int floor_mode,
+                      double floor_value, double* alpha, double* value, int64_t* gidx,
+                      double* floor_used);
 /* One pick of a batch by hallucinated observations (GP-BUCB, Desautels et al. 2014, on
  * SafeOpt's rule, safeopt/gp_opt.py:635-649; the reference has no batch mode).  gps are CLONES
  * (sgp_gp_clone) of the grid's GPs, every one with the pending pick x* appended

@@ -37,6 +37,9 @@ MAX_JOINT = 8192          # SGP_MAX_JOINT: rows of one joint prediction
 MAX_PATHS = 64            # SGP_MAX_PATHS: sample paths of one call
 MAX_FEATURES = 16384      # SGP_MAX_FEATURES: random Fourier features of a sample path
 MAX_BATCH = 64            # SGP_MAX_BATCH: query points of one hallucinated batch
+MAX_MES = 64              # SGP_MAX_MES: maxima of one max-value entropy search
+MES_ALL, MES_S, MES_MG = 0, 1, 2                        # candidate rows of sgp_grid_mes
+MES_FLOOR_NONE, MES_FLOOR_MEAN, MES_FLOOR_VALUE = 0, 1, 2
 
 # name -> (restype, argtypes); mirrors include/safeopt_hip.h one to one
 PROTOTYPES = {
@@ -78,6 +81,12 @@ PROTOTYPES = {
     "sgp_grid_paths_comm": (C.c_int, [vp, vp, c_double_p, c_double_p, C.c_int, c_double_p,
                                       c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
                                       c_i64_p]),
+    "sgp_mes_eval": (C.c_int, [vp, c_double_p, c_double_p, C.c_int64, c_double_p, C.c_int,
+                               C.c_double, c_double_p]),
+    "sgp_grid_mes": (C.c_int, [vp, c_double_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                               c_double_p, c_double_p, c_i64_p, c_double_p]),
+    "sgp_grid_mes_comm": (C.c_int, [vp, c_double_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                    c_double_p, c_double_p, c_i64_p, c_double_p]),
     "sgp_gp_get_factor": (C.c_int, [vp, c_double_p, c_double_p]),
     "sgp_gp_clone": (C.c_int, [vp, vpp]),
     "sgp_grid_batch_next": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_int, C.c_double,
@@ -497,6 +506,18 @@ class Context(object):
 
     def barrier(self):
         self.check(lib().sgp_comm_barrier(self.h))
+
+    def mes_eval(self, mean, var, ystar, floor=-np.inf):
+        """Max-value entropy search acquisition at arbitrary points (``sgp_mes_eval``): the
+        posterior ``mean`` / ``var`` of the objective there, the maxima ``ystar`` (K) and a
+        ``floor`` under them (-inf: none) -> alpha, in the shape of ``mean``."""
+        mean, var, ystar = f64(mean), f64(var), f64(ystar).reshape(-1)
+        if mean.shape != var.shape:
+            raise ValueError("mean %r and var %r differ in shape" % (mean.shape, var.shape))
+        out = np.empty(mean.shape)
+        self.check(lib().sgp_mes_eval(self.h, dptr(mean), dptr(var), mean.size, dptr(ystar),
+                                      int(ystar.size), float(floor), dptr(out)))
+        return out
 
     def kern_K(self, kdesc, X1, X2):
         d, kinds, variances, inv_ls = kdesc
@@ -1303,6 +1324,31 @@ class DeviceGrid(object):
             None if vals is None else dptr(vals), None if bv is None else dptr(bv),
             None if bi is None else bi.ctypes.data_as(c_i64_p)))
         return vals, bv, bi
+
+    def mes(self, ystar, rows=MES_S, floor='mean', alpha=False, comm=False):
+        """Max-value entropy search over the resident posterior of GP 0 (``sgp_grid_mes``):
+        ``(alpha (N,) or None, value, global row, floor used)`` -- the arg-max of alpha over
+        the candidate ``rows`` (``MES_ALL`` / ``MES_S`` / ``MES_MG``), -inf / -1 when no row
+        qualifies.  ``floor``: ``'mean'`` (the largest mean of GP 0 over ``S``), ``None``, or
+        a float.  ``comm``: ``sgp_grid_mes_comm`` -- floor and arg-max
+        over the rows of ALL ranks of the context's communicator, the same on every rank
+        (``alpha`` stays this rank's block); a collective."""
+        ystar = f64(ystar).reshape(-1)
+        if floor is None:
+            mode, fv = MES_FLOOR_NONE, 0.0
+        elif isinstance(floor, str):
+            if floor != 'mean':
+                raise ValueError("floor must be 'mean', None or a float, got %r" % (floor,))
+            mode, fv = MES_FLOOR_MEAN, 0.0
+        else:
+            mode, fv = MES_FLOOR_VALUE, float(floor)
+        al = np.empty(self.N) if alpha else None
+        v, i, fu = C.c_double(0), C.c_int64(0), C.c_double(0)
+        call = lib().sgp_grid_mes_comm if comm else lib().sgp_grid_mes
+        self.ctx.check(call(self.h, dptr(ystar), int(ystar.size), int(rows), mode, fv,
+                            None if al is None else dptr(al), C.byref(v), C.byref(i),
+                            C.byref(fu)))
+        return al, v.value, i.value, fu.value
 
     def download(self, what, out=None):
         if what == Q:

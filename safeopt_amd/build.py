@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(PKG, "libsafeopt_hip.so")
 SOURCES = ["api.hip", "expander_api.hip", "batch.hip", "sweep.hip", "expander.hip", "sweep_pair.hip",
            "sweep_mid.hip", "sweep_tiny.hip", "step_small.hip",
-           "factor.hip", "hyper.hip", "joint.hip", "paths.hip", "sets.hip", "swarm.hip",
+           "factor.hip", "hyper.hip", "joint.hip", "mes.hip", "paths.hip", "sets.hip", "swarm.hip",
            "swarm_api.hip", "swarm_batch.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "kern_eval.h", "fitness.h",
                                             "small_path.h", "sweep_shared.h",
@@ -37,7 +37,7 @@ BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 # flags or without them every one of them is the same instruction stream as before the
 # split (profiles/expander_split/isa_diff.txt), and it holds no inline asm to warn about.
 EXTRA = {"sets.hip": ["-ffp-contract=off"], "swarm.hip": ["-ffp-contract=off"],
-         "swarm_batch.hip": ["-ffp-contract=off"],
+         "swarm_batch.hip": ["-ffp-contract=off"], "mes.hip": ["-ffp-contract=off"],
          "sweep.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-Wno-inline-asm"]}
 # e.g. SGP_HIPCC_FLAGS=-DSGP_INSTRUMENT for scripts/ablate.py (use --force)
 USER = os.environ.get("SGP_HIPCC_FLAGS", "").split()

@@ -862,6 +862,7 @@ int sgp_grid_set_context(sgp_grid* g, const double* c, int nc) {
   SGP_CHECK(ctx, nc >= 0 && nc <= g->d && nc <= SGP_MAX_GPS,
             "bad number of context columns %d", nc);
   if (nc == 0) return 0;
+  g->post_valid = false;     // the rows change: mean / var describe the old ones
   if (g->axes_valid) {
     // the context columns are constant columns of the tensor grid: new axis values
     for (int i = 0; i < nc; ++i) {
@@ -1104,6 +1105,7 @@ int sgp_grid_confidence(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
   SepLaunch sl;
   SGP_TRY(launch_sweep_conf(ctx, g->gpdev, host, G, g->d, sp, co,
                             sep_launch(g, gps, host, G, &sl), /*rows_sharded=*/true));
+  g->post_valid = true;
   return finish_safe_partials(g, ctx->sweep_partials, out2);
 }
 
@@ -1118,8 +1120,10 @@ int sgp_grid_posterior(sgp_grid* g, sgp_gp* const* gps, int G) {
   co.beta = 0.0;
   for (int i = 0; i < SGP_MAX_GPS; ++i) co.fmin[i] = -INFINITY;
   SepLaunch sl;
-  return launch_sweep_conf(ctx, g->gpdev, host, G, g->d, sp, co,
-                           sep_launch(g, gps, host, G, &sl), /*rows_sharded=*/true);
+  SGP_TRY(launch_sweep_conf(ctx, g->gpdev, host, G, g->d, sp, co,
+                            sep_launch(g, gps, host, G, &sl), /*rows_sharded=*/true));
+  g->post_valid = true;
+  return 0;
 }
 
 // sgp_grid_rank1_update / sgp_grid_rank1_remove: the flagged GPs carry the record of an
@@ -1149,6 +1153,7 @@ static int rank1_refresh(sgp_grid* g, sgp_gp* const* gps, int G, const int* whic
   ra.partial = g->partial;
   ra.beta = beta;
   SweepPoints sp{g->pts, g->N, 1, g->N};
+  // (post_valid stays as it is: the refresh keeps a swept posterior current, it makes none)
   SGP_TRY(launch_rank1(ctx, g->gpdev, G, g->d, sp, ra, remove));
   return finish_safe_partials(g, rank1_num_blocks(g->N), out2);
 }
@@ -1555,7 +1560,7 @@ int sgp_grid_sets_front(sgp_grid* g, double max_l, int have_max_var,
 static bool have_comm(const sgp_ctx* ctx) {
   return ctx->comm != nullptr || ctx->hostcomm.allgather != nullptr;
 }
-static int coll_allreduce_max_f64(sgp_ctx* ctx, double* dev, size_t n) {
+int coll_allreduce_max_f64(sgp_ctx* ctx, double* dev, size_t n) {
   if (ctx->comm) {
     SGP_NCCL(ctx, g_rccl.AllReduce(dev, dev, n, ncclFloat64, ncclMax,
                                    static_cast<ncclComm_t>(ctx->comm), ctx->stream));
@@ -1792,6 +1797,7 @@ int sgp_grid_step_small(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
   const uint64_t seq = ++ctx->step_seq;
   SGP_TRY(launch_step_small(g, g->gpdev, host, G, beta, fmin, scaling, thr_beta, ctx->step_dev,
                             seq));
+  g->post_valid = true;
   // No read-back copy, no stream synchronisation: the kernel writes its result block into
   // host memory and a completion word behind it; spin on that word (a launch of 20-40 us),
   // fall back to the stream when it does not turn up.

@@ -189,6 +189,10 @@ enum ScratchSlot : int {
   kSlotLooC = 23,       // ... C = diag(sqrt(b)) Ky^-1 of sgp_gp_loo_lml (n x n: like every slot
                         // it stays at its largest size until sgp_destroy, 2.1 GB after one
                         // call at kMaxObservations)
+  kSlotMesIn = 24,      // mes.hip: ystar | floor of sgp_mes_eval, its rows' mean | var | out; ystar
+                        // and the alpha array of a grid call
+  kSlotMesPart = 25,    // ... per-workgroup (value, row) pairs and floor partials of a grid call,
+                        // its records and result (MesScratch)
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }
@@ -312,6 +316,10 @@ struct sgp_grid {
   double* scal = nullptr;    // [8] resident scalars: [0] = max l0 over S
   int l0_pending = 0;        // > 0: scal[0] is still spread over that many
                              // entries of `partial` (deferred confidence pass)
+  bool post_valid = false;   // mean / var hold the posterior of the resident rows: set by the
+                             // passes that sweep them (sgp_grid_confidence, sgp_grid_posterior,
+                             // sgp_grid_step_small), cleared when the rows change
+                             // (sgp_grid_set_context); what sgp_grid_mes asks for
   // tensor-grid structure (sgp_grid_set_axes; SepLaunch)
   bool axes_valid = false;
   uint32_t ax_count[SGP_MAX_D] = {0};
@@ -529,6 +537,8 @@ struct PsoSchedule {
 extern "C" int comm_or_single(sgp_ctx* ctx, bool* comm);   // is there one?  Error: rank of several without
 // recv (device) = the nbytes of every rank, in rank order
 extern "C" int coll_allgather(sgp_ctx* ctx, const void* send, void* recv, size_t nbytes);
+// dev[n] (device) = the element-wise maximum over the ranks; no communicator: untouched
+extern "C" int coll_allreduce_max_f64(sgp_ctx* ctx, double* dev, size_t n);
 // few-points posterior / small-swarm step: small_path.h
 constexpr int kSmallPoints = 4096;  // few-points posterior path (factor.hip)
 constexpr int kSmallSwarm = 64;     // ... with the whole PSO step in one workgroup (swarm.hip)

@@ -24,6 +24,7 @@ import numpy as np
 
 __all__ = ["shard_range", "allgather_rows", "LocalComm", "RcclComm", "SocketComm", "init_from_env",
            "merge_topk", "merge_argmax", "merge_path_records", "merge_batch_records",
+           "merge_mes_records",
            "gather_shard_columns", "check_same_paths",
            "launch_check"]
 
@@ -523,3 +524,13 @@ def merge_batch_records(records):
     records = np.asarray(records, dtype=np.float64).reshape(-1, 3)
     v, i = merge_argmax(records[:, 0], records[:, 1].astype(np.int64))
     return v, i, bool(np.any(records[:, 2] != 0))
+
+
+def merge_mes_records(records):
+    """The pick of a sharded max-value entropy search from the ranks' records ``(world, 2)``:
+    ``{alpha, global row}`` per rank (the host form of ``k_mes_merge``), merged as in
+    :func:`merge_argmax`: the largest value, the lowest global row among equal values; a rank
+    without a candidate row (row -1) never wins, none on any rank gives ``(-inf, -1)``.
+    Returns ``(value, global row)``."""
+    records = np.asarray(records, dtype=np.float64).reshape(-1, 2)
+    return merge_argmax(records[:, 0], records[:, 1].astype(np.int64))

@@ -32,8 +32,8 @@ import numpy as np
 
 from . import _hip
 from .dist import (LocalComm, allgather_rows, check_same_paths, gather_shard_columns,
-                   merge_argmax, merge_batch_records, merge_path_records, merge_topk,
-                   shard_range)
+                   merge_argmax, merge_batch_records, merge_mes_records, merge_path_records,
+                   merge_topk, shard_range)
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
 
 __all__ = ['SafeOpt', 'SafeOptSwarm']
@@ -563,6 +563,15 @@ class _HipGridBackend(object):
         the arg-max merged over the ranks in the grid's stream (``sgp_grid_paths_comm``)."""
         return self.grid.paths(pp.device, pp.Omega, pp.phase, pp.W, pp.V, mask=mask,
                                values=values, comm=comm)
+
+    def mes(self, ystar, rows, floor, alpha=False, comm=False):
+        """Max-value entropy search over the resident posterior of the objective
+        (``DeviceGrid.mes``); the posterior is swept first when it is not that of the GPs as
+        they are.  ``comm``: floor and arg-max merged over the ranks in the grid's stream
+        (``sgp_grid_mes_comm``)."""
+        if not self.posterior_is_current():
+            self.refresh_posterior()
+        return self.grid.mes(ystar, rows=rows, floor=floor, alpha=alpha, comm=comm)
 
 
 class SafeOpt(GaussianProcessOptimization):
@@ -1586,6 +1595,117 @@ class SafeOpt(GaussianProcessOptimization):
             raise RuntimeError('There are no safe points to sample in.')
         x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
         return (x, best, values) if return_values else (x, best)
+
+    def mes_point(self, paths=16, features=1024, within='safe', floor='mean',
+                  return_values=False):
+        """The safe row whose measurement tells most about the VALUE of the safe optimum:
+        max-value entropy search (Wang & Jegelka 2017) inside the safe set.
+
+        ``paths`` sample paths of the objective GP (``gps[0]``, ``posterior_paths(paths,
+        features)``) give ``paths`` draws ``ystar`` of the maximum over ``S`` (their maxima
+        over the resident grid, as ``thompson_points`` takes them); with ``mu``, ``v`` the
+        resident posterior of the objective, ``sigma = sqrt(max(v, 1e-15))``,
+        ``y_k = max(ystar_k, floor)`` and ``gamma_k = (y_k - mu) / sigma``,
+
+            ``alpha(x) = mean_k [gamma_k phi(gamma_k) / (2 Phi(gamma_k)) - ln Phi(gamma_k)]``,
+
+        and the pick is the row of ``S`` with the largest ``alpha`` (the lowest row among
+        equals).  One pass over the resident rows on the device, finite for every ``gamma``.
+        It needs no Lipschitz constant and no width rule, and it stops sampling the
+        incumbent, which UCB and Thompson picks do not.
+
+        ``floor='mean'`` (default): the largest posterior mean over ``S``.  A path maximum
+        slightly below the mean -- the paths' prior term is approximate, and the maximum is
+        taken over ``S`` only -- would make ``gamma`` negative where the mean is high, and the
+        pick would collapse onto the incumbent with the smallest ``sigma``; with the floor
+        ``gamma >= 0`` on every candidate.  ``floor=None``: none; a float: that value.
+
+        ``within='safe'``: candidates ``S``.  ``'MG'``: candidates ``M | G`` as they stand --
+        call it after ``optimize()`` / ``compute_sets()``, which compute them; maxima and
+        floor are still those of ``S``.  ``'all'``: no mask for maxima, floor and candidates
+        -- NOT a safe pick, for diagnostics and unconstrained problems only.
+
+        Returns ``(x, alpha)``: the row, context columns stripped as ``optimize()`` strips
+        them, and its ``alpha``; with ``return_values=True`` ``(x, alpha, values (N,),
+        ystar (paths,))``: ``alpha`` of every row and the maxima used.  Raises
+        ``RuntimeError`` when no row qualifies.  Changes no state of the optimiser or its
+        GPs -- except that pending in-place edits of ``opt.Q`` / ``opt.S`` are flushed first,
+        as before a set pass, and that the resident posterior is swept again if data came
+        in since the last interval update; the random numbers come from NumPy's global
+        generator.
+
+        N ranks (SPMD, as ``thompson_points``: the same seed and the same call on every
+        rank, verified by its digest check): maxima, floor and pick are those of all
+        shards -- merged in the grid's stream with an in-stream communicator
+        (``sgp_grid_paths_comm``, ``sgp_grid_mes_comm``), else through ``allreduce_max`` of
+        the floor (one extra pass over the shard with one maximum finds the shard's), one
+        ``allgather`` of the ranks' records and ``dist.merge_mes_records``; both give the
+        bits of the one-rank run, on every rank.  ``values`` is gathered in global row
+        order.  "No row qualifies" raises on every rank, behind the collective."""
+        if within not in ('safe', 'MG', 'all'):
+            raise ValueError("within must be 'safe', 'MG' or 'all', got %r" % (within,))
+        paths = int(paths)
+        if paths < 1 or paths > _hip.MAX_MES:
+            raise ValueError("paths must be in 1 .. SGP_MAX_MES = %d, got %d"
+                             % (_hip.MAX_MES, paths))
+        if isinstance(floor, str):
+            if floor != 'mean':
+                raise ValueError("floor must be 'mean', None or a float, got %r" % (floor,))
+        elif floor is not None:
+            floor = float(floor)
+            if np.isnan(floor):
+                raise ValueError("floor is NaN")
+        comm = self._comm
+        world = comm.world
+        if world > 1 and not all(callable(getattr(comm, f, None))
+                                 for f in ('allreduce_max', 'allgather')):
+            raise NotImplementedError(
+                "mes_point on more than one rank merges the ranks' picks through the "
+                "communicator's allreduce_max and allgather: this communicator of %d ranks "
+                "implements neither" % world)
+        if not (hasattr(self._backend, 'paths') and hasattr(self._backend, 'mes')):
+            raise NotImplementedError("this grid backend runs no max-value entropy search")
+        self._flush_Q()
+        self._flush_masks()
+        safe = within != 'all'
+        rows = {'safe': _hip.MES_S, 'MG': _hip.MES_MG, 'all': _hip.MES_ALL}[within]
+        # (N ranks: raised behind the collective, where every rank is sure to arrive)
+        if world == 1 and safe and self._any_safe is not None and not self._any_safe:
+            raise RuntimeError('There are no safe points to sample in.')
+        pp = self.gp.posterior_paths(size=paths, features=features)
+        in_stream = world > 1 and getattr(comm, 'in_stream', False)
+        if world == 1:
+            _, ystar, at = self._backend.paths(pp, safe, False)
+        else:
+            check_same_paths(comm, pp)
+            if in_stream:
+                _, ystar, at = self._backend.paths(pp, safe, False, comm=True)
+            else:
+                _, bv, bi = self._backend.paths(pp, safe, False)
+                rec = np.empty((2, bv.shape[0]))
+                rec[0], rec[1] = bv, bi                           # (rows < 2^53)
+                rec = comm.allgather(rec)
+                ystar, at = merge_path_records(rec[:, 0], rec[:, 1].astype(np.int64))
+        if np.any(at < 0):
+            raise RuntimeError('There are no safe points to sample in.')
+        if world == 1 or in_stream:
+            values, alpha, idx, _floor = self._backend.mes(ystar, rows, floor, return_values,
+                                                           comm=world > 1)
+        else:
+            if floor == 'mean':
+                # the shard's floor from a pass with one maximum, then the ranks' largest
+                floor = self._backend.mes(ystar[:1], rows, 'mean')[3]
+                floor = float(comm.allreduce_max(np.array([floor]))[0])
+            values, v, i, _floor = self._backend.mes(ystar, rows, floor, return_values)
+            alpha, idx = merge_mes_records(comm.allgather(np.array([v, float(i)])))
+        if world > 1 and return_values:
+            N = self.inputs.shape[0]
+            values = allgather_rows(comm, values, [
+                hi - lo for lo, hi in (shard_range(N, r, world) for r in range(world))])
+        if idx < 0:
+            raise RuntimeError('There are no safe points to sample in.')
+        x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
+        return (x, alpha, values, ystar) if return_values else (x, alpha)
 
     def get_maximum(self, context=None):
         """Best lower bound inside the safe set: ``(x, l)`` or ``None``."""

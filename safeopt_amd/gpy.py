@@ -467,6 +467,20 @@ class GPRegression(object):
                                      lambda X: dev.paths_eval(Om, b, W, V, X),
                                      self._paths_token, device=dev)
 
+    def max_value_entropy(self, X, ystar, floor=None):
+        """Max-value entropy search acquisition (Wang & Jegelka 2017) at the rows of ``X``,
+        ``(N, 1)``: with ``mu, v = predict_noiseless(X)``, ``sigma = sqrt(max(v, 1e-15))``,
+        ``y_k = max(ystar[k], floor)`` and ``gamma_k = (y_k - mu) / sigma``, the mean over
+        ``k`` of ``gamma phi(gamma) / (2 Phi(gamma)) - ln Phi(gamma)`` -- the information a
+        noiseless measurement at the row carries about the value of the maximum, ``ystar``
+        being ``K <= 64`` draws of that maximum (``posterior_paths(...).paths(X).max(0)``).
+        ``floor``: a value no maximum can lie below (the best posterior mean, say); None for
+        none.  One device call behind the prediction (``sgp_mes_eval``), finite for every
+        ``gamma``."""
+        mean, var = self.predict_noiseless(X)
+        dev = self._fitted()
+        return dev.ctx.mes_eval(mean, var, ystar, -np.inf if floor is None else float(floor))
+
     def posterior_samples(self, X, size=10):
         """``posterior_samples_f`` plus observation noise: ``sqrt(noise_var)`` times a
         second draw ``np.random.randn(N, 1, size)``."""
