@@ -664,6 +664,33 @@ int sgp_swarm_fitness_hall(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* clon
                            const double* fmin, const double* scaling, double best_lower_bound,
                            double* values, uint8_t* safe, double* var_h);
 
+/* The fitness of a MES swarm: max-value entropy search (Wang & Jegelka 2017; the rule of
+ * sgp_grid_mes) without a grid.  ystar[K] are K maxima of the objective (GP 0) over the safe
+ * region, floor a value no maximum can lie below (-inf: none; +-inf allowed, NaN refused).
+ * With mu_g, var_g the posterior of GP g at x and lower_g = mu_g - beta sqrt(var_g), for every
+ * GP with a finite fmin[g]:
+ *   slack = lower_g - fmin[g];  safe &= slack >= 0;  total_pen += penalty(slack / scaling[g])
+ * (the penalty and safety rule of SGP_SWARM_MAXIMIZERS), and with
+ *   sigma = sqrt(max(var_0, 1e-15)),  y_k = max(ystar[k], floor),  gamma_k = (y_k - mu_0) / sigma,
+ *   alpha = (1 / K) sum_k term(gamma_k)   (the terms added in the order of k; sgp_mes_eval),
+ *   values = alpha + total_pen;
+ * alpha has the bits of sgp_mes_eval on post; a particle's value depends on its posterior and
+ * (ystar, floor) alone -- not on P, its row or the launch -- and the same inputs give the same
+ * bits.  The posterior is formed by the kernels sgp_swarm_fitness takes for that P and n; alpha
+ * is one more launch behind the shaping pass: one thread per particle on the fp64 VALU, the K
+ * floored maxima staged in LDS once per workgroup, no atomics.  The maxima are staged on the
+ * device once per call.  post (2,P) receives the posterior of GP 0 the term was formed from
+ * (row 0 the mean, row 1 the variance), or NULL.  scaling[0] does not scale alpha (it is a
+ * number of nats, not a function value).
+ * Checked in this order: G >= 1 and gps[0]; 1 <= K <= SGP_MAX_MES and every ystar[k] finite;
+ * floor not NaN -- a refused call writes nothing; P <= 0 then returns 0 and writes nothing;
+ * then the checks of sgp_swarm_fitness (GP 0 .. G-1 fitted, in ctx, one input dimension).
+ * particles (P,d) row-major; values (P) f64; safe (P) u8.                             */
+int sgp_swarm_fitness_mes(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                          int64_t P, double beta, const double* fmin, const double* scaling,
+                          const double* ystar, int K, double floor, double* values,
+                          uint8_t* safe, double* post);
+
 /* ---- SafeOptSwarm safe-set growth (gp_opt.py:1089-1111) ---------------------
  * After a maximizer / expander swarm run the reference appends, in order, every
  * best position B_j (n,d row-major) whose prior correlation
@@ -778,6 +805,39 @@ int sgp_swarm_run_hall_shard(sgp_ctx* ctx, sgp_gp* const* gps, sgp_gp* const* cl
                              int iters, double inertia0, double step, const double* rand,
                              uint64_t seed, int64_t p0, int64_t P_total);
 
+/* sgp_swarm_run for a MES swarm: the fitness is that of sgp_swarm_fitness_mes (post = NULL),
+ * the state arrays, init / iters / inertia, rand and seed as for sgp_swarm_run, ystar / K /
+ * floor in place of the path of sgp_swarm_run_path.  One call is the whole run: the maxima are
+ * staged on the device once per call.  Like a path run it ALWAYS takes the general launches --
+ * move, fitness (posterior, shaping, alpha), personal bests, global best -- never the
+ * one-workgroup step of a small swarm: with rand != NULL the run is bit-identical to the host
+ * loop over sgp_swarm_fitness_mes.  The whole swarm in one call (a rank's block:
+ * sgp_swarm_run_mes_shard).  The refusals of sgp_swarm_fitness_mes, in its order; P <= 0
+ * returns 0 and writes nothing.                                                   */
+int sgp_swarm_run_mes(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                      const double* fmin, const double* scaling, int64_t P, double* positions,
+                      double* velocities, double* best_positions, double* best_values,
+                      double* global_best, const double* velocity_scale,
+                      const double* bounds, int init, int iters, double inertia0,
+                      double step, const double* rand, uint64_t seed,
+                      const double* ystar, int K, double floor);
+
+/* sgp_swarm_run_mes on a rank's block [p0, p0 + P) of a MES swarm of P_total: the block, the
+ * merge of the global best after init and after every iteration, the Philox indexing and the
+ * layout of rand are those of sgp_swarm_run_shard; the posterior kernel follows P_total; every
+ * rank passes the same ystar and floor.  alpha is per particle, so a block computes the bits
+ * the whole swarm computes for its particles.  P <= 0 and P_total <= 0 returns 0; an empty
+ * block of a sharded swarm is refused ("bad swarm size"), as is a block without a
+ * communicator on ctx.  p0 = 0, P = P_total is sgp_swarm_run_mes.                    */
+int sgp_swarm_run_mes_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                            const double* fmin, const double* scaling, int64_t P,
+                            double* positions, double* velocities, double* best_positions,
+                            double* best_values, double* global_best,
+                            const double* velocity_scale, const double* bounds, int init,
+                            int iters, double inertia0, double step, const double* rand,
+                            uint64_t seed, const double* ystar, int K, double floor,
+                            int64_t p0, int64_t P_total);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------
  * The only cross-rank traffic of the path is a handful of scalars per
  * iteration (max / any / arg-max / top-k merge).                             */
@@ -815,6 +875,9 @@ int sgp_timer_stop(sgp_ctx* ctx, float* ms);
 int sgp_profile_enable(sgp_ctx* ctx, int on);
 int sgp_profile_read(sgp_ctx* ctx, double* total_ms, int64_t* launches,
                      double* flops);
+/* ... and the time of the LAST timed launch alone (0 when none ran): the term of a 'mes'
+ * swarm is the last timed launch of a sgp_swarm_fitness_mes call, behind the sweep's     */
+int sgp_profile_read_last(sgp_ctx* ctx, double* ms);
 /* device allocations (hipMalloc) this context has made so far: buffers grow on
  * demand, and a growth is an allocation plus a stream sync -- a steady-state
  * loop (same n, same grid) must leave this number unchanged                  */

@@ -190,6 +190,10 @@ PROTOTYPES = {
                                          C.c_int64, C.c_double, c_double_p,
                                          c_double_p, C.c_double, c_double_p,
                                          c_u8_p, c_double_p]),
+    "sgp_swarm_fitness_mes": (C.c_int, [vp, vpp, C.c_int, c_double_p, C.c_int64,
+                                        C.c_double, c_double_p, c_double_p,
+                                        c_double_p, C.c_int, C.c_double, c_double_p,
+                                        c_u8_p, c_double_p]),
     "sgp_swarm_grow": (C.c_int, [vp, vp, c_double_p, C.c_int64, c_double_p,
                                  C.c_int64, C.c_double, C.c_double, c_u8_p]),
     "sgp_swarm_run": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
@@ -210,6 +214,19 @@ PROTOTYPES = {
                                            c_double_p, c_double_p, c_double_p, C.c_int,
                                            C.c_int, C.c_double, C.c_double, c_double_p,
                                            C.c_uint64, C.c_int64, C.c_int64]),
+    "sgp_swarm_run_mes": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                    c_double_p, c_double_p, C.c_int64,
+                                    c_double_p, c_double_p, c_double_p, c_double_p,
+                                    c_double_p, c_double_p, c_double_p, C.c_int,
+                                    C.c_int, C.c_double, C.c_double, c_double_p,
+                                    C.c_uint64, c_double_p, C.c_int, C.c_double]),
+    "sgp_swarm_run_mes_shard": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                          c_double_p, c_double_p, C.c_int64,
+                                          c_double_p, c_double_p, c_double_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, C.c_int,
+                                          C.c_int, C.c_double, C.c_double, c_double_p,
+                                          C.c_uint64, c_double_p, C.c_int, C.c_double,
+                                          C.c_int64, C.c_int64]),
     "sgp_swarm_run_path": (C.c_int, [vp, vpp, C.c_int, C.c_double,
                                      c_double_p, c_double_p, C.c_int64,
                                      c_double_p, c_double_p, c_double_p, c_double_p,
@@ -241,6 +258,7 @@ PROTOTYPES = {
     "sgp_timer_stop": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "sgp_profile_enable": (C.c_int, [vp, C.c_int]),
     "sgp_profile_read": (C.c_int, [vp, c_double_p, c_i64_p, c_double_p]),
+    "sgp_profile_read_last": (C.c_int, [vp, c_double_p]),
     "sgp_ctx_alloc_count": (C.c_int64, [vp]),
     "sgp_comm_count": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "sgp_ctx_set_sweep": (C.c_int, [vp, C.c_int]),
@@ -383,6 +401,12 @@ class Context(object):
         self.check(lib().sgp_profile_read(self.h, C.byref(ms), C.byref(n),
                                           C.byref(fl)))
         return ms.value, n.value, fl.value
+
+    def profile_read_last(self):
+        """Milliseconds of the last timed launch alone (``sgp_profile_read_last``)."""
+        ms = C.c_double(0)
+        self.check(lib().sgp_profile_read_last(self.h, C.byref(ms)))
+        return ms.value
 
     def alloc_count(self):
         """Device allocations made so far (a warm loop must not add any)."""
@@ -1404,11 +1428,14 @@ def _swarm_path_args(gp, path):
     return Omega, phase, m, w, v
 
 
-def _swarm_call(ctx, name, gps, swarm_type, path, clones):
-    """The C symbol ``sgp_swarm_<name>[_path|_hall]`` of a swarm variant, the head of its
+def _swarm_call(ctx, name, gps, swarm_type, path, clones, mes=None):
+    """The C symbol ``sgp_swarm_<name>[_path|_hall|_mes]`` of a swarm variant, the head of its
     argument list -- ``ctx, gps[, clones], G[, swarm type]`` -- and the staged-on-the-host
     path arguments that close it (``path = (Omega, phase, w, v)``, one sample path of
-    ``gps[0]``; ``clones[g]``: ``gps[g].clone()`` with the pending picks appended)."""
+    ``gps[0]``; ``clones[g]``: ``gps[g].clone()`` with the pending picks appended; ``mes =
+    (ystar, floor)``: the maxima of a max-value entropy search and the floor under them)."""
+    if mes is not None and (path is not None or clones is not None):
+        raise NotImplementedError("a 'mes' swarm takes neither a path nor clones")
     head, tail = (ctx.h, _gp_array(gps)), ()
     if clones is not None:
         if len(clones) != len(gps):
@@ -1418,34 +1445,38 @@ def _swarm_call(ctx, name, gps, swarm_type, path, clones):
     if path is not None:
         Omega, phase, m, w, v = _swarm_path_args(gps[0], path)
         name, tail = name + "_path", (dptr(Omega), dptr(phase), m, dptr(w), dptr(v))
+    elif mes is not None:
+        ystar = f64(mes[0]).reshape(-1)
+        name, tail = name + "_mes", (dptr(ystar), int(ystar.size), float(mes[1]))
     else:
         head += (SWARM_TYPES[swarm_type],)
     return name, head, tail
 
 
 def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=None,
-               shard=None):
+               shard=None, mes=None):
     """Every whole PSO run on the device: ``fit = (beta, fmin, scaling, best_lower_bound)``,
     ``state = (positions, velocities, best_positions, best_values, global_best,
     velocity_scale, bounds)`` -- the first five updated in place -- and ``schedule = (init,
     iters, inertia0, step, rand, seed)``, the structs of the C side.  ``path`` (a Thompson
     swarm; ``swarm_type`` and the best lower bound are not used), ``clones`` (a hallucinated
-    swarm) and ``shard = (p0, P_total)`` pick the entry point (``sgp_swarm_run[_hall|_path]
-    [_shard]``)."""
+    swarm), ``mes = (ystar, floor)`` (a max-value entropy search swarm; ``swarm_type`` and the
+    best lower bound are not used) and ``shard = (p0, P_total)`` pick the entry point
+    (``sgp_swarm_run[_hall|_path|_mes][_shard]``)."""
     beta, fmin, scaling, best_lower_bound = fit
     init, iters, inertia0, step, rand, seed = schedule
     P = state[0].shape[0]
     if clones is not None and path is not None:
         raise NotImplementedError("a hallucinated swarm is a maximizers or an expanders "
                                   "swarm, not a Thompson swarm")
-    name, head, tail = _swarm_call(ctx, "sgp_swarm_run", gps, swarm_type, path, clones)
+    name, head, tail = _swarm_call(ctx, "sgp_swarm_run", gps, swarm_type, path, clones, mes)
     for a in state[:5]:
         assert a.dtype == np.float64 and a.flags.c_contiguous
     vscale = f64(state[5])
     bnd = None if state[6] is None else f64(state[6])
     rnd = None if rand is None else f64(rand).ravel()
     args = head + (float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
-    if path is None:
+    if path is None and mes is None:
         args += (float(best_lower_bound),)
     args += (P,) + tuple(dptr(a) for a in state[:5]) + (
         dptr(vscale), None if bnd is None else dptr(bnd), int(bool(init)), int(iters),
@@ -1456,25 +1487,32 @@ def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=Non
 
 
 def _swarm_fitness(ctx, gps, swarm_type, particles, fit, path=None, clones=None,
-                   want_var=False):
+                   want_var=False, mes=None, want_post=False):
     """Every swarm fitness call: ``(values, safe)`` of ``particles``, with ``want_var`` (a
-    hallucinated swarm's) also the hallucinated variances ``(G, P)``; ``fit``, ``path`` and
-    ``clones`` as for :func:`_swarm_run`."""
+    hallucinated swarm's) also the hallucinated variances ``(G, P)``, with ``want_post`` (a
+    'mes' swarm's) also the posterior ``(2, P)`` of GP 0 the term was formed from; ``fit``,
+    ``path``, ``clones`` and ``mes`` as for :func:`_swarm_run`."""
     beta, fmin, scaling, best_lower_bound = fit
-    name, head, tail = _swarm_call(ctx, "sgp_swarm_fitness", gps, swarm_type, path, clones)
+    name, head, tail = _swarm_call(ctx, "sgp_swarm_fitness", gps, swarm_type, path, clones, mes)
     particles = f64(particles).reshape(-1, gps[0].d)
     P = particles.shape[0]
     values = np.empty(P)
     safe = np.empty(P, dtype=np.uint8)
     var_h = np.empty((len(gps), P)) if want_var else None
     args = head + (dptr(particles), P, float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
-    if path is None:
+    if path is None and mes is None:
         args += (float(best_lower_bound),)
     args += tail + (dptr(values), safe.ctypes.data_as(c_u8_p))
     if clones is not None:
         args += (None if var_h is None else dptr(var_h),)
-    if P or clones is not None:        # (an empty hallucinated call still checks its clones)
+    post = np.empty((2, P)) if want_post else None
+    if mes is not None:
+        args += (None if post is None else dptr(post),)
+    # (an empty hallucinated call still checks its clones, an empty 'mes' call its maxima)
+    if P or clones is not None or mes is not None:
         ctx.check(getattr(lib(), name)(*args))
+    if want_post:
+        return values, safe.view(np.bool_), post
     if want_var:
         return values, safe.view(np.bool_), var_h
     return values, safe.view(np.bool_)
@@ -1547,3 +1585,30 @@ def swarm_run_hall(ctx, gps, clones, swarm_type, beta, fmin, scaling, best_lower
                (positions, velocities, best_positions, best_values, global_best,
                 velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
                clones=clones, shard=shard)
+
+
+def swarm_fitness_mes(ctx, gps, particles, beta, fmin, scaling, ystar, floor=-np.inf,
+                      want_post=False):
+    """Fitness and safety of ``particles`` for a max-value entropy search swarm
+    (``sgp_swarm_fitness_mes``): ``values = alpha + total_pen`` with ``alpha`` the acquisition
+    of :meth:`Context.mes_eval` on the posterior of ``gps[0]``, ``ystar`` (K) the maxima and
+    ``floor`` the value under them (-inf: none), the penalty and ``safe`` those of the
+    maximizers swarm.  ``want_post``: also that posterior, ``(2, P)`` mean | var."""
+    return _swarm_fitness(ctx, gps, None, particles, (beta, fmin, scaling, 0.0),
+                          mes=(ystar, floor), want_post=want_post)
+
+
+def swarm_run_mes(ctx, gps, beta, fmin, scaling, positions, velocities, best_positions,
+                  best_values, global_best, velocity_scale, bounds, init, iters, inertia0,
+                  step, rand, ystar, floor=-np.inf, seed=0, shard=None):
+    """Whole PSO run of a max-value entropy search swarm on the device
+    (``sgp_swarm_run_mes``); the state arrays are updated in place, ``ystar`` and ``floor`` as
+    for :func:`swarm_fitness_mes`.
+
+    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
+    ``P_total`` sharded over the ranks of ``ctx``'s communicator
+    (``sgp_swarm_run_mes_shard``), as for :func:`swarm_run`."""
+    _swarm_run(ctx, gps, None, (beta, fmin, scaling, 0.0),
+               (positions, velocities, best_positions, best_values, global_best,
+                velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
+               mes=(ystar, floor), shard=shard)

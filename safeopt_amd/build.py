@@ -25,7 +25,7 @@ HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "kern_eval.h", "fitness.h
                                             "small_path.h", "sweep_shared.h",
                                             "sweep_slots.h", "set_order.h",
                                             "tiny_row.h", "sets_front.h",
-                                            "expander_layout.h")] + \
+                                            "expander_layout.h", "mes_term.h")] + \
           [os.path.join(REPO, "include", "safeopt_hip.h")]
 BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
         "-I", os.path.join(REPO, "include"), "-I", CSRC, "-Wall",

@@ -1969,6 +1969,17 @@ int sgp_profile_read(sgp_ctx* ctx, double* total_ms, int64_t* launches,
   return 0;
 }
 
+int sgp_profile_read_last(sgp_ctx* ctx, double* ms) {
+  SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *ms = 0.0;
+  if (ctx->prof_used < 2) return 0;
+  float t = 0.f;
+  SGP_HIP(ctx, hipEventElapsedTime(&t, ctx->prof_events[ctx->prof_used - 2],
+                                   ctx->prof_events[ctx->prof_used - 1]));
+  *ms = t;
+  return 0;
+}
+
 // ---- RCCL -----------------------------------------------------------------------
 int sgp_comm_unique_id(void* id128) {
   SGP_TRY(load_rccl(nullptr));

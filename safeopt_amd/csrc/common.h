@@ -190,12 +190,33 @@ enum ScratchSlot : int {
                         // it stays at its largest size until sgp_destroy, 2.1 GB after one
                         // call at kMaxObservations)
   kSlotMesIn = 24,      // mes.hip: ystar | floor of sgp_mes_eval, its rows' mean | var | out; ystar
-                        // and the alpha array of a grid call
+                        // and the alpha array of a grid call; swarm_api.hip: ystar and post of a
+                        // 'mes' swarm call (SwarmMesLayout) -- neither swarm_fitness nor
+                        // swarm_run asks for this slot, so what the entry point staged stays put
   kSlotMesPart = 25,    // ... per-workgroup (value, row) pairs and floor partials of a grid call,
                         // its records and result (MesScratch)
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }
+// The head of kSlotMesIn, in doubles: ystar[SGP_MAX_MES] | floor, the rows' arrays behind it
+constexpr size_t kMesHead = SGP_MAX_MES + 8;
+// The block of a 'mes' swarm call in kSlotMesIn (sgp_swarm_fitness_mes, sgp_swarm_run_mes[_shard]):
+//   ystar[SGP_MAX_MES] (the first K staged, ONCE per call) | 8 doubles unused |
+//   post[2][P] f64 (mean | var of GP 0; a fitness call that asks for it)
+struct SwarmMesLayout {
+  size_t ystar, post, bytes;
+};
+constexpr SwarmMesLayout swarm_mes_layout(int64_t P, bool post) {
+  SwarmMesLayout l{};
+  l.ystar = 0;
+  l.post = kMesHead * 8;
+  l.bytes = l.post + (post && P > 0 ? 2 * size_t(P) * 8 : 0);
+  return l;
+}
+static_assert(swarm_mes_layout(3, true).post >= SGP_MAX_MES * 8 &&
+                  swarm_mes_layout(3, true).bytes == swarm_mes_layout(3, true).post + 48 &&
+                  swarm_mes_layout(3, false).bytes == swarm_mes_layout(3, false).post,
+              "SwarmMesLayout: post overlaps the maxima or ends outside the block");
 
 // ---- host-side objects ------------------------------------------------------
 struct DevBuf {
@@ -452,6 +473,22 @@ struct ConfOut {
 // The swarm type of sgp_swarm_fitness_path / sgp_swarm_run_path inside the library (the
 // public entry points that take a swarm type keep to SGP_SWARM_GREEDY .. SGP_SWARM_SAFE_SET)
 constexpr int kSwarmThompson = 4;
+// ... and of sgp_swarm_fitness_mes / sgp_swarm_run_mes: max-value entropy search.  The shaping
+// pass treats it as kSwarmThompson (value = total_pen, the maximizers' safety rule); the term
+// on top is alpha of GP 0's posterior (launch_swarm_mes behind the shaping launch)
+constexpr int kSwarmMes = 5;
+// The maxima of a 'mes' swarm as the kernel takes them
+struct SwarmMes {
+  const double* ystar;   // [K] on the device (SwarmMesLayout), not floored
+  int K;                 // 1 .. SGP_MAX_MES; 0: not a 'mes' swarm
+  double floor;          // -inf: none
+  double* post;          // [2][P] on the device: receives mean | var of GP 0, or null
+};
+// mes.hip: 1 <= K <= SGP_MAX_MES and every ystar[k] (host) finite
+int mes_checks(sgp_ctx* ctx, const double* ystar, int K);
+// values[p] = alpha(mean[p], var[p]) + values[p] over P particles (k_swarm_mes)
+int launch_swarm_mes(sgp_ctx* ctx, int64_t P, const double* mean, const double* var,
+                     const SwarmMes& m, double* values);
 struct FitnessArgs {
   int swarm_type;
   double beta;
@@ -465,6 +502,9 @@ struct FitnessArgs {
   // var_h = max(var - down, 1e-15); var_h: [G][P] receives it, or null
   const double* down;
   double* var_h;
+  // a 'mes' swarm (swarm_type == kSwarmMes; K = 0 otherwise): read by launch_fitness_small on
+  // the host, which launches the term behind the shaping kernel -- no kernel reads it
+  SwarmMes mes;
 };
 // rows_sharded: the rows are a rank's shard of a grid -- the sweep kernel is then chosen
 // by the GPs alone (the same on every rank), never by the number of rows
@@ -507,18 +547,19 @@ int launch_swarm_path(sgp_ctx* ctx, const GpDev* gps_dev, int d, const SwarmPath
 // GpDev::share as collect_gps sets it
 int launch_swarm_down(sgp_ctx* ctx, const GpDev* clones_dev, int G, int d, int b,
                       SweepPoints pts, double* down);
-// swarm_api.hip: what the eight sgp_swarm_fitness* / sgp_swarm_run* entry points hand to the
+// swarm_api.hip: what the sgp_swarm_fitness* / sgp_swarm_run* entry points hand to the
 // one fitness routine and the one run routine.
 struct SwarmSpec {             // what the fitness is
   sgp_gp* const* gps;
   int G;
-  int swarm_type;              // SGP_SWARM_*, or kSwarmThompson with a path
+  int swarm_type;              // SGP_SWARM_*, kSwarmThompson with a path, kSwarmMes with maxima
   double beta;
   const double* fmin;          // [G]
   const double* scaling;       // [G]
   double best_lower_bound;
   const SwarmPath* path;       // a Thompson swarm: the STAGED path; null otherwise
   sgp_gp* const* clones;       // a hallucinated swarm: [G]; null otherwise
+  const SwarmMes* mes;         // a 'mes' swarm: the STAGED maxima; null otherwise
 };
 struct SwarmState {            // the caller's arrays (host), rows [p0, p0 + P) of a swarm of Pt
   double *positions, *velocities, *best_positions, *best_values, *global_best;

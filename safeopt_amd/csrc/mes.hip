@@ -22,9 +22,10 @@
 // fp64: the pass is bound by the fp64 VALU, not by the 17 bytes per row it reads.  The K
 // floored maxima are staged in LDS once per workgroup (every lane reads the same word: a
 // broadcast).  A row's alpha is a function of (mu, v, y, floor) alone -- the same device
-// function and the same order of additions in the row kernel (sgp_mes_eval) and in the grid
-// kernel -- so it has the same bits whatever N, the launch shape, the row's position or
-// the rank.  The arg-max is an epilogue: per-workgroup (value, local row) pairs, one small
+// function (mes_term.h) and the same order of additions in the row kernel (sgp_mes_eval), in
+// the grid kernel and in the particle kernel of a 'mes' swarm (k_swarm_mes, behind the shaping
+// pass of sgp_swarm_fitness_mes / sgp_swarm_run_mes) -- so it has the same bits whatever N,
+// the launch shape, the row's position or the rank.  The arg-max is an epilogue: per-workgroup (value, local row) pairs, one small
 // final kernel; the largest value, the lowest row among equals, rows outside the mask never.
 // No atomics.  The floor is reduced on the device and read from device memory by the grid
 // kernel: nothing comes back to the host between the two.
@@ -33,6 +34,7 @@
 #include <cstring>
 #include <limits>
 
+#include "mes_term.h"
 #include "sweep_shared.h"
 
 namespace {
@@ -42,49 +44,12 @@ constexpr int kMesFloorWg = 1024;             // workgroups of the floor reducti
 constexpr int64_t kMesEvalRows = 1 << 20;     // rows per launch of sgp_mes_eval
 constexpr long long kNoRow = std::numeric_limits<long long>::max();
 
-// term(g) = g phi(g) / (2 Phi(g)) - ln Phi(g), with t = |g| / sqrt 2, e = erfcx(t),
-// x = exp(-t^2), q = e x / 2 = Phi(-|g|):
-//   g <  0:  phi / Phi = sqrt(2 / pi) / e          ln Phi = ln(e / 2) - t^2
-//   g >= 0:  phi / Phi = x / sqrt(2 pi) / (1 - q)  ln Phi = log1p(-q)
-// For g >= 38.6 x underflows to 0 and the term is exactly 0; the product g x 0 is not formed
-// (g = +inf, from a floor of +inf, would make it NaN).
-__device__ __forceinline__ double mes_term(double g) {
-  const double t = fabs(g) * 0.70710678118654752440;
-  const double e = erfcx(t);
-  const double x = exp(-(t * t));
-  const double q = 0.5 * e * x;
-  double r, lnp;
-  if (g < 0.0) {
-    r = 0.79788456080286535588 / e;
-    lnp = log(0.5 * e) - t * t;
-  } else {
-    r = x / 2.50662827463100050242 / (1.0 - q);
-    lnp = log1p(-q);
-  }
-  const double gr = x > 0.0 || g < 0.0 ? g * r : 0.0;
-  return 0.5 * gr - lnp;
-}
-
-// alpha of one row; ys: the K floored maxima (LDS)
-__device__ __forceinline__ double mes_alpha(double mu, double v, const double* ys, int K) {
-  const double sigma = sqrt(fmax(v, 1e-15));
-  double acc = 0.0;
-  for (int k = 0; k < K; ++k) acc += mes_term((ys[k] - mu) / sigma);
-  return acc / double(K);
-}
-
 // (value, row) pairs: the larger value, the lower row among equals
 __device__ __forceinline__ void take_better(double& v, long long& i, double v2, long long i2) {
   if (v2 > v || (v2 == v && i2 < i)) {
     v = v2;
     i = i2;
   }
-}
-
-__device__ __forceinline__ void stage_ystar(double* ys, const double* ystar, int K,
-                                            const double* floor) {
-  if (int(threadIdx.x) < K) ys[threadIdx.x] = fmax(ystar[threadIdx.x], floor[0]);
-  __syncthreads();
 }
 
 // sgp_mes_eval: out[r] = alpha(mean[r], var[r])
@@ -203,7 +168,36 @@ __global__ void k_mes_set(double* p, double v) {
   if (threadIdx.x == 0) p[0] = v;
 }
 
-// The argument checks the entry points share.
+// The fitness term of a 'mes' swarm (sgp_swarm_fitness_mes / sgp_swarm_run_mes), behind the
+// shaping pass of fitness.h (kSwarmMes): one thread per particle,
+//   values[p] = alpha(mean[p], var[p]) + values[p],
+// mean / var the posterior of GP 0 the shaping pass has just consumed, values[p] the
+// total_pen it left.  The maxima are floored by the floor of the kernel argument while they
+// are staged; alpha is mes_alpha's, the bits of k_mes_rows on the same (mu, v).
+// post: [2][P] receives mu | v, or null.
+__global__ __launch_bounds__(kMesThreads) void k_swarm_mes(const double* mean, const double* var,
+                                                           int64_t P, const double* ystar, int K,
+                                                           double floor, double* values,
+                                                           double* post) {
+  __shared__ double ys[SGP_MAX_MES];
+  if (int(threadIdx.x) < K) ys[threadIdx.x] = fmax(ystar[threadIdx.x], floor);
+  __syncthreads();
+  const int64_t p = int64_t(blockIdx.x) * kMesThreads + threadIdx.x;
+  if (p >= P) return;
+  const double mu = mean[p], v = var[p];
+  const double alpha = mes_alpha(mu, v, ys, K);
+  values[p] = alpha + values[p];
+  if (post) {
+    post[p] = mu;
+    post[P + p] = v;
+  }
+}
+
+inline unsigned mes_blocks(int64_t N) { return unsigned((N + kMesThreads - 1) / kMesThreads); }
+
+}  // namespace
+
+// The argument checks the entry points share (common.h).
 int mes_checks(sgp_ctx* ctx, const double* ystar, int K) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, K >= 1 && K <= SGP_MAX_MES, "K = %d maxima (1 .. SGP_MAX_MES = %d)", K,
@@ -213,10 +207,21 @@ int mes_checks(sgp_ctx* ctx, const double* ystar, int K) {
   return 0;
 }
 
-inline unsigned mes_blocks(int64_t N) { return unsigned((N + kMesThreads - 1) / kMesThreads); }
+// values[p] = alpha_p + values[p] for the P particles whose posterior of GP 0 is mean / var
+// (common.h).  The events time the kernel for scripts/bench_swarm_mes.py, as grid_mes times its
+// row kernel; no flops are booked.
+int launch_swarm_mes(sgp_ctx* ctx, int64_t P, const double* mean, const double* var,
+                     const SwarmMes& m, double* values) {
+  if (P <= 0) return 0;
+  SweepTimer tm;
+  SGP_TRY(tm.begin(ctx, 0.0));
+  hipLaunchKernelGGL(k_swarm_mes, dim3(mes_blocks(P)), dim3(kMesThreads), 0, ctx->stream, mean,
+                     var, P, m.ystar, m.K, m.floor, values, m.post);
+  SGP_HIP(ctx, hipGetLastError());
+  return tm.end(ctx);
+}
 
-// The head of kSlotMesIn: ystar[SGP_MAX_MES] | floor, the rows' arrays behind it
-constexpr size_t kMesHead = SGP_MAX_MES + 8;
+namespace {
 
 // The block of a grid call in kSlotMesPart, nwg workgroups of the grid kernel, nf of the
 // floor reduction, world ranks (0: no communicator):

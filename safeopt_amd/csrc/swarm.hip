@@ -534,6 +534,9 @@ int launch_fitness_small(sgp_ctx* ctx, int G, int64_t P, const double* mean,
     hipLaunchKernelGGL(k_fitness_small, dim3(unsigned((P + 255) / 256)), dim3(256),
                        0, ctx->stream, G, P, mean, var, fa);
   SGP_HIP(ctx, hipGetLastError());
+  // a 'mes' swarm: alpha of GP 0's posterior (mean[0][p], var[0][p]) on top of the penalty
+  // the shaping left in the values -- both posterior routes end here
+  if (fa.swarm_type == kSwarmMes) return launch_swarm_mes(ctx, P, mean, var, fa.mes, fa.values);
   return 0;
 }
 

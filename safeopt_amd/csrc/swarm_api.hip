@@ -1,6 +1,7 @@
 // The swarm entry points of the C ABI (include/safeopt_hip.h): host-side launch sequences
-// around the kernels of swarm.hip, paths.hip, swarm_batch.hip and the posterior sweeps.
-// Nine exported fitness / run functions fill SwarmSpec / SwarmState / PsoSchedule
+// around the kernels of swarm.hip, paths.hip, swarm_batch.hip, mes.hip and the posterior
+// sweeps.  Twelve exported fitness / run functions (plain, hallucinated, Thompson and 'mes':
+// one fitness, one run and one sharded run each) fill SwarmSpec / SwarmState / PsoSchedule
 // (common.h) and share ONE fitness routine and ONE run routine.
 #include <string.h>
 
@@ -76,7 +77,15 @@ static FitnessArgs make_fitness_args(const SwarmSpec& s) {
     fa.fmin[i] = (i < s.G) ? s.fmin[i] : -INFINITY;
     fa.scaling[i] = (i < s.G) ? s.scaling[i] : 1.0;
   }
+  if (s.mes) fa.mes = *s.mes;
   return fa;
+}
+
+// a path comes with kSwarmThompson, maxima with kSwarmMes, the public types otherwise
+static bool swarm_type_ok(const SwarmSpec& s) {
+  if (s.path) return s.swarm_type == kSwarmThompson && !s.mes;
+  if (s.mes) return s.swarm_type == kSwarmMes;
+  return s.swarm_type >= SGP_SWARM_GREEDY && s.swarm_type <= SGP_SWARM_SAFE_SET;
 }
 
 // The checks a Thompson entry point makes in front of its early return; behind that
@@ -105,17 +114,21 @@ static int path_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, int m) {
 //                           sgp_swarm_run_shard (an empty block of a sharded swarm is the
 //                           "bad swarm size" error, not a silent return: the other ranks
 //                           would wait in the all-gather)
-// A Thompson call passes "type" and the second "no GP" by construction.
+//   sgp_swarm_fitness_mes   "no GP", "maxima" (mes_checks: 1 <= K <= SGP_MAX_MES, every ystar[k]
+//                           finite), "the floor is NaN", return 0 if P <= 0, GPs
+//   sgp_swarm_run_mes[_shard]  "no GP", "maxima", "the floor is NaN", return 0 if P <= 0 and
+//                           P_total <= 0, then as sgp_swarm_run_shard (an empty block of a
+//                           sharded swarm: "bad swarm size", as for a path run)
+// A Thompson and a 'mes' call pass "type" and the second "no GP" by construction.
 
-// All three fitness entry points: import the points, the real posterior and the shaping
+// All four fitness entry points: import the points, the real posterior and the shaping
 // pass (few-points path or sweep), with clones the downdate (launch_swarm_down) in front of
-// the shaping, with a path the path term (launch_swarm_path) behind it.
+// the shaping, with a path the path term (launch_swarm_path) behind it, with maxima alpha
+// (launch_swarm_mes, inside launch_fitness_small where mean and var are at hand).
 static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particles, int64_t P,
                          double* values, uint8_t* safe, double* var_h) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, s.path ? s.swarm_type == kSwarmThompson
-                        : s.swarm_type >= SGP_SWARM_GREEDY && s.swarm_type <= SGP_SWARM_SAFE_SET,
-            "Invalid swarm type %d", s.swarm_type);
+  SGP_CHECK(ctx, swarm_type_ok(s), "Invalid swarm type %d", s.swarm_type);
   SGP_CHECK(ctx, s.G >= 1 && s.gps[0], "no GP");
   const int G = s.G;
   GpDev host[SGP_MAX_GPS], chost[SGP_MAX_GPS];
@@ -163,15 +176,14 @@ static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particl
 // The particles [p0, p0 + P) of a swarm of Pt; P < Pt: a rank's block of a sharded
 // swarm -- the global best goes through the record all-gather.
 // s.path: a Thompson swarm, s.clones: a hallucinated swarm (the downdate in front of every
-// shaping pass); both always take the general launches below.
+// shaping pass), s.mes: a 'mes' swarm (alpha behind every shaping pass, launched by
+// launch_fitness_small); all three always take the general launches below.
 static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
                      const PsoSchedule& sch) {
   const int G = s.G, init = sch.init, iters = sch.iters;
   const int64_t P = st.P, p0 = st.p0, Pt = st.Pt;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
-  SGP_CHECK(ctx, s.path ? s.swarm_type == kSwarmThompson
-                        : s.swarm_type >= SGP_SWARM_GREEDY && s.swarm_type <= SGP_SWARM_SAFE_SET,
-            "Invalid swarm type %d", s.swarm_type);
+  SGP_CHECK(ctx, swarm_type_ok(s), "Invalid swarm type %d", s.swarm_type);
   SGP_CHECK(ctx, G >= 1 && s.gps[0], "no GP");
   SGP_CHECK(ctx, P >= 1 && iters >= 0, "bad swarm size %lld / iterations %d",
             (long long)P, iters);
@@ -225,7 +237,7 @@ static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
   const bool few_swept = Pt <= kSmallSwarm && !few;
   const double* r = drand;
   double inertia = sch.inertia0;
-  if ((few || few_swept) && !shard && !s.path && !s.clones) {
+  if ((few || few_swept) && !shard && !s.path && !s.clones && !s.mes) {
     // small swarm: three launches per iteration -- k(X, particles), the block
     // products on the matrix cores, and ONE workgroup for everything else
     // (fitness, bests, and the move that opens the next iteration)
@@ -338,6 +350,32 @@ static int swarm_run_path(sgp_ctx* ctx, SwarmSpec s, const SwarmState& st,
   SGP_TRY(swarm_path_stage(s.gps[0], pin[0], pin[1], m, pin[2], pin[3], &path));
   s.path = &path;
   return swarm_run(ctx, s, st, sch);
+}
+
+// The checks a 'mes' entry point makes in front of its early return; behind that return it
+// stages the maxima (swarm_mes_stage: ONCE per call, in kSlotMesIn, which neither routine
+// above asks for)
+static int swarm_mes_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* ystar, int K,
+                            double floor) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
+  SGP_TRY(mes_checks(ctx, ystar, K));
+  SGP_CHECK(ctx, !std::isnan(floor), "the floor is NaN");
+  return 0;
+}
+
+// post: the block also holds [2][P] for the posterior of GP 0 (a fitness call)
+static int swarm_mes_stage(sgp_ctx* ctx, const double* ystar, int K, double floor, int64_t P,
+                           bool post, SwarmMes* out) {
+  const SwarmMesLayout l = swarm_mes_layout(P, post);   // (common.h)
+  char* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotMesIn, l.bytes, &buf));
+  SGP_TRY(sgp_h2d(ctx, buf + l.ystar, ystar, size_t(K) * 8));
+  out->ystar = reinterpret_cast<const double*>(buf + l.ystar);
+  out->K = K;
+  out->floor = floor;
+  out->post = post ? reinterpret_cast<double*>(buf + l.post) : nullptr;
+  return 0;
 }
 
 extern "C" {
@@ -460,6 +498,51 @@ int sgp_swarm_run_path_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double bet
   const double* const pin[4] = {Omega, phase, w, v};
   return swarm_run_path(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed},
                         pin, m);
+}
+
+int sgp_swarm_fitness_mes(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                          int64_t P, double beta, const double* fmin, const double* scaling,
+                          const double* ystar, int K, double floor, double* values,
+                          uint8_t* safe, double* post) {
+  SGP_TRY(swarm_mes_checks(ctx, gps, G, ystar, K, floor));
+  if (P <= 0) return 0;
+  SwarmMes mes;
+  SGP_TRY(swarm_mes_stage(ctx, ystar, K, floor, P, post != nullptr, &mes));
+  const SwarmSpec s{gps, G, kSwarmMes, beta, fmin, scaling, 0.0, nullptr, nullptr, &mes};
+  SGP_TRY(swarm_fitness(ctx, s, particles, P, values, safe, nullptr));
+  if (post) SGP_TRY(sgp_d2h(ctx, post, mes.post, 2 * size_t(P) * 8));
+  return 0;
+}
+
+int sgp_swarm_run_mes(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                      const double* fmin, const double* scaling, int64_t P, double* positions,
+                      double* velocities, double* best_positions, double* best_values,
+                      double* global_best, const double* velocity_scale,
+                      const double* bounds, int init, int iters, double inertia0,
+                      double step_size, const double* rand, uint64_t seed,
+                      const double* ystar, int K, double floor) {
+  return sgp_swarm_run_mes_shard(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
+                                 best_positions, best_values, global_best, velocity_scale,
+                                 bounds, init, iters, inertia0, step_size, rand, seed, ystar, K,
+                                 floor, 0, P);
+}
+
+int sgp_swarm_run_mes_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                            const double* fmin, const double* scaling, int64_t P,
+                            double* positions, double* velocities, double* best_positions,
+                            double* best_values, double* global_best,
+                            const double* velocity_scale, const double* bounds, int init,
+                            int iters, double inertia0, double step_size, const double* rand,
+                            uint64_t seed, const double* ystar, int K, double floor,
+                            int64_t p0, int64_t P_total) {
+  SGP_TRY(swarm_mes_checks(ctx, gps, G, ystar, K, floor));
+  if (P <= 0 && P_total <= 0) return 0;
+  SwarmMes mes;
+  SGP_TRY(swarm_mes_stage(ctx, ystar, K, floor, P, false, &mes));
+  const SwarmSpec s{gps, G, kSwarmMes, beta, fmin, scaling, 0.0, nullptr, nullptr, &mes};
+  const SwarmState st{positions, velocities, best_positions, best_values, global_best,
+                      velocity_scale, bounds, P, p0, P_total};
+  return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});
 }
 
 // SafeOptSwarm safe-set growth, gp_opt.py:1089-1111 (kernels in swarm.hip).

@@ -25,7 +25,7 @@ import numpy as np
 __all__ = ["shard_range", "allgather_rows", "LocalComm", "RcclComm", "SocketComm", "init_from_env",
            "merge_topk", "merge_argmax", "merge_path_records", "merge_batch_records",
            "merge_mes_records",
-           "gather_shard_columns", "check_same_paths",
+           "gather_shard_columns", "check_same_paths", "check_same_maxima",
            "launch_check"]
 
 
@@ -91,6 +91,21 @@ def check_same_paths(comm, pp):
             "the ranks hold different sample paths (digest %012x on rank %d, the ranks' digests "
             "span %012x .. %012x): seed NumPy's global generator alike on every rank before "
             "thompson_points" % (int(h), comm.rank, int(-red[1]), int(red[0])))
+
+
+def check_same_maxima(comm, ystar, floor):
+    """``ValueError`` -- on EVERY rank, as :func:`check_same_paths` -- unless all ranks hold
+    the same maxima ``ystar`` and the same ``floor`` of a max-value entropy search: both are
+    functions of replicated data.  One ``allreduce_max`` of ``[h, -h]``, ``h`` a 48-bit digest
+    of their bytes."""
+    h = _digest48((ystar, np.array([floor])))
+    red = comm.allreduce_max(np.array([h, -h]))
+    if red[0] != -red[1]:
+        raise ValueError(
+            "the ranks hold different maxima or floors (digest %012x on rank %d, the ranks' "
+            "digests span %012x .. %012x): pass the same ystar and floor, and seed NumPy's "
+            "global generator alike, on every rank before mes_point"
+            % (int(h), comm.rank, int(-red[1]), int(red[0])))
 
 
 class LocalComm(object):

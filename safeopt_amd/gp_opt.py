@@ -31,7 +31,8 @@ import weakref
 import numpy as np
 
 from . import _hip
-from .dist import (LocalComm, allgather_rows, check_same_paths, gather_shard_columns,
+from .dist import (LocalComm, allgather_rows, check_same_maxima, check_same_paths,
+                   gather_shard_columns,
                    merge_argmax, merge_batch_records, merge_mes_records, merge_path_records,
                    merge_topk, shard_range)
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
@@ -1930,6 +1931,14 @@ class SafeOptSwarm(GaussianProcessOptimization):
         the host loop."""
         return self._swarm_fitness(swarm_type, particles, clones=clones)
 
+    def _compute_mes_fitness(self, mes, particles):
+        """Fitness and safety of ``particles`` for a max-value entropy search swarm with
+        ``mes = (ystar, floor)``: ``values = alpha + `` the maximizers' penalty, ``alpha`` the
+        acquisition of ``gp.max_value_entropy`` on the posterior of the objective GP, ``safe``
+        the maximizers' safety flag (``sgp_swarm_fitness_mes``).  The fitness callback of the
+        host loop."""
+        return self._swarm_fitness(None, particles, mes=mes)
+
     def _side_swarm_pick(self, swarm, configure, fitness, iters, empty_ok=False):
         """One side swarm of ``optimize_batch`` / ``thompson_points`` and its pick ``(x,
         index)``: ``swarm_size`` draws of ``S`` as start positions (one ``randint``), then the
@@ -2130,6 +2139,119 @@ class SafeOptSwarm(GaussianProcessOptimization):
                 partial(self._compute_path_fitness, path), iters)
         values = np.array([pp.paths(x[s][None])[0, 0, s] for s in range(size)])
         return (x, values, pp) if return_paths else (x, values)
+
+    def mes_point(self, paths=16, features=1024, floor='mean', ystar=None, max_iters=None,
+                  return_state=False):
+        """The safe point whose measurement tells most about the VALUE of the safe optimum,
+        without a grid: max-value entropy search (Wang & Jegelka 2017; ``SafeOpt.mes_point``
+        on a grid) by a swarm.  It needs no Lipschitz constant and no width rule.
+
+        1. The refusals below come before anything is drawn or run.
+        2. ``ystar=None``: ``x_t, values = self.thompson_points(size=paths, features=features,
+           max_iters=max_iters)`` and ``ystar = values`` -- a path's value at its own safe
+           pick is a lower bound of its maximum over the safe region.  ``ystar`` given (``1 ..
+           SGP_MAX_MES`` finite maxima): no path is drawn; ``_recheck_safe_set()`` runs once.
+        3. ``floor='mean'`` (default): the largest posterior mean of the objective GP over
+           the rows of ``S`` and the Thompson picks (one ``predict_noiseless`` call) -- a
+           maximum cannot lie below a value the mean already reaches, and without the floor
+           such a ``ystar`` would make ``gamma`` negative and the pick collapse onto the point
+           with the smallest ``sigma``.  ``None``: no floor; a float: that value.
+        4. One swarm (``DeviceSwarmOptimization(..., 'mes')``; ``pso='host'``: the reference
+           loop over ``_compute_mes_fitness``) starts from ``swarm_size`` draws from ``S`` and
+           runs ``max_iters`` (default ``self.max_iters``) iterations.  The fitness of a
+           particle is ``alpha(x) + total_pen``: with ``mu``, ``v`` the posterior of the
+           objective, ``sigma = sqrt(max(v, 1e-15))``, ``y_k = max(ystar_k, floor)`` and
+           ``gamma_k = (y_k - mu) / sigma``, ``alpha = mean_k [gamma_k phi(gamma_k) / (2
+           Phi(gamma_k)) - ln Phi(gamma_k)]``, formed on the device inside the swarm
+           iteration (``k_swarm_mes``, ``csrc/mes.hip``), under the penalty and safety rule
+           of the maximizers swarm.  The pick is the personal best with the largest value
+           among those that are safe under the current posterior (one ``safe_set`` fitness
+           call), the lowest index among equals.
+        5. Returns ``(x (d,), alpha)`` with ``alpha = gp.max_value_entropy(x[None], ystar,
+           floor)[0, 0]``; with ``return_state=True`` ``(x, alpha, {'ystar', 'floor',
+           'thompson_x'})`` (``thompson_x``: the Thompson picks, ``None`` with ``ystar`` given).
+
+        Raises ``ValueError`` for ``paths`` (or ``len(ystar)``) outside ``1 .. SGP_MAX_MES``
+        (64), a maximum that is not finite, a floor that is NaN or a string other than
+        ``'mean'``; ``NotImplementedError`` for several ranks whose communicator carries no
+        device context (``thompson_points``' refusal); ``RuntimeError`` when the safe set is
+        empty or the swarm ends with no safe personal best.
+
+        Changes no state of the optimiser beyond what ``_recheck_safe_set`` does (it may drop
+        points that are no longer safe): ``S`` does not grow, ``greedy_point``,
+        ``best_lower_bound`` and the greedy / maximizers / expanders swarm objects are
+        untouched.  NumPy's global generator is consumed in this order:
+
+        1. with ``ystar=None``, what ``thompson_points(size=paths, ...)`` draws, in its order;
+        2. ``pso='device-rng'`` only: one ``randint`` for the key of the swarm's device
+           generator;
+        3. one swarm's worth, as step 3 of ``thompson_points``, once: one
+           ``randint(len(S), size=swarm_size)`` for the start positions, then ``'host'``:
+           ``rand(swarm_size, d)`` in ``init_swarm`` and ``rand(2 swarm_size, d)`` per
+           iteration; ``'device'``: the same numbers as ``rand(swarm_size d)`` and ``rand(2
+           swarm_size d max_iters)``; ``'device-rng'``: nothing.
+
+        N ranks (``comm=``; SPMD, the same seed and call on every rank): the Thompson swarms
+        are sharded as ``thompson_points`` shards them and the 'mes' swarm is split over the
+        ranks by particle like every other swarm (``sgp_swarm_run_mes_shard``).  ``ystar``
+        and ``floor`` are functions of replicated data: one ``allreduce_max`` of a digest
+        verifies that the ranks hold the same, ``ValueError`` on every rank otherwise.  The
+        ``safe_set`` call and the pick run replicated on the gathered personal bests: the
+        bits of the one-rank run on every rank.
+
+        Out of scope: greedy batches of MES picks through the hallucination clones,
+        noisy-observation MES, running the Thompson swarms as one launch."""
+        if ystar is None:
+            paths = int(paths)
+            if paths < 1 or paths > _hip.MAX_MES:
+                raise ValueError("paths must be in 1 .. SGP_MAX_MES = %d, got %d"
+                                 % (_hip.MAX_MES, paths))
+        else:
+            ystar = np.array(ystar, dtype=float).reshape(-1)
+            if ystar.size < 1 or ystar.size > _hip.MAX_MES:
+                raise ValueError("ystar must hold 1 .. SGP_MAX_MES = %d maxima, got %d"
+                                 % (_hip.MAX_MES, ystar.size))
+            if not np.all(np.isfinite(ystar)):
+                raise ValueError("a maximum in ystar is not finite")
+        if isinstance(floor, str):
+            if floor != 'mean':
+                raise ValueError("floor must be 'mean', None or a float, got %r" % (floor,))
+        elif floor is not None:
+            floor = float(floor)
+            if np.isnan(floor):
+                raise ValueError("floor is NaN")
+        world = self._comm.world
+        if world > 1 and getattr(self._comm, 'ctx', None) is None:
+            raise NotImplementedError(
+                "the sharded 'mes' swarm merges the global best in the stream of the "
+                "communicator's device context: a merge over this host-only communicator of "
+                "%d ranks is not implemented" % world)
+        thompson_x = None
+        if ystar is None:
+            thompson_x, ystar = self.thompson_points(size=paths, features=features,
+                                                     max_iters=max_iters)
+        else:
+            self._recheck_safe_set()
+        if floor is None:
+            floor = -np.inf
+        elif floor == 'mean':
+            rows = self.S if thompson_x is None else np.vstack((self.S, thompson_x))
+            floor = float(np.max(self.gp.predict_noiseless(rows)[0]))
+        if world > 1:
+            check_same_maxima(self._comm, ystar, floor)
+        iters = int(max_iters or self.max_iters)
+        swarm = None                      # pso='host': a reference loop
+        if isinstance(self.swarms['maximizers'], DeviceSwarmOptimization):
+            swarm = DeviceSwarmOptimization(
+                self.swarm_size, self.optimal_velocities, self, 'mes',
+                bounds=self.bounds, rng=self.swarms['maximizers']._rng, comm=self._comm)
+        x, _ = self._side_swarm_pick(
+            swarm, lambda run: run.set_maxima(ystar, floor),
+            partial(self._compute_mes_fitness, (ystar, floor)), iters)
+        alpha = float(self.gp.max_value_entropy(x[None, :], ystar, floor)[0, 0])
+        if return_state:
+            return x, alpha, dict(ystar=ystar, floor=floor, thompson_x=thompson_x)
+        return x, alpha
 
     # -- one swarm run, in the steps of gp_opt.py:1015-1134 -------------------------
     def _recheck_safe_set(self):

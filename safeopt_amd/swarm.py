@@ -115,6 +115,8 @@ def _hip_swarm_types():
 #: type code of the Thompson swarm in the Philox seed mix (``_hip.SWARM_TYPES`` holds 0..3,
 #: the types ``sgp_swarm_fitness`` takes; a Thompson swarm has entry points of its own)
 THOMPSON_CODE = 4
+#: ... and of the max-value entropy search swarm (``kSwarmMes`` on the C side)
+MES_CODE = 5
 
 
 class DeviceSwarmOptimization(SwarmOptimization):
@@ -153,6 +155,13 @@ class DeviceSwarmOptimization(SwarmOptimization):
     clones of the owner's GPs, which carry the pending picks (``sgp_swarm_fitness_hall`` /
     ``sgp_swarm_run_hall``); with ``comm`` it is sharded like every other swarm
     (``sgp_swarm_run_hall_shard``), every rank holding clones with the same pending picks.
+
+    ``swarm_type='mes'``: max-value entropy search -- the fitness is ``alpha + total_pen``,
+    ``alpha`` the acquisition of ``GPRegression.max_value_entropy`` on the posterior of the
+    owner's objective GP, under the maximizers' penalty and safety rule
+    (``sgp_swarm_fitness_mes`` / ``sgp_swarm_run_mes``); ``set_maxima(ystar, floor)`` comes
+    before ``init_swarm``; with ``comm`` it is sharded like every other swarm
+    (``sgp_swarm_run_mes_shard``), every rank holding the same maxima and floor.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
@@ -178,11 +187,14 @@ class DeviceSwarmOptimization(SwarmOptimization):
         # expanders swarms of one optimiser must not draw the same numbers
         if rng == 'device' and seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
-        code = THOMPSON_CODE if swarm_type == 'thompson' else _hip_swarm_types()[swarm_type]
+        code = {'thompson': THOMPSON_CODE, 'mes': MES_CODE}.get(swarm_type)
+        if code is None:
+            code = _hip_swarm_types()[swarm_type]
         self._seed = (int(seed or 0) * 4 + code) & (2 ** 43 - 1)
         self._calls = 0
         self._path = None
         self._clones = None
+        self._maxima = None
         self.global_best = np.zeros(self.ndim)
 
     def set_path(self, path):
@@ -203,6 +215,29 @@ class DeviceSwarmOptimization(SwarmOptimization):
             clones = list(clones)
         self._clones = clones
 
+    def set_maxima(self, ystar, floor=None):
+        """The maxima ``ystar`` (``1 .. SGP_MAX_MES`` finite values) and the ``floor`` under
+        them (``None``: none; a float, +-inf allowed) a 'mes' swarm scores its particles with
+        from the next ``init_swarm`` on."""
+        if self._type != 'mes':
+            raise ValueError("only a 'mes' swarm takes maxima, this is %r" % (self._type,))
+        from . import _hip
+        ystar = np.array(ystar, dtype=float).reshape(-1)
+        if ystar.size < 1 or ystar.size > _hip.MAX_MES:
+            raise ValueError("%d maxima, a 'mes' swarm takes 1 .. SGP_MAX_MES = %d"
+                             % (ystar.size, _hip.MAX_MES))
+        if not np.all(np.isfinite(ystar)):
+            raise ValueError("a maximum is not finite")
+        floor = -np.inf if floor is None else float(floor)
+        if np.isnan(floor):
+            raise ValueError("the floor is NaN")
+        self._maxima = (ystar, floor)
+
+    def _need_maxima(self):
+        if self._maxima is None:
+            raise ValueError("a 'mes' swarm needs set_maxima(ystar, floor) before init_swarm")
+        return self._maxima
+
     def _need_path(self):
         if self._path is None:
             raise ValueError("a 'thompson' swarm needs set_path(path) before init_swarm")
@@ -211,19 +246,24 @@ class DeviceSwarmOptimization(SwarmOptimization):
     def fitness(self, positions):                 # kept for API parity
         if self._type == 'thompson':
             return self._owner._compute_path_fitness(self._need_path(), positions)
+        if self._type == 'mes':
+            maxima = self._need_maxima()
+            return self._owner._compute_mes_fitness(maxima, positions)
         if self._clones is not None:
             return self._owner._compute_hall_fitness(self._type, self._clones, positions)
         return self._owner._compute_particle_fitness(self._type, positions)
 
     def _device_run(self, init, iters, inertia0, step):
         from . import _hip
+        # (a missing path or missing maxima are refused before anything is touched or drawn)
+        path = self._need_path() if self._type == 'thompson' else None
+        maxima = self._need_maxima() if self._type == 'mes' else None
         o = self._owner
         devs = [g._fitted() for g in o.gps]
         sharded = self._comm.world > 1
         d = self.positions.shape[1]
         P = self.swarm_size if sharded else self.positions.shape[0]
         self._calls += 1
-        path = self._need_path() if self._type == 'thompson' else None
         rand = None
         if self._rng == 'numpy':
             # the whole swarm's numbers on every rank, as one rank draws them
@@ -239,7 +279,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
             (self.positions, self.velocities, best_positions, best_values, self.global_best,
              np.broadcast_to(self.velocity_scale, (d,)), self.bounds),
             (init, iters, inertia0, step, rand, (self._seed << 20) + self._calls),
-            path=path, clones=self._clones,
+            path=path, clones=self._clones, mes=maxima,
             shard=(self._rows[0], self.swarm_size) if sharded else None)
         if sharded:
             self.best_positions, self.best_values = self._gather(best_positions, best_values)
@@ -272,6 +312,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
     def init_swarm(self, positions):
         if self._type == 'thompson':
             self._need_path()
+        if self._type == 'mes':
+            self._need_maxima()
         positions = np.ascontiguousarray(positions, dtype=float)
         if self._comm.world > 1:
             lo, hi = self._rows
