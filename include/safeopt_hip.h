@@ -37,6 +37,7 @@ extern "C" {
 #define SGP_MAX_FEATURES 16384 /* random Fourier features of a sample path     */
 #define SGP_MAX_BATCH 64   /* query points of one hallucinated batch           */
 #define SGP_MAX_MES 64     /* maxima of one max-value entropy search (= SGP_MAX_PATHS) */
+#define SGP_MAX_BLOCK 16   /* observations of one block append                 */
 
 /* kernel kinds: GPy.kern.RBF / Matern32 / Matern52 (Stationary.K_of_r)        */
 enum { SGP_RBF = 0, SGP_MATERN32 = 1, SGP_MATERN52 = 2 };
@@ -83,6 +84,18 @@ int sgp_gp_set_data(sgp_gp* gp, const double* X, const double* Y, int64_t n,
  * applies GPy's jitter), -1 no spare capacity (same remedy).                  */
 int sgp_gp_append(sgp_gp* gp, const double* x, double y, int* info);
 int sgp_gp_pop(sgp_gp* gp);
+/* b observations at once (X (b,d) row-major, y (b), 1 <= b <= SGP_MAX_BLOCK): the bordered
+ * update with a b x b corner.  With n0 = n, Kc = k(X_old, X), T = L^-1 Kc,
+ * W = L^-T T:  C = k(X, X) + (noise + 1e-8 + jitter) I - T^T T = Lc Lc^T, rows n0 .. n0+b-1
+ * of the dense L^-1 become Lc^-1 [ -W^T | I ], gamma_j = (row n0+j) . y, and
+ * alpha <- [alpha; 0] + sum_j (row n0+j)^T gamma_j.  One read-back, one re-pack of the sweep
+ * operands; every sum in a fixed order.  info = 0 ok; n0 + j + 1: pivot j of C fails the test
+ * of sgp_gp_append (s2_j > 1e-12 (k(x,x) + noise + 1e-8 + jitter), finite); -1: n + b exceeds
+ * the row capacity -- in both cases the GP is exactly as it was (refit with
+ * sgp_gp_set_data).  On success the GP carries the BLOCK RECORD {b, n0, gamma} for
+ * sgp_grid_rankb_update instead of a one-row record; any other change of the GP drops it, a
+ * clone carries none.  The host bookkeeping (shared factors) is that of b sgp_gp_append.   */
+int sgp_gp_append_block(sgp_gp* gp, const double* X, const double* y, int b, int* info);
 /* Forget training row `index` (0 .. n-1, n >= 2), whichever it is: an O(n^2) downdate of
  * L^-1 and alpha instead of the refit gp.set_XY would cost (the reference has only
  * remove_last_data_point).  With M = L^-1, c = column index of M, P_ii = |c|^2 and
@@ -278,6 +291,18 @@ int sgp_grid_rank1_update(sgp_grid* grid, sgp_gp* const* gps, int G,
 int sgp_grid_rank1_remove(sgp_grid* grid, sgp_gp* const* gps, int G,
                           const int* which, double beta, const double* fmin,
                           double* out2);
+/* ... and after ONE sgp_gp_append_block on the GPs flagged in which[] (b_g from the GP's block
+ * record, it may differ per GP): per row x, with X' the data after the block and
+ *   t_j(x) = sum_{i <= n0+j} L^-1[n0+j][i] k(X'_i, x),   j = 0 .. b-1 in that order,
+ *   mean += sum_j t_j gamma_j,   var = max(var - sum_j t_j^2, 1e-15),
+ * n + b covariance evaluations per row and GP where b rank-1 updates take about b n; then Q
+ * and S for all GPs; out2, the deferred form and context columns as sgp_grid_rank1_update.  A
+ * GP that shares the factor of a flagged GP in front of it with the same b takes that GP's
+ * t_j.  Fixed summation order, no atomics: a row's result depends on its coordinates and the
+ * GPs alone.  A flagged GP without a valid block record is an error that names it; mean,
+ * var, Q and S are then untouched.                                              */
+int sgp_grid_rankb_update(sgp_grid* grid, sgp_gp* const* gps, int G, const int* which,
+                          double beta, const double* fmin, double* out2);
 /* replace Q by host values (N x 2G row-major) and recompute S (tests, and
  * users who edit opt.Q by hand).                                             */
 int sgp_grid_upload_Q(sgp_grid* grid, const double* Q, const double* fmin,

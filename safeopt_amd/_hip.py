@@ -37,6 +37,7 @@ MAX_JOINT = 8192          # SGP_MAX_JOINT: rows of one joint prediction
 MAX_PATHS = 64            # SGP_MAX_PATHS: sample paths of one call
 MAX_FEATURES = 16384      # SGP_MAX_FEATURES: random Fourier features of a sample path
 MAX_BATCH = 64            # SGP_MAX_BATCH: query points of one hallucinated batch
+MAX_BLOCK = 16            # SGP_MAX_BLOCK: observations of one block append
 MAX_MES = 64              # SGP_MAX_MES: maxima of one max-value entropy search
 MES_ALL, MES_S, MES_MG = 0, 1, 2                        # candidate rows of sgp_grid_mes
 MES_FLOOR_NONE, MES_FLOOR_MEAN, MES_FLOOR_VALUE = 0, 1, 2
@@ -61,6 +62,7 @@ PROTOTYPES = {
     "sgp_gp_loo_lml": (C.c_int, [vp, c_double_p, c_double_p, C.c_double, c_double_p,
                                  c_int_p]),
     "sgp_gp_append": (C.c_int, [vp, c_double_p, C.c_double, c_int_p]),
+    "sgp_gp_append_block": (C.c_int, [vp, c_double_p, c_double_p, C.c_int, c_int_p]),
     "sgp_gp_pop": (C.c_int, [vp]),
     "sgp_gp_remove": (C.c_int, [vp, C.c_int64, c_int_p]),
     "sgp_gp_predict": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
@@ -110,6 +112,8 @@ PROTOTYPES = {
     "sgp_grid_rank1_update": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
                                         c_double_p, c_double_p]),
     "sgp_grid_rank1_remove": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
+                                        c_double_p, c_double_p]),
+    "sgp_grid_rankb_update": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
                                         c_double_p, c_double_p]),
     "sgp_grid_upload_Q": (C.c_int, [vp, c_double_p, c_double_p, c_double_p]),
     "sgp_grid_maximizers": (C.c_int, [vp, C.c_double, c_double_p]),
@@ -584,6 +588,9 @@ class DeviceGP(object):
         self.version = 0
         self.appended = False
         self.removed = False
+        # ... `block` = b > 0: it was a block append of b rows (`append_block`) whose block
+        # record is on the device
+        self.block = 0
         self.serial = next(DeviceGP._serials)
 
     def __del__(self):
@@ -608,6 +615,7 @@ class DeviceGP(object):
         self.jitter = jit.value
         self.version += 1
         self.appended = self.removed = False
+        self.block = 0
 
     def _hyper(self, variances, inv_ls):
         variances = f64(variances).reshape(-1)
@@ -627,6 +635,7 @@ class DeviceGP(object):
                                     float(noise_var), C.byref(info), C.byref(jit))
         self.version += 1
         self.appended = self.removed = False
+        self.block = 0
         if rc > 0 or info.value != 0:
             self.n = 0
             raise np.linalg.LinAlgError(
@@ -644,6 +653,7 @@ class DeviceGP(object):
         info = C.c_int(0)
         self.version += 1
         self.appended = self.removed = False
+        self.block = 0
         self.ctx.check(lib().sgp_gp_lml(self.h, dptr(variances), dptr(inv_ls),
                                         float(noise_var), dptr(out), C.byref(info)))
         self.jitter = 0.0
@@ -660,6 +670,7 @@ class DeviceGP(object):
         info = C.c_int(0)
         self.version += 1
         self.appended = self.removed = False
+        self.block = 0
         self.ctx.check(lib().sgp_gp_loo_lml(self.h, dptr(variances), dptr(inv_ls),
                                             float(noise_var), dptr(out), C.byref(info)))
         self.jitter = 0.0
@@ -692,6 +703,28 @@ class DeviceGP(object):
         self.n += 1
         self.version += 1
         self.appended, self.removed = True, False
+        self.block = 0
+        return True
+
+    def append_block(self, X, y):
+        """``b`` more observations (``1 <= b <= MAX_BLOCK``) by ONE bordered update with a
+        ``b x b`` corner (``sgp_gp_append_block``): one read-back and one re-pack instead of
+        ``b``.  False = not possible (no capacity / a pivot not positive), the GP is then
+        exactly as it was: the caller refits with set_data."""
+        X = f64(X).reshape(-1, self.d)
+        y = f64(y).reshape(-1)
+        b = X.shape[0]
+        if y.size != b or not 1 <= b <= MAX_BLOCK:
+            raise ValueError("a block of 1..%d rows with one value each, got X %r, y %r"
+                             % (MAX_BLOCK, X.shape, y.shape))
+        info = C.c_int(0)
+        self.ctx.check(lib().sgp_gp_append_block(self.h, dptr(X), dptr(y), b, C.byref(info)))
+        if info.value != 0:
+            return False
+        self.n += b
+        self.version += 1
+        self.appended = self.removed = False
+        self.block = b
         return True
 
     def pop(self):
@@ -700,6 +733,7 @@ class DeviceGP(object):
         self.n -= 1
         self.version += 1
         self.appended = self.removed = False
+        self.block = 0
 
     def remove(self, index):
         """Forget observation ``index`` (0 .. n-1), whichever it is, by an O(n^2) downdate
@@ -712,6 +746,7 @@ class DeviceGP(object):
         self.n -= 1
         self.version += 1
         self.appended, self.removed = False, True
+        self.block = 0
         return True
 
     def predict(self, Xnew):
@@ -828,6 +863,7 @@ class DeviceGP(object):
         twin.n_parts, twin.n, twin.jitter = self.n_parts, self.n, self.jitter
         twin.version, twin.appended = self.version, self.appended
         twin.removed = self.removed
+        twin.block = 0            # (a clone carries no block record)
         twin.serial = next(DeviceGP._serials)
         return twin
 
@@ -959,6 +995,17 @@ class DeviceGrid(object):
         w = np.ascontiguousarray(which, dtype=np.int32)
         out = np.empty(2)
         self.ctx.check(lib().sgp_grid_rank1_update(
+            self.h, _gp_array(gps), len(gps), w.ctypes.data_as(c_int_p),
+            float(beta), dptr(fmin), None if defer else dptr(out)))
+        return (None, None) if defer else (out[0], bool(out[1]))
+
+    def rankb_update(self, gps, which, beta, fmin, defer=False):
+        """``rank1_update`` after one ``DeviceGP.append_block`` on the GPs of ``which``
+        (``b`` from each GP's block record; it may differ per GP)."""
+        fmin = f64(fmin)
+        w = np.ascontiguousarray(which, dtype=np.int32)
+        out = np.empty(2)
+        self.ctx.check(lib().sgp_grid_rankb_update(
             self.h, _gp_array(gps), len(gps), w.ctypes.data_as(c_int_p),
             float(beta), dptr(fmin), None if defer else dptr(out)))
         return (None, None) if defer else (out[0], bool(out[1]))

@@ -17,7 +17,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(PKG, "libsafeopt_hip.so")
-SOURCES = ["api.hip", "expander_api.hip", "batch.hip", "sweep.hip", "expander.hip", "sweep_pair.hip",
+SOURCES = ["api.hip", "expander_api.hip", "batch.hip", "block.hip", "sweep.hip", "expander.hip", "sweep_pair.hip",
            "sweep_mid.hip", "sweep_tiny.hip", "step_small.hip",
            "factor.hip", "hyper.hip", "joint.hip", "mes.hip", "paths.hip", "sets.hip", "swarm.hip",
            "swarm_api.hip", "swarm_batch.hip"]

@@ -343,7 +343,7 @@ void sgp_gp_destroy(sgp_gp* gp) {
   (void)hipStreamSynchronize(ctx->stream);
   DevBuf* bufs[] = {&gp->X, &gp->Y, &gp->Xpad, &gp->Xs, &gp->XA, &gp->alpha, &gp->Apack,
                     &gp->Linv, &gp->Kmat, &gp->work, &gp->tvec, &gp->updw,
-                    &gp->upd};
+                    &gp->upd, &gp->blk};
   for (DevBuf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   delete gp;
@@ -394,6 +394,7 @@ static int rewrite_hyper(sgp_gp* gp, const double* variances, const double* inv_
   ++gp->data_version;
   gp->upd_valid = false;
   gp->rem_valid = false;
+  gp->blk_valid = false;
   // (a refit at the current n: the history of appends and removals no longer matters)
   gp->prov = 0x9e3779b97f4a7c15ull ^ uint64_t(gp->n);
   return 0;
@@ -521,6 +522,36 @@ int sgp_gp_append(sgp_gp* gp, const double* x, double y, int* info) {
     gp->xhash.resize(size_t(n0));
     gp->xhash.push_back(hash_rows(n0 > 0 ? gp->xhash.back() : 14695981039346656037ull, x,
                                   size_t(d)));
+    gp->prov = gp->prov * 1099511628211ull + 2;
+  }
+  return 0;
+}
+
+int sgp_gp_append_block(sgp_gp* gp, const double* X, const double* y, int b, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
+  SGP_CHECK(ctx, b >= 1 && b <= SGP_MAX_BLOCK, "a block of %d observations (1..%d)", b,
+            SGP_MAX_BLOCK);
+  *info = -1;
+  if (gp->n + b > gp->ld) return 0;  // no room: caller refits with set_data
+  const int d = gp->kern.d;
+  const int64_t n0 = gp->n;
+  double* Xd = static_cast<double*>(gp->X.p);
+  double* Yd = static_cast<double*>(gp->Y.p);
+  SGP_TRY(sgp_h2d(ctx, Xd + size_t(n0) * d, X, size_t(b) * d * sizeof(double)));
+  SGP_TRY(sgp_h2d(ctx, Yd + n0, y, size_t(b) * sizeof(double)));
+  SGP_TRY(append_block_gp(gp, b, info));
+  if (gp->n != n0 + b) return 0;               // a pivot is not positive: the GP is as it was
+  // the books of b one-row appends: equal histories keep a shared factor shared
+  gp->data_version += uint64_t(b);
+  gp->xhost.resize(size_t(n0) * d);
+  gp->xhost.insert(gp->xhost.end(), X, X + size_t(b) * d);
+  gp->xhash.resize(size_t(n0));
+  for (int r = 0; r < b; ++r) {
+    gp->xhash.push_back(hash_rows(gp->xhash.empty() ? 14695981039346656037ull : gp->xhash.back(),
+                                  X + size_t(r) * d, size_t(d)));
     gp->prov = gp->prov * 1099511628211ull + 2;
   }
   return 0;
@@ -1167,6 +1198,35 @@ int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
 int sgp_grid_rank1_remove(sgp_grid* g, sgp_gp* const* gps, int G, const int* which,
                           double beta, const double* fmin, double* out2) {
   return rank1_refresh(g, gps, G, which, beta, fmin, out2, true);
+}
+
+int sgp_grid_rankb_update(sgp_grid* g, sgp_gp* const* gps, int G, const int* which,
+                          double beta, const double* fmin, double* out2) {
+  sgp_ctx* ctx = g->ctx;
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
+  RankbArgs rb{};
+  Rank1Args& ra = rb.r;
+  for (int i = 0; i < SGP_MAX_GPS; ++i) {
+    ra.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
+    ra.which[i] = (i < G) ? which[i] : 0;
+    rb.blk[i] = nullptr;
+    if (i < G && which[i]) {
+      SGP_CHECK(ctx, gps[i]->blk_valid && gps[i]->blk.p,
+                "GP %d has no block record for a rank-b update", i);
+      rb.blk[i] = static_cast<const double*>(gps[i]->blk.p);
+    }
+  }
+  ra.Q = g->Q;
+  ra.mean = g->mean;
+  ra.var = g->var;
+  ra.S = g->S;
+  ra.partial = g->partial;
+  ra.beta = beta;
+  SweepPoints sp{g->pts, g->N, 1, g->N};
+  // (post_valid stays as it is, as in rank1_refresh)
+  SGP_TRY(launch_rankb(ctx, g->gpdev, G, g->d, sp, rb));
+  return finish_safe_partials(g, rank1_num_blocks(g->N), out2);
 }
 
 int sgp_grid_upload_Q(sgp_grid* g, const double* Q, const double* fmin,

@@ -114,6 +114,12 @@ struct GpDev {
   double prior;
   KernDesc kern;
 };
+// The record of the last block append (sgp_gp_append_block), consumed by the rank-b refresh of
+// the resident posterior (block.hip), in a small device buffer of the GP's own (sgp_gp::blk), in
+// doubles: [0] = b, [1] = n0 (the rows in front of the block), [2 .. 2 + b) = gamma_j = (row
+// n0 + j of L^-1) . y, zero behind b.  The launch hands the kernel the buffers of its flagged
+// GPs (RankbArgs): GpDev stays as every sweep kernel knows it.
+constexpr int kBlkB = 0, kBlkN0 = 1, kBlkGamma = 2, kBlkWords = 2 + SGP_MAX_BLOCK;
 
 // GP whose covariances k(X, x) are bit for bit those of `g` (GpDev::share <= -2), or -1
 inline int gp_cov_lead(const GpDev& g) { return g.share <= -2 ? -2 - g.share : -1; }
@@ -306,9 +312,11 @@ struct sgp_gp {
   bool upd_valid = false;  // dev.upd* describes the step to the current data
   bool rem_valid = false;  // ... as the record of a REMOVAL (sgp_gp_remove): the row that left,
                            // in the layout of an append of that row to the reduced GP
+  bool blk_valid = false;  // `blk` describes the step to the current data: the last change was
+                           // a block append (sgp_gp_append_block); a clone carries none
   bool factored = true;    // false: sgp_gp_lml / sgp_gp_loo_lml met a non-positive pivot: the data are
                            // resident, the factor is not valid until the next fit
-  DevBuf X, Y, Xpad, Xs, XA, alpha, Apack, Linv, Kmat, work, tvec, updw, upd;
+  DevBuf X, Y, Xpad, Xs, XA, alpha, Apack, Linv, Kmat, work, tvec, updw, upd, blk;
   GpDev dev;      // filled by set_data
 };
 
@@ -429,6 +437,9 @@ int launch_loo_lml(sgp_gp* gp, const int* info_dev, double* out_dev);
 // each, n rounded up to 64) | sum of the log predictive densities | info (as a double)
 int launch_loo(sgp_gp* gp, const double** out_dev, int* np);
 int append_gp(sgp_gp* gp, double y, int* info);  // row n already in gp->X
+// rows n .. n + b - 1 already in gp->X / gp->Y, 1 <= b <= SGP_MAX_BLOCK, n + b <= ld; *info != 0
+// leaves the GP untouched
+int append_block_gp(sgp_gp* gp, int b, int* info);
 int pop_gp(sgp_gp* gp);
 // row `index` leaves (0 <= index < n, n >= 2); *info != 0 leaves the GP untouched
 int remove_gp(sgp_gp* gp, int index, int* info);
@@ -633,6 +644,14 @@ int rank1_num_blocks(int64_t N);
 // remove: the records are removal records (sgp_gp_remove) -- both signs of the update flip
 int launch_rank1(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d,
                  SweepPoints pts, Rank1Args ra, bool remove = false);
+// block.hip: the same refresh after a block append on the flagged GPs (their records: blk); partials
+// as launch_rank1 leaves them (rank1_num_blocks)
+struct RankbArgs {
+  Rank1Args r;
+  const double* blk[SGP_MAX_GPS];   // the block records of the flagged GPs (device), else null
+};
+int launch_rankb(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d, SweepPoints pts,
+                 const RankbArgs& ra);
 
 // batch.hip: one pick of a hallucinated batch (sgp_grid_batch_next).  Every GP carries the
 // append record of the previous pick: var_out = max(var_in - c(x)^2 / s2, 1e-15) per row and

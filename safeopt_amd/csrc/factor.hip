@@ -478,6 +478,7 @@ int factor_gp(sgp_gp* gp, int* info, const int** info_dev_out) {
   int* info_dev = reinterpret_cast<int*>(tv + ld);
   gp->upd_valid = false;
   gp->rem_valid = false;
+  gp->blk_valid = false;
 
   // padded rows of X are never read: n_valid = n turns them into identity
   SGP_TRY(launch_kernel_matrix(ctx, gp->kern, static_cast<double*>(gp->X.p),
@@ -596,6 +597,162 @@ int append_gp(sgp_gp* gp, double y, int* info) {
   gp->n_f = (n + 1 + 31) / 32 * 32;
   gp->upd_valid = true;
   gp->rem_valid = false;
+  gp->blk_valid = false;
+  return publish_gp(gp);
+}
+
+// ---- block append ----------------------------------------------------------------------
+// b rows at once: with Kc = k(X, Xnew), T = L^-1 Kc, W = L^-T T (one vector
+// per new row, pitch `pitch`),
+//   C = k(Xnew, Xnew) + (noise + 1e-8 + jitter) I - T^T T = Lc Lc^T,
+//   rows n0 .. n0+b-1 of L^-1 = Lc^-1 [ -W^T | I ],
+//   gamma_j = (row n0+j) . y' = sum_{c <= j} Lc^-1[j][c] (y_c - k_c^T alpha),
+//   alpha <- [alpha; 0] + sum_j (row n0+j)^T gamma_j       (j = 0 .. b-1, in that order).
+// One workgroup: the b (b + 1) / 2 + b dot products over the old rows go one per wave, lanes
+// striding, folded by shuffles; thread 0 factors the corner with k_append_finish's pivot rule
+// (pivot j = the s2 a one-row append of row j behind rows 0 .. j-1 would meet); nothing of the
+// GP is written before every pivot has passed.  blk receives the block record (common.h, kBlk*).
+__global__ __launch_bounds__(1024) void k_append_block_finish(
+    double* Li, int64_t ld, int n0, int b, const double* Kc, const double* Tt, const double* Wt,
+    int64_t pitch, const double* Knn, double prior, const double* ynew, double* alpha,
+    double* blk, int n_pad_new, int* info) {
+  constexpr int B = SGP_MAX_BLOCK;
+  __shared__ double cm[B][B + 1];    // T^T T (lower), then Lc
+  __shared__ double inv[B][B + 1];   // Lc^-1 (lower), zero above the diagonal
+  __shared__ double res[B], gam[B];
+  __shared__ int bad;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int npairs = b * (b + 1) / 2;
+  for (int p = wave; p < npairs + b; p += 1024 / 64) {
+    int a = 0, c = p - npairs;
+    const double *u = Kc + (p >= npairs ? c : 0) * pitch, *v = alpha;
+    if (p < npairs) {
+      while ((a + 1) * (a + 2) / 2 <= p) ++a;
+      c = p - a * (a + 1) / 2;
+      u = Tt + a * pitch;
+      v = Tt + c * pitch;
+    }
+    double s = 0.0;
+    for (int i = lane; i < n0; i += 64) s = fma(u[i], v[i], s);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) {
+      if (p < npairs) cm[a][c] = s;
+      else res[c] = ynew[c] - s;
+    }
+  }
+  if (tid == 0) bad = 0;
+  for (int e = tid; e < B * (B + 1); e += 1024) (&inv[0][0])[e] = 0.0;
+  __syncthreads();
+  if (tid == 0) {
+    for (int j = 0; j < b && bad == 0; ++j) {
+      for (int c = 0; c <= j; ++c) {
+        double s = (c == j ? prior : Knn[j * B + c]) - cm[j][c];
+        for (int k = 0; k < c; ++k) s -= cm[j][k] * cm[c][k];
+        if (c < j) {
+          cm[j][c] = s / cm[c][c];
+        } else if (!(s > 1e-12 * prior) || !isfinite(s)) {
+          // GPy would retry with jitter here; report and let the host refit instead
+          bad = n0 + j + 1;
+        } else {
+          cm[j][j] = sqrt(s);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (bad != 0) {
+    if (tid == 0) info[0] = bad;
+    return;
+  }
+  if (tid < b) {                      // column tid of Lc^-1 by forward substitution
+    const int c = tid;
+    for (int i = c; i < b; ++i) {
+      double s = (i == c) ? 1.0 : 0.0;
+      for (int k = c; k < i; ++k) s -= cm[i][k] * inv[k][c];
+      inv[i][c] = s / cm[i][i];
+    }
+  }
+  __syncthreads();
+  if (tid < B) {
+    double g = 0.0;
+    for (int c = 0; c <= tid && tid < b; ++c) g = fma(inv[tid][c], res[c], g);
+    gam[tid] = g;                     // (zero behind b)
+  }
+  __syncthreads();
+  for (int i = tid; i < n_pad_new; i += 1024) {
+    if (i < n0) {
+      double w[B];
+#pragma unroll
+      for (int c = 0; c < B; ++c) w[c] = (c < b) ? Wt[c * pitch + i] : 0.0;
+      double da = 0.0;
+#pragma unroll 1
+      for (int j = 0; j < b; ++j) {   // (inv is zero above the diagonal, w behind b)
+        double row = 0.0;
+#pragma unroll
+        for (int c = 0; c < B; ++c) row = fma(inv[j][c], w[c], row);
+        Li[int64_t(n0 + j) * ld + i] = -row;
+        da = fma(-row, gam[j], da);
+      }
+      alpha[i] += da;
+    } else if (i < n0 + b) {
+      const int c = i - n0;
+      double da = 0.0;
+      for (int j = 0; j < b; ++j) {
+        Li[int64_t(n0 + j) * ld + i] = inv[j][c];
+        da = fma(inv[j][c], gam[j], da);
+      }
+      alpha[i] = da;
+    } else {
+      alpha[i] = 0.0;
+    }
+  }
+  if (tid < B) blk[kBlkGamma + tid] = gam[tid];
+  if (tid == 0) {
+    blk[kBlkB] = double(b);
+    blk[kBlkN0] = double(n0);
+    info[0] = 0;
+  }
+}
+
+// gp->X / gp->Y already hold the new rows at gp->n .. gp->n + b - 1 (uploaded by the caller).
+// On success n grows by b; *info != 0 leaves the GP untouched.
+int append_block_gp(sgp_gp* gp, int b, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  const int n = int(gp->n), ld = gp->ld, d = gp->kern.d;
+  double* Li = static_cast<double*>(gp->Linv.p);
+  double* X = static_cast<double*>(gp->X.p);
+  SGP_TRY(sgp_reserve(ctx, &gp->blk, size_t(kBlkWords) * sizeof(double)));
+  double* buf;
+  const size_t vec = size_t(SGP_MAX_BLOCK) * ld;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage,
+                      (3 * vec + SGP_MAX_BLOCK * SGP_MAX_BLOCK) * sizeof(double) + 64, &buf));
+  double* Kc = buf;
+  double* Tt = buf + vec;
+  double* Wt = buf + 2 * vec;
+  double* Knn = buf + 3 * vec;
+  int* info_dev = reinterpret_cast<int*>(Knn + SGP_MAX_BLOCK * SGP_MAX_BLOCK);
+  const double* xnew = X + size_t(n) * d;
+  SGP_TRY(launch_kernel_matrix(ctx, gp->kern, xnew, b, X, n, Kc, ld, 0, 0.0, INT64_MAX));
+  SGP_TRY(launch_kernel_matrix(ctx, gp->kern, xnew, b, xnew, b, Knn, SGP_MAX_BLOCK, 0, 0.0,
+                               INT64_MAX));
+  SGP_TRY(launch_tri_mv(ctx, Li, ld, n, Kc, ld, b, Tt, ld));
+  SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, Tt, ld, b, Wt, ld, n));
+  const int np_new = (n + b + 15) / 16 * 16;
+  const double prior = gp->kern.kdiag + gp->noise_var + 1e-8 + gp->jitter;
+  hipLaunchKernelGGL(k_append_block_finish, dim3(1), dim3(1024), 0, ctx->stream, Li,
+                     int64_t(ld), n, b, Kc, Tt, Wt, int64_t(ld), Knn, prior,
+                     static_cast<const double*>(gp->Y.p) + n, static_cast<double*>(gp->alpha.p),
+                     static_cast<double*>(gp->blk.p), np_new, info_dev);
+  SGP_HIP(ctx, hipGetLastError());
+  SGP_TRY(sgp_d2h(ctx, info, info_dev, sizeof(int)));
+  if (*info != 0) return 0;
+  gp->n = n + b;
+  gp->n_pad = np_new;
+  gp->n_f = (n + b + 31) / 32 * 32;
+  gp->upd_valid = false;
+  gp->rem_valid = false;
+  gp->blk_valid = true;
   return publish_gp(gp);
 }
 
@@ -611,6 +768,7 @@ int pop_gp(sgp_gp* gp) {
   gp->n_f = (n + 31) / 32 * 32;
   gp->upd_valid = false;
   gp->rem_valid = false;
+  gp->blk_valid = false;
   SGP_TRY(launch_tri_mv(ctx, Li, ld, n, static_cast<double*>(gp->Y.p), 0, 1, tv, 0));
   SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, tv, 0, 1,
                          static_cast<double*>(gp->alpha.p), 0, gp->n_pad));
@@ -815,6 +973,7 @@ int remove_gp(sgp_gp* gp, int index, int* info) {
   gp->n_f = (n - 1 + 31) / 32 * 32;
   gp->upd_valid = false;
   gp->rem_valid = true;
+  gp->blk_valid = false;
   return publish_gp(gp);
 }
 

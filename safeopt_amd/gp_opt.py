@@ -153,6 +153,36 @@ class GaussianProcessOptimization(object):
         self._x = np.concatenate((self._x, x), axis=0)
         self._y = np.concatenate((self._y, y), axis=0)
 
+    def _add_data_points(self, gp, rows, y):
+        """Append the rows ``(rows, y)`` to one GP only: block appends of the factor
+        (``GPRegression.append_XY``), a refit for a handle without them."""
+        if hasattr(gp, 'append_XY'):
+            gp.append_XY(rows, y)
+        else:
+            gp.set_XY(np.vstack([gp.X, rows]), np.vstack([gp.Y, y]))
+
+    def add_new_data_points(self, X, Y, context=None):
+        """Log ``b`` measurements at once -- the way back from ``optimize_batch`` -- and hand
+        them to the GPs: ``X`` (b, d_parameters), ``Y`` (b, n_gps), a ``nan`` in ``Y[r, g]``
+        meaning GP ``g`` did not observe row ``r`` (it then appends its own rows only).  The
+        log ends up as after ``b`` calls of ``add_new_data_point``; every GP takes its rows
+        by block appends of up to 16 rows (one O(b n^2) update each instead of ``b``), and
+        the next ``optimize()`` of a ``SafeOpt`` corrects the resident posterior in ONE
+        closed-form pass over the grid instead of sweeping it again."""
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        Y = np.atleast_2d(np.asarray(Y, dtype=float))
+        if X.shape[0] != Y.shape[0] or Y.shape[1] != len(self.gps):
+            raise ValueError("X (b, d) and Y (b, %d) expected, got %r and %r"
+                             % (len(self.gps), X.shape, Y.shape))
+        if self.num_contexts:
+            X = _with_context(X, context)
+        for i, gp in enumerate(self.gps):
+            seen = ~np.isnan(Y[:, i])
+            if seen.any():
+                self._add_data_points(gp, X[seen, :], Y[seen][:, [i]])
+        self._x = np.concatenate((self._x, X), axis=0)
+        self._y = np.concatenate((self._y, Y), axis=0)
+
     def _remove_last_data_point(self, gp):
         """Drop the newest row of one GP (a one-row ``sgp_gp_pop``)."""
         gp.set_XY(gp.X[:-1, :], gp.Y[:-1, :])
@@ -328,24 +358,30 @@ class _HipGridBackend(object):
         devs = self._dev()
         tags = self._tags(devs)
         which = [0] * len(devs)
-        rank1 = self.incremental and self._rank1_streak < self.refresh_every
-        kinds = set()                            # of the stale GPs' one-row changes
+        rank1 = self.incremental
+        kinds = set()                            # of the stale GPs' changes
+        rows = 1                                 # rows the refresh absorbs (the drift budget)
         for i, dv in enumerate(devs):
             if self._seen[i] == tags[i]:
                 continue                                  # up to date
             removed = getattr(dv, 'removed', False)
-            if (rank1 and (dv.appended or removed) and self._seen[i] is not None
+            block = getattr(dv, 'block', 0)
+            if (rank1 and (dv.appended or removed or block) and self._seen[i] is not None
                     and self._seen[i] == (dv.serial, dv.version - 1)):
-                which[i] = 1                              # one append / one removal behind
-                kinds.add(removed)
+                which[i] = 1                 # one append / one removal / one block behind
+                kinds.add('block' if block else ('remove' if removed else 'append'))
+                rows = max(rows, block)
             else:
                 rank1 = False
-        rank1 = rank1 and len(kinds) == 1        # (appends and removals mixed: a sweep)
+        # (kinds mixed: a sweep; the streak counts absorbed rows, a block of b counts b)
+        rank1 = (rank1 and len(kinds) == 1
+                 and self._rank1_streak + rows <= self.refresh_every)
         self._seen = [None] * len(devs)          # unknown until the call is through
         if rank1 and any(which):
-            refresh = self.grid.rank1_remove if kinds.pop() else self.grid.rank1_update
+            refresh = getattr(self.grid, {'append': 'rank1_update', 'remove': 'rank1_remove',
+                                          'block': 'rankb_update'}[kinds.pop()])
             out = refresh(devs, which, beta, fmin, defer)
-            self._rank1_streak += 1
+            self._rank1_streak += rows
         else:
             out = self.grid.confidence(devs, beta, fmin, defer)
             self._rank1_streak = 0

@@ -248,6 +248,30 @@ class GPRegression(object):
         dev.set_data(X, Y[:, 0])
         self._dev_fitted = True
 
+    def append_XY(self, X, Y):
+        """``b >= 1`` more observations (``X`` (b, d), ``Y`` (b, 1)) behind the data: block
+        appends on the device (``sgp_gp_append_block``, chunks of at most ``MAX_BLOCK`` rows:
+        one O(b n^2) update and one read-back per chunk) when the model is fitted,
+        ``incremental`` is on and the device GP is in step; otherwise, or when a chunk is
+        refused (no capacity, a pivot not positive), ``set_XY`` with the stacked arrays."""
+        Xn = np.array(np.atleast_2d(X), dtype=float)
+        Yn = np.array(np.atleast_2d(Y), dtype=float)
+        if Yn.shape[0] != Xn.shape[0] and Yn.shape == (1, Xn.shape[0]):
+            Yn = Yn.T
+        if (Xn.shape[0] != Yn.shape[0] or Xn.shape[1] != self.input_dim or Yn.shape[1] != 1
+                or Xn.shape[0] < 1):
+            raise ValueError("inconsistent X %r / Y %r" % (Xn.shape, Yn.shape))
+        X, Y = np.vstack([self.X, Xn]), np.vstack([self.Y, Yn])
+        dev = self._device_gp()
+        if self._dev_fitted and dev.n == self.X.shape[0] and self.incremental:
+            for s in range(0, Xn.shape[0], _hip.MAX_BLOCK):
+                if not dev.append_block(Xn[s:s + _hip.MAX_BLOCK], Yn[s:s + _hip.MAX_BLOCK, 0]):
+                    break
+            else:
+                self.X, self.Y = X, Y
+                return
+        self.set_XY(X, Y)
+
     def remove_data(self, index):
         """Forget observation ``index`` (0 .. n-1), whichever it is: an O(n^2) downdate
         of the factor on the device (``sgp_gp_remove``) instead of the refit ``set_XY``
