@@ -38,6 +38,7 @@ extern "C" {
 #define SGP_MAX_BATCH 64   /* query points of one hallucinated batch           */
 #define SGP_MAX_MES 64     /* maxima of one max-value entropy search (= SGP_MAX_PATHS) */
 #define SGP_MAX_BLOCK 16   /* observations of one block append                 */
+#define SGP_MAX_ISE 4096   /* candidates of one information-theoretic safe exploration */
 
 /* kernel kinds: GPy.kern.RBF / Matern32 / Matern52 (Stationary.K_of_r)        */
 enum { SGP_RBF = 0, SGP_MATERN32 = 1, SGP_MATERN52 = 2 };
@@ -588,6 +589,50 @@ int sgp_grid_mes(sgp_grid* grid, const double* ystar, int K, int rows, int floor
 int sgp_grid_mes_comm(sgp_grid* grid, const double* ystar, int K, int rows, int floor_mode,
                       double floor_value, double* alpha, double* value, int64_t* gidx,
                       double* floor_used);
+
+/* Information-theoretic safe exploration (Bottero, Luis, Vinogradska, Berkenkamp, Peters 2022):
+ * the approximate mutual information, in nats, between a noisy measurement at x and the safety
+ * indicator [f(z) >= fmin] of a row z.  With mu = mean(z) - fmin, vz = max(var(z), 1e-15),
+ * vx = max(var(x), 1e-15), c = cov(z, x), s the variance of the measurement's noise and
+ * c1 = 1 / (pi ln 2):
+ *   t = c1 mu^2 / vz,  r2 = min(c^2 / (vx vz), 1),  q = r2 vx,  B = (s + vx) + (2 c1 - 1) q,
+ *   e = q / B,  w = min(2 c1 e, 1),
+ *   I = -ln2 exp(-t) expm1(log1p(-w) / 2 - t (1 - 2 c1) e)
+ * (csrc/ise_term.h: ise_term) -- the stable form of ln2 [e^-t - sqrt(A / B) e^(-t (s + vx) / B)],
+ * A = s + vx (1 - r2): >= 0, 0 exactly at c = 0, <= ln2 e^-t, finite for every finite input.  A
+ * term depends on (mu, vz, vx, c, s) alone: the same bits from sgp_ise_eval and from
+ * sgp_grid_ise, whatever N, the row's position or the launch.
+ *
+ * sgp_ise_eval: the term at N arbitrary points from HOST arrays mu[N], vz[N], vx[N], c[N] ->
+ * out[N].  N <= 0 returns 0 and writes nothing; a NaN or negative s is refused with nothing
+ * launched.                                                                                  */
+enum { SGP_ISE_UNSAFE = 0, SGP_ISE_ALL = 1 };                     /* the rows z                */
+int sgp_ise_eval(sgp_ctx* ctx, const double* mu, const double* vz, const double* vx,
+                 const double* c, int64_t N, double s, double* out);
+/* The K candidates cand[K] (GLOBAL rows of this rank's shard; duplicates allowed) against the
+ * rows z of the grid -- the rows outside S as it stands on the device (about = SGP_ISE_UNSAFE)
+ * or every row (SGP_ISE_ALL) -- over the grid's RESIDENT posterior (the rule of sgp_grid_mes: a
+ * pass that sweeps it must have run since the rows last changed).  A GP g is active when
+ * fmin[g] is finite; with s_g = noise_var_g + 1e-8 and c_g the posterior covariance
+ *   c_g(z, x) = k_g(z, x) - k_g(X, z)^T Ky^-1 k_g(X, x),
+ *   pair(x, z) = sum over the active g, in the order of g, of I_g(x; z),
+ *   alpha[j]   = max_z pair(cand[j], z)        (-inf when no row qualifies),
+ *   target[j]  = the lowest GLOBAL row z attaining it                  (-1),
+ *   value, gidx = the largest alpha and its candidate's global row, the lowest such row among
+ *                 equal values (-inf / -1 when no row qualifies).
+ * The operands Ky^-1 k_g(X, x_j) are formed once per call; the row kernel contracts them with
+ * k_g(z, X), evaluated once per tile of rows, on the fp64 matrix cores (csrc/ise.hip).  No
+ * atomics; partials bounded by 512 x K pairs.  A candidate's alpha, target and row of pairs
+ * depend on the candidate alone, not on K or on its position in cand.  pairs (K x N_local) and
+ * cov (G x K x N_local, zeros for an inactive GP) may be NULL: test and diagnostic outputs,
+ * refused when G K N_local > 2^24.
+ * Refused, with nothing launched or written: K < 1 or K > SGP_MAX_ISE; an unknown `about`; a
+ * candidate outside the shard; no active GP; a grid without a current posterior; a GP that is
+ * not fitted, lives in another context or has another input dimension.  One rank: the call
+ * never communicates.  Q, S, M, G, mean and var are only read.                               */
+int sgp_grid_ise(sgp_grid* grid, sgp_gp* const* gps, int G, const double* fmin,
+                 const int64_t* cand, int K, int about, double* alpha, int64_t* target,
+                 double* value, int64_t* gidx, double* pairs, double* cov);
 /* One pick of a batch by hallucinated observations (GP-BUCB, Desautels et al. 2014, on
  * SafeOpt's rule, safeopt/gp_opt.py:635-649; the reference has no batch mode).  gps are CLONES
  * (sgp_gp_clone) of the grid's GPs, every one with the pending pick x* appended

@@ -41,6 +41,8 @@ MAX_BLOCK = 16            # SGP_MAX_BLOCK: observations of one block append
 MAX_MES = 64              # SGP_MAX_MES: maxima of one max-value entropy search
 MES_ALL, MES_S, MES_MG = 0, 1, 2                        # candidate rows of sgp_grid_mes
 MES_FLOOR_NONE, MES_FLOOR_MEAN, MES_FLOOR_VALUE = 0, 1, 2
+MAX_ISE = 4096            # SGP_MAX_ISE: candidates of one information-theoretic safe exploration
+ISE_UNSAFE, ISE_ALL = 0, 1                              # the rows z of sgp_grid_ise
 
 # name -> (restype, argtypes); mirrors include/safeopt_hip.h one to one
 PROTOTYPES = {
@@ -89,6 +91,11 @@ PROTOTYPES = {
                                c_double_p, c_double_p, c_i64_p, c_double_p]),
     "sgp_grid_mes_comm": (C.c_int, [vp, c_double_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                     c_double_p, c_double_p, c_i64_p, c_double_p]),
+    "sgp_ise_eval": (C.c_int, [vp, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64,
+                               C.c_double, c_double_p]),
+    "sgp_grid_ise": (C.c_int, [vp, vpp, C.c_int, c_double_p, c_i64_p, C.c_int, C.c_int,
+                               c_double_p, c_i64_p, c_double_p, c_i64_p, c_double_p,
+                               c_double_p]),
     "sgp_gp_get_factor": (C.c_int, [vp, c_double_p, c_double_p]),
     "sgp_gp_clone": (C.c_int, [vp, vpp]),
     "sgp_grid_batch_next": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_int, C.c_double,
@@ -545,6 +552,21 @@ class Context(object):
         out = np.empty(mean.shape)
         self.check(lib().sgp_mes_eval(self.h, dptr(mean), dptr(var), mean.size, dptr(ystar),
                                       int(ystar.size), float(floor), dptr(out)))
+        return out
+
+    def ise_eval(self, mu, vz, vx, c, s):
+        """The term of information-theoretic safe exploration at arbitrary points
+        (``sgp_ise_eval``): ``mu = mean(z) - fmin``, the variances ``vz`` at ``z`` and ``vx``
+        at the measured point, their posterior covariance ``c`` -- arrays of one shape -- and
+        the noise variance ``s`` of a measurement -> the approximate mutual information in
+        nats, in that shape."""
+        mu, vz, vx, c = f64(mu), f64(vz), f64(vx), f64(c)
+        if not (mu.shape == vz.shape == vx.shape == c.shape):
+            raise ValueError("mu %r, vz %r, vx %r and c %r differ in shape"
+                             % (mu.shape, vz.shape, vx.shape, c.shape))
+        out = np.empty(mu.shape)
+        self.check(lib().sgp_ise_eval(self.h, dptr(mu), dptr(vz), dptr(vx), dptr(c), mu.size,
+                                      float(s), dptr(out)))
         return out
 
     def kern_K(self, kdesc, X1, X2):
@@ -1420,6 +1442,28 @@ class DeviceGrid(object):
                             None if al is None else dptr(al), C.byref(v), C.byref(i),
                             C.byref(fu)))
         return al, v.value, i.value, fu.value
+
+    def ise(self, gps, fmin, cand, about=ISE_UNSAFE, pairs=False, cov=False):
+        """Information-theoretic safe exploration over the resident posterior
+        (``sgp_grid_ise``): the candidates ``cand`` (global rows of this shard) against the
+        rows outside ``S`` (``ISE_UNSAFE``) or every row (``ISE_ALL``) ->
+        ``(alpha (K,), target (K,), value, global row, pairs (K, N) or None, cov (G, K, N) or
+        None)``; -inf / -1 where no row qualifies.  ``pairs`` / ``cov``: test outputs."""
+        fmin = f64(fmin).reshape(-1)
+        cand = np.ascontiguousarray(cand, dtype=np.int64).reshape(-1)
+        K, G = int(cand.size), len(gps)
+        if fmin.size != G:
+            raise ValueError("%d fmin for %d GPs" % (fmin.size, G))
+        alpha = np.empty(K)
+        target = np.empty(K, dtype=np.int64)
+        pr = np.empty((K, self.N)) if pairs else None
+        cv = np.empty((G, K, self.N)) if cov else None
+        v, i = C.c_double(0), C.c_int64(0)
+        self.ctx.check(lib().sgp_grid_ise(
+            self.h, _gp_array(gps), G, dptr(fmin), cand.ctypes.data_as(c_i64_p), K, int(about),
+            dptr(alpha), target.ctypes.data_as(c_i64_p), C.byref(v), C.byref(i),
+            None if pr is None else dptr(pr), None if cv is None else dptr(cv)))
+        return alpha, target, v.value, i.value, pr, cv
 
     def download(self, what, out=None):
         if what == Q:

@@ -201,6 +201,11 @@ enum ScratchSlot : int {
                         // swarm_run asks for this slot, so what the entry point staged stays put
   kSlotMesPart = 25,    // ... per-workgroup (value, row) pairs and floor partials of a grid call,
                         // its records and result (MesScratch)
+  kSlotIseIn = 26,      // ise.hip (IseLayout): the candidates' rows | coordinates | variances of a
+                        // grid call; mu | vz | vx | c | out of sgp_ise_eval's rows
+  kSlotIseW = 27,       // ... the operands W_g of the active GPs, the workspace T behind them
+  kSlotIsePart = 28,    // ... per-workgroup (pair, row) partials, alpha | target | result
+  kSlotIseOut = 29,     // ... pairs | cov, the test outputs of a grid call that asks for them
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }

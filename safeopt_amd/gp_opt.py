@@ -610,6 +610,44 @@ class _HipGridBackend(object):
             self.refresh_posterior()
         return self.grid.mes(ystar, rows=rows, floor=floor, alpha=alpha, comm=comm)
 
+    def ise_state(self):
+        """What the host-side candidate selection of ``SafeOpt.ise_point`` reads, in one
+        download each: the resident variances ``(G, N)``, the safe set ``(N,)`` and the
+        GPs' measurement noise ``s_g = noise_var_g + 1e-8``; the posterior is swept first
+        when it is not that of the GPs as they are."""
+        if not self.posterior_is_current():
+            self.refresh_posterior()
+        s = np.array([float(g.noise_var) + 1e-8 for g in self.gps])
+        return (np.array(self.grid.download(_hip.VAR)),
+                np.array(self.grid.download(_hip.S), dtype=bool), s)
+
+    def ise(self, fmin, cand, about, pairs=False):
+        """Information-theoretic safe exploration over the resident posterior
+        (``DeviceGrid.ise``): ``(alpha (K,), target (K,), value, global row, pairs or None)``;
+        the posterior is swept first when it is not that of the GPs as they are."""
+        if not self.posterior_is_current():
+            self.refresh_posterior()
+        al, tg, v, i, pr, _ = self.grid.ise(self._dev(), fmin, cand, about=about, pairs=pairs)
+        return al, tg, v, i, pr
+
+
+def ise_candidates(var, S, s, active, K):
+    """The candidate rows of ``SafeOpt.ise_point``: the ``min(K, |S|)`` rows of ``S`` with the
+    largest ``sum_{g active} log1p(var_g / s_g) / 2`` (added in the order of ``g``), the lower
+    row first among equals.  ``var`` ``(G, N)``, ``S`` ``(N,)`` bool, ``s`` ``(G,)``, ``active``
+    ``(G,)`` bool."""
+    ids = np.flatnonzero(S)
+    key = np.zeros(ids.size)
+    for g in np.flatnonzero(active):
+        key = key + 0.5 * np.log1p(var[g, ids] / s[g])
+    K = int(K)
+    if K < ids.size:
+        # (only the rows at or above the K-th largest key can be picked: sort those)
+        keep = key >= np.partition(key, ids.size - K)[ids.size - K]
+        ids, key = ids[keep], key[keep]
+    order = np.lexsort((ids, -key))[:K]
+    return ids[order].astype(np.int64)
+
 
 class SafeOpt(GaussianProcessOptimization):
     """Safe Bayesian optimisation over a discretised parameter set.
@@ -1743,6 +1781,115 @@ class SafeOpt(GaussianProcessOptimization):
             raise RuntimeError('There are no safe points to sample in.')
         x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
         return (x, alpha, values, ystar) if return_values else (x, alpha)
+
+    def _ise(self, candidates, about):
+        """The body of ``ise_point``: ``(rows, values, targets, alpha, global row)``, the
+        last two ``-inf`` / ``-1`` when no row qualifies as ``z``."""
+        if about not in ('unsafe', 'all'):
+            raise ValueError("about must be 'unsafe' or 'all', got %r" % (about,))
+        if self._comm.world > 1:
+            raise NotImplementedError(
+                "ise_point runs on one rank (this communicator has %d)" % self._comm.world)
+        if not (hasattr(self._backend, 'ise') and hasattr(self._backend, 'ise_state')):
+            raise NotImplementedError(
+                "this grid backend runs no information-theoretic safe exploration")
+        fmin = np.asarray(self.fmin, dtype=float).reshape(-1)
+        active = np.isfinite(fmin)
+        if not active.any():
+            raise ValueError("no GP has a finite fmin: there is no safety indicator to learn")
+        by_count = np.ndim(candidates) == 0
+        if by_count:
+            K = int(candidates)
+            if K < 1 or K > _hip.MAX_ISE or K != candidates:
+                raise ValueError("candidates must be in 1 .. SGP_MAX_ISE = %d, got %r"
+                                 % (_hip.MAX_ISE, candidates))
+        else:
+            rows = np.asarray(candidates)
+            if (rows.ndim != 1 or rows.size < 1 or rows.size > _hip.MAX_ISE
+                    or not np.issubdtype(rows.dtype, np.integer)):
+                raise ValueError("candidates must be a count or a 1-D index array of 1 .. "
+                                 "SGP_MAX_ISE = %d rows" % _hip.MAX_ISE)
+            rows = rows.astype(np.int64)
+            if rows.min() < 0 or rows.max() >= self.inputs.shape[0]:
+                raise ValueError("candidate rows outside 0 .. %d" % (self.inputs.shape[0] - 1))
+        self._flush_Q()
+        self._flush_masks()
+        var, S, s = self._backend.ise_state()
+        if not S.any():
+            raise RuntimeError('There are no safe points to sample in.')
+        if by_count:
+            rows = ise_candidates(var, S, s, active, K)
+        elif not np.all(S[rows]):
+            raise ValueError("candidate rows outside the safe set: %r"
+                             % (rows[~S[rows]][:8].tolist(),))
+        code = _hip.ISE_UNSAFE if about == 'unsafe' else _hip.ISE_ALL
+        values, targets, alpha, idx = self._backend.ise(fmin, rows, code)[:4]
+        return rows, values, targets, alpha, idx
+
+    def ise_point(self, candidates=256, about='unsafe', return_values=False):
+        """The safe row whose measurement tells most about whether some OTHER row is safe:
+        information-theoretic safe exploration (Bottero, Luis, Vinogradska, Berkenkamp,
+        Peters 2022) over the resident grid -- the expansion counterpart of ``mes_point``,
+        without a Lipschitz constant and without a width rule.
+
+        A GP ``g`` is active when ``fmin_g`` is finite.  For a candidate ``x`` in ``S`` and a
+        row ``z``, with ``mu = mean_g(z) - fmin_g``, the resident variances ``vz``, ``vx``
+        (clipped at 1e-15), the posterior covariance ``c = c_g(z, x)``, ``s = noise_var_g +
+        1e-8`` and ``c1 = 1 / (pi ln 2)``,
+
+            ``t = c1 mu^2 / vz,  r2 = min(c^2 / (vx vz), 1),  e = r2 vx / (s + vx + (2 c1 - 1)
+            r2 vx)``,
+            ``I_g = -ln2 exp(-t) expm1(log1p(-min(2 c1 e, 1)) / 2 - t (1 - 2 c1) e)``
+
+        approximates the mutual information, in nats, between the measurement at ``x`` and
+        the indicator ``[f_g(z) >= fmin_g]``.  The GPs are measured together, so
+        ``pair(x, z) = sum_g I_g`` (in the order of ``g``), ``alpha(x) = max_z pair(x, z)``
+        and the pick is the candidate with the largest ``alpha``, the lowest row among
+        equals.  ``z`` ranges over the rows outside ``S`` (``about='unsafe'``, the rows the
+        expander test scans) or over every row (``about='all'``, the paper's domain).  The
+        covariances are formed on the device, row tile by row tile, and never stored
+        (``sgp_grid_ise``).
+
+        ``candidates``: an int ``K`` -- the ``min(K, |S|)`` rows of ``S`` with the largest
+        ``sum_{g active} log1p(var_g / s_g) / 2``, the lower row first among equals: the
+        data-processing bound on what a measurement there can tell about anything.  In this
+        version the selection runs on the HOST, from one download of the resident variances
+        and of ``S``.  Or a 1-D integer array of rows, every one of them in ``S`` (else
+        ``ValueError``).  At most ``SGP_MAX_ISE`` = 4096 either way.
+
+        Returns ``(x, alpha)``: the row, context columns stripped as ``optimize()`` strips
+        them, and its ``alpha``; with ``return_values=True`` ``(x, alpha, rows (K,), values
+        (K,), targets (K,))``: the candidates, their ``alpha`` and the rows ``z`` that attain
+        them.  Raises ``RuntimeError`` when ``S`` is empty or no row qualifies as ``z``,
+        ``ValueError`` when no GP has a finite ``fmin``, ``NotImplementedError`` on more
+        than one rank, before anything runs.  Changes no state of the optimiser or its GPs
+        -- except that pending in-place edits of ``opt.Q`` / ``opt.S`` are flushed first and
+        the resident posterior is swept again if data came in since the last interval
+        update, as for ``mes_point``.  Draws no random numbers."""
+        rows, values, targets, alpha, idx = self._ise(candidates, about)
+        if idx < 0:
+            raise RuntimeError("no row qualifies as z: every row is in the safe set "
+                               "(about='all' takes every row)")
+        x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
+        return (x, alpha, rows, values, targets) if return_values else (x, alpha)
+
+    def info_point(self, paths=16, features=1024, candidates=256, about='unsafe'):
+        """ISE-BO (Bottero et al. 2023): the ``mes_point`` pick (what a measurement tells
+        about the VALUE of the safe optimum) or the ``ise_point`` pick (what it tells about
+        the SAFETY of another row), whichever acquisition is larger -- both are mutual
+        informations in nats.  Returns ``(x, alpha, which)``, ``which`` in ``{'mes',
+        'ise'}``; MES wins a tie, and is returned when no row qualifies for ISE.
+        ``paths`` / ``features`` as for ``mes_point`` (candidates ``S``, floor ``'mean'``),
+        ``candidates`` / ``about`` as for ``ise_point``.  One rank
+        (``NotImplementedError`` otherwise, before anything runs)."""
+        if self._comm.world > 1:
+            raise NotImplementedError(
+                "info_point runs on one rank (this communicator has %d)" % self._comm.world)
+        xm, am = self.mes_point(paths=paths, features=features)
+        _rows, _values, _targets, ai, idx = self._ise(candidates, about)
+        if idx >= 0 and ai > am:
+            return self.inputs[idx, :self.inputs.shape[1] - self.num_contexts], ai, 'ise'
+        return xm, am, 'mes'
 
     def get_maximum(self, context=None):
         """Best lower bound inside the safe set: ``(x, l)`` or ``None``."""
