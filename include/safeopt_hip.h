@@ -418,12 +418,16 @@ int sgp_grid_expander_batch(sgp_grid* grid, sgp_gp* const* gps, int G, double be
  *   out6 = { candidates tested, expanders among them,
  *            mode 0: key and global row of the FIRST expander in visiting order (nothing is
  *                    marked in G: the caller settles exact ties, gp_opt.py:542-552),
- *            key below which the candidates are still untested (-inf: none left),
+ *            key below which the candidates are still untested (-inf: none left; finite
+ *            with 0 tested: the histogram counted keys an ulp below the edge of the picked bin,
+ *            which the list does not take -- go on with cut_w = key_hi = this key),
  *            scaling != NULL and mode 0: the global row of sgp_grid_argmax(SGP_ARGMAX_MG_WIDTH)
  *            taken behind the test (gp_opt.py:631-641) -- the next query point when the pass
  *            ends the loop without an expander, for no further round trip; else -1 }
  *   mode 1 (full_sets): every expander of the pass is marked in G on the device.
- * One rank (the shard is the grid).                                                   */
+ * No GP with a constraint (every fmin_i = -inf): nothing is an expander (gp_opt.py:559, 580:
+ * the loop over the GPs only continues) -- 0 hits, nothing marked.
+ * One rank (the shard is the grid).                                                  */
 int sgp_grid_expander_pass(sgp_grid* grid, sgp_gp* const* gps, int G, double beta,
                            const double* fmin, int mode, double cut_w, int64_t cut_idx,
                            double key_lo, double key_hi, int want, const double* scaling,

@@ -271,7 +271,28 @@ static int pass_select(sgp_grid* g, int mode, double cut_w, int64_t cut_idx, dou
   SGP_TRY(sgp_d2h(ctx, &hs, ps->sel, sizeof(hs)));
   *count = hs.count;
   out6[0] = double(hs.count);
-  out6[4] = hs.count == 0 ? -INFINITY : hs.thr;
+  // Nothing listed is the end only when the histogram counted nothing either (est == 0: thr is
+  // -inf then).  The histogram bins by a product, the list compares with the bin's lower edge: a
+  // key an ulp below the edge is counted in the picked bin and not listed.  The caller goes on
+  // from thr (cut and top of the key range), where those keys fall into the top bin.
+  out6[4] = (hs.count == 0 && hs.est == 0) ? -INFINITY : hs.thr;
+  return 0;
+}
+
+// No GP with a constraint: the reference's loop over the GPs only continues (gp_opt.py:559,
+// 580) and G_safe stays False -- the listed candidates count as tested, none is a hit, nothing
+// is marked, and no arg-max is taken (-1: unknown).
+static bool any_constraint(const double* fmin, int G) {
+  for (int i = 0; i < G; ++i)
+    if (fmin[i] != -INFINITY) return true;
+  return false;
+}
+
+static int pass_without_constraint(double* out6) {
+  out6[1] = 0.0;
+  out6[2] = -INFINITY;
+  out6[3] = -1.0;
+  out6[5] = -1.0;
   return 0;
 }
 
@@ -311,6 +332,7 @@ int sgp_grid_expander_pass(sgp_grid* g, sgp_gp* const* gps, int G, double beta,
   int count = 0;
   SGP_TRY(pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, out6, &ps, &count));
   if (count == 0) return 0;
+  if (!any_constraint(fmin, G)) return pass_without_constraint(out6);
   int32_t* dfl;
   SGP_TRY(expander_many_test(g, host, beta, fmin, count, ps.list, nullptr, nullptr, &dfl));
   return pass_result_and_argmax(g, ps.list, count, dfl, many_flag_bytes(count, G),
@@ -330,6 +352,7 @@ int sgp_grid_lipschitz_pass(sgp_grid* g, int G, const double* fmin, const double
   int count = 0;
   SGP_TRY(pass_select(g, mode, cut_w, cut_idx, key_lo, key_hi, want, out6, &ps, &count));
   if (count == 0) return 0;
+  if (!any_constraint(fmin, G)) return pass_without_constraint(out6);
   double* work;
   int32_t* dfl;
   SGP_TRY(lipschitz_bufs(g, count, &work, &dfl));
@@ -408,6 +431,10 @@ int sgp_grid_pass_lipschitz_test(sgp_grid* g, int G, const double* fmin, const d
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, G == g->G, "grid was created for %d GPs, got %d", g->G, G);
   if (K <= 0) return 0;
+  if (!any_constraint(fmin, G)) {
+    memset(flags, 0, size_t(K) * G * 4);
+    return 0;
+  }
   double* work;
   int32_t* dfl;
   SGP_TRY(lipschitz_bufs(g, K, &work, &dfl));

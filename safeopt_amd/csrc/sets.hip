@@ -1187,10 +1187,12 @@ __global__ __launch_bounds__(T) void k_lip_items(LipPass a) {
           s += df * df;
         }
         const double dist = sqrt(s);
-        bool hit = true;
-        for (int g = 0; g < a.G; ++g) {
+        bool hit = false;                          // (no GP with a constraint: no hit)
+        for (int g = 0, first = 1; g < a.G; ++g) {
           if (a.fmin.v[g] == -INFINITY) continue;
-          hit = hit && (a.uc[c * a.G + g] - a.lips.v[g] * dist >= a.fmin.v[g]);
+          const bool ok = a.uc[c * a.G + g] - a.lips.v[g] * dist >= a.fmin.v[g];
+          hit = first ? ok : (hit && ok);
+          first = 0;
         }
         if (hit && a.flags[c * a.G] == 0)
           for (int g = 0; g < a.G; ++g) atomicOr(&a.flags[c * a.G + g], 1);
@@ -1229,8 +1231,10 @@ __global__ __launch_bounds__(1024) void k_pass_result(const int* list, int count
   __shared__ unsigned shn[1024 / 64];
   Pair best{-INFINITY, -1};
   unsigned hits = 0;
+  bool constrained = false;                        // (no GP with a constraint: no hit)
+  for (int g = 0; g < G; ++g) constrained = constrained || fmin.v[g] != -INFINITY;
   for (int pos = threadIdx.x; pos < count; pos += 1024) {
-    bool ok = true;
+    bool ok = constrained;
     for (int g = 0; g < G; ++g)
       if (fmin.v[g] != -INFINITY && flags[int64_t(pos) * G + g] == 0) ok = false;
     if (!ok) continue;

@@ -290,8 +290,9 @@ _Front = collections.namedtuple(
     '_Front', 'n_cand n_unsafe w_c idx_c x_c mu_c q_c fused n_tied')
 
 #: what one big pass of the expander loop found (``SafeOpt._pass_*``): candidates tested
-#: (0: none left), the key and global row of the first expander in visiting order (row -1:
-#: none), the cut in front of the next pass (-inf: none), the step's arg-max (-1: unknown)
+#: (0 with a finite cut: counted by the histogram, not listed), the key and global row of the
+#: first expander in visiting order (row -1: none), the cut in front of the next pass (-inf:
+#: nothing left, the end of the loop), the step's arg-max (-1: unknown)
 _Pass = collections.namedtuple('_Pass', 'tested key row left amax')
 
 
@@ -1246,7 +1247,15 @@ class SafeOpt(GaussianProcessOptimization):
         order (``pass_sizes``; chosen by a histogram of the keys, not a sort) and tests ALL of
         them in one scan of the unsafe rows: the first expander in visiting order is the widest
         hit of the first pass that has one -- every candidate in front of it has been tested --
-        and exact ties among equal widths are settled as always."""
+        and exact ties among equal widths are settled as always.
+
+        The loop ends when nothing is left behind the cut: ``left == -inf`` (the pass took
+        everything, or its histogram was empty).  A pass that tested NOTHING although its
+        histogram counted candidates is not the end: the histogram bins by a product, the list
+        compares with the bin's lower edge, and a key an ulp below the edge is counted in the
+        picked bin but not listed.  Such a pass reports its threshold as ``left``; with the cut
+        and the top of the range moved there its keys fall into the top bin of the next pass,
+        whose threshold lies at least a bin's width below them."""
         if full_sets:
             lo, hi, mode = -(float(self.inputs.shape[0]) + 1.0), 1.0, 1   # keys: minus the row
         else:
@@ -1255,12 +1264,12 @@ class SafeOpt(GaussianProcessOptimization):
             p = step(beta, active, mode, cut_w, cut_idx, lo, hi, self._pass_size(k))
             if p.row >= 0 and not full_sets:
                 return self._first_expander(beta, active, p.key, p.row)
-            if p.tested == 0 or p.left == -np.inf:
+            if p.left == -np.inf:
                 if p.amax >= 0 and p.tested > 0:
                     self._argmax_cache = (None, p.amax)
                 return
             cut_w, cut_idx = p.left, -1
-            if not full_sets:
+            if not full_sets or p.tested == 0:
                 hi = p.left
 
     def _pass_one_rank(self, beta, active, mode, cut_w, cut_idx, lo, hi, want):
@@ -1305,7 +1314,9 @@ class SafeOpt(GaussianProcessOptimization):
         part[:, 2:2 + d], part[:, 2 + d:] = xc, resid
         rows = allgather_rows(comm, part, count_dtype=np.float64)
         if rows.shape[0] == 0:
-            return _Pass(0, None, -1, -np.inf, -1)
+            # counted, not listed (keys an ulp below the edge of the picked bin): an empty
+            # pass, not the end -- the loop goes on from the threshold
+            return _Pass(0, None, -1, thr, -1)
         if self.use_lipschitz:
             flags = be.pass_lipschitz_test(self.fmin, self.liptschitz, rows[:, 2:2 + d],
                                            rows[:, 2 + d:])
