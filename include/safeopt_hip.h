@@ -637,6 +637,53 @@ int sgp_ise_eval(sgp_ctx* ctx, const double* mu, const double* vz, const double*
 int sgp_grid_ise(sgp_grid* grid, sgp_gp* const* gps, int G, const double* fmin,
                  const int64_t* cand, int K, int about, double* alpha, int64_t* target,
                  double* value, int64_t* gidx, double* pairs, double* cov);
+/* sgp_grid_ise with the candidates BY VALUE: cand[K] are GLOBAL rows anywhere in the whole grid
+ * (>= 0; read by the pick's tie rule and returned as gidx, nothing else), xc[K][d] their
+ * coordinates and vx[G][K] their variances, host arrays -- on a row-sharded grid a candidate
+ * usually lies in another rank's shard.  The same operand kernels, row kernel and reductions as
+ * sgp_grid_ise over this shard's rows: with the resident coordinates and variances of rows of
+ * this shard it returns the bits of sgp_grid_ise.  alpha, target, value, gidx as there (the
+ * shard's: -inf / -1 where none of ITS rows qualifies as z).  Refusals as sgp_grid_ise, with a
+ * negative row or a missing xc / vx in place of a candidate outside the shard.  Never
+ * communicates.                                                                              */
+int sgp_grid_ise_at(sgp_grid* grid, sgp_gp* const* gps, int G, const double* fmin,
+                    const int64_t* cand, const double* xc, const double* vx, int K, int about,
+                    double* alpha, int64_t* target, double* value, int64_t* gidx);
+/* sgp_grid_ise_at over the shards of all ranks of the context's communicator (sgp_comm_init or
+ * sgp_comm_init_host), in the grid's stream: ONE all-gather of the ranks' alpha | target blocks,
+ * a merge per candidate -- the largest alpha, the lowest global target among equals, a rank
+ * without a target (-inf / -1) never wins --, the pick over the merged values, then ONE
+ * read-back.  Every rank returns the same alpha, target, value and gidx: what sgp_grid_ise
+ * returns on one rank that holds the whole grid, bit for bit (a pair depends on the candidate
+ * and the row alone).  A collective: every rank calls it with the same candidates.  Without a
+ * communicator it equals sgp_grid_ise_at.                                                    */
+int sgp_grid_ise_comm(sgp_grid* grid, sgp_gp* const* gps, int G, const double* fmin,
+                      const int64_t* cand, const double* xc, const double* vx, int K, int about,
+                      double* alpha, int64_t* target, double* value, int64_t* gidx);
+/* Choosing the candidates of sgp_grid_ise where the variances are.  The key of a row of S is
+ *   key = sum over the active g, in the order of g, of log1p(var_g / s_g) / 2,
+ * s_g = noise_var_g + 1e-8, over the RESIDENT var and S (only read).  The device's log1p is not
+ * the host's to the last bit: a caller that must reproduce a host ordering lists a superset and
+ * orders it itself (SafeOpt._ise_select).  Three HBM-bound passes, the pattern of
+ * sgp_grid_pass_hist / sgp_grid_pass_list; each refuses as sgp_grid_ise does (G of the grid, no
+ * active GP, no current posterior, a GP that is not fitted or lives in another context) with
+ * nothing launched or written.
+ *   sgp_grid_ise_keys: *count = the rows of S in this shard, *key_min / *key_max their
+ *     smallest and largest key (+inf / -inf when there is none).
+ *   sgp_grid_ise_hist: hist[4096] = how many of the shard's safe rows fall into each of 4096
+ *     equal bins over [key_lo, key_hi], bin = int((key - key_lo) * (4096 / (key_hi - key_lo)))
+ *     clamped to 0 .. 4095 (sgp_grid_pass_hist's rule); integer counts, key_hi > key_lo.
+ *   sgp_grid_ise_list: the shard's safe rows with key >= thr in ASCENDING global row, compacted
+ *     by prefix sums (deterministic): gidx[m], key[m] (the device's), x[m][d] and var[m][G] (the
+ *     bits of the resident arrays).  *count = the rows that qualify, even above cap; only the
+ *     first min(*count, cap) are written.                                                    */
+int sgp_grid_ise_keys(sgp_grid* grid, sgp_gp* const* gps, int G, const double* fmin,
+                      int64_t* count, double* key_min, double* key_max);
+int sgp_grid_ise_hist(sgp_grid* grid, sgp_gp* const* gps, int G, const double* fmin,
+                      double key_lo, double key_hi, uint32_t* hist);
+int sgp_grid_ise_list(sgp_grid* grid, sgp_gp* const* gps, int G, const double* fmin, double thr,
+                      int cap, int64_t* count, int64_t* gidx, double* key, double* x,
+                      double* var);
 /* One pick of a batch by hallucinated observations (GP-BUCB, Desautels et al. 2014, on
  * SafeOpt's rule, safeopt/gp_opt.py:635-649; the reference has no batch mode).  gps are CLONES
  * (sgp_gp_clone) of the grid's GPs, every one with the pending pick x* appended

@@ -96,6 +96,17 @@ PROTOTYPES = {
     "sgp_grid_ise": (C.c_int, [vp, vpp, C.c_int, c_double_p, c_i64_p, C.c_int, C.c_int,
                                c_double_p, c_i64_p, c_double_p, c_i64_p, c_double_p,
                                c_double_p]),
+    "sgp_grid_ise_at": (C.c_int, [vp, vpp, C.c_int, c_double_p, c_i64_p, c_double_p, c_double_p,
+                                  C.c_int, C.c_int, c_double_p, c_i64_p, c_double_p, c_i64_p]),
+    "sgp_grid_ise_comm": (C.c_int, [vp, vpp, C.c_int, c_double_p, c_i64_p, c_double_p,
+                                    c_double_p, C.c_int, C.c_int, c_double_p, c_i64_p,
+                                    c_double_p, c_i64_p]),
+    "sgp_grid_ise_keys": (C.c_int, [vp, vpp, C.c_int, c_double_p, c_i64_p, c_double_p,
+                                    c_double_p]),
+    "sgp_grid_ise_hist": (C.c_int, [vp, vpp, C.c_int, c_double_p, C.c_double, C.c_double,
+                                    c_u32_p]),
+    "sgp_grid_ise_list": (C.c_int, [vp, vpp, C.c_int, c_double_p, C.c_double, C.c_int, c_i64_p,
+                                    c_i64_p, c_double_p, c_double_p, c_double_p]),
     "sgp_gp_get_factor": (C.c_int, [vp, c_double_p, c_double_p]),
     "sgp_gp_clone": (C.c_int, [vp, vpp]),
     "sgp_grid_batch_next": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_int, C.c_double,
@@ -1464,6 +1475,66 @@ class DeviceGrid(object):
             dptr(alpha), target.ctypes.data_as(c_i64_p), C.byref(v), C.byref(i),
             None if pr is None else dptr(pr), None if cv is None else dptr(cv)))
         return alpha, target, v.value, i.value, pr, cv
+
+    def ise_at(self, gps, fmin, cand, xc, vx, about=ISE_UNSAFE, comm=False):
+        """``ise`` with the candidates by value (``sgp_grid_ise_at``): ``cand`` global rows of
+        the WHOLE grid, ``xc (K, d)`` their coordinates, ``vx (G, K)`` their variances ->
+        ``(alpha (K,), target (K,), value, global row)`` over this shard's rows.  ``comm``:
+        ``sgp_grid_ise_comm`` -- merged over the shards of all ranks of the context's
+        communicator, the same on every rank; a collective."""
+        fmin = f64(fmin).reshape(-1)
+        cand = np.ascontiguousarray(cand, dtype=np.int64).reshape(-1)
+        K, G = int(cand.size), len(gps)
+        if fmin.size != G:
+            raise ValueError("%d fmin for %d GPs" % (fmin.size, G))
+        xc = f64(xc).reshape(K, self.d)
+        vx = f64(vx).reshape(G, K)
+        alpha = np.empty(K)
+        target = np.empty(K, dtype=np.int64)
+        v, i = C.c_double(0), C.c_int64(0)
+        call = lib().sgp_grid_ise_comm if comm else lib().sgp_grid_ise_at
+        self.ctx.check(call(
+            self.h, _gp_array(gps), G, dptr(fmin), cand.ctypes.data_as(c_i64_p), dptr(xc),
+            dptr(vx), K, int(about), dptr(alpha), target.ctypes.data_as(c_i64_p), C.byref(v),
+            C.byref(i)))
+        return alpha, target, v.value, i.value
+
+    def ise_keys(self, gps, fmin):
+        """``(count, min, max)`` of the keys ``sum_{g active} log1p(var_g / s_g) / 2`` of this
+        shard's safe rows (``sgp_grid_ise_keys``); ``(0, inf, -inf)`` without one."""
+        fmin = f64(fmin).reshape(-1)
+        n, lo, hi = C.c_int64(0), C.c_double(0), C.c_double(0)
+        self.ctx.check(lib().sgp_grid_ise_keys(self.h, _gp_array(gps), len(gps), dptr(fmin),
+                                               C.byref(n), C.byref(lo), C.byref(hi)))
+        return n.value, lo.value, hi.value
+
+    def ise_hist(self, gps, fmin, key_lo, key_hi):
+        """This shard's histogram (4096 bins over [key_lo, key_hi]) of the keys of its safe
+        rows (``sgp_grid_ise_hist``)."""
+        fmin = f64(fmin).reshape(-1)
+        hist = np.zeros(4096, dtype=np.uint32)
+        self.ctx.check(lib().sgp_grid_ise_hist(
+            self.h, _gp_array(gps), len(gps), dptr(fmin), float(key_lo), float(key_hi),
+            hist.ctypes.data_as(c_u32_p)))
+        return hist
+
+    def ise_list(self, gps, fmin, thr, cap):
+        """This shard's safe rows with key >= thr in ascending row (``sgp_grid_ise_list``):
+        ``(count, global rows, device keys, x (m, d), var (m, G))``, ``m = min(count, cap)``:
+        a count above ``cap`` is the caller's to notice."""
+        fmin = f64(fmin).reshape(-1)
+        cap = max(int(cap), 0)
+        room = max(cap, 1)
+        gidx = np.empty(room, dtype=np.int64)
+        key = np.empty(room)
+        x = np.empty((room, self.d))
+        var = np.empty((room, self.G))
+        n = C.c_int64(0)
+        self.ctx.check(lib().sgp_grid_ise_list(
+            self.h, _gp_array(gps), len(gps), dptr(fmin), float(thr), cap, C.byref(n),
+            gidx.ctypes.data_as(c_i64_p), dptr(key), dptr(x), dptr(var)))
+        m = min(n.value, cap)
+        return n.value, gidx[:m], key[:m], x[:m], var[:m]
 
     def download(self, what, out=None):
         if what == Q:

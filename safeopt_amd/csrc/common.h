@@ -202,9 +202,12 @@ enum ScratchSlot : int {
   kSlotMesPart = 25,    // ... per-workgroup (value, row) pairs and floor partials of a grid call,
                         // its records and result (MesScratch)
   kSlotIseIn = 26,      // ise.hip (IseLayout): the candidates' rows | coordinates | variances of a
-                        // grid call; mu | vz | vx | c | out of sgp_ise_eval's rows
+                        // grid call; mu | vz | vx | c | out of sgp_ise_eval's rows; the records
+                        // of sgp_grid_ise_list
   kSlotIseW = 27,       // ... the operands W_g of the active GPs, the workspace T behind them
-  kSlotIsePart = 28,    // ... per-workgroup (pair, row) partials, alpha | target | result
+  kSlotIsePart = 28,    // ... per-workgroup (pair, row) partials, alpha | target | result, the
+                        // ranks' gathered blocks and their merge; the partials, histogram and
+                        // chunk counts of a selection call (IseSelLayout)
   kSlotIseOut = 29,     // ... pairs | cov, the test outputs of a grid call that asks for them
   kScratchSlots
 };

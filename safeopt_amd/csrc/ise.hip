@@ -33,7 +33,20 @@
 //
 // A candidate's W column, its covariances, its pairs, alpha and target depend on the candidate
 // and the rows alone: not on K, not on its position in cand.  (A column of an MFMA's result is
-// a function of that column of B.)
+// a function of that column of B.)  Nor on the shard the rows lie in: sgp_grid_ise_at takes the
+// candidates BY VALUE (global row, coordinates, variances) and runs the same kernels over this
+// shard's rows, and sgp_grid_ise_comm merges the ranks' alpha | target blocks behind one
+// all-gather (k_ise_merge: the largest alpha, the lowest global target among equals) -- the bits
+// of one rank over the whole grid, on every rank.
+//
+// The candidates themselves -- the K safe rows with the largest
+//   key = sum over the active g, in the order of g, of log1p(var_g / s_g) / 2 --
+// are chosen where the variances are, by the pattern of the big passes (sets.hip: k_pass_hist,
+// k_pass_list): sgp_grid_ise_keys (count, min and max of the shard's keys), sgp_grid_ise_hist
+// (kPassBins bins over an agreed range, integer counts) and sgp_grid_ise_list (the safe rows at
+// or above a threshold in ascending row, compacted by prefix sums: deterministic).  Three
+// HBM-bound reads of var and S.  The device's log1p is not NumPy's to the last bit, so the
+// device only ever picks a SUPERSET (SafeOpt._ise_select) and the host orders it exactly.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -329,6 +342,197 @@ __global__ __launch_bounds__(256) void k_ise_pick(const double* alpha, const lon
   }
 }
 
+// ---- candidate selection: the keys of the safe rows ------------------------------------------
+struct IseKeyArgs {
+  const double* var;             // [G][N]
+  const uint8_t* S;
+  int64_t N;
+  int G;
+  unsigned active;
+  double s[SGP_MAX_GPS];         // noise_var + 1e-8
+};
+
+// (built without contraction: a product and a sum, as NumPy forms key + 0.5 * log1p(var / s))
+__device__ __forceinline__ double ise_key(const IseKeyArgs& a, int64_t r) {
+  double key = 0.0;
+  for (int g = 0; g < a.G; ++g)
+    if ((a.active >> g) & 1u) key = key + 0.5 * log1p(a.var[int64_t(g) * a.N + r] / a.s[g]);
+  return key;
+}
+
+constexpr int kIseKeyWg = 1024;               // workgroups of k_ise_keys, at most
+
+// part[b] = {count, min, max} of the keys of the safe rows workgroup b walks
+__global__ __launch_bounds__(256) void k_ise_keys(IseKeyArgs a, double* part) {
+  __shared__ double rc[4], rlo[4], rhi[4];
+  double cnt = 0.0, lo = INFINITY, hi = -INFINITY;      // (a count below 2^53: exact)
+  for (int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x; r < a.N; r += int64_t(gridDim.x) * 256) {
+    if (!a.S[r]) continue;
+    const double key = ise_key(a, r);
+    cnt += 1.0;
+    lo = fmin(lo, key);
+    hi = fmax(hi, key);
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    cnt += __shfl_xor(cnt, o, 64);
+    lo = fmin(lo, __shfl_xor(lo, o, 64));
+    hi = fmax(hi, __shfl_xor(hi, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    rc[threadIdx.x >> 6] = cnt;
+    rlo[threadIdx.x >> 6] = lo;
+    rhi[threadIdx.x >> 6] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[3 * blockIdx.x + 0] = (rc[0] + rc[1]) + (rc[2] + rc[3]);
+    part[3 * blockIdx.x + 1] = fmin(fmin(rlo[0], rlo[1]), fmin(rlo[2], rlo[3]));
+    part[3 * blockIdx.x + 2] = fmax(fmax(rhi[0], rhi[1]), fmax(rhi[2], rhi[3]));
+  }
+}
+
+// One workgroup: out[3] = the fold of the workgroups' {count, min, max}
+__global__ __launch_bounds__(256) void k_ise_keys_final(const double* part, int nwg, double* out) {
+  __shared__ double sc[256], slo[256], shi[256];
+  const int tid = threadIdx.x;
+  double cnt = 0.0, lo = INFINITY, hi = -INFINITY;
+  for (int w = tid; w < nwg; w += 256) {
+    cnt += part[3 * w];
+    lo = fmin(lo, part[3 * w + 1]);
+    hi = fmax(hi, part[3 * w + 2]);
+  }
+  sc[tid] = cnt;
+  slo[tid] = lo;
+  shi[tid] = hi;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) {
+      sc[tid] += sc[tid + o];
+      slo[tid] = fmin(slo[tid], slo[tid + o]);
+      shi[tid] = fmax(shi[tid], shi[tid + o]);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    out[0] = sc[0];
+    out[1] = slo[0];
+    out[2] = shi[0];
+  }
+}
+
+// k_pass_hist's rule (sets.hip): bin = int((key - lo) * (kPassBins / (hi - lo))), clamped
+__global__ __launch_bounds__(256) void k_ise_hist(IseKeyArgs a, double lo, double hi,
+                                                  unsigned* hist) {
+  __shared__ unsigned sh[kPassBins];
+  for (int b = threadIdx.x; b < kPassBins; b += 256) sh[b] = 0;
+  __syncthreads();
+  const double scale = double(kPassBins) / (hi - lo);
+  for (int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x; r < a.N; r += int64_t(gridDim.x) * 256) {
+    if (!a.S[r]) continue;
+    int b = int((ise_key(a, r) - lo) * scale);
+    b = b < 0 ? 0 : (b >= kPassBins ? kPassBins - 1 : b);
+    atomicAdd(&sh[b], 1u);
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < kPassBins; b += 256)
+    if (sh[b]) atomicAdd(&hist[b], sh[b]);
+}
+
+// The list, k_pass_count / k_pass_scan / k_pass_list's way: counts[c] = the rows chunk c (256
+// consecutive rows) lists; their exclusive prefix sum; then every listed row behind its chunk's
+// offset -- ascending row, whatever the order the workgroups run in.
+__device__ __forceinline__ bool ise_take(const IseKeyArgs& a, int64_t r, double thr, double* key) {
+  if (r >= a.N || !a.S[r]) return false;
+  *key = ise_key(a, r);
+  return *key >= thr;
+}
+
+__global__ __launch_bounds__(256) void k_ise_count(IseKeyArgs a, double thr, int* counts) {
+  __shared__ int wc[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t r0 = int64_t(blockIdx.x) * 256; r0 < a.N; r0 += int64_t(gridDim.x) * 256) {
+    double key;
+    const unsigned long long b = __ballot(ise_take(a, r0 + threadIdx.x, thr, &key));
+    if (lane == 0) wc[wave] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) counts[r0 / 256] = (wc[0] + wc[1]) + (wc[2] + wc[3]);
+    __syncthreads();
+  }
+}
+
+// exclusive prefix sum of the chunk counts (in place), the total into *total (k_pass_scan)
+__global__ __launch_bounds__(1024) void k_ise_scan(int* counts, int nchunks, long long* total) {
+  __shared__ int part[1024];
+  __shared__ int carry;
+  const int t = threadIdx.x;
+  if (t == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nchunks; base += 1024) {
+    const int i = base + t;
+    const int v = i < nchunks ? counts[i] : 0;
+    part[t] = v;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+      const int u = (t >= o) ? part[t - o] : 0;
+      __syncthreads();
+      part[t] += u;
+      __syncthreads();
+    }
+    if (i < nchunks) counts[i] = carry + part[t] - v;
+    __syncthreads();
+    if (t == 1023) carry += part[1023];
+    __syncthreads();
+  }
+  if (t == 0) *total = carry;
+}
+
+// rec[p] = {global row (int64), key, x[d], var[G]} of the p-th listed row, p < cap
+__global__ __launch_bounds__(256) void k_ise_fill(IseKeyArgs a, const double* pts, int d,
+                                                  int64_t goff, double thr, const int* offsets,
+                                                  int cap, double* rec) {
+  __shared__ int wc[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int words = 2 + d + a.G;
+  for (int64_t r0 = int64_t(blockIdx.x) * 256; r0 < a.N; r0 += int64_t(gridDim.x) * 256) {
+    const int64_t r = r0 + threadIdx.x;
+    double key = 0.0;
+    const bool take = ise_take(a, r, thr, &key);
+    const unsigned long long b = __ballot(take);
+    if (lane == 0) wc[wave] = __popcll(b);
+    __syncthreads();
+    int at = offsets[r0 / 256];
+    for (int q = 0; q < wave; ++q) at += wc[q];
+    at += __popcll(b & ((1ull << lane) - 1ull));
+    if (take && at < cap) {
+      double* o = rec + int64_t(at) * words;
+      reinterpret_cast<long long*>(o)[0] = goff + r;
+      o[1] = key;
+      for (int k = 0; k < d; ++k) o[2 + k] = pts[int64_t(k) * a.N + r];
+      for (int g = 0; g < a.G; ++g) o[2 + d + g] = a.var[int64_t(g) * a.N + r];
+    }
+    __syncthreads();
+  }
+}
+
+// The ranks' alpha | target blocks ([world][2][Kp], in rank order) -> the whole grid's:
+// per candidate the largest alpha, the lowest GLOBAL target among equals; a rank without a
+// target (-inf / -1) never wins, none on any rank gives -inf / -1.
+__global__ __launch_bounds__(256) void k_ise_merge(const double* recs, int world, int K, int Kp,
+                                                   double* alpha, long long* target) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= K) return;
+  double v = -INFINITY;
+  long long i = kNoRow;
+  for (int r = 0; r < world; ++r) {
+    const double* blk = recs + int64_t(r) * 2 * Kp;
+    const long long t = reinterpret_cast<const long long*>(blk + Kp)[j];
+    if (t >= 0) take_better(v, i, blk[j], t);
+  }
+  alpha[j] = i == kNoRow ? -INFINITY : v;
+  target[j] = i == kNoRow ? -1 : i;
+}
+
 #define ISE_DISPATCH(d, call)                                                      \
   switch (d) {                                                                     \
     case 1: call(1); break;                                                        \
@@ -350,13 +554,17 @@ inline unsigned ise_blocks(int64_t N) { return unsigned((N + kIseThreads - 1) / 
 //   kSlotIseIn:   idx[Kp] (int64, local rows) | xc[Kp][d] | vx[G][Kp]
 //   kSlotIseW:    W_g[n_pad_g][Kp] of every active GP, one after the other | T[n_max][Kp]
 //   kSlotIsePart: pval[nwg][Kp] | pidx[nwg][Kp] | alpha[Kp] | target[Kp] | res[2]
+//                 | recs[world][2][Kp] | malpha[Kp] | mtarget[Kp] | mres[2]
+//                 (world ranks of sgp_grid_ise_comm, 0 otherwise: the gathered alpha | target
+//                 blocks and their merge, read back in one piece like alpha | target | res)
 //   kSlotIseOut:  pairs[K][N] | cov[G][K][N]   (the test outputs, when asked for)
 struct IseLayout {
   size_t idx, xc, vx, in_words;
   size_t w[SGP_MAX_GPS], t, w_words;
-  size_t pval, pidx, alpha, target, res, part_words;
+  size_t pval, pidx, alpha, target, res, recs, malpha, mtarget, mres, part_words;
 };
-IseLayout ise_layout(const GpDev* host, int G, unsigned active, int d, int Kp, int nwg) {
+IseLayout ise_layout(const GpDev* host, int G, unsigned active, int d, int Kp, int nwg,
+                     int world) {
   IseLayout l{};
   l.idx = 0;
   l.xc = l.idx + size_t(Kp);
@@ -376,8 +584,57 @@ IseLayout ise_layout(const GpDev* host, int G, unsigned active, int d, int Kp, i
   l.alpha = l.pidx + size_t(nwg) * Kp;
   l.target = l.alpha + size_t(Kp);
   l.res = l.target + size_t(Kp);
-  l.part_words = l.res + 2;
+  l.recs = l.res + 2;
+  l.malpha = l.recs + size_t(world) * 2 * Kp;
+  l.mtarget = l.malpha + size_t(Kp);
+  l.mres = l.mtarget + size_t(Kp);
+  l.part_words = world ? l.mres + 2 : l.recs;
   return l;
+}
+
+// The scratch of a selection call, in kSlotIsePart (doubles):
+//   part[kIseKeyWg][3] | out[3] | total (int64) | hist[kPassBins] (u32) | counts[N / 256 + 2] (i32)
+struct IseSelLayout {
+  size_t part, out, total, hist, counts, words;
+};
+IseSelLayout ise_sel_layout(int64_t N) {
+  IseSelLayout l{};
+  l.part = 0;
+  l.out = l.part + 3 * size_t(kIseKeyWg);
+  l.total = l.out + 3;
+  l.hist = l.total + 1;
+  l.counts = l.hist + kPassBins / 2;
+  l.words = l.counts + (size_t(N / 256 + 2) + 1) / 2;
+  return l;
+}
+
+// The refusals the selection entry points share with sgp_grid_ise, before anything is launched
+// or written; fills the key arguments.
+int ise_key_args(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, IseKeyArgs* a) {
+  sgp_ctx* ctx = g->ctx;
+  SGP_CHECK(ctx, gps && fmin, "gps and fmin are required");
+  SGP_CHECK(ctx, G >= 1 && G <= SGP_MAX_GPS && G == g->G, "grid was created for %d GPs, got %d",
+            g->G, G);
+  unsigned active = 0;
+  for (int q = 0; q < G; ++q)
+    if (std::isfinite(fmin[q])) active |= 1u << q;
+  SGP_CHECK(ctx, active != 0, "no GP is active: every fmin is infinite or NaN");
+  SGP_CHECK(ctx, g->post_valid,
+            "the grid holds no current posterior: run a confidence pass (sgp_grid_confidence "
+            "/ sgp_grid_posterior) first");
+  GpDev host[SGP_MAX_GPS];
+  SGP_TRY(grid_gps(g, gps, G, host));
+  a->var = g->var;
+  a->S = g->S;
+  a->N = g->N;
+  a->G = G;
+  a->active = active;
+  for (int q = 0; q < G; ++q) a->s[q] = gps[q]->noise_var + 1e-8;
+  return 0;
+}
+
+inline unsigned ise_key_blocks(int64_t N) {
+  return unsigned(std::min<int64_t>((N + 255) / 256, kIseKeyWg));
 }
 
 }  // namespace
@@ -405,9 +662,18 @@ int sgp_ise_eval(sgp_ctx* ctx, const double* mu, const double* vz, const double*
   return 0;
 }
 
-int sgp_grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, const int64_t* cand,
-                 int K, int about, double* alpha, int64_t* target, double* value, int64_t* gidx,
-                 double* pairs, double* cov) {
+namespace {
+
+// The body of sgp_grid_ise, sgp_grid_ise_at and sgp_grid_ise_comm: the same operand kernels,
+// k_ise_rows, k_ise_final and k_ise_pick.  by_value: the candidates' coordinates xc_host [K][d]
+// and variances vx_host [G][K] come from the host and cand holds GLOBAL rows of the whole grid,
+// read by the pick's tie rule and returned, nothing else; otherwise cand are rows of this shard
+// and both are gathered from the resident arrays.  merge: the ranks' alpha | target blocks are
+// all-gathered and merged in the grid's stream before the pick (a collective).
+int grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, const int64_t* cand,
+             int K, int about, bool by_value, const double* xc_host, const double* vx_host,
+             double* alpha, int64_t* target, double* value, int64_t* gidx, double* pairs,
+             double* cov, bool merge) {
   sgp_ctx* ctx = g->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   // ---- every refusal before anything is launched, staged or written
@@ -417,13 +683,19 @@ int sgp_grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, con
             "about = %d is not SGP_ISE_UNSAFE / SGP_ISE_ALL", about);
   SGP_CHECK(ctx, gps && fmin && cand && alpha && target && value && gidx,
             "gps, fmin, cand, alpha, target, value and gidx are required");
+  SGP_CHECK(ctx, !by_value || (xc_host && vx_host), "xc and vx are required");
   SGP_CHECK(ctx, G >= 1 && G <= SGP_MAX_GPS && G == g->G, "grid was created for %d GPs, got %d",
             g->G, G);
   const int64_t N = g->N;
-  for (int j = 0; j < K; ++j)
-    SGP_CHECK(ctx, cand[j] >= g->goff && cand[j] < g->goff + N,
-              "candidate %d = row %lld is outside the shard [%lld, %lld)", j, (long long)cand[j],
-              (long long)g->goff, (long long)(g->goff + N));
+  const int64_t goff = by_value ? 0 : g->goff;       // what the candidates' rows are relative to
+  for (int j = 0; j < K; ++j) {
+    if (by_value)
+      SGP_CHECK(ctx, cand[j] >= 0, "candidate %d = row %lld is negative", j, (long long)cand[j]);
+    else
+      SGP_CHECK(ctx, cand[j] >= g->goff && cand[j] < g->goff + N,
+                "candidate %d = row %lld is outside the shard [%lld, %lld)", j,
+                (long long)cand[j], (long long)g->goff, (long long)(g->goff + N));
+  }
   unsigned active = 0;
   for (int q = 0; q < G; ++q)
     if (std::isfinite(fmin[q])) active |= 1u << q;
@@ -442,7 +714,10 @@ int sgp_grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, con
   const int Kp = (K + kIseCols - 1) / kIseCols * kIseCols;
   const int64_t ntiles = (N + kIseRows - 1) / kIseRows;
   const int nwg = int(std::min<int64_t>(ntiles, kIseMaxWg));
-  const IseLayout l = ise_layout(host, G, active, d, Kp, nwg);
+  bool comm = false;
+  if (merge) SGP_TRY(comm_or_single(ctx, &comm));
+  const int world = comm ? ctx->world : 0;
+  const IseLayout l = ise_layout(host, G, active, d, Kp, nwg, world);
   double *in, *wbuf, *part, *outb = nullptr;
   SGP_TRY(sgp_scratch(ctx, kSlotIseIn, l.in_words * 8, &in));
   SGP_TRY(sgp_scratch(ctx, kSlotIseW, l.w_words * 8, &wbuf));
@@ -451,15 +726,25 @@ int sgp_grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, con
   const size_t cov_words = cov ? size_t(G) * K * N : 0;
   if (pairs || cov) SGP_TRY(sgp_scratch(ctx, kSlotIseOut, (pair_words + cov_words) * 8, &outb));
 
-  // ---- candidates: local rows up, coordinates and variances gathered on the device
-  std::vector<int64_t> idx(size_t(Kp), 0);
-  for (int j = 0; j < K; ++j) idx[j] = cand[j] - g->goff;
   int64_t* idx_dev = reinterpret_cast<int64_t*>(in + l.idx);
-  SGP_TRY(sgp_h2d(ctx, idx_dev, idx.data(), size_t(Kp) * 8));
-  SGP_HIP(ctx, hipMemsetAsync(in + l.xc, 0, (l.in_words - l.xc) * 8, ctx->stream));
-  hipLaunchKernelGGL(k_ise_gather, dim3(unsigned((K + 255) / 256)), dim3(256), 0, ctx->stream,
-                     g->pts, g->var, N, d, G, idx_dev, K, Kp, in + l.xc, in + l.vx);
-  SGP_HIP(ctx, hipGetLastError());
+  if (by_value) {
+    // ---- candidates by value: the whole block idx | xc | vx in one upload, zero in the padding
+    std::vector<double> blk(l.in_words, 0.0);
+    for (int j = 0; j < K; ++j) memcpy(&blk[l.idx + j], &cand[j], 8);
+    memcpy(&blk[l.xc], xc_host, size_t(K) * d * 8);
+    for (int q = 0; q < G; ++q)
+      memcpy(&blk[l.vx + size_t(q) * Kp], vx_host + size_t(q) * K, size_t(K) * 8);
+    SGP_TRY(sgp_h2d(ctx, in, blk.data(), l.in_words * 8));
+  } else {
+    // ---- candidates: local rows up, coordinates and variances gathered on the device
+    std::vector<int64_t> idx(size_t(Kp), 0);
+    for (int j = 0; j < K; ++j) idx[j] = cand[j] - g->goff;
+    SGP_TRY(sgp_h2d(ctx, idx_dev, idx.data(), size_t(Kp) * 8));
+    SGP_HIP(ctx, hipMemsetAsync(in + l.xc, 0, (l.in_words - l.xc) * 8, ctx->stream));
+    hipLaunchKernelGGL(k_ise_gather, dim3(unsigned((K + 255) / 256)), dim3(256), 0, ctx->stream,
+                       g->pts, g->var, N, d, G, idx_dev, K, Kp, in + l.xc, in + l.vx);
+    SGP_HIP(ctx, hipGetLastError());
+  }
 
   // ---- operands: W_g = L^-T (L^-1 k_g(X, x_j)), [n_pad][Kp], zero in the padding
   SGP_HIP(ctx, hipMemsetAsync(wbuf, 0, l.t * 8, ctx->stream));
@@ -518,8 +803,18 @@ int sgp_grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, con
   long long* target_dev = reinterpret_cast<long long*>(part + l.target);
   hipLaunchKernelGGL(k_ise_final, dim3(unsigned(K)), dim3(256), 0, ctx->stream, a.pval, a.pidx,
                      nwg, Kp, g->goff, alpha_dev, target_dev);
+  SGP_HIP(ctx, hipGetLastError());
+  if (comm) {
+    // the ranks' alpha | target blocks (contiguous, 2 Kp words), merged candidate by candidate
+    SGP_TRY(coll_allgather(ctx, alpha_dev, part + l.recs, 2 * size_t(Kp) * 8));
+    alpha_dev = part + l.malpha;
+    target_dev = reinterpret_cast<long long*>(part + l.mtarget);
+    hipLaunchKernelGGL(k_ise_merge, dim3(unsigned((K + 255) / 256)), dim3(256), 0, ctx->stream,
+                       part + l.recs, world, K, Kp, alpha_dev, target_dev);
+  }
+  // (alpha | target | res and malpha | mtarget | mres are laid out alike)
   hipLaunchKernelGGL(k_ise_pick, dim3(1), dim3(256), 0, ctx->stream, alpha_dev, target_dev,
-                     idx_dev, K, g->goff, part + l.res);
+                     idx_dev, K, goff, alpha_dev + 2 * size_t(Kp));
   SGP_HIP(ctx, hipGetLastError());
   // one read-back of alpha | target | {value, gidx}: contiguous in the block
   std::vector<double> h(2 * size_t(Kp) + 2);
@@ -530,5 +825,119 @@ int sgp_grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, con
   memcpy(gidx, &h[2 * size_t(Kp) + 1], 8);
   if (pairs) SGP_TRY(sgp_d2h(ctx, pairs, a.pairs, pair_words * 8));
   if (cov) SGP_TRY(sgp_d2h(ctx, cov, a.cov, cov_words * 8));
+  return 0;
+}
+
+}  // namespace
+
+int sgp_grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, const int64_t* cand,
+                 int K, int about, double* alpha, int64_t* target, double* value, int64_t* gidx,
+                 double* pairs, double* cov) {
+  return grid_ise(g, gps, G, fmin, cand, K, about, false, nullptr, nullptr, alpha, target, value,
+                  gidx, pairs, cov, false);
+}
+
+int sgp_grid_ise_at(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin,
+                    const int64_t* cand, const double* xc, const double* vx, int K, int about,
+                    double* alpha, int64_t* target, double* value, int64_t* gidx) {
+  return grid_ise(g, gps, G, fmin, cand, K, about, true, xc, vx, alpha, target, value, gidx,
+                  nullptr, nullptr, false);
+}
+
+int sgp_grid_ise_comm(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin,
+                      const int64_t* cand, const double* xc, const double* vx, int K, int about,
+                      double* alpha, int64_t* target, double* value, int64_t* gidx) {
+  return grid_ise(g, gps, G, fmin, cand, K, about, true, xc, vx, alpha, target, value, gidx,
+                  nullptr, nullptr, true);
+}
+
+// ---- candidate selection ------------------------------------------------------------------------
+int sgp_grid_ise_keys(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, int64_t* count,
+                      double* key_min, double* key_max) {
+  sgp_ctx* ctx = g->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, count && key_min && key_max, "count, key_min and key_max are required");
+  IseKeyArgs a{};
+  SGP_TRY(ise_key_args(g, gps, G, fmin, &a));
+  const IseSelLayout l = ise_sel_layout(g->N);
+  double* w;
+  SGP_TRY(sgp_scratch(ctx, kSlotIsePart, l.words * 8, &w));
+  const unsigned nwg = ise_key_blocks(g->N);
+  hipLaunchKernelGGL(k_ise_keys, dim3(nwg), dim3(256), 0, ctx->stream, a, w + l.part);
+  hipLaunchKernelGGL(k_ise_keys_final, dim3(1), dim3(256), 0, ctx->stream, w + l.part, int(nwg),
+                     w + l.out);
+  SGP_HIP(ctx, hipGetLastError());
+  double h[3];
+  SGP_TRY(sgp_d2h(ctx, h, w + l.out, sizeof(h)));
+  *count = int64_t(h[0]);
+  *key_min = h[1];
+  *key_max = h[2];
+  return 0;
+}
+
+int sgp_grid_ise_hist(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, double key_lo,
+                      double key_hi, uint32_t* hist) {
+  sgp_ctx* ctx = g->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, hist, "hist is required");
+  SGP_CHECK(ctx, std::isfinite(key_lo) && std::isfinite(key_hi) && key_hi > key_lo,
+            "empty key range %g .. %g", key_lo, key_hi);
+  IseKeyArgs a{};
+  SGP_TRY(ise_key_args(g, gps, G, fmin, &a));
+  const IseSelLayout l = ise_sel_layout(g->N);
+  double* w;
+  SGP_TRY(sgp_scratch(ctx, kSlotIsePart, l.words * 8, &w));
+  unsigned* hist_dev = reinterpret_cast<unsigned*>(w + l.hist);
+  SGP_HIP(ctx, hipMemsetAsync(hist_dev, 0, kPassBins * sizeof(unsigned), ctx->stream));
+  hipLaunchKernelGGL(k_ise_hist, dim3(ise_key_blocks(g->N)), dim3(256), 0, ctx->stream, a, key_lo,
+                     key_hi, hist_dev);
+  SGP_HIP(ctx, hipGetLastError());
+  return sgp_d2h(ctx, hist, hist_dev, kPassBins * sizeof(uint32_t));
+}
+
+int sgp_grid_ise_list(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, double thr,
+                      int cap, int64_t* count, int64_t* gidx, double* key, double* x,
+                      double* var) {
+  sgp_ctx* ctx = g->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, count, "count is required");
+  SGP_CHECK(ctx, cap >= 0 && (cap == 0 || (gidx && key && x && var)),
+            "cap = %d rows need gidx, key, x and var", cap);
+  SGP_CHECK(ctx, !std::isnan(thr), "the threshold is NaN");
+  SGP_CHECK(ctx, g->N < (int64_t(1) << 31), "%lld rows", (long long)g->N);
+  IseKeyArgs a{};
+  SGP_TRY(ise_key_args(g, gps, G, fmin, &a));
+  const int64_t N = g->N;
+  const int d = g->d, words = 2 + d + G;
+  const IseSelLayout l = ise_sel_layout(N);
+  double *w, *rec = nullptr;
+  SGP_TRY(sgp_scratch(ctx, kSlotIsePart, l.words * 8, &w));
+  // (at most min(cap, N) records are written, whatever the count)
+  const int room = int(std::min<int64_t>(cap, N));
+  if (room) SGP_TRY(sgp_scratch(ctx, kSlotIseIn, size_t(room) * words * 8, &rec));
+  int* counts = reinterpret_cast<int*>(w + l.counts);
+  long long* total = reinterpret_cast<long long*>(w + l.total);
+  const int nchunks = int((N + 255) / 256);
+  const unsigned nb = unsigned(std::min(nchunks, 2048));
+  hipLaunchKernelGGL(k_ise_count, dim3(nb), dim3(256), 0, ctx->stream, a, thr, counts);
+  hipLaunchKernelGGL(k_ise_scan, dim3(1), dim3(1024), 0, ctx->stream, counts, nchunks, total);
+  if (room)
+    hipLaunchKernelGGL(k_ise_fill, dim3(nb), dim3(256), 0, ctx->stream, a, g->pts, d, g->goff,
+                       thr, counts, room, rec);
+  SGP_HIP(ctx, hipGetLastError());
+  long long n = 0;
+  SGP_TRY(sgp_d2h(ctx, &n, total, 8));
+  *count = n;
+  const size_t m = size_t(std::min<long long>(n, room));
+  if (m == 0) return 0;
+  std::vector<double> host(m * words);
+  SGP_TRY(sgp_d2h(ctx, host.data(), rec, host.size() * 8));
+  for (size_t p = 0; p < m; ++p) {
+    const double* r = &host[p * words];
+    memcpy(&gidx[p], r, 8);
+    key[p] = r[1];
+    memcpy(x + p * d, r + 2, size_t(d) * 8);
+    memcpy(var + p * G, r + 2 + d, size_t(G) * 8);
+  }
   return 0;
 }

@@ -24,7 +24,7 @@ import numpy as np
 
 __all__ = ["shard_range", "allgather_rows", "LocalComm", "RcclComm", "SocketComm", "init_from_env",
            "merge_topk", "merge_argmax", "merge_path_records", "merge_batch_records",
-           "merge_mes_records",
+           "merge_mes_records", "merge_ise_records", "pick_ise",
            "gather_shard_columns", "check_same_paths", "check_same_maxima",
            "launch_check"]
 
@@ -549,3 +549,26 @@ def merge_mes_records(records):
     Returns ``(value, global row)``."""
     records = np.asarray(records, dtype=np.float64).reshape(-1, 2)
     return merge_argmax(records[:, 0], records[:, 1].astype(np.int64))
+
+
+def merge_ise_records(alphas, targets):
+    """The candidates' ``alpha`` and ``target`` of a sharded ``ise_point`` from the ranks'
+    ``(world, K)`` blocks -- what ``sgp_grid_ise_at`` returns on every shard, -inf / -1 where
+    none of a shard's rows qualifies as ``z`` -- merged candidate by candidate with
+    :func:`merge_argmax` (the host form of ``k_ise_merge``): the largest alpha, the lowest
+    global target among equals, a rank without a target never wins, none on any rank gives
+    -inf / -1.  Returns ``(alpha (K,), target (K,) int64)``."""
+    alphas = np.asarray(alphas, dtype=np.float64)
+    targets = np.asarray(targets, dtype=np.int64)
+    K = alphas.shape[1]
+    al, tg = np.empty(K), np.empty(K, dtype=np.int64)
+    for j in range(K):
+        al[j], tg[j] = merge_argmax(alphas[:, j], targets[:, j])
+    return al, tg
+
+
+def pick_ise(alpha, target, rows):
+    """The pick of ``k_ise_pick`` on the host: ``(value, global row)`` of the candidate with the
+    largest ``alpha``, the lowest row of ``rows`` among equals; a candidate without a target
+    never, ``(-inf, -1)`` when there is none."""
+    return merge_argmax(alpha, np.where(np.asarray(target) >= 0, rows, -1))

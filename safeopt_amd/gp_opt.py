@@ -33,8 +33,8 @@ import numpy as np
 from . import _hip
 from .dist import (LocalComm, allgather_rows, check_same_maxima, check_same_paths,
                    gather_shard_columns,
-                   merge_argmax, merge_batch_records, merge_mes_records, merge_path_records,
-                   merge_topk, shard_range)
+                   merge_argmax, merge_batch_records, merge_ise_records, merge_mes_records,
+                   merge_path_records, merge_topk, pick_ise, shard_range)
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
 
 __all__ = ['SafeOpt', 'SafeOptSwarm']
@@ -631,6 +631,39 @@ class _HipGridBackend(object):
         al, tg, v, i, pr, _ = self.grid.ise(self._dev(), fmin, cand, about=about, pairs=pairs)
         return al, tg, v, i, pr
 
+    def ise_at(self, fmin, cand, xc, vx, about, comm=False):
+        """``ise`` with the candidates by value -- global rows of the WHOLE grid, their
+        coordinates ``(K, d)`` and variances ``(G, K)`` -- over this shard's rows
+        (``DeviceGrid.ise_at``): ``(alpha (K,), target (K,), value, global row)``.  ``comm``:
+        merged over the ranks in the grid's stream (``sgp_grid_ise_comm``), a collective."""
+        if not self.posterior_is_current():
+            self.refresh_posterior()
+        return self.grid.ise_at(self._dev(), fmin, cand, xc, vx, about=about, comm=comm)
+
+    # candidate selection of ise_point where the variances are (SafeOpt._ise_select)
+    def ise_keys(self, fmin):
+        """``(count, min key, max key)`` of this shard's safe rows; the posterior is swept
+        first when it is not that of the GPs as they are."""
+        if not self.posterior_is_current():
+            self.refresh_posterior()
+        return self.grid.ise_keys(self._dev(), fmin)
+
+    def ise_hist(self, fmin, key_lo, key_hi):
+        return self.grid.ise_hist(self._dev(), fmin, key_lo, key_hi)
+
+    def ise_list(self, fmin, thr, cap):
+        return self.grid.ise_list(self._dev(), fmin, thr, cap)
+
+    def ise_noise(self):
+        """``s_g = noise_var_g + 1e-8`` of the GPs, ``(G,)``."""
+        return np.array([float(g.noise_var) + 1e-8 for g in self.gps])
+
+    def ise_safe(self, gidx):
+        """Which of the global rows ``gidx`` OF THIS SHARD are in ``S`` as it stands on the
+        device."""
+        S = np.array(self.grid.download(_hip.S), dtype=bool)
+        return S[np.asarray(gidx, dtype=np.int64) - self.lo]
+
 
 def ise_candidates(var, S, s, active, K):
     """The candidate rows of ``SafeOpt.ise_point``: the ``min(K, |S|)`` rows of ``S`` with the
@@ -648,6 +681,49 @@ def ise_candidates(var, S, s, active, K):
         ids, key = ids[keep], key[keep]
     order = np.lexsort((ids, -key))[:K]
     return ids[order].astype(np.int64)
+
+
+#: Bound on |device key - NumPy key| of an ``ise_point`` candidate, in units of ``max(1, largest
+#: key)``, the rounding of the histogram's bin edges included: 64 ulp.  A term ``log1p(var / s) /
+#: 2`` has the same quotient on both sides, a ``log1p`` within 2 ulp (device) and 1 ulp (host) of
+#: the truth and an exact halving; the in-order sum over at most ``SGP_MAX_GPS`` = 8 such terms
+#: adds half an ulp of the running sum per addition on either side -- below 3 + 8 ulp of the
+#: key together, and the two roundings of ``(key - lo) * scale`` at a bin edge are 2 more.
+#: tests/test_gpu_ise_select.py measures the key error and holds it below a quarter of this.
+ISE_KEY_EPS = 2.0 ** -46
+ISE_BINS = 4096
+
+
+def ise_list_cap(K):
+    """Rows the device selection of ``ise_point`` may list for ``K`` candidates before the host
+    selection takes over (masses of equal keys)."""
+    return 4 * int(K) + 4096
+
+
+def ise_threshold(hist, want, lo, hi, nbins=ISE_BINS):
+    """``(thr, listed)``: the key from which the candidates are listed and how many the
+    histogram ``hist`` (``nbins`` bins over ``[lo, hi]``, summed over the ranks) counts there.
+    ``b`` is the highest bin at which the count from the top reaches ``want``; the list starts
+    at the lower edge of bin ``b - 1`` (``-inf`` for ``b <= 1``: everything).  With a bin wider
+    than ``2 eps``, ``eps`` bounding |device key - host key|: at least ``want`` rows have a
+    device key in the bins from ``b`` up, so a host key ``>= edge_b - eps``; the ``want``-th
+    largest HOST key is therefore ``>= edge_b - eps``, every row at or above it -- its ties
+    included -- has a device key ``>= edge_b - 2 eps >= edge_(b-1)`` and is listed."""
+    from_top = np.cumsum(np.asarray(hist, dtype=np.float64)[::-1])
+    b = nbins - 1 - int(np.argmax(from_top >= want))
+    if b <= 1:
+        return -np.inf, int(from_top[-1])
+    return lo + (hi - lo) * (float(b - 1) / nbins), int(from_top[nbins - b])
+
+
+def ise_order(gidx, var, s, active, K):
+    """The exact ordering behind a device selection: positions, in pick order, of the
+    ``min(K, m)`` listed rows (``gidx (m,)`` ascending, ``var (m, G)`` their resident variances)
+    that ``ise_candidates`` takes -- NumPy keys, largest first, the lower row first among
+    equals."""
+    assert np.all(np.diff(gidx) > 0)
+    return ise_candidates(np.ascontiguousarray(var.T), np.ones(gidx.size, dtype=bool), s, active,
+                          K)
 
 
 class SafeOpt(GaussianProcessOptimization):
@@ -1798,12 +1874,9 @@ class SafeOpt(GaussianProcessOptimization):
         last two ``-inf`` / ``-1`` when no row qualifies as ``z``."""
         if about not in ('unsafe', 'all'):
             raise ValueError("about must be 'unsafe' or 'all', got %r" % (about,))
-        if self._comm.world > 1:
-            raise NotImplementedError(
-                "ise_point runs on one rank (this communicator has %d)" % self._comm.world)
-        if not (hasattr(self._backend, 'ise') and hasattr(self._backend, 'ise_state')):
-            raise NotImplementedError(
-                "this grid backend runs no information-theoretic safe exploration")
+        self._ise_guard()
+        be, comm = self._backend, self._comm
+        world = comm.world
         fmin = np.asarray(self.fmin, dtype=float).reshape(-1)
         active = np.isfinite(fmin)
         if not active.any():
@@ -1825,17 +1898,155 @@ class SafeOpt(GaussianProcessOptimization):
                 raise ValueError("candidate rows outside 0 .. %d" % (self.inputs.shape[0] - 1))
         self._flush_Q()
         self._flush_masks()
-        var, S, s = self._backend.ise_state()
-        if not S.any():
-            raise RuntimeError('There are no safe points to sample in.')
-        if by_count:
-            rows = ise_candidates(var, S, s, active, K)
-        elif not np.all(S[rows]):
-            raise ValueError("candidate rows outside the safe set: %r"
-                             % (rows[~S[rows]][:8].tolist(),))
         code = _hip.ISE_UNSAFE if about == 'unsafe' else _hip.ISE_ALL
-        values, targets, alpha, idx = self._backend.ise(fmin, rows, code)[:4]
+        on_device = all(hasattr(be, f) for f in ('ise_keys', 'ise_hist', 'ise_list'))
+        self._ise_path = 'host'
+        if world == 1:
+            picked = self._ise_select(K, fmin, active) if by_count and on_device else None
+            if picked is not None:
+                rows = picked[0]
+            else:
+                var, S, s = be.ise_state()
+                if not S.any():
+                    raise RuntimeError('There are no safe points to sample in.')
+                if by_count:
+                    rows = ise_candidates(var, S, s, active, K)
+                elif not np.all(S[rows]):
+                    raise ValueError("candidate rows outside the safe set: %r"
+                                     % (rows[~S[rows]][:8].tolist(),))
+            values, targets, alpha, idx = be.ise(fmin, rows, code)[:4]
+            return rows, values, targets, alpha, idx
+        # ---- N ranks: the same candidates, by value, on every rank
+        if by_count:
+            picked = self._ise_select(K, fmin, active)
+            rows, xc, vx = picked if picked is not None else self._ise_select_host(K, active)
+        else:
+            xc, vx = self._ise_rows_by_value(rows, fmin)
+        if getattr(comm, 'in_stream', False):
+            values, targets, alpha, idx = be.ise_at(fmin, rows, xc, vx, code, comm=True)
+        else:
+            al, tg = be.ise_at(fmin, rows, xc, vx, code)[:2]
+            rec = comm.allgather(np.stack([al, tg.astype(np.float64)]))   # (rows < 2^53)
+            values, targets = merge_ise_records(rec[:, 0], rec[:, 1].astype(np.int64))
+            alpha, idx = pick_ise(values, targets, rows)
         return rows, values, targets, alpha, idx
+
+    def _ise_guard(self):
+        """What ``ise_point`` / ``info_point`` need of communicator and backend, before
+        anything runs."""
+        comm, be = self._comm, self._backend
+        if comm.world > 1 and not all(callable(getattr(comm, f, None))
+                                      for f in ('allreduce_max', 'allgather')):
+            raise NotImplementedError(
+                "ise_point runs on one rank with this communicator: on its %d ranks the "
+                "candidates and the ranks' picks are agreed on through allreduce_max and "
+                "allgather, and it implements neither" % comm.world)
+        if not (hasattr(be, 'ise') and hasattr(be, 'ise_state')):
+            raise NotImplementedError(
+                "this grid backend runs no information-theoretic safe exploration")
+        if comm.world > 1 and not all(hasattr(be, f) for f in ('ise_at', 'ise_keys', 'ise_hist',
+                                                               'ise_list', 'ise_safe')):
+            raise NotImplementedError(
+                "this grid backend runs information-theoretic safe exploration on one rank "
+                "only (this communicator has %d)" % comm.world)
+
+    def _ise_safe_count(self, fmin):
+        """``(|S|, smallest key, largest key)`` over all ranks, the same on every rank."""
+        comm = self._comm
+        n, lo, hi = self._backend.ise_keys(fmin)
+        if comm.world > 1:
+            red = comm.allreduce_max(np.array([-lo, hi]))
+            lo, hi = -float(red[0]), float(red[1])
+            n = int(comm.allgather(np.array([float(n)])).sum())
+        return n, lo, hi
+
+    def _ise_select(self, K, fmin, active):
+        """The candidates of ``ise_point(candidates=K)``, chosen where the variances are:
+        ``(rows (min(K, |S|),), x (.., d), var (G, ..))`` -- what ``ise_candidates`` returns on
+        the downloaded state, on every rank -- or ``None`` when the host selection has to take
+        over (``self._ise_path`` says why).  The device only ever picks a SUPERSET
+        (``ise_threshold``): the ranks agree on count and range of the keys
+        (``sgp_grid_ise_keys``), sum their histograms (``sgp_grid_ise_hist``), take ONE
+        threshold, list the rows above it (``sgp_grid_ise_list``) and gather the lists; the
+        host orders the few listed rows exactly, from the NumPy keys of their variances
+        (``ise_order``).  ``RuntimeError`` on every rank when no row is safe."""
+        be, comm = self._backend, self._comm
+        world = comm.world
+        n, lo, hi = self._ise_safe_count(fmin)
+        if n == 0:
+            raise RuntimeError('There are no safe points to sample in.')
+        eps = ISE_KEY_EPS * max(1.0, hi)
+        if not hi - lo >= ISE_BINS * 2.0 * eps:
+            self._ise_path = 'host: degenerate key range'
+            return None
+        hist = be.ise_hist(fmin, lo, hi).astype(np.float64)
+        if world > 1:
+            hist = comm.allgather(hist).sum(axis=0)
+        thr, listed = ise_threshold(hist, min(K, n), lo, hi)
+        if listed > ise_list_cap(K):
+            self._ise_path = 'host: list above the cap'
+            return None
+        # (rounding at the edge can move a few rows across it: room for them, as in
+        # _pass_n_ranks; a count above the room is seen and handed to the host)
+        room = listed + 64
+        count, gi, _key, x, var = be.ise_list(fmin, thr, room)
+        if world > 1:
+            counts = comm.allgather(np.array([float(count)]))[:, 0]
+            if counts.max() > room:
+                self._ise_path = 'host: list above the cap'
+                return None
+            part = np.empty((gi.size, 1 + x.shape[1] + var.shape[1]))
+            part[:, 0], part[:, 1:1 + x.shape[1]] = gi, x               # (rows < 2^53)
+            part[:, 1 + x.shape[1]:] = var
+            part = allgather_rows(comm, part, counts=counts)
+            d = x.shape[1]
+            gi, x, var = part[:, 0].astype(np.int64), part[:, 1:1 + d], part[:, 1 + d:]
+            count = gi.size
+        if count > room or count < min(K, n):
+            self._ise_path = 'host: list above the cap' if count > room else 'host: short list'
+            return None
+        at = ise_order(gi, var, be.ise_noise(), active, K)
+        self._ise_path = 'device'
+        return gi[at], np.ascontiguousarray(x[at]), np.ascontiguousarray(var[at].T)
+
+    def _ise_select_host(self, K, active):
+        """``_ise_select``'s result by the host selection on N ranks: the shards' variances
+        and ``S`` gathered, ``ise_candidates`` on every rank."""
+        be, comm = self._backend, self._comm
+        N = self.inputs.shape[0]
+        var, S, s = be.ise_state()
+        var = gather_shard_columns(comm, var, N)
+        S = gather_shard_columns(comm, S[None, :].astype(np.float64), N)[0] > 0
+        rows = ise_candidates(var, S, s, active, K)
+        x = self._ise_rows_by_value(rows, None)[0]
+        return rows, x, np.ascontiguousarray(var[:, rows])
+
+    def _ise_rows_by_value(self, rows, fmin):
+        """Coordinates ``(K, d)`` and variances ``(G, K)`` of the global rows ``rows`` on every
+        rank: the owners fetch them (``gather_rows``), one ``allgather``.  With ``fmin`` the
+        rows must lie in ``S``: the owners look, and every rank raises the same
+        ``RuntimeError`` (no row is safe at all) or ``ValueError``."""
+        be, comm = self._backend, self._comm
+        world, N = comm.world, self.inputs.shape[0]
+        if fmin is not None and self._ise_safe_count(fmin)[0] == 0:
+            raise RuntimeError('There are no safe points to sample in.')
+        d, G = self.inputs.shape[1], len(self.gps)
+        lo, hi = self._shard
+        mine = (rows >= lo) & (rows < hi)
+        part = np.zeros((rows.size, d + G + 1))
+        if mine.any():
+            x, _mean, var, _q = be.gather_rows(rows[mine])
+            part[mine, :d], part[mine, d:d + G] = x, var
+            part[mine, -1] = 1.0 if fmin is None else be.ise_safe(rows[mine])
+        allp = comm.allgather(part)
+        starts = np.array([shard_range(N, r, world)[0] for r in range(world)])
+        owner = np.searchsorted(starts, rows, side='right') - 1
+        rec = allp[owner, np.arange(rows.size)]
+        bad = rec[:, -1] == 0
+        if bad.any():
+            raise ValueError("candidate rows outside the safe set: %r"
+                             % (rows[bad][:8].tolist(),))
+        return np.ascontiguousarray(rec[:, :d]), np.ascontiguousarray(rec[:, d:d + G].T)
 
     def ise_point(self, candidates=256, about='unsafe', return_values=False):
         """The safe row whose measurement tells most about whether some OTHER row is safe:
@@ -1863,20 +2074,35 @@ class SafeOpt(GaussianProcessOptimization):
 
         ``candidates``: an int ``K`` -- the ``min(K, |S|)`` rows of ``S`` with the largest
         ``sum_{g active} log1p(var_g / s_g) / 2``, the lower row first among equals: the
-        data-processing bound on what a measurement there can tell about anything.  In this
-        version the selection runs on the HOST, from one download of the resident variances
-        and of ``S``.  Or a 1-D integer array of rows, every one of them in ``S`` (else
+        data-processing bound on what a measurement there can tell about anything.  The
+        selection runs where the variances are: three passes over the resident ``var`` and
+        ``S`` (count and range of the keys, a 4096-bin histogram, the rows above one
+        threshold) list a superset of a few hundred rows, and the host orders those exactly
+        -- the rows are the ones ``ise_candidates`` takes from the downloaded state, in its
+        order; a degenerate key range or a mass of equal keys at the threshold falls back to
+        that download.  Or a 1-D integer array of rows, every one of them in ``S`` (else
         ``ValueError``).  At most ``SGP_MAX_ISE`` = 4096 either way.
 
         Returns ``(x, alpha)``: the row, context columns stripped as ``optimize()`` strips
         them, and its ``alpha``; with ``return_values=True`` ``(x, alpha, rows (K,), values
         (K,), targets (K,))``: the candidates, their ``alpha`` and the rows ``z`` that attain
         them.  Raises ``RuntimeError`` when ``S`` is empty or no row qualifies as ``z``,
-        ``ValueError`` when no GP has a finite ``fmin``, ``NotImplementedError`` on more
-        than one rank, before anything runs.  Changes no state of the optimiser or its GPs
-        -- except that pending in-place edits of ``opt.Q`` / ``opt.S`` are flushed first and
-        the resident posterior is swept again if data came in since the last interval
-        update, as for ``mes_point``.  Draws no random numbers."""
+        ``ValueError`` when no GP has a finite ``fmin``.  Changes no state of the optimiser
+        or its GPs -- except that pending in-place edits of ``opt.Q`` / ``opt.S`` are flushed
+        first and the resident posterior is swept again if data came in since the last
+        interval update, as for ``mes_point``.  Draws no random numbers.
+
+        N ranks (SPMD: the same call on every rank): the ranks agree on count and range of
+        the keys (``allreduce_max``, ``allgather``), sum their histograms, take ONE threshold
+        and gather their lists, which carry the rows' coordinates and variances; for an index
+        array the owners fetch both and check ``S``.  Every rank then evaluates ALL
+        candidates, by value, against its own rows (``sgp_grid_ise_at``), and the ranks'
+        ``alpha | target`` blocks are merged -- in the grid's stream with an in-stream
+        communicator (``sgp_grid_ise_comm``), else through one ``allgather`` and
+        ``dist.merge_ise_records``.  A pair depends on the candidate and the row alone, so
+        every rank returns the bits of the one-rank run; every error above is raised on every
+        rank, from agreed values.  A communicator of several ranks without ``allreduce_max``
+        / ``allgather`` gets ``NotImplementedError`` before anything runs."""
         rows, values, targets, alpha, idx = self._ise(candidates, about)
         if idx < 0:
             raise RuntimeError("no row qualifies as z: every row is in the safe set "
@@ -1891,11 +2117,9 @@ class SafeOpt(GaussianProcessOptimization):
         informations in nats.  Returns ``(x, alpha, which)``, ``which`` in ``{'mes',
         'ise'}``; MES wins a tie, and is returned when no row qualifies for ISE.
         ``paths`` / ``features`` as for ``mes_point`` (candidates ``S``, floor ``'mean'``),
-        ``candidates`` / ``about`` as for ``ise_point``.  One rank
-        (``NotImplementedError`` otherwise, before anything runs)."""
-        if self._comm.world > 1:
-            raise NotImplementedError(
-                "info_point runs on one rank (this communicator has %d)" % self._comm.world)
+        ``candidates`` / ``about`` as for ``ise_point``.  N ranks: the two N-rank picks, the
+        same on every rank (seed NumPy's generator alike, as for ``mes_point``)."""
+        self._ise_guard()
         xm, am = self.mes_point(paths=paths, features=features)
         _rows, _values, _targets, ai, idx = self._ise(candidates, about)
         if idx >= 0 and ai > am:
