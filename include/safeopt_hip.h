@@ -959,6 +959,62 @@ int sgp_swarm_run_mes_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta
                             uint64_t seed, const double* ystar, int K, double floor,
                             int64_t p0, int64_t P_total);
 
+/* The fitness of an ISE swarm: information-theoretic safe exploration (Bottero et al. 2022; the
+ * rule of sgp_grid_ise) without a grid.  The particles x_p are the points a measurement may be
+ * taken at, targets (T,d) a fixed set of points z_t whose safety the measurement should tell
+ * about, zmean / zvar (G,T) their posterior (noiseless).  GP g is active when fmin[g] is
+ * finite; s_g = noise_var_g + 1e-8.  With var_g(x_p) the posterior variance at the particle,
+ *   c_g(x_p, z_t) = k_g(x_p, z_t) - k_g(x_p, X) Ky^-1 k_g(X, z_t)
+ *   pair(p, t)    = sum over the active g, in the order of g, of
+ *                   I(zmean[g][t] - fmin[g], zvar[g][t], var_g(x_p), c_g(x_p, z_t); s_g)
+ *                   (I: the term of sgp_ise_eval)
+ *   alpha[p]      = max_t pair(p, t),   target[p] = the lowest t attaining it
+ *   values[p]     = alpha[p] + total_pen[p]
+ * with the penalty and the safety flag of SGP_SWARM_MAXIMIZERS (sgp_swarm_fitness_mes).
+ * scaling does not scale alpha (a number of nats).  A particle's alpha, target, value and row
+ * of pairs depend on its coordinates, the GPs and the target set alone -- not on P, its row or
+ * the launch; a pair's covariance on the particle and the target alone -- not on T or the
+ * target's position.  The posterior is formed by the kernels sgp_swarm_fitness takes for that P
+ * and n; alpha is one more launch behind the shaping pass (k_swarm_ise: 2 P T n flop per active
+ * GP on the fp64 matrix cores, no atomics); targets and operands are staged once per call.
+ * alpha (P), target (P), post (G,2,P: mean | var per GP), pairs (P,T) and cov (G,P,T; zeros for
+ * an inactive GP) may be NULL; pairs and cov are test outputs, refused above G P T = 2^24.
+ * Checked in this order, a refused call launches and writes nothing: G >= 1 and gps[0];
+ * 1 <= T <= SGP_MAX_ISE; targets, zmean and zvar present and finite, every zvar >= 0; one GP
+ * active; P <= 0 then returns 0; the size of the test outputs; then the checks of
+ * sgp_swarm_fitness.                                                                */
+int sgp_swarm_fitness_ise(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                          int64_t P, double beta, const double* fmin, const double* scaling,
+                          const double* targets, const double* zmean, const double* zvar, int T,
+                          double* values, uint8_t* safe, double* alpha, int64_t* target,
+                          double* post, double* pairs, double* cov);
+
+/* sgp_swarm_run for an ISE swarm: the fitness is that of sgp_swarm_fitness_ise (no outputs),
+ * everything else as for sgp_swarm_run_mes, targets / zmean / zvar / T in place of ystar / K /
+ * floor.  Targets and operands are staged once per call; the run ALWAYS takes the general
+ * launches: with rand != NULL it is bit-identical to the host loop over sgp_swarm_fitness_ise.
+ * The refusals of sgp_swarm_fitness_ise, in its order; P <= 0 returns 0 and writes nothing. */
+int sgp_swarm_run_ise(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                      const double* fmin, const double* scaling, int64_t P, double* positions,
+                      double* velocities, double* best_positions, double* best_values,
+                      double* global_best, const double* velocity_scale,
+                      const double* bounds, int init, int iters, double inertia0,
+                      double step, const double* rand, uint64_t seed,
+                      const double* targets, const double* zmean, const double* zvar, int T);
+
+/* sgp_swarm_run_ise on a rank's block [p0, p0 + P) of an ISE swarm of P_total: everything as
+ * sgp_swarm_run_mes_shard; every rank passes the same targets, zmean and zvar.  P <= 0 and
+ * P_total <= 0 returns 0; an empty block of a sharded swarm is refused ("bad swarm size"), as
+ * is a block without a communicator on ctx.  p0 = 0, P = P_total is sgp_swarm_run_ise.  */
+int sgp_swarm_run_ise_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                            const double* fmin, const double* scaling, int64_t P,
+                            double* positions, double* velocities, double* best_positions,
+                            double* best_values, double* global_best,
+                            const double* velocity_scale, const double* bounds, int init,
+                            int iters, double inertia0, double step, const double* rand,
+                            uint64_t seed, const double* targets, const double* zmean,
+                            const double* zvar, int T, int64_t p0, int64_t P_total);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------
  * The only cross-rank traffic of the path is a handful of scalars per
  * iteration (max / any / arg-max / top-k merge).                             */

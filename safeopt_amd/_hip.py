@@ -216,6 +216,11 @@ PROTOTYPES = {
                                         C.c_double, c_double_p, c_double_p,
                                         c_double_p, C.c_int, C.c_double, c_double_p,
                                         c_u8_p, c_double_p]),
+    "sgp_swarm_fitness_ise": (C.c_int, [vp, vpp, C.c_int, c_double_p, C.c_int64,
+                                        C.c_double, c_double_p, c_double_p,
+                                        c_double_p, c_double_p, c_double_p, C.c_int,
+                                        c_double_p, c_u8_p, c_double_p, c_i64_p, c_double_p,
+                                        c_double_p, c_double_p]),
     "sgp_swarm_grow": (C.c_int, [vp, vp, c_double_p, C.c_int64, c_double_p,
                                  C.c_int64, C.c_double, C.c_double, c_u8_p]),
     "sgp_swarm_run": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
@@ -249,6 +254,19 @@ PROTOTYPES = {
                                           C.c_int, C.c_double, C.c_double, c_double_p,
                                           C.c_uint64, c_double_p, C.c_int, C.c_double,
                                           C.c_int64, C.c_int64]),
+    "sgp_swarm_run_ise": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                    c_double_p, c_double_p, C.c_int64,
+                                    c_double_p, c_double_p, c_double_p, c_double_p,
+                                    c_double_p, c_double_p, c_double_p, C.c_int,
+                                    C.c_int, C.c_double, C.c_double, c_double_p,
+                                    C.c_uint64, c_double_p, c_double_p, c_double_p, C.c_int]),
+    "sgp_swarm_run_ise_shard": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                          c_double_p, c_double_p, C.c_int64,
+                                          c_double_p, c_double_p, c_double_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, C.c_int,
+                                          C.c_int, C.c_double, C.c_double, c_double_p,
+                                          C.c_uint64, c_double_p, c_double_p, c_double_p,
+                                          C.c_int, C.c_int64, C.c_int64]),
     "sgp_swarm_run_path": (C.c_int, [vp, vpp, C.c_int, C.c_double,
                                      c_double_p, c_double_p, C.c_int64,
                                      c_double_p, c_double_p, c_double_p, c_double_p,
@@ -1590,12 +1608,29 @@ def _swarm_path_args(gp, path):
     return Omega, phase, m, w, v
 
 
-def _swarm_call(ctx, name, gps, swarm_type, path, clones, mes=None):
-    """The C symbol ``sgp_swarm_<name>[_path|_hall|_mes]`` of a swarm variant, the head of its
+def _swarm_ise_args(gps, ise):
+    """``(targets, zmean, zvar, T)`` of an 'ise' swarm as contiguous float64 arrays: targets
+    ``(T, d)``, the targets' posterior ``(G, T)`` each."""
+    targets, zmean, zvar = ise
+    targets = f64(targets).reshape(-1, gps[0].d)
+    T = targets.shape[0]
+    zmean, zvar = f64(zmean), f64(zvar)
+    if zmean.shape != (len(gps), T) or zvar.shape != (len(gps), T):
+        raise ValueError("zmean and zvar must be (G, T) = (%d, %d), got %r and %r"
+                         % (len(gps), T, zmean.shape, zvar.shape))
+    return targets, zmean, zvar, T
+
+
+def _swarm_call(ctx, name, gps, swarm_type, path, clones, mes=None, ise=None):
+    """The C symbol ``sgp_swarm_<name>[_path|_hall|_mes|_ise]`` of a swarm variant, the head of its
     argument list -- ``ctx, gps[, clones], G[, swarm type]`` -- and the staged-on-the-host
     path arguments that close it (``path = (Omega, phase, w, v)``, one sample path of
     ``gps[0]``; ``clones[g]``: ``gps[g].clone()`` with the pending picks appended; ``mes =
-    (ystar, floor)``: the maxima of a max-value entropy search and the floor under them)."""
+    (ystar, floor)``: the maxima of a max-value entropy search and the floor under them;
+    ``ise = (targets, zmean, zvar)``: the targets of an information-theoretic safe exploration
+    and their posterior)."""
+    if ise is not None and (path is not None or clones is not None or mes is not None):
+        raise NotImplementedError("an 'ise' swarm takes neither a path, clones nor maxima")
     if mes is not None and (path is not None or clones is not None):
         raise NotImplementedError("a 'mes' swarm takes neither a path nor clones")
     head, tail = (ctx.h, _gp_array(gps)), ()
@@ -1610,35 +1645,40 @@ def _swarm_call(ctx, name, gps, swarm_type, path, clones, mes=None):
     elif mes is not None:
         ystar = f64(mes[0]).reshape(-1)
         name, tail = name + "_mes", (dptr(ystar), int(ystar.size), float(mes[1]))
+    elif ise is not None:
+        targets, zmean, zvar, T = _swarm_ise_args(gps, ise)
+        name, tail = name + "_ise", (dptr(targets), dptr(zmean), dptr(zvar), T)
     else:
         head += (SWARM_TYPES[swarm_type],)
     return name, head, tail
 
 
 def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=None,
-               shard=None, mes=None):
+               shard=None, mes=None, ise=None):
     """Every whole PSO run on the device: ``fit = (beta, fmin, scaling, best_lower_bound)``,
     ``state = (positions, velocities, best_positions, best_values, global_best,
     velocity_scale, bounds)`` -- the first five updated in place -- and ``schedule = (init,
     iters, inertia0, step, rand, seed)``, the structs of the C side.  ``path`` (a Thompson
     swarm; ``swarm_type`` and the best lower bound are not used), ``clones`` (a hallucinated
     swarm), ``mes = (ystar, floor)`` (a max-value entropy search swarm; ``swarm_type`` and the
-    best lower bound are not used) and ``shard = (p0, P_total)`` pick the entry point
-    (``sgp_swarm_run[_hall|_path|_mes][_shard]``)."""
+    best lower bound are not used), ``ise = (targets, zmean, zvar)`` (an information-theoretic
+    safe exploration swarm, likewise) and ``shard = (p0, P_total)`` pick the entry point
+    (``sgp_swarm_run[_hall|_path|_mes|_ise][_shard]``)."""
     beta, fmin, scaling, best_lower_bound = fit
     init, iters, inertia0, step, rand, seed = schedule
     P = state[0].shape[0]
     if clones is not None and path is not None:
         raise NotImplementedError("a hallucinated swarm is a maximizers or an expanders "
                                   "swarm, not a Thompson swarm")
-    name, head, tail = _swarm_call(ctx, "sgp_swarm_run", gps, swarm_type, path, clones, mes)
+    name, head, tail = _swarm_call(ctx, "sgp_swarm_run", gps, swarm_type, path, clones, mes,
+                                   ise)
     for a in state[:5]:
         assert a.dtype == np.float64 and a.flags.c_contiguous
     vscale = f64(state[5])
     bnd = None if state[6] is None else f64(state[6])
     rnd = None if rand is None else f64(rand).ravel()
     args = head + (float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
-    if path is None and mes is None:
+    if path is None and mes is None and ise is None:
         args += (float(best_lower_bound),)
     args += (P,) + tuple(dptr(a) for a in state[:5]) + (
         dptr(vscale), None if bnd is None else dptr(bnd), int(bool(init)), int(iters),
@@ -1649,20 +1689,23 @@ def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=Non
 
 
 def _swarm_fitness(ctx, gps, swarm_type, particles, fit, path=None, clones=None,
-                   want_var=False, mes=None, want_post=False):
+                   want_var=False, mes=None, want_post=False, ise=None, want=()):
     """Every swarm fitness call: ``(values, safe)`` of ``particles``, with ``want_var`` (a
     hallucinated swarm's) also the hallucinated variances ``(G, P)``, with ``want_post`` (a
     'mes' swarm's) also the posterior ``(2, P)`` of GP 0 the term was formed from; ``fit``,
-    ``path``, ``clones`` and ``mes`` as for :func:`_swarm_run`."""
+    ``path``, ``clones``, ``mes`` and ``ise`` as for :func:`_swarm_run`.  An 'ise' swarm
+    returns ``(values, safe, out)``, ``out`` a dict of the arrays named in ``want``: 'alpha'
+    (P), 'target' (P, int64), 'post' (G, 2, P), 'pairs' (P, T), 'cov' (G, P, T)."""
     beta, fmin, scaling, best_lower_bound = fit
-    name, head, tail = _swarm_call(ctx, "sgp_swarm_fitness", gps, swarm_type, path, clones, mes)
+    name, head, tail = _swarm_call(ctx, "sgp_swarm_fitness", gps, swarm_type, path, clones, mes,
+                                   ise)
     particles = f64(particles).reshape(-1, gps[0].d)
     P = particles.shape[0]
     values = np.empty(P)
     safe = np.empty(P, dtype=np.uint8)
     var_h = np.empty((len(gps), P)) if want_var else None
     args = head + (dptr(particles), P, float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
-    if path is None and mes is None:
+    if path is None and mes is None and ise is None:
         args += (float(best_lower_bound),)
     args += tail + (dptr(values), safe.ctypes.data_as(c_u8_p))
     if clones is not None:
@@ -1670,9 +1713,25 @@ def _swarm_fitness(ctx, gps, swarm_type, particles, fit, path=None, clones=None,
     post = np.empty((2, P)) if want_post else None
     if mes is not None:
         args += (None if post is None else dptr(post),)
-    # (an empty hallucinated call still checks its clones, an empty 'mes' call its maxima)
-    if P or clones is not None or mes is not None:
+    out = {}
+    if ise is not None:
+        unknown = set(want) - {"alpha", "target", "post", "pairs", "cov"}
+        if unknown:
+            raise ValueError("unknown outputs %r of an 'ise' swarm" % sorted(unknown))
+        G, T = len(gps), tail[3]
+        shapes = {"alpha": (P,), "target": (P,), "post": (G, 2, P), "pairs": (P, T),
+                  "cov": (G, P, T)}
+        for k in ("alpha", "target", "post", "pairs", "cov"):
+            if k in want:
+                out[k] = np.empty(shapes[k], dtype=np.int64 if k == "target" else np.float64)
+        args += tuple((out[k].ctypes.data_as(c_i64_p) if k == "target" else dptr(out[k]))
+                      if k in out else None for k in ("alpha", "target", "post", "pairs", "cov"))
+    # (an empty hallucinated call still checks its clones, an empty 'mes' call its maxima, an
+    # empty 'ise' call its targets)
+    if P or clones is not None or mes is not None or ise is not None:
         ctx.check(getattr(lib(), name)(*args))
+    if ise is not None:
+        return values, safe.view(np.bool_), out
     if want_post:
         return values, safe.view(np.bool_), post
     if want_var:
@@ -1774,3 +1833,30 @@ def swarm_run_mes(ctx, gps, beta, fmin, scaling, positions, velocities, best_pos
                (positions, velocities, best_positions, best_values, global_best,
                 velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
                mes=(ystar, floor), shard=shard)
+
+
+def swarm_fitness_ise(ctx, gps, particles, beta, fmin, scaling, targets, zmean, zvar, want=()):
+    """Fitness and safety of ``particles`` for an information-theoretic safe exploration swarm
+    (``sgp_swarm_fitness_ise``): ``values = alpha + total_pen`` with ``alpha[p] = max_t pair(p,
+    t)`` over the ``targets`` (T, d), whose noiseless posterior is ``zmean`` / ``zvar`` (G, T);
+    the penalty and ``safe`` are those of the maximizers swarm.  Returns ``(values, safe,
+    out)``; ``want`` names the further arrays of ``out``: 'alpha' (P), 'target' (P), 'post'
+    (G, 2, P), and the test outputs 'pairs' (P, T) and 'cov' (G, P, T)."""
+    return _swarm_fitness(ctx, gps, None, particles, (beta, fmin, scaling, 0.0),
+                          ise=(targets, zmean, zvar), want=want)
+
+
+def swarm_run_ise(ctx, gps, beta, fmin, scaling, positions, velocities, best_positions,
+                  best_values, global_best, velocity_scale, bounds, init, iters, inertia0,
+                  step, rand, targets, zmean, zvar, seed=0, shard=None):
+    """Whole PSO run of an information-theoretic safe exploration swarm on the device
+    (``sgp_swarm_run_ise``); the state arrays are updated in place, ``targets``, ``zmean`` and
+    ``zvar`` as for :func:`swarm_fitness_ise`.
+
+    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
+    ``P_total`` sharded over the ranks of ``ctx``'s communicator
+    (``sgp_swarm_run_ise_shard``), as for :func:`swarm_run`."""
+    _swarm_run(ctx, gps, None, (beta, fmin, scaling, 0.0),
+               (positions, velocities, best_positions, best_values, global_best,
+                velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
+               ise=(targets, zmean, zvar), shard=shard)

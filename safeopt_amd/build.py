@@ -20,7 +20,7 @@ OUT = os.path.join(PKG, "libsafeopt_hip.so")
 SOURCES = ["api.hip", "expander_api.hip", "batch.hip", "block.hip", "sweep.hip", "expander.hip", "sweep_pair.hip",
            "sweep_mid.hip", "sweep_tiny.hip", "step_small.hip",
            "factor.hip", "hyper.hip", "ise.hip", "joint.hip", "mes.hip", "paths.hip", "sets.hip", "swarm.hip",
-           "swarm_api.hip", "swarm_batch.hip"]
+           "swarm_api.hip", "swarm_batch.hip", "swarm_ise.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "kern_eval.h", "fitness.h",
                                             "small_path.h", "sweep_shared.h",
                                             "sweep_slots.h", "set_order.h",
@@ -39,7 +39,7 @@ BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 # split (profiles/expander_split/isa_diff.txt), and it holds no inline asm to warn about.
 EXTRA = {"sets.hip": ["-ffp-contract=off"], "swarm.hip": ["-ffp-contract=off"],
          "swarm_batch.hip": ["-ffp-contract=off"], "mes.hip": ["-ffp-contract=off"],
-         "ise.hip": ["-ffp-contract=off"],
+         "ise.hip": ["-ffp-contract=off"], "swarm_ise.hip": ["-ffp-contract=off"],
          "sweep.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-Wno-inline-asm"]}
 # e.g. SGP_HIPCC_FLAGS=-DSGP_INSTRUMENT for scripts/ablate.py (use --force)
 USER = os.environ.get("SGP_HIPCC_FLAGS", "").split()

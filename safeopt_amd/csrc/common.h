@@ -209,6 +209,12 @@ enum ScratchSlot : int {
                         // ranks' gathered blocks and their merge; the partials, histogram and
                         // chunk counts of a selection call (IseSelLayout)
   kSlotIseOut = 29,     // ... pairs | cov, the test outputs of a grid call that asks for them
+  kSlotSwarmIseW = 30,  // swarm_ise.hip (SwarmIseLayout): the operands W_g of an 'ise' swarm call, the
+                        // workspace T behind them -- staged ONCE per call; neither swarm_fitness
+                        // nor swarm_run asks for the three slots, so they stay put
+  kSlotSwarmIseIn = 31, // ... targets[Tp][d] | zmean[G][Tp] | zvar[G][Tp] | bestv[P] | bestt[P]
+  kSlotSwarmIseOut = 32,// ... alpha[P] | target[P] | post[G][2][P] | pairs[P][T] | cov[G][P][T] of a
+                        // fitness call that asks for them
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }
@@ -508,6 +514,40 @@ int mes_checks(sgp_ctx* ctx, const double* ystar, int K);
 // values[p] = alpha(mean[p], var[p]) + values[p] over P particles (k_swarm_mes)
 int launch_swarm_mes(sgp_ctx* ctx, int64_t P, const double* mean, const double* var,
                      const SwarmMes& m, double* values);
+// ... and of sgp_swarm_fitness_ise / sgp_swarm_run_ise: information-theoretic safe exploration.
+// The same branch of the shaping pass; the term on top is alpha = max_t pair(p, t) over the
+// staged targets (launch_swarm_ise behind the shaping launch)
+constexpr int kSwarmIse = 6;
+// ise.hip: W = Ky^-1 k(X, x_j) of the K points xc [K][d] (device) in [n_pad][Kp], Kp a multiple
+// of 64, W zeroed by the caller, T an [n][Kp] workspace: the operand kernels of sgp_grid_ise
+int launch_ise_operands(sgp_ctx* ctx, sgp_gp* gp, const double* xc, int K, int Kp, double* W,
+                        double* T);
+// The targets of an 'ise' swarm as the kernel takes them (swarm_ise.hip), all on the device
+struct SwarmIse {
+  const double* W[SGP_MAX_GPS];  // [n_pad][Tp], zero padded; null for an inactive GP
+  const double* tg;              // [Tp][d] targets, zero rows behind T
+  const double* zmean;           // [G][Tp] the targets' posterior
+  const double* zvar;
+  int T, Tp;                     // 1 .. SGP_MAX_ISE, rounded up to 64
+  unsigned active;               // bit g: GP g has a finite fmin
+  double s[SGP_MAX_GPS];         // noise_var + 1e-8
+  int n_pad[SGP_MAX_GPS];        // rows of W_g
+  double* alpha;                 // [P], or null
+  long long* target;             // [P], or null
+  double* post;                  // [G][2][P] mean | var per GP, or null
+  double* pairs;                 // [P][T], or null
+  double* cov;                   // [G][P][T] (zeroed by the stage), or null
+  double* bestv;                 // [P] scratch of the kernel: a row's best pair, block to block
+  long long* bestt;              // [P] ... and its column
+  // what the fitness / run routine adds: the particles and the descriptors on the device
+  const GpDev* gps_dev;
+  const double* base;            // SweepPoints of the particles
+  int64_t stride_row, stride_col;
+  int d;
+};
+// values[p] = max_t pair(p, t) + values[p] over P particles whose posterior is mean / var [G][P]
+int launch_swarm_ise(sgp_ctx* ctx, int G, int64_t P, const double* mean, const double* var,
+                     const double* fmin, const SwarmIse& m, double* values);
 struct FitnessArgs {
   int swarm_type;
   double beta;
@@ -524,6 +564,9 @@ struct FitnessArgs {
   // a 'mes' swarm (swarm_type == kSwarmMes; K = 0 otherwise): read by launch_fitness_small on
   // the host, which launches the term behind the shaping kernel -- no kernel reads it
   SwarmMes mes;
+  // an 'ise' swarm (swarm_type == kSwarmIse; null otherwise): a HOST pointer, read by
+  // launch_fitness_small alone, which launches the term behind the shaping kernel
+  const SwarmIse* ise;
 };
 // rows_sharded: the rows are a rank's shard of a grid -- the sweep kernel is then chosen
 // by the GPs alone (the same on every rank), never by the number of rows
@@ -579,7 +622,28 @@ struct SwarmSpec {             // what the fitness is
   const SwarmPath* path;       // a Thompson swarm: the STAGED path; null otherwise
   sgp_gp* const* clones;       // a hallucinated swarm: [G]; null otherwise
   const SwarmMes* mes;         // a 'mes' swarm: the STAGED maxima; null otherwise
+  const struct SwarmIseIn* ise = nullptr;   // an 'ise' swarm: the caller's targets (host); the two
+                               // routines stage them behind their checks (swarm_ise_stage)
 };
+struct SwarmIseIn {
+  const double *targets, *zmean, *zvar;   // (T,d), (G,T), (G,T) on the host
+  int T;
+  // outputs of a fitness call (host), each may be null
+  double* alpha;
+  int64_t* target;
+  double *post, *pairs, *cov;
+};
+// swarm_ise.hip.  "no GP", 1 <= T <= SGP_MAX_ISE, targets / zmean / zvar present and finite with
+// every zvar >= 0, one GP active: the checks in front of an entry point's early return
+int swarm_ise_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* fmin,
+                     const SwarmIseIn& in);
+// pairs / cov are test outputs: G P T <= 2^24
+int swarm_ise_out_check(sgp_ctx* ctx, int G, int64_t P, const SwarmIseIn& in);
+// targets, their posterior and the operands onto the device, ONCE per call (host: collect_gps')
+int swarm_ise_stage(sgp_ctx* ctx, sgp_gp* const* gps, const GpDev* host, int G, int d,
+                    const double* fmin, const SwarmIseIn& in, int64_t P, SwarmIse* out);
+// the outputs a fitness call asked for, back to the host
+int swarm_ise_read(sgp_ctx* ctx, const SwarmIseIn& in, const SwarmIse& m, int G, int64_t P);
 struct SwarmState {            // the caller's arrays (host), rows [p0, p0 + P) of a swarm of Pt
   double *positions, *velocities, *best_positions, *best_values, *global_best;
   const double *velocity_scale, *bounds;   // bounds may be null

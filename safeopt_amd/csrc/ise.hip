@@ -662,6 +662,24 @@ int sgp_ise_eval(sgp_ctx* ctx, const double* mu, const double* vz, const double*
   return 0;
 }
 
+// W = Ky^-1 k(X, x_j) of the K points xc [K][d] (device), [n_pad][Kp] with Kp a multiple of 64
+// and W zeroed by the caller; T: [n][Kp] workspace (common.h).  The covariance-matrix kernel of
+// the factorisation, then k_ise_fwd and k_ise_bwd: a column's sums run in an order that depends
+// on n alone, so a column has the same bits whatever K, Kp or its position.
+int launch_ise_operands(sgp_ctx* ctx, sgp_gp* gp, const double* xc, int K, int Kp, double* W,
+                        double* T) {
+  const int n = int(gp->n);
+  const double* Linv = static_cast<const double*>(gp->Linv.p);
+  SGP_TRY(launch_kernel_matrix(ctx, gp->kern, static_cast<const double*>(gp->X.p), n, xc, K, W,
+                               Kp, 0, 0.0, INT64_MAX));
+  const dim3 grid(unsigned(n), unsigned(Kp / 64));
+  hipLaunchKernelGGL(k_ise_fwd, grid, dim3(256), 0, ctx->stream, Linv, int64_t(gp->ld), Kp, W, T);
+  hipLaunchKernelGGL(k_ise_bwd, grid, dim3(256), 0, ctx->stream, Linv, int64_t(gp->ld), n, Kp, T,
+                     W);
+  SGP_HIP(ctx, hipGetLastError());
+  return 0;
+}
+
 namespace {
 
 // The body of sgp_grid_ise, sgp_grid_ise_at and sgp_grid_ise_comm: the same operand kernels,
@@ -751,18 +769,7 @@ int grid_ise(sgp_grid* g, sgp_gp* const* gps, int G, const double* fmin, const i
   double flops = 0.0;
   for (int q = 0; q < G; ++q) {
     if (!((active >> q) & 1u)) continue;
-    sgp_gp* gp = gps[q];
-    const int n = int(gp->n);
-    double *Wq = wbuf + l.w[q], *T = wbuf + l.t;
-    const double* Linv = static_cast<const double*>(gp->Linv.p);
-    SGP_TRY(launch_kernel_matrix(ctx, gp->kern, static_cast<const double*>(gp->X.p), n,
-                                 in + l.xc, K, Wq, Kp, 0, 0.0, INT64_MAX));
-    const dim3 grid(unsigned(n), unsigned(Kp / 64));
-    hipLaunchKernelGGL(k_ise_fwd, grid, dim3(256), 0, ctx->stream, Linv, int64_t(gp->ld), Kp, Wq,
-                       T);
-    hipLaunchKernelGGL(k_ise_bwd, grid, dim3(256), 0, ctx->stream, Linv, int64_t(gp->ld), n, Kp,
-                       T, Wq);
-    SGP_HIP(ctx, hipGetLastError());
+    SGP_TRY(launch_ise_operands(ctx, gps[q], in + l.xc, K, Kp, wbuf + l.w[q], wbuf + l.t));
     flops += 2.0 * double(N) * host[q].n_pad * Kp;
   }
 

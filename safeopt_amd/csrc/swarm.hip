@@ -537,6 +537,9 @@ int launch_fitness_small(sgp_ctx* ctx, int G, int64_t P, const double* mean,
   // a 'mes' swarm: alpha of GP 0's posterior (mean[0][p], var[0][p]) on top of the penalty
   // the shaping left in the values -- both posterior routes end here
   if (fa.swarm_type == kSwarmMes) return launch_swarm_mes(ctx, P, mean, var, fa.mes, fa.values);
+  // an 'ise' swarm: alpha over the staged targets, from every active GP's posterior
+  if (fa.swarm_type == kSwarmIse)
+    return launch_swarm_ise(ctx, G, P, mean, var, fa.fmin, *fa.ise, fa.values);
   return 0;
 }
 

@@ -1,7 +1,7 @@
 // The swarm entry points of the C ABI (include/safeopt_hip.h): host-side launch sequences
-// around the kernels of swarm.hip, paths.hip, swarm_batch.hip, mes.hip and the posterior
-// sweeps.  Twelve exported fitness / run functions (plain, hallucinated, Thompson and 'mes':
-// one fitness, one run and one sharded run each) fill SwarmSpec / SwarmState / PsoSchedule
+// around the kernels of swarm.hip, paths.hip, swarm_batch.hip, mes.hip, swarm_ise.hip and the
+// posterior sweeps.  Fifteen exported fitness / run functions (plain, hallucinated, Thompson,
+// 'mes' and 'ise': one fitness, one run and one sharded run each) fill SwarmSpec / SwarmState / PsoSchedule
 // (common.h) and share ONE fitness routine and ONE run routine.
 #include <string.h>
 
@@ -78,11 +78,14 @@ static FitnessArgs make_fitness_args(const SwarmSpec& s) {
     fa.scaling[i] = (i < s.G) ? s.scaling[i] : 1.0;
   }
   if (s.mes) fa.mes = *s.mes;
+  fa.ise = nullptr;            // (the routine points it at what it staged)
   return fa;
 }
 
-// a path comes with kSwarmThompson, maxima with kSwarmMes, the public types otherwise
+// a path comes with kSwarmThompson, maxima with kSwarmMes, targets with kSwarmIse, the public
+// types otherwise
 static bool swarm_type_ok(const SwarmSpec& s) {
+  if (s.ise) return s.swarm_type == kSwarmIse && !s.path && !s.clones && !s.mes;
   if (s.path) return s.swarm_type == kSwarmThompson && !s.mes;
   if (s.mes) return s.swarm_type == kSwarmMes;
   return s.swarm_type >= SGP_SWARM_GREEDY && s.swarm_type <= SGP_SWARM_SAFE_SET;
@@ -119,12 +122,21 @@ static int path_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, int m) {
 //   sgp_swarm_run_mes[_shard]  "no GP", "maxima", "the floor is NaN", return 0 if P <= 0 and
 //                           P_total <= 0, then as sgp_swarm_run_shard (an empty block of a
 //                           sharded swarm: "bad swarm size", as for a path run)
-// A Thompson and a 'mes' call pass "type" and the second "no GP" by construction.
+//   sgp_swarm_fitness_ise   "no GP", "targets" (swarm_ise_checks: 1 <= T <= SGP_MAX_ISE; targets,
+//                           zmean and zvar present and finite, every zvar >= 0), "no GP is
+//                           active", return 0 if P <= 0, "test outputs" (pairs / cov above
+//                           G P T = 2^24), GPs; the targets and operands are staged behind GPs
+//   sgp_swarm_run_ise[_shard]  "no GP", "targets", "no GP is active", return 0 if P <= 0 and
+//                           P_total <= 0, then as sgp_swarm_run_shard (an empty block of a
+//                           sharded swarm: "bad swarm size", as for a path run); staged behind GPs
+// A Thompson, a 'mes' and an 'ise' call pass "type" and the second "no GP" by construction.
 
-// All four fitness entry points: import the points, the real posterior and the shaping
+// All five fitness entry points: import the points, the real posterior and the shaping
 // pass (few-points path or sweep), with clones the downdate (launch_swarm_down) in front of
 // the shaping, with a path the path term (launch_swarm_path) behind it, with maxima alpha
-// (launch_swarm_mes, inside launch_fitness_small where mean and var are at hand).
+// (launch_swarm_mes, inside launch_fitness_small where mean and var are at hand), with targets
+// alpha of the 'ise' rule (launch_swarm_ise, likewise; the targets and operands are staged
+// here, ONCE, behind the last check).
 static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particles, int64_t P,
                          double* values, uint8_t* safe, double* var_h) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
@@ -151,6 +163,15 @@ static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particl
   fa.values = fb.values;
   fa.safe = fb.safe;
   const SweepPoints sp{fb.pts, P, 1, P};
+  SwarmIse ise{};
+  if (s.ise) {
+    SGP_TRY(swarm_ise_stage(ctx, s.gps, host, G, d, s.fmin, *s.ise, P, &ise));
+    ise.gps_dev = fb.gpdev;
+    ise.base = sp.base;
+    ise.stride_row = sp.stride_row;
+    ise.stride_col = sp.stride_col;
+    fa.ise = &ise;
+  }
   if (s.clones) {
     SGP_TRY(sgp_h2d(ctx, fb.clones, chost, sizeof(GpDev) * G));
     SGP_TRY(launch_swarm_down(ctx, fb.clones, G, d, b, sp, fb.down));
@@ -168,6 +189,7 @@ static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particl
   SGP_TRY(sgp_d2h(ctx, values, fb.values, nv));
   SGP_TRY(sgp_d2h(ctx, safe, fb.safe, size_t(P)));
   if (s.clones && var_h) SGP_TRY(sgp_d2h(ctx, var_h, fb.var_h, size_t(G) * nv));
+  if (s.ise) SGP_TRY(swarm_ise_read(ctx, *s.ise, ise, G, P));
   return 0;
 }
 
@@ -177,7 +199,8 @@ static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particl
 // swarm -- the global best goes through the record all-gather.
 // s.path: a Thompson swarm, s.clones: a hallucinated swarm (the downdate in front of every
 // shaping pass), s.mes: a 'mes' swarm (alpha behind every shaping pass, launched by
-// launch_fitness_small); all three always take the general launches below.
+// launch_fitness_small), s.ise: an 'ise' swarm (likewise, the targets and operands staged once
+// behind the checks); all four always take the general launches below.
 static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
                      const PsoSchedule& sch) {
   const int G = s.G, init = sch.init, iters = sch.iters;
@@ -228,6 +251,15 @@ static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
   fa.safe = rb.safe;
   if (s.clones) fa.down = rb.down;
   const SweepPoints sp{rb.pos, P, d, 1};          // row-major (P, d) in place
+  SwarmIse ise{};
+  if (s.ise) {
+    SGP_TRY(swarm_ise_stage(ctx, s.gps, host, G, d, s.fmin, *s.ise, P, &ise));
+    ise.gps_dev = rb.gpdev;
+    ise.base = sp.base;
+    ise.stride_row = sp.stride_row;
+    ise.stride_col = sp.stride_col;
+    fa.ise = &ise;
+  }
   // (the paths and the posterior kernel follow the whole swarm: same bits on every rank)
   const bool few = Pt <= kSmallSwarm && small_path_pays_all(s.gps, G, Pt);
   // a small swarm against GPs with few observations (SafeOptSwarm's defaults on the
@@ -237,7 +269,7 @@ static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
   const bool few_swept = Pt <= kSmallSwarm && !few;
   const double* r = drand;
   double inertia = sch.inertia0;
-  if ((few || few_swept) && !shard && !s.path && !s.clones && !s.mes) {
+  if ((few || few_swept) && !shard && !s.path && !s.clones && !s.mes && !s.ise) {
     // small swarm: three launches per iteration -- k(X, particles), the block
     // products on the matrix cores, and ONE workgroup for everything else
     // (fitness, bests, and the move that opens the next iteration)
@@ -540,6 +572,49 @@ int sgp_swarm_run_mes_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta
   SwarmMes mes;
   SGP_TRY(swarm_mes_stage(ctx, ystar, K, floor, P, false, &mes));
   const SwarmSpec s{gps, G, kSwarmMes, beta, fmin, scaling, 0.0, nullptr, nullptr, &mes};
+  const SwarmState st{positions, velocities, best_positions, best_values, global_best,
+                      velocity_scale, bounds, P, p0, P_total};
+  return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});
+}
+
+int sgp_swarm_fitness_ise(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                          int64_t P, double beta, const double* fmin, const double* scaling,
+                          const double* targets, const double* zmean, const double* zvar, int T,
+                          double* values, uint8_t* safe, double* alpha, int64_t* target,
+                          double* post, double* pairs, double* cov) {
+  const SwarmIseIn in{targets, zmean, zvar, T, alpha, target, post, pairs, cov};
+  SGP_TRY(swarm_ise_checks(ctx, gps, G, fmin, in));
+  if (P <= 0) return 0;
+  SGP_TRY(swarm_ise_out_check(ctx, G, P, in));
+  const SwarmSpec s{gps, G, kSwarmIse, beta, fmin, scaling, 0.0, nullptr, nullptr, nullptr, &in};
+  return swarm_fitness(ctx, s, particles, P, values, safe, nullptr);
+}
+
+int sgp_swarm_run_ise(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                      const double* fmin, const double* scaling, int64_t P, double* positions,
+                      double* velocities, double* best_positions, double* best_values,
+                      double* global_best, const double* velocity_scale,
+                      const double* bounds, int init, int iters, double inertia0,
+                      double step_size, const double* rand, uint64_t seed,
+                      const double* targets, const double* zmean, const double* zvar, int T) {
+  return sgp_swarm_run_ise_shard(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
+                                 best_positions, best_values, global_best, velocity_scale,
+                                 bounds, init, iters, inertia0, step_size, rand, seed, targets,
+                                 zmean, zvar, T, 0, P);
+}
+
+int sgp_swarm_run_ise_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                            const double* fmin, const double* scaling, int64_t P,
+                            double* positions, double* velocities, double* best_positions,
+                            double* best_values, double* global_best,
+                            const double* velocity_scale, const double* bounds, int init,
+                            int iters, double inertia0, double step_size, const double* rand,
+                            uint64_t seed, const double* targets, const double* zmean,
+                            const double* zvar, int T, int64_t p0, int64_t P_total) {
+  const SwarmIseIn in{targets, zmean, zvar, T, nullptr, nullptr, nullptr, nullptr, nullptr};
+  SGP_TRY(swarm_ise_checks(ctx, gps, G, fmin, in));
+  if (P <= 0 && P_total <= 0) return 0;
+  const SwarmSpec s{gps, G, kSwarmIse, beta, fmin, scaling, 0.0, nullptr, nullptr, nullptr, &in};
   const SwarmState st{positions, velocities, best_positions, best_values, global_best,
                       velocity_scale, bounds, P, p0, P_total};
   return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});

@@ -108,6 +108,21 @@ def check_same_maxima(comm, ystar, floor):
             % (int(h), comm.rank, int(-red[1]), int(red[0])))
 
 
+def check_same_targets(comm, targets, zmean, zvar):
+    """``ValueError`` -- on EVERY rank, as :func:`check_same_maxima` -- unless all ranks hold
+    the same targets of an information-theoretic safe exploration swarm and the same posterior
+    of them: functions of replicated data and the shared seed.  One ``allreduce_max`` of ``[h,
+    -h]``, ``h`` a 48-bit digest of their bytes."""
+    h = _digest48((targets, zmean, zvar))
+    red = comm.allreduce_max(np.array([h, -h]))
+    if red[0] != -red[1]:
+        raise ValueError(
+            "the ranks hold different targets (digest %012x on rank %d, the ranks' digests "
+            "span %012x .. %012x): pass the same targets, and seed NumPy's global generator "
+            "alike, on every rank before ise_point"
+            % (int(h), comm.rank, int(-red[1]), int(red[0])))
+
+
 class LocalComm(object):
     """world_size == 1: every collective is the identity."""
     rank, world = 0, 1

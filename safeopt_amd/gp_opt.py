@@ -32,6 +32,7 @@ import numpy as np
 
 from . import _hip
 from .dist import (LocalComm, allgather_rows, check_same_maxima, check_same_paths,
+                   check_same_targets,
                    gather_shard_columns,
                    merge_argmax, merge_batch_records, merge_ise_records, merge_mes_records,
                    merge_path_records, merge_topk, pick_ise, shard_range)
@@ -2217,6 +2218,65 @@ def swarm_batch_loop(x0, sd0, size, devs, next_pick):
     return np.vstack(X), np.vstack(sds)
 
 
+class NoIseTarget(RuntimeError):
+    """``ise_targets`` has no target left: every one is certified safe.  The one outcome of
+    ``SafeOptSwarm.ise_point`` that ``info_point`` answers with the MES pick."""
+
+
+def _ise_about(about):
+    if about not in ('unsafe', 'all'):
+        raise ValueError("about must be 'unsafe' or 'all', got %r" % (about,))
+
+
+def ise_target_rows(targets, d):
+    """The ``targets`` argument of ``SafeOptSwarm.ise_point``, checked before anything is drawn:
+    an int ``T`` in ``1 .. SGP_MAX_ISE`` (returned as it is) or an array of ``T`` finite rows
+    ``(T, d)`` (returned as a float copy); ``ValueError`` otherwise."""
+    if isinstance(targets, (int, np.integer)) and not isinstance(targets, bool):
+        if targets < 1 or targets > _hip.MAX_ISE:
+            raise ValueError("targets must be in 1 .. SGP_MAX_ISE = %d, got %d"
+                             % (_hip.MAX_ISE, targets))
+        return int(targets)
+    rows = np.array(targets, dtype=float)
+    if rows.ndim != 2 or rows.shape[1] != d or not 1 <= rows.shape[0] <= _hip.MAX_ISE:
+        raise ValueError("targets must be an int or (T, d) rows with d = %d and T in 1 .. "
+                         "SGP_MAX_ISE = %d, got shape %r" % (d, _hip.MAX_ISE, rows.shape))
+    if not np.all(np.isfinite(rows)):
+        raise ValueError("a target is not finite")
+    return rows
+
+
+def ise_targets(targets, bounds, about, fmin, beta, posterior):
+    """The targets of ``SafeOptSwarm.ise_point`` and their posterior: ``(rows (T', d), zmean
+    (G, T'), zvar (G, T'))``.  ``targets``: an int ``T`` -- ONE ``np.random.rand(T, d)`` scaled
+    into ``bounds`` (``d`` pairs ``(low, high)``) -- or ``(T, d)`` rows, nothing drawn.
+    ``posterior(rows) -> (zmean, zvar)``, the noiseless posterior of every GP, is called once.
+    ``about='unsafe'`` drops the rows that are certified safe -- ``mean_g - beta sd_g >=
+    fmin_g`` for every GP with a finite ``fmin_g`` --, ``'all'`` keeps every row.  No row
+    left: ``NoIseTarget``, a ``RuntimeError``.  A pure function of its arguments and NumPy's
+    generator."""
+    _ise_about(about)
+    bounds = np.asarray(bounds, dtype=float)
+    if isinstance(targets, (int, np.integer)):
+        low, high = bounds[:, 0], bounds[:, 1]
+        rows = low + np.random.rand(int(targets), bounds.shape[0]) * (high - low)
+    else:
+        rows = np.array(targets, dtype=float)
+    zmean, zvar = posterior(rows)
+    zmean, zvar = np.asarray(zmean, dtype=float), np.asarray(zvar, dtype=float)
+    if about == 'unsafe':
+        fmin = np.asarray(fmin, dtype=float)
+        active = np.isfinite(fmin)
+        lower = zmean[active] - beta * np.sqrt(zvar[active])
+        keep = ~np.all(lower >= fmin[active, None], axis=0)
+        rows, zmean, zvar = rows[keep], zmean[:, keep], zvar[:, keep]
+    if rows.shape[0] == 0:
+        raise NoIseTarget("no target is left: every one is certified safe (about='all' "
+                          "keeps every target)")
+    return (np.ascontiguousarray(rows), np.ascontiguousarray(zmean),
+            np.ascontiguousarray(zvar))
+
+
 class SafeOptSwarm(GaussianProcessOptimization):
     """SafeOpt for higher dimensions with adaptive swarm discretisation.
 
@@ -2325,9 +2385,9 @@ class SafeOptSwarm(GaussianProcessOptimization):
         return self._swarm_fitness(swarm_type, particles)
 
     def _swarm_fitness(self, swarm_type, particles, **variant):
-        """What the three fitness callbacks share: the current ``beta``, the fitted device
-        GPs and this optimiser's ``fmin`` / ``scaling`` / best lower bound; ``variant``:
-        ``path=`` or ``clones=`` of ``_hip._swarm_fitness``."""
+        """What the fitness callbacks share: the current ``beta``, the fitted device GPs and
+        this optimiser's ``fmin`` / ``scaling`` / best lower bound; ``variant``: ``path=``,
+        ``clones=``, ``mes=`` or ``ise=`` (with ``want=``) of ``_hip._swarm_fitness``."""
         beta = self.beta(self.t)
         devs = [g._fitted() for g in self.gps]
         return _hip._swarm_fitness(devs[0].ctx, devs, swarm_type, np.atleast_2d(particles),
@@ -2356,6 +2416,15 @@ class SafeOptSwarm(GaussianProcessOptimization):
         the maximizers' safety flag (``sgp_swarm_fitness_mes``).  The fitness callback of the
         host loop."""
         return self._swarm_fitness(None, particles, mes=mes)
+
+    def _compute_ise_fitness(self, ise, particles, want=None):
+        """Fitness and safety of ``particles`` for an information-theoretic safe exploration
+        swarm with ``ise = (targets, zmean, zvar)``: ``values = alpha + `` the maximizers'
+        penalty, ``alpha[p] = max_t pair(p, t)`` over the targets, ``safe`` the maximizers'
+        safety flag (``sgp_swarm_fitness_ise``).  The fitness callback of the host loop;
+        ``want``: ``(values, safe, out)`` with the arrays named in it (``_hip._swarm_fitness``)."""
+        res = self._swarm_fitness(None, particles, ise=ise, want=want or ())
+        return res if want else res[:2]
 
     def _side_swarm_pick(self, swarm, configure, fitness, iters, empty_ok=False):
         """One side swarm of ``optimize_batch`` / ``thompson_points`` and its pick ``(x,
@@ -2670,6 +2739,122 @@ class SafeOptSwarm(GaussianProcessOptimization):
         if return_state:
             return x, alpha, dict(ystar=ystar, floor=floor, thompson_x=thompson_x)
         return x, alpha
+
+    def _ise_refusals(self, targets, about):
+        """The argument refusals ``ise_point`` and ``info_point`` share, before anything is
+        drawn or run; returns ``ise_target_rows``' form of ``targets``."""
+        targets = ise_target_rows(targets, self.gp.input_dim)
+        _ise_about(about)
+        if not np.any(np.isfinite(self.fmin)):
+            raise ValueError("no GP is active: every fmin is infinite")
+        return targets
+
+    def ise_point(self, targets=256, about='unsafe', max_iters=None, return_state=False):
+        """The safe point whose measurement tells most about whether some OTHER point is safe,
+        without a grid: information-theoretic safe exploration (Bottero, Luis, Vinogradska,
+        Berkenkamp, Peters 2022; ``SafeOpt.ise_point`` on a grid) by a swarm.  It needs no
+        Lipschitz constant and no width rule.
+
+        1. The refusals below come before anything is drawn or run.
+        2. ``_recheck_safe_set()`` runs once.
+        3. Targets ``z_t``: an int ``T`` -- one ``np.random.rand(T, d)`` scaled into
+           ``bounds`` -- or ``(T, d)`` rows, nothing drawn.  ``about='unsafe'`` (default) drops
+           the targets that are certified safe (``mean_g - beta sd_g >= fmin_g`` for every GP
+           with a finite ``fmin_g``, one ``predict_noiseless`` per GP); ``'all'`` keeps every
+           one (``ise_targets``).
+        4. One swarm (``DeviceSwarmOptimization(..., 'ise')``; ``pso='host'``: the reference
+           loop over ``_compute_ise_fitness``) starts from ``swarm_size`` draws from ``S`` and
+           runs ``max_iters`` (default ``self.max_iters``) iterations.  The fitness of a
+           particle is ``alpha(x) + total_pen`` with ``alpha(x) = max_t sum_{g active} I_g(x;
+           z_t)``, ``I_g`` the term of ``SafeOpt.ise_point`` from the posterior covariance of
+           particle and target, formed on the device inside the swarm iteration
+           (``k_swarm_ise``, ``csrc/swarm_ise.hip``), under the penalty and safety rule of
+           the maximizers swarm.  The pick is the personal best with the largest value among
+           those that are safe under the current posterior (one ``safe_set`` fitness call),
+           the lowest index among equals.
+        5. Returns ``(x (d,), alpha)``, ``alpha`` from one fitness call on ``x`` alone (a
+           particle's bits do not depend on the swarm it sits in); with ``return_state=True``
+           ``(x, alpha, {'targets' (T', d), 'target' (d,): the z attained, 'zmean', 'zvar' (G,
+           T')})``.
+
+        Raises ``ValueError`` for ``targets`` outside ``1 .. SGP_MAX_ISE`` (4096) or an array
+        that is not ``(T, d)`` or not finite, an ``about`` other than ``'unsafe'`` / ``'all'``,
+        a ``max_iters`` below 1, or when no ``fmin`` is finite; ``NotImplementedError`` for several ranks whose
+        communicator carries no device context; ``RuntimeError`` when the safe set is empty
+        or the swarm ends with no safe personal best, its subclass ``NoIseTarget`` when no
+        target is left.
+
+        Changes no state of the optimiser beyond what ``_recheck_safe_set`` does.  NumPy's
+        global generator is consumed in this order:
+
+        1. with an int ``targets``, one ``rand(T, d)``;
+        2. ``pso='device-rng'`` only: one ``randint`` for the key of the swarm's device
+           generator;
+        3. one swarm's worth, as step 3 of ``mes_point``.
+
+        N ranks (``comm=``; SPMD, the same seed and call on every rank): the targets are a
+        function of replicated data and the shared seed; one ``allreduce_max`` of a digest
+        verifies that the ranks hold the same, ``ValueError`` on every rank otherwise.  The
+        swarm is split over the ranks by particle (``sgp_swarm_run_ise_shard``); the
+        ``safe_set`` call and the pick run replicated on the gathered personal bests: the
+        bits of the one-rank run on every rank.
+
+        Out of scope: optimising ``z`` jointly with ``x`` (the paper's continuous variant),
+        target proposals concentrated at the boundary of ``S``, batches of ISE picks."""
+        targets = self._ise_refusals(targets, about)
+        iters = self.max_iters if max_iters is None else int(max_iters)
+        if iters < 1:
+            raise ValueError("max_iters must be at least 1, got %r" % (max_iters,))
+        world = self._comm.world
+        if world > 1 and getattr(self._comm, 'ctx', None) is None:
+            raise NotImplementedError(
+                "the sharded 'ise' swarm merges the global best in the stream of the "
+                "communicator's device context: a merge over this host-only communicator of "
+                "%d ranks is not implemented" % world)
+        self._recheck_safe_set()
+
+        def posterior(rows):
+            post = [gp.predict_noiseless(rows) for gp in self.gps]
+            return (np.stack([np.asarray(m).reshape(-1) for m, _ in post]),
+                    np.stack([np.asarray(v).reshape(-1) for _, v in post]))
+
+        ise = ise_targets(targets, self.bounds, about, self.fmin, self.beta(self.t), posterior)
+        if world > 1:
+            check_same_targets(self._comm, *ise)
+        swarm = None                      # pso='host': a reference loop
+        if isinstance(self.swarms['maximizers'], DeviceSwarmOptimization):
+            swarm = DeviceSwarmOptimization(
+                self.swarm_size, self.optimal_velocities, self, 'ise',
+                bounds=self.bounds, rng=self.swarms['maximizers']._rng, comm=self._comm)
+        x, _ = self._side_swarm_pick(
+            swarm, lambda run: run.set_targets(*ise),
+            partial(self._compute_ise_fitness, ise), iters)
+        _, _, out = self._compute_ise_fitness(ise, x[None, :], want=('alpha', 'target'))
+        alpha = float(out['alpha'][0])
+        if return_state:
+            return x, alpha, dict(targets=ise[0], target=ise[0][int(out['target'][0])],
+                                  zmean=ise[1], zvar=ise[2])
+        return x, alpha
+
+    def info_point(self, paths=16, features=1024, targets=256, about='unsafe'):
+        """ISE-BO (Bottero et al. 2023) without a grid: the ``mes_point`` pick (what a
+        measurement tells about the VALUE of the safe optimum) or the ``ise_point`` pick (what
+        it tells about the SAFETY of another point), whichever acquisition is larger -- both
+        are mutual informations in nats.  Returns ``(x, alpha, which)``, ``which`` in
+        ``{'mes', 'ise'}``; MES wins a tie, and is returned when no target is left for ISE
+        (``NoIseTarget``, that outcome alone: every other error of either pick propagates).
+        ``paths`` / ``features`` as for ``mes_point`` (floor ``'mean'``), ``targets`` /
+        ``about`` as for ``ise_point``, whose argument refusals come before anything is drawn.
+        NumPy's generator: what ``mes_point`` draws, then what ``ise_point`` draws."""
+        self._ise_refusals(targets, about)
+        xm, am = self.mes_point(paths=paths, features=features)
+        try:
+            xi, ai = self.ise_point(targets=targets, about=about)
+        except NoIseTarget:               # (and nothing else: every other error is an error)
+            return xm, am, 'mes'
+        if ai > am:
+            return xi, ai, 'ise'
+        return xm, am, 'mes'
 
     # -- one swarm run, in the steps of gp_opt.py:1015-1134 -------------------------
     def _recheck_safe_set(self):

@@ -117,6 +117,8 @@ def _hip_swarm_types():
 THOMPSON_CODE = 4
 #: ... and of the max-value entropy search swarm (``kSwarmMes`` on the C side)
 MES_CODE = 5
+#: ... and of the information-theoretic safe exploration swarm (``kSwarmIse``)
+ISE_CODE = 6
 
 
 class DeviceSwarmOptimization(SwarmOptimization):
@@ -162,6 +164,14 @@ class DeviceSwarmOptimization(SwarmOptimization):
     (``sgp_swarm_fitness_mes`` / ``sgp_swarm_run_mes``); ``set_maxima(ystar, floor)`` comes
     before ``init_swarm``; with ``comm`` it is sharded like every other swarm
     (``sgp_swarm_run_mes_shard``), every rank holding the same maxima and floor.
+
+    ``swarm_type='ise'``: information-theoretic safe exploration -- the fitness is ``alpha +
+    total_pen``, ``alpha[p]`` the largest mutual information between a measurement at the
+    particle and the safety of one of a fixed set of targets, under the maximizers' penalty
+    and safety rule (``sgp_swarm_fitness_ise`` / ``sgp_swarm_run_ise``);
+    ``set_targets(targets, zmean, zvar)`` comes before ``init_swarm``; with ``comm`` it is
+    sharded like every other swarm (``sgp_swarm_run_ise_shard``), every rank holding the same
+    targets.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
@@ -187,7 +197,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
         # expanders swarms of one optimiser must not draw the same numbers
         if rng == 'device' and seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
-        code = {'thompson': THOMPSON_CODE, 'mes': MES_CODE}.get(swarm_type)
+        code = {'thompson': THOMPSON_CODE, 'mes': MES_CODE, 'ise': ISE_CODE}.get(swarm_type)
         if code is None:
             code = _hip_swarm_types()[swarm_type]
         self._seed = (int(seed or 0) * 4 + code) & (2 ** 43 - 1)
@@ -195,6 +205,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
         self._path = None
         self._clones = None
         self._maxima = None
+        self._targets = None
         self.global_best = np.zeros(self.ndim)
 
     def set_path(self, path):
@@ -233,6 +244,42 @@ class DeviceSwarmOptimization(SwarmOptimization):
             raise ValueError("the floor is NaN")
         self._maxima = (ystar, floor)
 
+    def set_targets(self, targets, zmean, zvar):
+        """The targets ``(T, d)``, ``1 <= T <= SGP_MAX_ISE`` finite rows, and their noiseless
+        posterior ``zmean`` / ``zvar`` ``(G, T)`` (finite, every variance ``>= 0``) an 'ise'
+        swarm scores its particles with from the next ``init_swarm`` on.  The arrays are
+        copied; a refused call leaves the swarm as it was."""
+        if self._type != 'ise':
+            raise ValueError("only an 'ise' swarm takes targets, this is %r" % (self._type,))
+        from . import _hip
+        targets = np.array(targets, dtype=float)
+        if targets.ndim != 2 or targets.shape[1] != self.ndim:
+            raise ValueError("targets must be (T, d) with d = %d, got %r"
+                             % (self.ndim, targets.shape))
+        T = targets.shape[0]
+        if T < 1 or T > _hip.MAX_ISE:
+            raise ValueError("%d targets, an 'ise' swarm takes 1 .. SGP_MAX_ISE = %d"
+                             % (T, _hip.MAX_ISE))
+        zmean, zvar = np.array(zmean, dtype=float), np.array(zvar, dtype=float)
+        gps = getattr(self._owner, 'gps', None)
+        G = len(gps) if gps is not None else (zmean.shape[0] if zmean.ndim == 2 else 0)
+        if G < 1 or zmean.shape != (G, T) or zvar.shape != (G, T):
+            raise ValueError("zmean and zvar must be (G, T) = (%d, %d), got %r and %r"
+                             % (G, T, zmean.shape, zvar.shape))
+        if not (np.all(np.isfinite(targets)) and np.all(np.isfinite(zmean))
+                and np.all(np.isfinite(zvar))):
+            raise ValueError("a target, a mean or a variance is not finite")
+        if np.any(zvar < 0):
+            raise ValueError("a variance is negative")
+        self._targets = (np.ascontiguousarray(targets), np.ascontiguousarray(zmean),
+                         np.ascontiguousarray(zvar))
+
+    def _need_targets(self):
+        if self._targets is None:
+            raise ValueError("an 'ise' swarm needs set_targets(targets, zmean, zvar) before "
+                             "init_swarm")
+        return self._targets
+
     def _need_maxima(self):
         if self._maxima is None:
             raise ValueError("a 'mes' swarm needs set_maxima(ystar, floor) before init_swarm")
@@ -249,6 +296,9 @@ class DeviceSwarmOptimization(SwarmOptimization):
         if self._type == 'mes':
             maxima = self._need_maxima()
             return self._owner._compute_mes_fitness(maxima, positions)
+        if self._type == 'ise':
+            targets = self._need_targets()
+            return self._owner._compute_ise_fitness(targets, positions)
         if self._clones is not None:
             return self._owner._compute_hall_fitness(self._type, self._clones, positions)
         return self._owner._compute_particle_fitness(self._type, positions)
@@ -258,6 +308,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
         # (a missing path or missing maxima are refused before anything is touched or drawn)
         path = self._need_path() if self._type == 'thompson' else None
         maxima = self._need_maxima() if self._type == 'mes' else None
+        targets = self._need_targets() if self._type == 'ise' else None
         o = self._owner
         devs = [g._fitted() for g in o.gps]
         sharded = self._comm.world > 1
@@ -279,7 +330,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
             (self.positions, self.velocities, best_positions, best_values, self.global_best,
              np.broadcast_to(self.velocity_scale, (d,)), self.bounds),
             (init, iters, inertia0, step, rand, (self._seed << 20) + self._calls),
-            path=path, clones=self._clones, mes=maxima,
+            path=path, clones=self._clones, mes=maxima, ise=targets,
             shard=(self._rows[0], self.swarm_size) if sharded else None)
         if sharded:
             self.best_positions, self.best_values = self._gather(best_positions, best_values)
@@ -314,6 +365,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
             self._need_path()
         if self._type == 'mes':
             self._need_maxima()
+        if self._type == 'ise':
+            self._need_targets()
         positions = np.ascontiguousarray(positions, dtype=float)
         if self._comm.world > 1:
             lo, hi = self._rows
