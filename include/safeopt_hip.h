@@ -109,6 +109,42 @@ int sgp_gp_append_block(sgp_gp* gp, const double* X, const double* y, int b, int
  * is untouched (refit the reduced data with sgp_gp_set_data).  An index outside 0 .. n-1,
  * n == 1 and a GP that is not fitted are errors.                                          */
 int sgp_gp_remove(sgp_gp* gp, int64_t index, int* info);
+/* Per-observation noise.  Observation i has a NOISE SCALE r_i > 0:
+ *   Ky = K + diag((noise_var + 1e-8) r_i) + jitter I       (the jitter is not scaled).
+ * A GP that never received a scale holds none, runs the code without scales and returns its
+ * bits; r = NULL below means all ones and takes that path, and all ones given explicitly
+ * give the same bits.  k measurements (y_j, rho_j) at one input are, for the posterior, ONE
+ * observation with r = 1 / sum 1/rho_j and y = r sum y_j / rho_j.  sgp_gp_remove, sgp_gp_pop
+ * and sgp_gp_clone carry the scales along; GPs with different scales share no factor; the
+ * noise slot of sgp_gp_lml / sgp_gp_loo_lml is the derivative in noise_var with
+ * dKy/dnoise_var = diag(r).  A scale that is not finite or not positive is an error, and
+ * nothing is written.
+ * sgp_gp_set_data_w: sgp_gp_set_data with the n scales r (or NULL).                        */
+int sgp_gp_set_data_w(sgp_gp* gp, const double* X, const double* Y, const double* r,
+                      int64_t n, int* chol_info, double* jitter_used);
+/* sgp_gp_append with the scale *r of the new row (r = NULL: 1); the pivot rule uses the
+ * row's own diagonal k(x,x) + (noise + 1e-8) r + jitter.                                   */
+int sgp_gp_append_w(sgp_gp* gp, const double* x, double y, const double* r, int* info);
+/* sgp_gp_append_block with the b scales of the new rows (or NULL) on the corner's diagonal. */
+int sgp_gp_append_block_w(sgp_gp* gp, const double* X, const double* y, const double* r,
+                          int b, int* info);
+/* Observation `index` (0 .. n-1) becomes (y_new, r_new) IN PLACE: Ky' = Ky + delta e_i e_i^T
+ * with delta = (noise + 1e-8) (r_new - r_i), y_i -> y_i + dy.  n and the inputs stay.  With
+ * M = L^-1, c = column i of M, P_ii = |c|^2, p = M^T c:
+ *   tau = delta / (1 + delta P_ii),  eta = (dy - delta alpha_i) / (1 + delta P_ii),
+ *   alpha' = alpha + eta p,  L'^-1 = F M with F lower triangular, F^T F = I - tau c c^T:
+ *   q_k = 1 + delta sum_{i <= j <= k} c_j^2,
+ *   row k of L'^-1 = sqrt(q_{k-1} / q_k) M[k] - delta c_k / sqrt(q_{k-1} q_k) sum_{i<=j<k} c_j M[j]
+ * for k = i .. n-1; the rows above i stay.  O(n^2), written into the spare matrix and
+ * committed after the pivot word has been read; every sum in a fixed order (the same inputs
+ * give the same bits).  It leaves the REWEIGH RECORD {x_i, w = -p / P_ii off row i,
+ * P_ii eta, tau P_ii^2} for sgp_grid_rank1_reweigh.  info = 0 ok; > 0: P_ii or a q_k is not
+ * positive and finite -- the GP is untouched (refit with sgp_gp_set_data_w).  An index
+ * outside 0 .. n-1, a y_new that is not finite, a scale that is not finite or not positive
+ * and a GP that is not fitted are errors; nothing is written.                              */
+int sgp_gp_reweigh(sgp_gp* gp, int64_t index, double y_new, double r_new, int* info);
+/* The n noise scales as the device holds them (ones for a GP without scales): a test hook. */
+int sgp_gp_get_noise_scale(sgp_gp* gp, double* r_out);
 /* gp.predict_noiseless / gp._raw_predict (gp_opt.py:469, 591, 929, 973, 1117,
  * 1132; utilities.py:203, 282, 355).  Xnew element (r,c) at
  * Xnew[r*stride_row + c*stride_col] (strides in elements: C or F order).
@@ -292,6 +328,15 @@ int sgp_grid_rank1_update(sgp_grid* grid, sgp_gp* const* gps, int G,
 int sgp_grid_rank1_remove(sgp_grid* grid, sgp_gp* const* gps, int G,
                           const int* which, double beta, const double* fmin,
                           double* out2);
+/* ... and after ONE sgp_gp_reweigh on the GPs flagged in which[]: with x_i the re-weighted
+ * row and w, u0 = P_ii eta, u1 = tau P_ii^2 of its record,
+ *   c(x) = k(x,x_i) - k(X,x)^T w  (= k(X,x)^T p / P_ii),  mean += c u0,
+ *   var = max(var + c^2 u1, 1e-15)     (the sign of the change is that of delta),
+ * then Q and S for all GPs; out2, the deferred form, context columns and shared factors
+ * as sgp_grid_rank1_update.  Each of the three refuses the other two's records.          */
+int sgp_grid_rank1_reweigh(sgp_grid* grid, sgp_gp* const* gps, int G,
+                           const int* which, double beta, const double* fmin,
+                           double* out2);
 /* ... and after ONE sgp_gp_append_block on the GPs flagged in which[] (b_g from the GP's block
  * record, it may differ per GP): per row x, with X' the data after the block and
  *   t_j(x) = sum_{i <= n0+j} L^-1[n0+j][i] k(X'_i, x),   j = 0 .. b-1 in that order,

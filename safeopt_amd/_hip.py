@@ -67,6 +67,13 @@ PROTOTYPES = {
     "sgp_gp_append_block": (C.c_int, [vp, c_double_p, c_double_p, C.c_int, c_int_p]),
     "sgp_gp_pop": (C.c_int, [vp]),
     "sgp_gp_remove": (C.c_int, [vp, C.c_int64, c_int_p]),
+    "sgp_gp_set_data_w": (C.c_int, [vp, c_double_p, c_double_p, c_double_p, C.c_int64,
+                                    c_int_p, c_double_p]),
+    "sgp_gp_append_w": (C.c_int, [vp, c_double_p, C.c_double, c_double_p, c_int_p]),
+    "sgp_gp_append_block_w": (C.c_int, [vp, c_double_p, c_double_p, c_double_p, C.c_int,
+                                        c_int_p]),
+    "sgp_gp_reweigh": (C.c_int, [vp, C.c_int64, C.c_double, C.c_double, c_int_p]),
+    "sgp_gp_get_noise_scale": (C.c_int, [vp, c_double_p]),
     "sgp_gp_predict": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
                                  C.c_int64, c_double_p, c_double_p]),
     "sgp_gp_predict_cov": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int64,
@@ -131,6 +138,8 @@ PROTOTYPES = {
                                         c_double_p, c_double_p]),
     "sgp_grid_rank1_remove": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
                                         c_double_p, c_double_p]),
+    "sgp_grid_rank1_reweigh": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
+                                         c_double_p, c_double_p]),
     "sgp_grid_rankb_update": (C.c_int, [vp, vpp, C.c_int, c_int_p, C.c_double,
                                         c_double_p, c_double_p]),
     "sgp_grid_upload_Q": (C.c_int, [vp, c_double_p, c_double_p, c_double_p]),
@@ -639,6 +648,8 @@ class DeviceGP(object):
         self.version = 0
         self.appended = False
         self.removed = False
+        # ... `reweighed` = it re-weighted one observation in place (`reweigh`), likewise
+        self.reweighed = False
         # ... `block` = b > 0: it was a block append of b rows (`append_block`) whose block
         # record is on the device
         self.block = 0
@@ -652,12 +663,30 @@ class DeviceGP(object):
         except Exception:
             pass
 
-    def set_data(self, X, Y):
+    def _scales(self, noise_scale, rows):
+        """``noise_scale`` as ``rows`` float64 values, or None (all ones, the code without
+        scales).  Refused here, before anything is written: a scale that is not finite or
+        not positive."""
+        if noise_scale is None:
+            return None
+        r = np.ascontiguousarray(np.broadcast_to(f64(noise_scale).reshape(-1), (rows,)))
+        if not (np.all(np.isfinite(r)) and np.all(r > 0)):
+            raise ValueError("noise scales must be finite and positive, got %r" % (r,))
+        return r
+
+    def set_data(self, X, Y, noise_scale=None):
+        """Fit to ``(X, Y)``; ``noise_scale``: one scale ``r_i > 0`` per observation, its
+        noise variance is ``(noise_var + 1e-8) r_i`` (None: all ones)."""
         X = f64(X).reshape(-1, self.d)
         Y = f64(Y).reshape(-1)
+        r = self._scales(noise_scale, X.shape[0])
         info, jit = C.c_int(0), C.c_double(0)
-        rc = lib().sgp_gp_set_data(self.h, dptr(X), dptr(Y), X.shape[0],
-                                   C.byref(info), C.byref(jit))
+        if r is None:
+            rc = lib().sgp_gp_set_data(self.h, dptr(X), dptr(Y), X.shape[0],
+                                       C.byref(info), C.byref(jit))
+        else:
+            rc = lib().sgp_gp_set_data_w(self.h, dptr(X), dptr(Y), dptr(r), X.shape[0],
+                                         C.byref(info), C.byref(jit))
         if rc > 0 or info.value != 0:
             raise np.linalg.LinAlgError(
                 lib().sgp_last_error(self.ctx.h).decode())
@@ -665,7 +694,7 @@ class DeviceGP(object):
         self.n = X.shape[0]
         self.jitter = jit.value
         self.version += 1
-        self.appended = self.removed = False
+        self.appended = self.removed = self.reweighed = False
         self.block = 0
 
     def _hyper(self, variances, inv_ls):
@@ -685,7 +714,7 @@ class DeviceGP(object):
         rc = lib().sgp_gp_set_hyper(self.h, dptr(variances), dptr(inv_ls),
                                     float(noise_var), C.byref(info), C.byref(jit))
         self.version += 1
-        self.appended = self.removed = False
+        self.appended = self.removed = self.reweighed = False
         self.block = 0
         if rc > 0 or info.value != 0:
             self.n = 0
@@ -703,7 +732,7 @@ class DeviceGP(object):
         out = np.empty(2 + P + P * d)
         info = C.c_int(0)
         self.version += 1
-        self.appended = self.removed = False
+        self.appended = self.removed = self.reweighed = False
         self.block = 0
         self.ctx.check(lib().sgp_gp_lml(self.h, dptr(variances), dptr(inv_ls),
                                         float(noise_var), dptr(out), C.byref(info)))
@@ -720,7 +749,7 @@ class DeviceGP(object):
         out = np.empty(2 + P + P * d)
         info = C.c_int(0)
         self.version += 1
-        self.appended = self.removed = False
+        self.appended = self.removed = self.reweighed = False
         self.block = 0
         self.ctx.check(lib().sgp_gp_loo_lml(self.h, dptr(variances), dptr(inv_ls),
                                             float(noise_var), dptr(out), C.byref(info)))
@@ -742,22 +771,28 @@ class DeviceGP(object):
                                         % (info.value - 1))
         return mean, var, float(total.value)
 
-    def append(self, x, y):
+    def append(self, x, y, noise_scale=None):
         """One more observation by a bordered update; False = not possible
-        (no capacity / pivot not positive): the caller refits with set_data."""
+        (no capacity / pivot not positive): the caller refits with set_data.
+        ``noise_scale``: the scale of the new observation (None: 1)."""
         x = f64(x).reshape(self.d)
+        r = self._scales(noise_scale, 1)
         info = C.c_int(0)
-        self.ctx.check(lib().sgp_gp_append(self.h, dptr(x), float(y),
-                                           C.byref(info)))
+        if r is None:
+            self.ctx.check(lib().sgp_gp_append(self.h, dptr(x), float(y),
+                                               C.byref(info)))
+        else:
+            self.ctx.check(lib().sgp_gp_append_w(self.h, dptr(x), float(y), dptr(r),
+                                                 C.byref(info)))
         if info.value != 0:
             return False
         self.n += 1
         self.version += 1
-        self.appended, self.removed = True, False
+        self.appended, self.removed, self.reweighed = True, False, False
         self.block = 0
         return True
 
-    def append_block(self, X, y):
+    def append_block(self, X, y, noise_scale=None):
         """``b`` more observations (``1 <= b <= MAX_BLOCK``) by ONE bordered update with a
         ``b x b`` corner (``sgp_gp_append_block``): one read-back and one re-pack instead of
         ``b``.  False = not possible (no capacity / a pivot not positive), the GP is then
@@ -768,13 +803,19 @@ class DeviceGP(object):
         if y.size != b or not 1 <= b <= MAX_BLOCK:
             raise ValueError("a block of 1..%d rows with one value each, got X %r, y %r"
                              % (MAX_BLOCK, X.shape, y.shape))
+        r = self._scales(noise_scale, b)
         info = C.c_int(0)
-        self.ctx.check(lib().sgp_gp_append_block(self.h, dptr(X), dptr(y), b, C.byref(info)))
+        if r is None:
+            self.ctx.check(lib().sgp_gp_append_block(self.h, dptr(X), dptr(y), b,
+                                                     C.byref(info)))
+        else:
+            self.ctx.check(lib().sgp_gp_append_block_w(self.h, dptr(X), dptr(y), dptr(r), b,
+                                                       C.byref(info)))
         if info.value != 0:
             return False
         self.n += b
         self.version += 1
-        self.appended = self.removed = False
+        self.appended = self.removed = self.reweighed = False
         self.block = b
         return True
 
@@ -783,7 +824,7 @@ class DeviceGP(object):
         self.ctx.check(lib().sgp_gp_pop(self.h))
         self.n -= 1
         self.version += 1
-        self.appended = self.removed = False
+        self.appended = self.removed = self.reweighed = False
         self.block = 0
 
     def remove(self, index):
@@ -796,9 +837,38 @@ class DeviceGP(object):
             return False
         self.n -= 1
         self.version += 1
-        self.appended, self.removed = False, True
+        self.appended, self.removed, self.reweighed = False, True, False
         self.block = 0
         return True
+
+    def reweigh(self, index, y, r):
+        """Observation ``index`` (0 .. n-1) becomes ``(y, r)`` in place: value ``y``, noise
+        scale ``r``, by an O(n^2) update of the factor (``sgp_gp_reweigh``); ``n`` and the
+        inputs stay.  False = a pivot of the update is not positive: the GP is untouched
+        and the caller refits with set_data.  Refused with nothing written: an index
+        outside 0 .. n-1, a value that is not finite, a scale that is not finite or not
+        positive."""
+        index = int(index)
+        if not 0 <= index < self.n:
+            raise IndexError("row %d of %d observations" % (index, self.n))
+        y = float(y)
+        if not np.isfinite(y):
+            raise ValueError("the value of an observation must be finite, got %r" % (y,))
+        r = float(self._scales(r, 1)[0])
+        info = C.c_int(0)
+        self.ctx.check(lib().sgp_gp_reweigh(self.h, index, y, r, C.byref(info)))
+        if info.value != 0:
+            return False
+        self.version += 1
+        self.appended, self.removed, self.reweighed = False, False, True
+        self.block = 0
+        return True
+
+    def noise_scale(self):
+        """The ``n`` noise scales as the device holds them (ones without scales)."""
+        r = np.empty(self.n)
+        self.ctx.check(lib().sgp_gp_get_noise_scale(self.h, dptr(r)))
+        return r
 
     def predict(self, Xnew):
         Xnew = np.asarray(Xnew, dtype=np.float64)
@@ -914,6 +984,7 @@ class DeviceGP(object):
         twin.n_parts, twin.n, twin.jitter = self.n_parts, self.n, self.jitter
         twin.version, twin.appended = self.version, self.appended
         twin.removed = self.removed
+        twin.reweighed = self.reweighed
         twin.block = 0            # (a clone carries no block record)
         twin.serial = next(DeviceGP._serials)
         return twin
@@ -1067,6 +1138,16 @@ class DeviceGrid(object):
         w = np.ascontiguousarray(which, dtype=np.int32)
         out = np.empty(2)
         self.ctx.check(lib().sgp_grid_rank1_remove(
+            self.h, _gp_array(gps), len(gps), w.ctypes.data_as(c_int_p),
+            float(beta), dptr(fmin), None if defer else dptr(out)))
+        return (None, None) if defer else (out[0], bool(out[1]))
+
+    def rank1_reweigh(self, gps, which, beta, fmin, defer=False):
+        """``rank1_update`` after one ``DeviceGP.reweigh`` on the GPs of ``which``."""
+        fmin = f64(fmin)
+        w = np.ascontiguousarray(which, dtype=np.int32)
+        out = np.empty(2)
+        self.ctx.check(lib().sgp_grid_rank1_reweigh(
             self.h, _gp_array(gps), len(gps), w.ctypes.data_as(c_int_p),
             float(beta), dptr(fmin), None if defer else dptr(out)))
         return (None, None) if defer else (out[0], bool(out[1]))

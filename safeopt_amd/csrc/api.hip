@@ -129,6 +129,7 @@ int collect_gps(sgp_ctx* ctx, sgp_gp* const* gps, int G, int d, GpDev* host) {
           a->prov == b->prov &&
           memcmp(&a->kern, &b->kern, sizeof(KernDesc)) == 0 &&
           a->noise_var == b->noise_var && a->jitter == b->jitter &&
+          a->rhost == b->rhost &&        // (noise scales: both none, or the same values)
           // (the hashes only nominate: a collision must not hand one GP the other's
           // |L^-1 k|^2 -- the rows themselves decide, a few KB of memcmp per launch)
           a->xhost.size() == b->xhost.size() &&
@@ -343,7 +344,7 @@ void sgp_gp_destroy(sgp_gp* gp) {
   (void)hipStreamSynchronize(ctx->stream);
   DevBuf* bufs[] = {&gp->X, &gp->Y, &gp->Xpad, &gp->Xs, &gp->XA, &gp->alpha, &gp->Apack,
                     &gp->Linv, &gp->Kmat, &gp->work, &gp->tvec, &gp->updw,
-                    &gp->upd, &gp->blk};
+                    &gp->upd, &gp->blk, &gp->R};
   for (DevBuf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   delete gp;
@@ -360,6 +361,11 @@ static int fit_with_jitter(sgp_gp* gp, int* chol_info, double* jitter_used) {
   SGP_TRY(jitchol_loop(
       [&](double* dm) {
         *dm = gp->kern.kdiag + gp->noise_var + 1e-8;
+        if (!gp->rhost.empty()) {        // mean of the diagonal with noise scales
+          double rs = 0.0;
+          for (double r : gp->rhost) rs += r;
+          *dm = gp->kern.kdiag + (gp->noise_var + 1e-8) * (rs / double(gp->rhost.size()));
+        }
         return 0;
       },
       [&](double j, int* i) {
@@ -395,17 +401,45 @@ static int rewrite_hyper(sgp_gp* gp, const double* variances, const double* inv_
   gp->upd_valid = false;
   gp->rem_valid = false;
   gp->blk_valid = false;
+  gp->rw_valid = false;
   // (a refit at the current n: the history of appends and removals no longer matters)
   gp->prov = 0x9e3779b97f4a7c15ull ^ uint64_t(gp->n);
   return 0;
 }
 
+// The device image of the noise scales follows the host's (a GP without scales has none)
+static int sync_scales(sgp_gp* gp) {
+  if (gp->rhost.empty()) return 0;
+  sgp_ctx* ctx = gp->ctx;
+  SGP_TRY(sgp_reserve(ctx, &gp->R, size_t(std::max<int64_t>(gp->ld, gp->n)) * sizeof(double)));
+  return sgp_h2d(ctx, gp->R.p, gp->rhost.data(), gp->rhost.size() * sizeof(double));
+}
+
+static bool scales_ok(const double* r, int64_t n) {
+  for (int64_t i = 0; r && i < n; ++i)
+    if (!std::isfinite(r[i]) || !(r[i] > 0.0)) return false;
+  return true;
+}
+
+// the bits of a scale, folded into the history of a factor (sgp_gp::prov)
+static uint64_t scale_bits(double r) {
+  uint64_t u;
+  memcpy(&u, &r, sizeof(u));
+  return u * 0x9e3779b97f4a7c15ull;
+}
+
 int sgp_gp_set_data(sgp_gp* gp, const double* X, const double* Y, int64_t n,
                     int* chol_info, double* jitter_used) {
+  return sgp_gp_set_data_w(gp, X, Y, nullptr, n, chol_info, jitter_used);
+}
+
+int sgp_gp_set_data_w(sgp_gp* gp, const double* X, const double* Y, const double* r, int64_t n,
+                      int* chol_info, double* jitter_used) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, n >= 1 && n <= kMaxObservations, "n = %lld training points unsupported",
             (long long)n);
+  SGP_CHECK(ctx, scales_ok(r, n), "a noise scale is not finite or not positive");
   const int d = gp->kern.d;
   ++gp->data_version;
   gp->n = n;
@@ -427,6 +461,9 @@ int sgp_gp_set_data(sgp_gp* gp, const double* X, const double* Y, int64_t n,
     }
     gp->prov = 0x9e3779b97f4a7c15ull ^ uint64_t(n);
   }
+  if (r) gp->rhost.assign(r, r + n);
+  else gp->rhost.clear();
+  SGP_TRY(sync_scales(gp));
   return fit_with_jitter(gp, chol_info, jitter_used);
 }
 
@@ -502,10 +539,15 @@ int sgp_gp_loo(sgp_gp* gp, double* mean, double* var, double* sum_log_pred, int*
 }
 
 int sgp_gp_append(sgp_gp* gp, const double* x, double y, int* info) {
+  return sgp_gp_append_w(gp, x, y, nullptr, info);
+}
+
+int sgp_gp_append_w(sgp_gp* gp, const double* x, double y, const double* r, int* info) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, gp->n > 0, "GP has no data");
   SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
+  SGP_CHECK(ctx, scales_ok(r, 1), "the noise scale is not finite or not positive");
   *info = -1;
   if (gp->n + 1 > gp->ld) return 0;  // no room: caller refits with set_data
   const int d = gp->kern.d;
@@ -515,25 +557,37 @@ int sgp_gp_append(sgp_gp* gp, const double* x, double y, int* info) {
   SGP_TRY(sgp_h2d(ctx, Y + gp->n, &y, sizeof(double)));
   const int64_t n0 = gp->n;
   ++gp->data_version;
-  SGP_TRY(append_gp(gp, y, info));
+  SGP_TRY(append_gp(gp, y, info, r ? *r : 1.0));
   if (gp->n == n0 + 1) {
+    if (r || !gp->rhost.empty()) {
+      gp->rhost.resize(size_t(n0), 1.0);
+      gp->rhost.push_back(r ? *r : 1.0);
+      SGP_TRY(sync_scales(gp));
+    }
     gp->xhost.resize(size_t(n0) * d);
     gp->xhost.insert(gp->xhost.end(), x, x + d);
     gp->xhash.resize(size_t(n0));
     gp->xhash.push_back(hash_rows(n0 > 0 ? gp->xhash.back() : 14695981039346656037ull, x,
                                   size_t(d)));
     gp->prov = gp->prov * 1099511628211ull + 2;
+    if (r) gp->prov ^= scale_bits(*r);
   }
   return 0;
 }
 
 int sgp_gp_append_block(sgp_gp* gp, const double* X, const double* y, int b, int* info) {
+  return sgp_gp_append_block_w(gp, X, y, nullptr, b, info);
+}
+
+int sgp_gp_append_block_w(sgp_gp* gp, const double* X, const double* y, const double* rs, int b,
+                          int* info) {
   sgp_ctx* ctx = gp->ctx;
   SGP_HIP(ctx, hipSetDevice(ctx->device));
   SGP_CHECK(ctx, gp->n > 0, "GP has no data");
   SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
   SGP_CHECK(ctx, b >= 1 && b <= SGP_MAX_BLOCK, "a block of %d observations (1..%d)", b,
             SGP_MAX_BLOCK);
+  SGP_CHECK(ctx, scales_ok(rs, b), "a noise scale is not finite or not positive");
   *info = -1;
   if (gp->n + b > gp->ld) return 0;  // no room: caller refits with set_data
   const int d = gp->kern.d;
@@ -542,7 +596,7 @@ int sgp_gp_append_block(sgp_gp* gp, const double* X, const double* y, int b, int
   double* Yd = static_cast<double*>(gp->Y.p);
   SGP_TRY(sgp_h2d(ctx, Xd + size_t(n0) * d, X, size_t(b) * d * sizeof(double)));
   SGP_TRY(sgp_h2d(ctx, Yd + n0, y, size_t(b) * sizeof(double)));
-  SGP_TRY(append_block_gp(gp, b, info));
+  SGP_TRY(append_block_gp(gp, b, info, rs));
   if (gp->n != n0 + b) return 0;               // a pivot is not positive: the GP is as it was
   // the books of b one-row appends: equal histories keep a shared factor shared
   gp->data_version += uint64_t(b);
@@ -553,6 +607,12 @@ int sgp_gp_append_block(sgp_gp* gp, const double* X, const double* y, int b, int
     gp->xhash.push_back(hash_rows(gp->xhash.empty() ? 14695981039346656037ull : gp->xhash.back(),
                                   X + size_t(r) * d, size_t(d)));
     gp->prov = gp->prov * 1099511628211ull + 2;
+    if (rs) gp->prov ^= scale_bits(rs[r]);
+  }
+  if (rs || !gp->rhost.empty()) {
+    gp->rhost.resize(size_t(n0), 1.0);
+    for (int j = 0; j < b; ++j) gp->rhost.push_back(rs ? rs[j] : 1.0);
+    SGP_TRY(sync_scales(gp));
   }
   return 0;
 }
@@ -566,6 +626,7 @@ int sgp_gp_pop(sgp_gp* gp) {
   SGP_TRY(pop_gp(gp));
   gp->xhost.resize(size_t(gp->n) * gp->kern.d);
   gp->xhash.resize(size_t(gp->n));
+  if (!gp->rhost.empty()) gp->rhost.resize(size_t(gp->n));   // (the device image: a prefix)
   gp->prov = gp->prov * 1099511628211ull + 3;
   return 0;
 }
@@ -593,7 +654,52 @@ int sgp_gp_remove(sgp_gp* gp, int64_t index, int* info) {
   }
   // (the row that left is part of the history: equal removals keep a shared factor shared)
   gp->prov = (gp->prov * 1099511628211ull + 5) ^ (uint64_t(index) * 0x9e3779b97f4a7c15ull);
+  if (!gp->rhost.empty()) {
+    gp->rhost.erase(gp->rhost.begin() + i);
+    SGP_TRY(sync_scales(gp));
+  }
   return 0;
+}
+
+int sgp_gp_reweigh(sgp_gp* gp, int64_t index, double y_new, double r_new, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  SGP_CHECK(ctx, gp->factored, "GP is not fitted (infeasible hyper-parameters)");
+  SGP_CHECK(ctx, index >= 0 && index < gp->n, "row %lld of %lld training points",
+            (long long)index, (long long)gp->n);
+  SGP_CHECK(ctx, std::isfinite(y_new), "y_new is not finite");
+  SGP_CHECK(ctx, scales_ok(&r_new, 1), "the noise scale is not finite or not positive");
+  *info = -1;
+  const size_t i = size_t(index);
+  const double r_old = gp->rhost.empty() ? 1.0 : gp->rhost[i];
+  const double s = gp->noise_var + 1e-8;
+  const double delta = s * r_new - s * r_old;
+  SGP_TRY(reweigh_gp(gp, int(index), y_new, delta, info));
+  if (*info != 0) return 0;                    // pivot not positive: the GP is as it was
+  ++gp->data_version;
+  if (r_new != r_old) {
+    gp->rhost.resize(size_t(gp->n), 1.0);
+    gp->rhost[i] = r_new;
+    SGP_TRY(sync_scales(gp));
+  }
+  // (equal re-weightings keep a shared factor shared)
+  gp->prov = (gp->prov * 1099511628211ull + 7) ^ (uint64_t(index) * 0x9e3779b97f4a7c15ull) ^
+             scale_bits(r_new);
+  return 0;
+}
+
+int sgp_gp_get_noise_scale(sgp_gp* gp, double* r_out) {
+  sgp_ctx* ctx = gp->ctx;
+  SGP_CHECK(ctx, gp->n > 0, "GP has no data");
+  const size_t n = size_t(gp->n);
+  if (gp->rhost.empty()) {
+    for (size_t i = 0; i < n; ++i) r_out[i] = 1.0;
+    return 0;
+  }
+  // the device image, which is what the kernels read
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  return sgp_d2h(ctx, r_out, gp->R.p, n * sizeof(double));
 }
 
 int sgp_gp_predict(sgp_gp* gp, const double* Xnew, int64_t N,
@@ -735,6 +841,8 @@ int sgp_gp_clone(sgp_gp* src, sgp_gp** out) {
   gp->prov = src->prov;
   gp->upd_valid = src->upd_valid;
   gp->rem_valid = src->rem_valid;
+  gp->rw_valid = src->rw_valid;
+  gp->rhost = src->rhost;
   gp->factored = true;
   const int d = src->kern.d, ld0 = src->ld;
   const int ld = std::max(ld0, int((src->n + SGP_MAX_BATCH + 63) / 64) * 64);
@@ -771,6 +879,7 @@ int sgp_gp_clone(sgp_gp* src, sgp_gp** out) {
     sgp_set_error(ctx, "sgp_gp_clone: device copy of L^-1 failed");
     return fail(-1);
   }
+  if (int rc = sync_scales(gp)) return fail(rc);
   if (int rc = publish_gp(gp)) return fail(rc);
   *out = gp;
   return 0;
@@ -1157,10 +1266,11 @@ int sgp_grid_posterior(sgp_grid* g, sgp_gp* const* gps, int G) {
   return 0;
 }
 
-// sgp_grid_rank1_update / sgp_grid_rank1_remove: the flagged GPs carry the record of an
-// append / of a removal
+// sgp_grid_rank1_update / sgp_grid_rank1_remove / sgp_grid_rank1_reweigh: the flagged GPs
+// carry the record of an append / of a removal / of a re-weighting (the three flags exclude
+// each other: every entry point refuses the other two's records)
 static int rank1_refresh(sgp_grid* g, sgp_gp* const* gps, int G, const int* which, double beta,
-                         const double* fmin, double* out2, bool remove) {
+                         const double* fmin, double* out2, int kind) {
   sgp_ctx* ctx = g->ctx;
   GpDev host[SGP_MAX_GPS];
   SGP_TRY(grid_gps(g, gps, G, host));
@@ -1169,9 +1279,12 @@ static int rank1_refresh(sgp_grid* g, sgp_gp* const* gps, int G, const int* whic
     ra.fmin[i] = (i < G) ? fmin[i] : -INFINITY;
     ra.which[i] = (i < G) ? which[i] : 0;
     if (i < G && which[i]) {
-      if (remove)
+      if (kind == kRank1Remove)
         SGP_CHECK(ctx, gps[i]->rem_valid,
                   "GP %d has no removal record for a rank-1 update", i);
+      else if (kind == kRank1Reweigh)
+        SGP_CHECK(ctx, gps[i]->rw_valid,
+                  "GP %d has no reweigh record for a rank-1 update", i);
       else
         SGP_CHECK(ctx, gps[i]->upd_valid,
                   "GP %d has no append record for a rank-1 update", i);
@@ -1185,19 +1298,24 @@ static int rank1_refresh(sgp_grid* g, sgp_gp* const* gps, int G, const int* whic
   ra.beta = beta;
   SweepPoints sp{g->pts, g->N, 1, g->N};
   // (post_valid stays as it is: the refresh keeps a swept posterior current, it makes none)
-  SGP_TRY(launch_rank1(ctx, g->gpdev, G, g->d, sp, ra, remove));
+  SGP_TRY(launch_rank1(ctx, g->gpdev, G, g->d, sp, ra, kind));
   return finish_safe_partials(g, rank1_num_blocks(g->N), out2);
 }
 
 int sgp_grid_rank1_update(sgp_grid* g, sgp_gp* const* gps, int G,
                           const int* which, double beta, const double* fmin,
                           double* out2) {
-  return rank1_refresh(g, gps, G, which, beta, fmin, out2, false);
+  return rank1_refresh(g, gps, G, which, beta, fmin, out2, kRank1Append);
 }
 
 int sgp_grid_rank1_remove(sgp_grid* g, sgp_gp* const* gps, int G, const int* which,
                           double beta, const double* fmin, double* out2) {
-  return rank1_refresh(g, gps, G, which, beta, fmin, out2, true);
+  return rank1_refresh(g, gps, G, which, beta, fmin, out2, kRank1Remove);
+}
+
+int sgp_grid_rank1_reweigh(sgp_grid* g, sgp_gp* const* gps, int G, const int* which,
+                           double beta, const double* fmin, double* out2) {
+  return rank1_refresh(g, gps, G, which, beta, fmin, out2, kRank1Reweigh);
 }
 
 int sgp_grid_rankb_update(sgp_grid* g, sgp_gp* const* gps, int G, const int* which,

@@ -328,9 +328,15 @@ struct sgp_gp {
                            // in the layout of an append of that row to the reduced GP
   bool blk_valid = false;  // `blk` describes the step to the current data: the last change was
                            // a block append (sgp_gp_append_block); a clone carries none
+  bool rw_valid = false;   // ... as the record of a RE-WEIGHTING in place (sgp_gp_reweigh): x_i,
+                           // w = -p / P_ii off row i, upd[0] = P_ii eta, upd[1] = tau P_ii^2
+  // noise scales r_i of the observations (Ky = K + diag((noise_var + 1e-8) r_i) + jitter I):
+  // empty = the GP never received one, all ones, and runs the code without scales.  `R` is the
+  // device image of rhost (sync_scales), read by the fit and the likelihood kernels.
+  std::vector<double> rhost;
   bool factored = true;    // false: sgp_gp_lml / sgp_gp_loo_lml met a non-positive pivot: the data are
                            // resident, the factor is not valid until the next fit
-  DevBuf X, Y, Xpad, Xs, XA, alpha, Apack, Linv, Kmat, work, tvec, updw, upd, blk;
+  DevBuf X, Y, Xpad, Xs, XA, alpha, Apack, Linv, Kmat, work, tvec, updw, upd, blk, R;
   GpDev dev;      // filled by set_data
 };
 
@@ -439,7 +445,7 @@ int tri_mtv_dense(sgp_ctx* ctx, const double* Li, int64_t ld, int n, const doubl
 int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
                          int64_t n1, const double* X2, int64_t n2, double* out,
                          int64_t ld, int symmetric_diag, double diag_add,
-                         int64_t n_valid);
+                         int64_t n_valid, const double* diag_vec = nullptr);
 // Kmat -> Linv, Apack, alpha (info_dev_out: the pivot word stays on the device, factor.hip)
 int factor_gp(sgp_gp* gp, int* info, const int** info_dev_out = nullptr);
 // hyper.hip: log marginal likelihood and gradient of a GP factor_gp has just factorised
@@ -450,11 +456,20 @@ int launch_loo_lml(sgp_gp* gp, const int* info_dev, double* out_dev);
 // leave-one-out predictions from the factor as it stands: *out_dev = [mean | var] (*np doubles
 // each, n rounded up to 64) | sum of the log predictive densities | info (as a double)
 int launch_loo(sgp_gp* gp, const double** out_dev, int* np);
-int append_gp(sgp_gp* gp, double y, int* info);  // row n already in gp->X
+// row n already in gp->X; r: the noise scale of the new row (1: as without scales)
+int append_gp(sgp_gp* gp, double y, int* info, double r = 1.0);
 // rows n .. n + b - 1 already in gp->X / gp->Y, 1 <= b <= SGP_MAX_BLOCK, n + b <= ld; *info != 0
-// leaves the GP untouched
-int append_block_gp(sgp_gp* gp, int b, int* info);
+// leaves the GP untouched; r: the b noise scales of the new rows, or null (all ones)
+int append_block_gp(sgp_gp* gp, int b, int* info, const double* r = nullptr);
 int pop_gp(sgp_gp* gp);
+// observation `index` becomes (y_new, noise variance + delta) in place;
+// *info != 0 leaves the GP untouched
+int reweigh_gp(sgp_gp* gp, int index, double y_new, double delta, int* info);
+// the diagonal of Ky at a row of noise scale r, k(x,x) + (noise_var + 1e-8) r + jitter, in the
+// evaluation order of the unscaled code: at r = 1 the same bits
+inline double row_prior(const sgp_gp* gp, double r) {
+  return gp->kern.kdiag + gp->noise_var * r + 1e-8 * r + gp->jitter;
+}
 // row `index` leaves (0 <= index < n, n >= 2); *info != 0 leaves the GP untouched
 int remove_gp(sgp_gp* gp, int index, int* info);
 int publish_gp(sgp_gp* gp);  // Apack / Xpad / Xs / dev descriptor from Linv
@@ -713,9 +728,11 @@ struct Rank1Args {
   int which[SGP_MAX_GPS];
 };
 int rank1_num_blocks(int64_t N);
-// remove: the records are removal records (sgp_gp_remove) -- both signs of the update flip
+// kind: the records are append records, removal records (sgp_gp_remove) -- both signs of the
+// update flip -- or reweigh records (sgp_gp_reweigh): mean += c u0, var += c^2 u1
+constexpr int kRank1Append = 0, kRank1Remove = 1, kRank1Reweigh = 2;
 int launch_rank1(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d,
-                 SweepPoints pts, Rank1Args ra, bool remove = false);
+                 SweepPoints pts, Rank1Args ra, int kind = kRank1Append);
 // block.hip: the same refresh after a block append on the flagged GPs (their records: blk); partials
 // as launch_rank1 leaves them (rank1_num_blocks)
 struct RankbArgs {

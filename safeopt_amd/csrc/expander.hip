@@ -1343,12 +1343,17 @@ namespace {
 // mean -= c alpha_i, var += c^2 P_ii, with c(x) = k(x, x_i) - k(X_new, x)^T w as before.
 constexpr int kRank1Lds = 6144;   // doubles of staged training data (48 KB)
 
-// mean / var of a row after the record {u0, u1} of an append (of a removal: kRemove)
-template <bool kRemove>
+// mean / var of a row after the record {u0, u1} of an append (kKind = kRank1Append), of a
+// removal, or of a re-weighting in place (sgp_gp_reweigh: cx = c(x) / P_ii, u0 = P_ii eta, u1 =
+// tau P_ii^2 of either sign)
+template <int kKind>
 __device__ __forceinline__ void rank1_apply(double cx, double u0, double u1, double& mean,
                                             double& var) {
-  if (kRemove) {
+  if (kKind == kRank1Remove) {
     mean = fma(-cx, u0, mean);
+    var = fmax(var + cx * cx * u1, 1e-15);
+  } else if (kKind == kRank1Reweigh) {
+    mean = fma(cx, u0, mean);
     var = fmax(var + cx * cx * u1, 1e-15);
   } else {
     mean = fma(cx, u0, mean);
@@ -1356,7 +1361,7 @@ __device__ __forceinline__ void rank1_apply(double cx, double u0, double u1, dou
   }
 }
 
-template <int D, bool kRemove>
+template <int D, int kKind>
 __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
                                                SweepPoints pts, Rank1Args ra) {
   __shared__ double tab[kExpTabSize];
@@ -1390,7 +1395,7 @@ __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
     double var = ra.var[int64_t(g) * pts.N + rrow];
     if (ra.which[g] && gps[g].share >= 0 && have_cx) {
       const GpDev& gp = gps[g];
-      rank1_apply<kRemove>(cx_keep, gp.upd[0], gp.upd[1], mean, var);
+      rank1_apply<kKind>(cx_keep, gp.upd[0], gp.upd[1], mean, var);
       if (writer) {
         ra.mean[int64_t(g) * pts.N + row] = mean;
         ra.var[int64_t(g) * pts.N + row] = var;
@@ -1427,7 +1432,7 @@ __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
       const double cx = kf.raw(x, gp.upd + 2, tab) - dot;
       cx_keep = cx;
       have_cx = true;
-      rank1_apply<kRemove>(cx, gp.upd[0], gp.upd[1], mean, var);
+      rank1_apply<kKind>(cx, gp.upd[0], gp.upd[1], mean, var);
       if (writer) {
         ra.mean[int64_t(g) * pts.N + row] = mean;
         ra.var[int64_t(g) * pts.N + row] = var;
@@ -1459,16 +1464,19 @@ __global__ __launch_bounds__(256) void k_rank1(const GpDev* gps, int G,
 int rank1_num_blocks(int64_t N) { return int((N + 63) / 64); }
 
 int launch_rank1(sgp_ctx* ctx, const GpDev* gps_dev, int G, int d,
-                 SweepPoints pts, Rank1Args ra, bool remove) {
+                 SweepPoints pts, Rank1Args ra, int kind) {
   if (pts.N <= 0) return 0;
   const int nblocks = rank1_num_blocks(pts.N);
 #define R1_CASE(DD)                                                           \
   case DD:                                                                    \
-    if (remove)                                                               \
-      hipLaunchKernelGGL((k_rank1<DD, true>), dim3(nblocks), dim3(256), 0,    \
+    if (kind == kRank1Remove)                                                 \
+      hipLaunchKernelGGL((k_rank1<DD, kRank1Remove>), dim3(nblocks), dim3(256), 0,  \
+                         ctx->stream, gps_dev, G, pts, ra);                   \
+    else if (kind == kRank1Reweigh)                                           \
+      hipLaunchKernelGGL((k_rank1<DD, kRank1Reweigh>), dim3(nblocks), dim3(256), 0, \
                          ctx->stream, gps_dev, G, pts, ra);                   \
     else                                                                      \
-      hipLaunchKernelGGL((k_rank1<DD, false>), dim3(nblocks), dim3(256), 0,   \
+      hipLaunchKernelGGL((k_rank1<DD, kRank1Append>), dim3(nblocks), dim3(256), 0,  \
                          ctx->stream, gps_dev, G, pts, ra);                   \
     break;
   switch (d) {

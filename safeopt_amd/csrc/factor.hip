@@ -23,14 +23,16 @@ namespace {
 constexpr int NB = 32;  // leaf size
 
 // ---- covariance matrix --------------------------------------------------------
-// out[i*ld + j] = k(X1_i, X2_j) (+ diag_add on i == j when symmetric_diag).
+// out[i*ld + j] = k(X1_i, X2_j) (+ diag_add on i == j when symmetric_diag; diag_vec != null:
+// + diag_vec[i] instead, the diagonal of a GP with noise scales -- one addend chosen, one
+// addition, so that equal addends give equal bits).
 // Rows/cols >= n_valid (padding of a square factorisation matrix) become the
 // identity so the padded Cholesky stays well defined.
 template <int D>
 __global__ void k_kernel_matrix(KernDesc kd, const double* X1, int64_t n1,
                                 const double* X2, int64_t n2, double* out,
                                 int64_t ld, int symmetric_diag, double diag_add,
-                                int64_t n_valid) {
+                                int64_t n_valid, const double* diag_vec) {
   const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   const int64_t i = int64_t(blockIdx.y) * blockDim.y + threadIdx.y;
   if (i >= n1 || j >= n2) return;
@@ -45,9 +47,19 @@ __global__ void k_kernel_matrix(KernDesc kd, const double* X1, int64_t n1,
       b[k] = X2[j * D + k];
     }
     v = kern_eval<D>(kd, a, b);
-    if (symmetric_diag && i == j) v += diag_add;
+    if (symmetric_diag && i == j) {
+      const double add = diag_vec ? diag_vec[i] : diag_add;
+      v += add;
+    }
   }
   out[i * ld + j] = v;
+}
+
+// The diagonal addends of a GP with noise scales: s r_i + jitter (at r_i = 1 the bits of the
+// scalar s + jitter of a GP without scales).
+__global__ void k_scaled_diag(double* out, int n, const double* r, double s, double jitter) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = fma(s, r[i], jitter);
 }
 
 // ---- leaf: 32x32 Cholesky + inverse of the factor, one workgroup --------------
@@ -383,7 +395,7 @@ int tri_mtv_dense(sgp_ctx* ctx, const double* Li, int64_t ld, int n, const doubl
 int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
                          int64_t n1, const double* X2, int64_t n2, double* out,
                          int64_t ld, int symmetric_diag, double diag_add,
-                         int64_t n_valid) {
+                         int64_t n_valid, const double* diag_vec) {
   if (n1 <= 0 || n2 <= 0) return 0;
   dim3 block(64, 4);
   dim3 grid(unsigned((n2 + 63) / 64), unsigned((n1 + 3) / 4));
@@ -391,7 +403,7 @@ int launch_kernel_matrix(sgp_ctx* ctx, const KernDesc& kd, const double* X1,
   case DD:                                                                     \
     hipLaunchKernelGGL(k_kernel_matrix<DD>, grid, block, 0, ctx->stream, kd,   \
                        X1, n1, X2, n2, out, ld, symmetric_diag, diag_add,      \
-                       n_valid);                                               \
+                       n_valid, diag_vec);                                     \
     break;
   switch (kd.d) {
     KM_CASE(1) KM_CASE(2) KM_CASE(3) KM_CASE(4)
@@ -479,11 +491,19 @@ int factor_gp(sgp_gp* gp, int* info, const int** info_dev_out) {
   gp->upd_valid = false;
   gp->rem_valid = false;
   gp->blk_valid = false;
+  gp->rw_valid = false;
 
   // padded rows of X are never read: n_valid = n turns them into identity
+  const double* diag_vec = nullptr;
+  if (!gp->rhost.empty()) {          // (tvec is free until alpha is formed)
+    hipLaunchKernelGGL(k_scaled_diag, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, tv, n,
+                       static_cast<const double*>(gp->R.p), gp->noise_var + 1e-8, gp->jitter);
+    SGP_HIP(ctx, hipGetLastError());
+    diag_vec = tv;
+  }
   SGP_TRY(launch_kernel_matrix(ctx, gp->kern, static_cast<double*>(gp->X.p),
                                nf, static_cast<double*>(gp->X.p), nf, K, ld, 1,
-                               gp->noise_var + 1e-8 + gp->jitter, n));
+                               gp->noise_var + 1e-8 + gp->jitter, n, diag_vec));
   SGP_HIP(ctx, hipMemsetAsync(Li, 0, mat, ctx->stream));
   SGP_HIP(ctx, hipMemsetAsync(info_dev, 0, sizeof(int), ctx->stream));
   SGP_TRY(factor_rec(ctx, K, Li, T, ld, 0, nf, info_dev));
@@ -566,7 +586,7 @@ __global__ __launch_bounds__(1024) void k_append_finish(
 
 // gp->X already holds the new row at index gp->n (uploaded by the caller);
 // gp->Y gets y.  On success n grows by one; *info != 0 leaves the GP untouched.
-int append_gp(sgp_gp* gp, double y, int* info) {
+int append_gp(sgp_gp* gp, double y, int* info, double r) {
   sgp_ctx* ctx = gp->ctx;
   const int n = int(gp->n), ld = gp->ld, d = gp->kern.d;
   double* Li = static_cast<double*>(gp->Linv.p);
@@ -583,7 +603,7 @@ int append_gp(sgp_gp* gp, double y, int* info) {
   SGP_TRY(launch_tri_mv(ctx, Li, ld, n, Kc, ld, 1, Tt, ld));
   SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, Tt, ld, 1, Wt, ld, n));
   const int np_new = (n + 1 + 15) / 16 * 16;
-  const double prior = gp->kern.kdiag + gp->noise_var + 1e-8 + gp->jitter;
+  const double prior = row_prior(gp, r);
   hipLaunchKernelGGL(k_append_finish, dim3(1), dim3(1024), 0, ctx->stream, Li,
                      int64_t(ld), n, d, Kc, Tt, Wt, prior, y, xnew,
                      static_cast<double*>(gp->alpha.p),
@@ -598,6 +618,7 @@ int append_gp(sgp_gp* gp, double y, int* info) {
   gp->upd_valid = true;
   gp->rem_valid = false;
   gp->blk_valid = false;
+  gp->rw_valid = false;
   return publish_gp(gp);
 }
 
@@ -612,9 +633,12 @@ int append_gp(sgp_gp* gp, double y, int* info) {
 // striding, folded by shuffles; thread 0 factors the corner with k_append_finish's pivot rule
 // (pivot j = the s2 a one-row append of row j behind rows 0 .. j-1 would meet); nothing of the
 // GP is written before every pivot has passed.  blk receives the block record (common.h, kBlk*).
+struct BlockPriors {
+  double v[SGP_MAX_BLOCK];   // k(x,x) + (noise + 1e-8) r_j + jitter of new row j
+};
 __global__ __launch_bounds__(1024) void k_append_block_finish(
     double* Li, int64_t ld, int n0, int b, const double* Kc, const double* Tt, const double* Wt,
-    int64_t pitch, const double* Knn, double prior, const double* ynew, double* alpha,
+    int64_t pitch, const double* Knn, BlockPriors pri, const double* ynew, double* alpha,
     double* blk, int n_pad_new, int* info) {
   constexpr int B = SGP_MAX_BLOCK;
   __shared__ double cm[B][B + 1];    // T^T T (lower), then Lc
@@ -647,6 +671,7 @@ __global__ __launch_bounds__(1024) void k_append_block_finish(
   if (tid == 0) {
     for (int j = 0; j < b && bad == 0; ++j) {
       for (int c = 0; c <= j; ++c) {
+        const double prior = pri.v[j];
         double s = (c == j ? prior : Knn[j * B + c]) - cm[j][c];
         for (int k = 0; k < c; ++k) s -= cm[j][k] * cm[c][k];
         if (c < j) {
@@ -717,7 +742,7 @@ __global__ __launch_bounds__(1024) void k_append_block_finish(
 
 // gp->X / gp->Y already hold the new rows at gp->n .. gp->n + b - 1 (uploaded by the caller).
 // On success n grows by b; *info != 0 leaves the GP untouched.
-int append_block_gp(sgp_gp* gp, int b, int* info) {
+int append_block_gp(sgp_gp* gp, int b, int* info, const double* r) {
   sgp_ctx* ctx = gp->ctx;
   const int n = int(gp->n), ld = gp->ld, d = gp->kern.d;
   double* Li = static_cast<double*>(gp->Linv.p);
@@ -739,7 +764,8 @@ int append_block_gp(sgp_gp* gp, int b, int* info) {
   SGP_TRY(launch_tri_mv(ctx, Li, ld, n, Kc, ld, b, Tt, ld));
   SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, Tt, ld, b, Wt, ld, n));
   const int np_new = (n + b + 15) / 16 * 16;
-  const double prior = gp->kern.kdiag + gp->noise_var + 1e-8 + gp->jitter;
+  BlockPriors prior;
+  for (int j = 0; j < SGP_MAX_BLOCK; ++j) prior.v[j] = row_prior(gp, (r && j < b) ? r[j] : 1.0);
   hipLaunchKernelGGL(k_append_block_finish, dim3(1), dim3(1024), 0, ctx->stream, Li,
                      int64_t(ld), n, b, Kc, Tt, Wt, int64_t(ld), Knn, prior,
                      static_cast<const double*>(gp->Y.p) + n, static_cast<double*>(gp->alpha.p),
@@ -753,6 +779,7 @@ int append_block_gp(sgp_gp* gp, int b, int* info) {
   gp->upd_valid = false;
   gp->rem_valid = false;
   gp->blk_valid = true;
+  gp->rw_valid = false;
   return publish_gp(gp);
 }
 
@@ -769,6 +796,7 @@ int pop_gp(sgp_gp* gp) {
   gp->upd_valid = false;
   gp->rem_valid = false;
   gp->blk_valid = false;
+  gp->rw_valid = false;
   SGP_TRY(launch_tri_mv(ctx, Li, ld, n, static_cast<double*>(gp->Y.p), 0, 1, tv, 0));
   SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, tv, 0, 1,
                          static_cast<double*>(gp->alpha.p), 0, gp->n_pad));
@@ -974,6 +1002,180 @@ int remove_gp(sgp_gp* gp, int index, int* info) {
   gp->upd_valid = false;
   gp->rem_valid = true;
   gp->blk_valid = false;
+  gp->rw_valid = false;
+  return publish_gp(gp);
+}
+
+// ---- re-weighting ONE observation in place ------------------------------------------------
+// Ky' = Ky + delta e_i e_i^T (delta = s (r' - r)), y_i -> y_i + dy.  With
+// M = L^-1, c = column i of M, P_ii = |c|^2, p = M^T c:
+//   tau = delta / (1 + delta P_ii),  eta = (dy - delta alpha_i) / (1 + delta P_ii),
+//   alpha' = alpha + eta p,  Ky'^-1 = M^T (I - tau c c^T) M = (F M)^T (F M),
+// F lower triangular with F^T F = I - tau c c^T.  With the running sums q_k = 1 + delta
+// sum_{i <= j <= k} c_j^2 (q_{i-1} = 1, q_{n-1} = 1 + delta P_ii) the rows of F M are
+//   M'[k] = sqrt(q_{k-1} / q_k) M[k] - delta c_k / sqrt(q_{k-1} q_k) S_k,
+//   S_k = sum_{i <= j < k} c_j M[j]                      (k = i .. n-1; rows above i stay).
+// Every q_k lies between 1 and 1 + delta P_ii: all are positive exactly when the last one is.
+// The scratch is that of a removal: cs holds sqrt(q_{k-1} / q_k), sn the factor of S_k.
+
+// c, P_ii and the row coefficients: one workgroup, the scan of k_remove_coef.  info: 0, or
+// index + 1 when P_ii or a q_k is not positive and finite.
+__global__ __launch_bounds__(1024) void k_reweigh_coef(const double* Li, int64_t ld, int n, int i,
+                                                       double delta, RemoveBufs rb) {
+  __shared__ double sh[1024 / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int k = tid; k < i; k += 1024) rb.c[k] = 0.0;
+  const int m = n - i;                         // entries i .. n-1 of the column
+  const int per = (m + 1023) / 1024;
+  const int e0 = min(tid * per, m), e1 = min(e0 + per, m);
+  double local = 0.0;
+  for (int e = e0; e < e1; ++e) {
+    const double ck = Li[int64_t(i + e) * ld + i];
+    rb.c[i + e] = ck;
+    local = fma(ck, ck, local);
+  }
+  double v = local;                            // inclusive scan of the wave's runs
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  if (lane == 63) sh[wave] = v;
+  double before = __shfl_up(v, 1, 64);         // the runs in front of this one, in the wave
+  if (lane == 0) before = 0.0;
+  __syncthreads();
+  double base = 0.0, total = 0.0;
+  for (int w = 0; w < 1024 / 64; ++w) {
+    if (w < wave) base += sh[w];
+    total += sh[w];
+  }
+  bool bad = false;
+  double s = base + before;                    // sum of squares in front of the run
+  for (int e = e0; e < e1; ++e) {
+    const double ck = rb.c[i + e];             // (written by this thread)
+    const double s1 = fma(ck, ck, s);
+    const double q0 = fma(delta, s, 1.0), q1 = fma(delta, s1, 1.0);
+    rb.cs[i + e] = sqrt(q0 / q1);
+    rb.sn[i + e] = -delta * ck / sqrt(q0 * q1);
+    bad = bad || !(q1 > 0.0) || !isfinite(q1);
+    s = s1;
+  }
+  const double qn = fma(delta, total, 1.0);
+  bad = bad || !(total > 0.0) || !isfinite(total) || !(qn > 0.0) || !isfinite(qn);
+  const int bad_any = __syncthreads_or(bad);
+  if (tid == 0) {
+    rb.rec[1] = total;
+    rb.info[0] = bad_any ? i + 1 : 0;
+  }
+}
+
+// The images of what changes besides L^-1: alpha' (zero behind n, up to n_pad) and the record
+// in the layout of an append record: x_i, w = -p / P_ii off row i (so that k(x, x_i) -
+// k(X, x)^T w = c(x) / P_ii with c(x) = k(X, x)^T p), upd[0] = P_ii eta, upd[1] = tau P_ii^2.
+__global__ void k_reweigh_stage(const double* alpha, const double* X, const double* Y, int n,
+                                int d, int i, int n_pad, double y_new, double delta,
+                                RemoveBufs rb) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const double Pii = rb.rec[1];
+  const double q = fma(delta, Pii, 1.0);
+  const double eta = ((y_new - Y[i]) - delta * alpha[i]) / q;
+  if (e < n_pad) {
+    double w = 0.0, a = 0.0;
+    if (e < n) {
+      if (e != i) w = -rb.p[e] / Pii;
+      a = fma(eta, rb.p[e], alpha[e]);
+    }
+    rb.w[e] = w;
+    rb.alpha[e] = a;
+  }
+  if (e == 0) {
+    rb.X[0] = Pii * eta;                       // (rec[1] is read by every thread: staged apart)
+    rb.X[1] = delta / q * Pii * Pii;
+  }
+  if (e < d) rb.rec[2 + e] = X[i * d + e];
+}
+
+// out = F M; one thread per column j of M, rows k = max(i, j) .. n-1 in order with the running
+// sum S (the loads of a row are coalesced over the lanes and do not depend on S); the rows
+// above i are copied.  `out` is zero where nothing is written.
+__global__ __launch_bounds__(64) void k_reweigh_rows(const double* M, double* out, int64_t ld,
+                                                     int n, int i, const double* c,
+                                                     const double* sd, const double* g) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= n) return;
+  for (int k = j; k < i; ++k) out[int64_t(k) * ld + j] = M[int64_t(k) * ld + j];
+  double S = 0.0;
+  int k = max(i, j);
+  constexpr int kU = 8;                        // loads in flight per lane
+  for (; k + kU <= n; k += kU) {
+    double mv[kU], cc[kU], a[kU], b[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      mv[u] = M[int64_t(k + u) * ld + j];
+      cc[u] = c[k + u];
+      a[u] = sd[k + u];
+      b[u] = g[k + u];
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      out[int64_t(k + u) * ld + j] = fma(a[u], mv[u], b[u] * S);
+      S = fma(cc[u], mv[u], S);
+    }
+  }
+  for (; k < n; ++k) {
+    const double mv = M[int64_t(k) * ld + j];
+    out[int64_t(k) * ld + j] = fma(sd[k], mv, g[k] * S);
+    S = fma(c[k], mv, S);
+  }
+}
+
+// ... and the images copied over the GP, once the pivot word has said yes.
+__global__ void k_reweigh_commit(RemoveBufs rb, int d, int i, int n_pad, double y_new,
+                                 double* alpha, double* updw, double* upd, double* Y) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n_pad) {
+    alpha[e] = rb.alpha[e];
+    updw[e] = rb.w[e];
+  }
+  if (e < 2) upd[e] = rb.X[e];
+  else if (e < 2 + d) upd[e] = rb.rec[e];
+  if (e == 0) Y[i] = y_new;
+}
+
+int reweigh_gp(sgp_gp* gp, int index, double y_new, double delta, int* info) {
+  sgp_ctx* ctx = gp->ctx;
+  const int n = int(gp->n), ld = gp->ld, d = gp->kern.d, i = index, np = gp->n_pad;
+  const size_t mat = size_t(ld) * ld * sizeof(double);
+  // (a clone has no spare matrix before its first refit)
+  SGP_TRY(sgp_reserve(ctx, &gp->work, mat));
+  double* Li = static_cast<double*>(gp->Linv.p);
+  double* out = static_cast<double*>(gp->work.p);
+  double* alpha = static_cast<double*>(gp->alpha.p);
+  double* buf;
+  SGP_TRY(sgp_scratch(ctx, kSlotStage, remove_scratch_bytes(ld, d), &buf));
+  const RemoveBufs rb = remove_bufs(buf, ld, d);
+  const int elems = std::max(np, 2 + d);
+  hipLaunchKernelGGL(k_reweigh_coef, dim3(1), dim3(1024), 0, ctx->stream, Li, int64_t(ld), n, i,
+                     delta, rb);
+  SGP_TRY(launch_tri_mtv(ctx, Li, ld, n, rb.c, 0, 1, rb.p, 0, n));
+  hipLaunchKernelGGL(k_reweigh_stage, dim3((elems + 255) / 256), dim3(256), 0, ctx->stream,
+                     alpha, static_cast<const double*>(gp->X.p),
+                     static_cast<const double*>(gp->Y.p), n, d, i, np, y_new, delta, rb);
+  SGP_HIP(ctx, hipMemsetAsync(out, 0, mat, ctx->stream));
+  hipLaunchKernelGGL(k_reweigh_rows, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, Li, out,
+                     int64_t(ld), n, i, rb.c, rb.cs, rb.sn);
+  SGP_HIP(ctx, hipGetLastError());
+  SGP_TRY(sgp_d2h(ctx, info, rb.info, sizeof(int)));
+  if (*info != 0) return 0;
+  hipLaunchKernelGGL(k_reweigh_commit, dim3((elems + 255) / 256), dim3(256), 0, ctx->stream, rb,
+                     d, i, np, y_new, alpha, static_cast<double*>(gp->updw.p),
+                     static_cast<double*>(gp->upd.p), static_cast<double*>(gp->Y.p));
+  SGP_HIP(ctx, hipGetLastError());
+  std::swap(gp->Linv, gp->work);
+  gp->upd_valid = false;
+  gp->rem_valid = false;
+  gp->blk_valid = false;
+  gp->rw_valid = true;
   return publish_gp(gp);
 }
 

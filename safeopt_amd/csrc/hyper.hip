@@ -14,7 +14,7 @@
 //     RBF        c = -exp(-r^2 / 2)
 //     Matern-3/2 c = -3 exp(-sqrt(3) r)
 //     Matern-5/2 c = -(5/3) (1 + sqrt(5) r) exp(-sqrt(5) r)
-//   dKy/dnoise = I
+//   dKy/dnoise = I  (diag(r) for a GP with noise scales: sgp_gp::rhost)
 //
 // k_lml_tiles: one workgroup per lower-triangular 64 x 64 tile of the (i, j) pairs.  Its four
 // waves form the tile of Ky^-1 on the fp64 matrix cores (v_mfma_f64_16x16x4_f64: the A and
@@ -110,6 +110,7 @@ __global__ __launch_bounds__(256) void k_lml_tiles(KernDesc kd, const double* __
                                                    const double* __restrict__ X,
                                                    const double* __restrict__ alpha,
                                                    const double* __restrict__ u,
+                                                   const double* __restrict__ rs,
                                                    double* __restrict__ part) {
   __shared__ double sh[4][kMaxAcc];
   int ti, tj;
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(256) void k_lml_tiles(KernDesc kd, const double* __
       } else {
         w = fma(ai[r], aj, -acc[q][r]);
       }
-      if (i == j) s_noise += w;
+      if (i == j) s_noise += rs ? w * rs[i] : w;    // dKy/dnoise = diag(r)
       double d2[D];
 #pragma unroll
       for (int a = 0; a < D; ++a) {
@@ -524,11 +525,12 @@ int launch_lml(sgp_gp* gp, const int* info_dev, double* out_dev) {
   const double* X = static_cast<const double*>(gp->X.p);
   const double* Y = static_cast<const double*>(gp->Y.p);
   const double* alpha = static_cast<const double*>(gp->alpha.p);
+  const double* rs = gp->rhost.empty() ? nullptr : static_cast<const double*>(gp->R.p);
 #define LML_CASE(DD)                                                                       \
   case DD:                                                                                 \
     hipLaunchKernelGGL((k_lml_tiles<DD, false>), dim3(ntiles), dim3(256), 0, ctx->stream,  \
                        gp->kern, Li, int64_t(gp->ld), n, X, alpha,                         \
-                       static_cast<const double*>(nullptr), part);                         \
+                       static_cast<const double*>(nullptr), rs, part);                     \
     break;
   switch (gp->kern.d) {
     LML_CASE(1) LML_CASE(2) LML_CASE(3) LML_CASE(4)
@@ -572,6 +574,7 @@ int launch_loo_lml(sgp_gp* gp, const int* info_dev, double* out_dev) {
   const double* Li = static_cast<const double*>(gp->Linv.p);
   const double* X = static_cast<const double*>(gp->X.p);
   const double* alpha = static_cast<const double*>(gp->alpha.p);
+  const double* rs = gp->rhost.empty() ? nullptr : static_cast<const double*>(gp->R.p);
   // u = L^-T (L^-1 a)
   SGP_TRY(tri_mv_dense(ctx, Li, gp->ld, n, v.a, 0, 1, v.t, 0));
   SGP_TRY(tri_mtv_dense(ctx, Li, gp->ld, n, v.t, 0, 1, v.u, 0, n));
@@ -581,7 +584,7 @@ int launch_loo_lml(sgp_gp* gp, const int* info_dev, double* out_dev) {
 #define LOO_CASE(DD)                                                                      \
   case DD:                                                                                \
     hipLaunchKernelGGL((k_lml_tiles<DD, true>), dim3(ntiles), dim3(256), 0, ctx->stream,  \
-                       gp->kern, Cm, ldc, n, X, alpha, v.u, part);                        \
+                       gp->kern, Cm, ldc, n, X, alpha, v.u, rs, part);                    \
     break;
   switch (gp->kern.d) {
     LOO_CASE(1) LOO_CASE(2) LOO_CASE(3) LOO_CASE(4)

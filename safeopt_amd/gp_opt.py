@@ -31,6 +31,7 @@ import weakref
 import numpy as np
 
 from . import _hip
+from . import pooling as _pooling
 from .dist import (LocalComm, allgather_rows, check_same_maxima, check_same_paths,
                    check_same_targets,
                    gather_shard_columns,
@@ -75,10 +76,22 @@ class GaussianProcessOptimization(object):
     ``beta`` (always callable), ``scaling``, ``x`` / ``y`` / ``data`` / ``t``,
     ``add_new_data_point`` / ``remove_last_data_point``; ``remove_data_point`` forgets
     any measurement (not in the reference).
+
+    Not in the reference either: a measurement may come with a NOISE SCALE (``noise_scale=``
+    of ``add_new_data_point``: its noise variance is that many times the GP's), and with
+    ``pool_repeats=True`` a measurement at an input a GP already holds is pooled into that
+    row (``GPRegression.pool_data``) instead of appended: the log stays what it is, every
+    measurement in order, the posterior is the same, and the GPs grow with the number of
+    distinct inputs only.
     """
 
+    #: the map from the log to the rows of the pooled GPs (``pool_repeats=True``), else None
+    _pool = None
+    #: noise scales of the log, (t, n_gps), or None: none was ever given, all ones
+    _rho = None
+
     def __init__(self, gp, fmin, beta=2, num_contexts=0, threshold=0,
-                 scaling='auto'):
+                 scaling='auto', pool_repeats=False):
         self.gps = gp if isinstance(gp, list) else [gp]
         if len(self.gps) > _hip.MAX_GPS:
             raise ValueError("at most %d GPs are supported" % _hip.MAX_GPS)
@@ -110,6 +123,12 @@ class GaussianProcessOptimization(object):
                                           'measurements.')
         self._x = self.gp.X
         self._y = np.concatenate([g.Y for g in self.gps], axis=1)
+        if any(getattr(g, '_r', None) is not None for g in self.gps):
+            self._rho = np.stack([np.asarray(g.noise_scale, dtype=float) for g in self.gps],
+                                 axis=1)
+        if pool_repeats:
+            # the GPs' initial data are taken as they are: one row per initial measurement
+            self._pool = _pooling.PoolBook(self._x, np.ones(self._y.shape, dtype=bool))
 
     # -- measurement log ----------------------------------------------------------
     x = property(lambda self: self._x)
@@ -134,67 +153,172 @@ class GaussianProcessOptimization(object):
     def _add_context(self, x, context):
         return _with_context(x, context)
 
-    def _add_data_point(self, gp, x, y, context=None):
+    def _add_data_point(self, gp, x, y, context=None, noise_scale=None):
         """Append ``(x, y)`` to one GP only (``self.x`` / ``self.y`` untouched).
         One more row than before: the handle turns this ``set_XY`` into a
-        bordered update of the factor (``sgp_gp_append``)."""
+        bordered update of the factor (``sgp_gp_append``).  ``noise_scale``: the scales of the
+        new rows (None: ones); a GP that holds scales keeps them."""
         rows = x if context is None else _with_context(x, context)
-        gp.set_XY(np.vstack([gp.X, rows]), np.vstack([gp.Y, y]))
+        if noise_scale is None and getattr(gp, '_r', None) is None:
+            gp.set_XY(np.vstack([gp.X, rows]), np.vstack([gp.Y, y]))
+            return
+        new = np.ones(np.shape(rows)[0]) if noise_scale is None else np.ravel(noise_scale)
+        gp.set_XY(np.vstack([gp.X, rows]), np.vstack([gp.Y, y]),
+                  noise_scale=np.concatenate([gp.noise_scale, new]))
 
-    def add_new_data_point(self, x, y, context=None):
-        """Log a measurement and hand it to the GPs; a ``nan`` in column ``i``
-        of ``y`` means GP ``i`` did not observe it."""
-        x, y = np.atleast_2d(x), np.atleast_2d(y)
-        if self.num_contexts:
-            x = _with_context(x, context)
-        for i, gp in enumerate(self.gps):
-            seen = ~np.isnan(y[:, i])
-            if seen.any():
-                self._add_data_point(gp, x[seen, :], y[seen, [i]])
+    def _scales_per_gp(self, noise_scale, rows):
+        """``noise_scale`` -- a scalar, one value per GP, or (rows, n_gps) -- as (rows,
+        n_gps), or None."""
+        if noise_scale is None:
+            return None
+        r = np.asarray(noise_scale, dtype=float)
+        n_gps = len(self.gps)
+        if r.ndim == 0:
+            r = np.full((rows, n_gps), float(r))
+        elif r.ndim == 1 and r.size == n_gps:
+            r = np.tile(r, (rows, 1))
+        elif r.shape != (rows, n_gps):
+            raise ValueError("noise_scale: a scalar or one value per GP (%d), got shape %r"
+                             % (n_gps, r.shape))
+        if not (np.all(np.isfinite(r)) and np.all(r > 0)):
+            raise ValueError("noise scales must be finite and positive, got %r" % (r,))
+        return r
+
+    def _log(self, x, y, rho):
+        """The log grows by the rows ``(x, y)`` with the noise scales ``rho`` (or None)."""
+        if rho is not None or self._rho is not None:
+            old = self._rho if self._rho is not None else np.ones(self._y.shape)
+            new = rho if rho is not None else np.ones(y.shape)
+            self._rho = np.concatenate((old, new), axis=0)
         self._x = np.concatenate((self._x, x), axis=0)
         self._y = np.concatenate((self._y, y), axis=0)
 
-    def _add_data_points(self, gp, rows, y):
+    def add_new_data_point(self, x, y, context=None, noise_scale=None):
+        """Log a measurement and hand it to the GPs; a ``nan`` in column ``i``
+        of ``y`` means GP ``i`` did not observe it.  ``noise_scale``: the noise variance of
+        this measurement is that many times the GP's ``noise_var`` (a scalar, or one value
+        per GP; None: 1).  With ``pool_repeats`` a measurement at an input the GP holds is
+        pooled into that row."""
+        x, y = np.atleast_2d(x), np.atleast_2d(y)
+        rho = self._scales_per_gp(noise_scale, x.shape[0])
+        if self.num_contexts:
+            x = _with_context(x, context)
+        if self._pool is not None:
+            x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+            for k in range(x.shape[0]):
+                for g, act in enumerate(self._pool.add(x[k], ~np.isnan(y[k]))):
+                    if act is None:
+                        continue
+                    p = 1.0 if rho is None else rho[k, g]
+                    if act[0] == 'pool':
+                        self.gps[g].pool_data(act[1], y[k, g], p)
+                    else:
+                        self._add_data_point(self.gps[g], x[k:k + 1], y[k:k + 1, [g]],
+                                             noise_scale=None if rho is None else [p])
+            self._log(x, y, rho)
+            return
+        for i, gp in enumerate(self.gps):
+            seen = ~np.isnan(y[:, i])
+            if seen.any():
+                if rho is None:
+                    self._add_data_point(gp, x[seen, :], y[seen, [i]])
+                else:
+                    self._add_data_point(gp, x[seen, :], y[seen, [i]], noise_scale=rho[seen, i])
+        self._log(x, y, rho)
+
+    def _add_data_points(self, gp, rows, y, noise_scale=None):
         """Append the rows ``(rows, y)`` to one GP only: block appends of the factor
         (``GPRegression.append_XY``), a refit for a handle without them."""
-        if hasattr(gp, 'append_XY'):
+        if noise_scale is not None:
+            gp.append_XY(rows, y, noise_scale=noise_scale)
+        elif hasattr(gp, 'append_XY'):
             gp.append_XY(rows, y)
         else:
             gp.set_XY(np.vstack([gp.X, rows]), np.vstack([gp.Y, y]))
 
-    def add_new_data_points(self, X, Y, context=None):
+    def add_new_data_points(self, X, Y, context=None, noise_scale=None):
         """Log ``b`` measurements at once -- the way back from ``optimize_batch`` -- and hand
         them to the GPs: ``X`` (b, d_parameters), ``Y`` (b, n_gps), a ``nan`` in ``Y[r, g]``
         meaning GP ``g`` did not observe row ``r`` (it then appends its own rows only).  The
         log ends up as after ``b`` calls of ``add_new_data_point``; every GP takes its rows
         by block appends of up to 16 rows (one O(b n^2) update each instead of ``b``), and
         the next ``optimize()`` of a ``SafeOpt`` corrects the resident posterior in ONE
-        closed-form pass over the grid instead of sweeping it again."""
+        closed-form pass over the grid instead of sweeping it again.  ``noise_scale``: a
+        scalar, one value per GP, or ``(b, n_gps)``.  With ``pool_repeats`` the rows whose
+        input a GP holds (an earlier row of the batch included) are pooled one by one, the
+        rest is block-appended."""
         X = np.atleast_2d(np.asarray(X, dtype=float))
         Y = np.atleast_2d(np.asarray(Y, dtype=float))
         if X.shape[0] != Y.shape[0] or Y.shape[1] != len(self.gps):
             raise ValueError("X (b, d) and Y (b, %d) expected, got %r and %r"
                              % (len(self.gps), X.shape, Y.shape))
+        rho = self._scales_per_gp(noise_scale, X.shape[0])
         if self.num_contexts:
             X = _with_context(X, context)
+        if self._pool is not None:
+            # the batch's new inputs first (one block per GP), then the repeats row by row:
+            # a repeat of a row of the same batch finds it in the GP
+            acts = [self._pool.add(X[k], ~np.isnan(Y[k])) for k in range(X.shape[0])]
+            for g, gp in enumerate(self.gps):
+                new = [k for k, a in enumerate(acts) if a[g] is not None and a[g][0] == 'append']
+                if new:
+                    self._add_data_points(gp, X[new, :], Y[new][:, [g]],
+                                          noise_scale=None if rho is None else rho[new, g])
+                for k, a in enumerate(acts):
+                    if a[g] is not None and a[g][0] == 'pool':
+                        gp.pool_data(a[g][1], Y[k, g], 1.0 if rho is None else rho[k, g])
+            self._log(X, Y, rho)
+            return
         for i, gp in enumerate(self.gps):
             seen = ~np.isnan(Y[:, i])
             if seen.any():
-                self._add_data_points(gp, X[seen, :], Y[seen][:, [i]])
-        self._x = np.concatenate((self._x, X), axis=0)
-        self._y = np.concatenate((self._y, Y), axis=0)
+                self._add_data_points(gp, X[seen, :], Y[seen][:, [i]],
+                                      noise_scale=None if rho is None else rho[seen, i])
+        self._log(X, Y, rho)
 
     def _remove_last_data_point(self, gp):
         """Drop the newest row of one GP (a one-row ``sgp_gp_pop``)."""
-        gp.set_XY(gp.X[:-1, :], gp.Y[:-1, :])
+        if getattr(gp, '_r', None) is None:
+            gp.set_XY(gp.X[:-1, :], gp.Y[:-1, :])
+        else:
+            gp.set_XY(gp.X[:-1, :], gp.Y[:-1, :], noise_scale=gp.noise_scale[:-1])
+
+    def _unlog(self, index):
+        self._x = np.delete(self._x, index, axis=0)
+        self._y = np.delete(self._y, index, axis=0)
+        if self._rho is not None:
+            self._rho = np.delete(self._rho, index, axis=0)
+
+    def _unpool(self, index):
+        """``pool_repeats``: measurement ``index`` leaves the GPs -- taken back out of a row
+        that keeps other measurements (``unpool_data``, with its value and scale from the
+        log), the row removed otherwise."""
+        where = self._pool.locate(index)
+        for g, row in enumerate(where):
+            if row is not None and self._pool.count[g][row] == 1 and self._pool.rows(g) < 2:
+                raise ValueError("GP %d would be left without data" % g)
+        for g, act in enumerate(self._pool.remove(index)):
+            if act is None:
+                continue
+            if act[0] == 'unpool':
+                self.gps[g].unpool_data(act[1], self._y[index, g],
+                                        1.0 if self._rho is None else self._rho[index, g])
+            else:
+                self.gps[g].remove_data(act[1])
 
     def remove_last_data_point(self):
         """Undo the last ``add_new_data_point``: every GP that observed the
         newest measurement forgets it, then the log is shortened."""
+        if self._pool is not None:
+            self._unpool(self.t - 1)
+            self._unlog(self.t - 1)
+            return
         for gp, value in zip(self.gps, self._y[-1]):
             if not np.isnan(value):
                 self._remove_last_data_point(gp)
         self._x, self._y = self._x[:-1, :], self._y[:-1, :]
+        if self._rho is not None:
+            self._rho = self._rho[:-1, :]
 
     def remove_data_point(self, index):
         """Forget measurement ``index`` of the log (``0 <= index < t``), whichever it is: a
@@ -209,6 +333,10 @@ class GaussianProcessOptimization(object):
         if isinstance(index, bool) or index != int(index) or not 0 <= index < self.t:
             raise IndexError("measurement %r of %d" % (index, self.t))
         index = int(index)
+        if self._pool is not None:
+            self._unpool(index)
+            self._unlog(index)
+            return
         seen = ~np.isnan(self._y[index])
         rows = [int(np.count_nonzero(~np.isnan(self._y[:index, i])))
                 for i in range(len(self.gps))]
@@ -218,15 +346,29 @@ class GaussianProcessOptimization(object):
         for i, gp in enumerate(self.gps):
             if seen[i]:
                 gp.remove_data(rows[i])
-        self._x = np.delete(self._x, index, axis=0)
-        self._y = np.delete(self._y, index, axis=0)
+        self._unlog(index)
 
     def loo_residuals(self):
         """Standardised leave-one-out residuals of the log, ``(t, n_gps)``: column ``g`` holds
         GP ``g``'s ``z = (y - mean_-i) / sqrt(var_-i)`` of every measurement it observed
         (``GPRegression.loo_residuals``, O(n^2) per GP from its resident factor), ``nan``
-        where it did not.  Changes nothing in the optimiser."""
+        where it did not.  Changes nothing in the optimiser.  With ``pool_repeats`` a
+        measurement ``j`` (noise scale ``rho_j``) of a pooled row ``i`` (scale ``r_i``) is
+        judged against the prediction that leaves the whole row out: ``z = (y_j - mean_-i) /
+        sqrt(var_-i - s r_i + s rho_j)`` with ``s = noise_var + 1e-8`` -- the single reading,
+        not the row's mean."""
         out = np.full(self._y.shape, np.nan)
+        if self._pool is not None:
+            for g, gp in enumerate(self.gps):
+                mean, var = gp.loo()
+                s, r = gp.noise_var + 1e-8, np.asarray(gp.noise_scale)
+                for j in range(self.t):
+                    row = self._pool.where[j][g]
+                    if row is not None:
+                        rho = 1.0 if self._rho is None else self._rho[j, g]
+                        out[j, g] = ((self._y[j, g] - mean[row, 0])
+                                     / np.sqrt(var[row, 0] - s * r[row] + s * rho))
+            return out
         for g, gp in enumerate(self.gps):
             seen = ~np.isnan(self._y[:, g])
             out[seen, g] = gp.loo_residuals()[:, 0]
@@ -368,10 +510,14 @@ class _HipGridBackend(object):
                 continue                                  # up to date
             removed = getattr(dv, 'removed', False)
             block = getattr(dv, 'block', 0)
-            if (rank1 and (dv.appended or removed or block) and self._seen[i] is not None
+            reweighed = getattr(dv, 'reweighed', False)
+            if (rank1 and (dv.appended or removed or block or reweighed)
+                    and self._seen[i] is not None
                     and self._seen[i] == (dv.serial, dv.version - 1)):
-                which[i] = 1                 # one append / one removal / one block behind
-                kinds.add('block' if block else ('remove' if removed else 'append'))
+                # one append / one removal / one block / one reweigh behind
+                which[i] = 1
+                kinds.add('block' if block else ('remove' if removed else
+                                                 ('reweigh' if reweighed else 'append')))
                 rows = max(rows, block)
             else:
                 rank1 = False
@@ -381,6 +527,7 @@ class _HipGridBackend(object):
         self._seen = [None] * len(devs)          # unknown until the call is through
         if rank1 and any(which):
             refresh = getattr(self.grid, {'append': 'rank1_update', 'remove': 'rank1_remove',
+                                          'reweigh': 'rank1_reweigh',
                                           'block': 'rankb_update'}[kinds.pop()])
             out = refresh(devs, which, beta, fmin, defer)
             self._rank1_streak += rows
@@ -761,10 +908,11 @@ class SafeOpt(GaussianProcessOptimization):
 
     def __init__(self, gp, parameter_set, fmin, lipschitz=None, beta=2,
                  num_contexts=0, threshold=0, scaling='auto', comm=None,
-                 ):
+                 pool_repeats=False):
         super(SafeOpt, self).__init__(gp, fmin=fmin, beta=beta,
                                       num_contexts=num_contexts,
-                                      threshold=threshold, scaling=scaling)
+                                      threshold=threshold, scaling=scaling,
+                                      pool_repeats=pool_repeats)
         # candidate rows = parameters (+ zeroed context columns that the context
         # setter fills); `parameter_set` stays a view of the parameter columns
         params = np.asarray(parameter_set)
@@ -2296,7 +2444,7 @@ class SafeOptSwarm(GaussianProcessOptimization):
     """
 
     def __init__(self, gp, fmin, bounds, beta=2, scaling='auto', threshold=0,
-                 swarm_size=20, pso='device', comm=None):
+                 swarm_size=20, pso='device', comm=None, pool_repeats=False):
         if pso not in ('device', 'device-rng', 'host'):
             raise ValueError("pso must be 'device', 'device-rng' or 'host'")
         self._comm = comm if comm is not None else LocalComm()
@@ -2318,7 +2466,8 @@ class SafeOptSwarm(GaussianProcessOptimization):
                     raise ValueError("the GPs live on HIP device %d but the communicator"
                                      " context is device %d" % (g_ctx.device, ctx.device))
         GaussianProcessOptimization.__init__(self, gp, fmin=fmin, beta=beta, num_contexts=0,
-                                             threshold=threshold, scaling=scaling)
+                                             threshold=threshold, scaling=scaling,
+                                             pool_repeats=pool_repeats)
         # the safe set starts as the observed inputs; one (min, max) pair may
         # stand for every dimension
         safe_points = np.asarray(self.gps[0].X)

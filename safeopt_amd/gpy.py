@@ -178,7 +178,18 @@ class GPRegression(object):
     conditioning): no row limit, evaluated anywhere and again.
     """
 
-    def __init__(self, X, Y, kernel=None, noise_var=1., device=None):
+    #: noise scales of the observations (None: none were ever given, all ones) and, per row, the
+    #: sufficient statistics of the measurements it pools (None: one measurement; ``pool_data``)
+    _r = None
+    _stats = None
+
+    def _st(self):
+        st = self._stats
+        if st is None or len(st) != self.X.shape[0]:
+            st = self._stats = [None] * self.X.shape[0]
+        return st
+
+    def __init__(self, X, Y, kernel=None, noise_var=1., device=None, noise_scale=None):
         X = np.atleast_2d(np.asarray(X, dtype=float))
         Y = np.atleast_2d(np.asarray(Y, dtype=float))
         if Y.shape[1] != 1:
@@ -199,7 +210,27 @@ class GPRegression(object):
         self.incremental = True
         self.X = X
         self.Y = Y
-        self.set_XY(X, Y)
+        self.set_XY(X, Y, noise_scale=noise_scale)
+
+    @property
+    def noise_scale(self):
+        """Noise scale ``r_i`` of every observation, ``(n,)``, read-only: observation ``i``
+        has noise variance ``(noise_var + 1e-8) r_i``."""
+        r = np.ones(self.X.shape[0]) if self._r is None else self._r.copy()
+        r.flags.writeable = False
+        return r
+
+    def _scales_arg(self, noise_scale, rows):
+        if noise_scale is None:
+            return None
+        r = np.array(np.broadcast_to(np.asarray(noise_scale, dtype=float).reshape(-1),
+                                     (rows,)))
+        if not (np.all(np.isfinite(r)) and np.all(r > 0)):
+            raise ValueError("noise scales must be finite and positive, got %r" % (r,))
+        return r
+
+    def _eff(self, r, rows):
+        return np.ones(rows) if r is None else r
 
     @property
     def Gaussian_noise_variance(self):
@@ -224,31 +255,163 @@ class GPRegression(object):
         self._sig = (self.kern._signature(), self.noise_var)
         return self._dev
 
-    def set_XY(self, X, Y):
-        """Replace the training data and refit (device Cholesky + inverse)."""
+    def set_XY(self, X, Y, noise_scale=None):
+        """Replace the training data and refit (device Cholesky + inverse).
+        ``noise_scale``: one scale per observation (or one for all), None = all ones."""
         X = np.array(np.atleast_2d(X), dtype=float)
         Y = np.array(np.atleast_2d(Y), dtype=float)
         if X.shape[0] != Y.shape[0] or X.shape[1] != self.input_dim:
             raise ValueError("inconsistent X %r / Y %r" % (X.shape, Y.shape))
-        old_X, old_Y = self.X, self.Y
-        self.X, self.Y = X, Y
+        r = self._scales_arg(noise_scale, X.shape[0])
+        old_X, old_Y, old_r, old_stats = self.X, self.Y, self._r, self._st()
+        self.X, self.Y, self._r = X, Y, r
+        self._stats = [None] * X.shape[0]
         dev = self._device_gp()
         n = X.shape[0]
         # what SafeOpt does every iteration is one row more (or one fewer):
         # bordered O(n^2) update instead of the O(n^3) re-factorisation
         if self._dev_fitted and dev.n == old_X.shape[0] and self.incremental:
+            scaled = r is not None or old_r is not None
             if (n == dev.n + 1 and np.array_equal(X[:-1], old_X)
-                    and np.array_equal(Y[:-1], old_Y)):
-                if dev.append(X[-1], Y[-1, 0]):
+                    and np.array_equal(Y[:-1], old_Y)
+                    and (not scaled or np.array_equal(self._eff(r, n)[:-1],
+                                                      self._eff(old_r, n - 1)))):
+                if (dev.append(X[-1], Y[-1, 0], self._eff(r, n)[-1]) if scaled
+                        else dev.append(X[-1], Y[-1, 0])):
+                    self._stats = list(old_stats) + [None]
+                    if scaled:
+                        self._r = self._eff(r, n)
                     return
             elif (n == dev.n - 1 and n >= 1 and np.array_equal(X, old_X[:-1])
-                    and np.array_equal(Y, old_Y[:-1])):
+                    and np.array_equal(Y, old_Y[:-1])
+                    and (not scaled or np.array_equal(self._eff(r, n),
+                                                      self._eff(old_r, n + 1)[:-1]))):
                 dev.pop()
+                self._stats = list(old_stats[:-1])
+                if scaled:
+                    self._r = self._eff(r, n)
                 return
-        dev.set_data(X, Y[:, 0])
+        if r is None:
+            dev.set_data(X, Y[:, 0])
+        else:
+            dev.set_data(X, Y[:, 0], r)
         self._dev_fitted = True
 
-    def append_XY(self, X, Y):
+    def _refit(self):
+        """The data as the model holds them, fitted from scratch on the device."""
+        dev = self._device_gp()
+        if self._r is None:
+            dev.set_data(self.X, self.Y[:, 0])
+        else:
+            dev.set_data(self.X, self.Y[:, 0], self._r)
+        self._dev_fitted = True
+
+    def _reweigh(self, index, y, r):
+        """Row ``index`` becomes ``(y, r)``: one ``sgp_gp_reweigh`` on the device, or -- with
+        ``incremental = False``, a device GP out of step, or a failed pivot -- a refit."""
+        n = self.X.shape[0]
+        y, r = float(y), float(r)
+        if not np.isfinite(y):
+            raise ValueError("the value of an observation must be finite, got %r" % (y,))
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("noise scales must be finite and positive, got %r" % (r,))
+        Y = self.Y.copy()
+        Y[index, 0] = y
+        rs = self._eff(self._r, n).copy()
+        rs[index] = r
+        dev = self._device_gp()
+        in_step = self._dev_fitted and dev.n == n and self.incremental
+        self.Y = Y
+        if self._r is not None or r != 1.0:
+            self._r = rs
+        if not (in_step and dev.reweigh(index, y, r)):
+            self._refit()
+
+    def _row(self, index):
+        n = self.X.shape[0]
+        if not -n <= index < n:
+            raise IndexError("observation %d of %d" % (index, n))
+        return int(index) % n
+
+    def reweigh_data(self, index, y=None, noise_scale=None):
+        """Re-weight and / or replace observation ``index`` in place: its value becomes ``y``
+        (None: stays), its noise scale ``noise_scale`` (None: stays).  An O(n^2) update of
+        the factor on the device (``sgp_gp_reweigh``), ``n`` does not change: down-weighting
+        a suspect reading instead of removing it.  The row's pooling statistics are
+        dropped: it counts as one measurement from here on."""
+        i = self._row(index)
+        y = self.Y[i, 0] if y is None else y
+        r = self._eff(self._r, self.X.shape[0])[i] if noise_scale is None else noise_scale
+        self._reweigh(i, y, r)
+        self._st()[i] = None
+
+    def _row_stats(self, i):
+        """[k, sum 1/rho, sum y/rho, sum y^2/rho, sum log rho] of row ``i``."""
+        st = self._st()[i]
+        if st is None:
+            y, r = self.Y[i, 0], self._eff(self._r, self.X.shape[0])[i]
+            st = [1, 1.0 / r, y / r, y * y / r, np.log(r)]
+        return list(st)
+
+    def pool_data(self, index, y, noise_scale=1.0):
+        """One MORE measurement ``y`` (noise scale ``noise_scale``) at the input of row
+        ``index``: the row becomes the pooled observation ``r = 1 / sum_j 1/rho_j``, ``y =
+        r sum_j y_j/rho_j`` of all its measurements -- for the posterior exactly what a
+        separate row per measurement gives, at the cost of one append and without growing
+        ``n``.  ``log_likelihood`` and ``optimize`` account for the pooled measurements
+        (the model keeps the sufficient statistics per row)."""
+        i = self._row(index)
+        y, rho = float(y), float(noise_scale)
+        if not np.isfinite(y) or not (np.isfinite(rho) and rho > 0):
+            raise ValueError("a finite value and a finite positive noise scale, got %r, %r"
+                             % (y, rho))
+        st = self._row_stats(i)
+        st = [st[0] + 1, st[1] + 1.0 / rho, st[2] + y / rho, st[3] + y * y / rho,
+              st[4] + np.log(rho)]
+        self._reweigh(i, st[2] / st[1], 1.0 / st[1])
+        self._st()[i] = st
+
+    def unpool_data(self, index, y, noise_scale=1.0):
+        """Take BACK one measurement ``(y, noise_scale)`` that ``pool_data`` (or the row's
+        first observation) put into row ``index``.  ``ValueError`` for the last member of a
+        row: remove the row instead (``remove_data``)."""
+        i = self._row(index)
+        y, rho = float(y), float(noise_scale)
+        if not np.isfinite(y) or not (np.isfinite(rho) and rho > 0):
+            raise ValueError("a finite value and a finite positive noise scale, got %r, %r"
+                             % (y, rho))
+        st = self._row_stats(i)
+        if st[0] < 2:
+            raise ValueError("row %d holds one measurement: remove the row instead" % i)
+        st = [st[0] - 1, st[1] - 1.0 / rho, st[2] - y / rho, st[3] - y * y / rho,
+              st[4] - np.log(rho)]
+        if not st[1] > 0:
+            raise ValueError("measurement (%r, %r) is not part of row %d" % (y, rho, i))
+        self._reweigh(i, st[2] / st[1], 1.0 / st[1])
+        self._st()[i] = st if st[0] > 1 else None
+
+    def pooled_counts(self):
+        """Number of measurements every row stands for, ``(n,)`` (1 without pooling)."""
+        return np.array([1 if st is None else st[0] for st in self._st()], dtype=int)
+
+    def _pool_term(self, noise_var):
+        """``log p(measurements) - log p(pooled rows)`` and its derivative in ``noise_var``:
+        per pooled row ``-(k-1)/2 log(2 pi s) - 1/2 sum_j log rho_j + 1/2 log r - (sum_j
+        y_j^2/rho_j - ybar^2/r) / (2 s)`` with ``s = noise_var + 1e-8``; it depends on the
+        data and ``s`` only."""
+        s = float(noise_var) + 1e-8
+        val = grad = 0.0
+        for st in self._st():
+            if st is None:
+                continue
+            k, s1, sy, syy, slog = st
+            q = syy - sy * sy / s1             # sum y^2/rho - ybar^2 / r
+            val += -0.5 * (k - 1) * np.log(2 * np.pi * s) - 0.5 * slog - 0.5 * np.log(s1) \
+                - q / (2 * s)
+            grad += -0.5 * (k - 1) / s + q / (2 * s * s)
+        return val, grad
+
+    def append_XY(self, X, Y, noise_scale=None):
         """``b >= 1`` more observations (``X`` (b, d), ``Y`` (b, 1)) behind the data: block
         appends on the device (``sgp_gp_append_block``, chunks of at most ``MAX_BLOCK`` rows:
         one O(b n^2) update and one read-back per chunk) when the model is fitted,
@@ -261,22 +424,35 @@ class GPRegression(object):
         if (Xn.shape[0] != Yn.shape[0] or Xn.shape[1] != self.input_dim or Yn.shape[1] != 1
                 or Xn.shape[0] < 1):
             raise ValueError("inconsistent X %r / Y %r" % (Xn.shape, Yn.shape))
+        rn = self._scales_arg(noise_scale, Xn.shape[0])
         X, Y = np.vstack([self.X, Xn]), np.vstack([self.Y, Yn])
+        r = None
+        if rn is not None or self._r is not None:
+            r = np.concatenate([self._eff(self._r, self.X.shape[0]),
+                                self._eff(rn, Xn.shape[0])])
+        stats = list(self._st()) + [None] * Xn.shape[0]
         dev = self._device_gp()
         if self._dev_fitted and dev.n == self.X.shape[0] and self.incremental:
             for s in range(0, Xn.shape[0], _hip.MAX_BLOCK):
-                if not dev.append_block(Xn[s:s + _hip.MAX_BLOCK], Yn[s:s + _hip.MAX_BLOCK, 0]):
+                xb, yb = Xn[s:s + _hip.MAX_BLOCK], Yn[s:s + _hip.MAX_BLOCK, 0]
+                if not (dev.append_block(xb, yb) if r is None else dev.append_block(
+                        xb, yb, self._eff(rn, Xn.shape[0])[s:s + _hip.MAX_BLOCK])):
                     break
             else:
-                self.X, self.Y = X, Y
+                self.X, self.Y, self._r, self._stats = X, Y, r, stats
                 return
-        self.set_XY(X, Y)
+        if r is None:
+            self.set_XY(X, Y)
+        else:
+            self.set_XY(X, Y, noise_scale=r)
+        self._stats = stats
 
     def remove_data(self, index):
         """Forget observation ``index`` (0 .. n-1), whichever it is: an O(n^2) downdate
         of the factor on the device (``sgp_gp_remove``) instead of the refit ``set_XY``
         with the reduced arrays costs -- which is what happens with ``incremental =
-        False``, or when a pivot of the downdate is not positive."""
+        False``, or when a pivot of the downdate is not positive.  The row's noise scale and
+        pooling statistics go with it."""
         n = self.X.shape[0]
         if not -n <= index < n:
             raise IndexError("observation %d of %d" % (index, n))
@@ -284,12 +460,18 @@ class GPRegression(object):
             raise ValueError("cannot remove the only observation")
         index = int(index) % n
         X, Y = np.delete(self.X, index, axis=0), np.delete(self.Y, index, axis=0)
+        r = None if self._r is None else np.delete(self._r, index)
+        stats = self._st()[:index] + self._st()[index + 1:]
         dev = self._device_gp()
         if (self._dev_fitted and dev.n == n and self.incremental
                 and dev.remove(index)):
-            self.X, self.Y = X, Y
+            self.X, self.Y, self._r, self._stats = X, Y, r, stats
             return
-        self.set_XY(X, Y)
+        if r is None:
+            self.set_XY(X, Y)
+        else:
+            self.set_XY(X, Y, noise_scale=r)
+        self._stats = stats
 
     def _fitted(self):
         """Device GP, fitted.  Hot path: a comparison of the hyper-parameter bytes
@@ -300,7 +482,10 @@ class GPRegression(object):
                 return self._dev
         dev = self._device_gp(in_place=True)
         if not self._dev_fitted:
-            dev.set_data(self.X, self.Y[:, 0])
+            if self._r is None:
+                dev.set_data(self.X, self.Y[:, 0])
+            else:
+                dev.set_data(self.X, self.Y[:, 0], self._r)
             self._dev_fitted = True
         return dev
 
@@ -313,6 +498,10 @@ class GPRegression(object):
         if dev is None or dev.n != self.X.shape[0]:
             dev = self._fitted()
         out = (dev.loo_lml if loo else dev.lml)(variances, inv_ls, noise_var)
+        if not loo and any(st is not None for st in self._st()):
+            # pooled rows: the likelihood of the measurements they stand for
+            val, grad = self._pool_term(noise_var)
+            out = (out[0] + val, out[1] + grad) + tuple(out[2:])
         self._dev_fitted = out[4] == 0
         self._dev_key = (self.input_dim, self._dev_key[1], np.asarray(variances).tobytes(),
                          np.asarray(inv_ls).tobytes(), float(noise_var))
@@ -328,7 +517,8 @@ class GPRegression(object):
             self._sig = (self.kern._signature(), self.noise_var)
 
     def log_likelihood(self):
-        """``log p(y | X, theta)`` at the current hyper-parameters."""
+        """``log p(y | X, theta)`` at the current hyper-parameters; with pooled rows
+        (``pool_data``) the likelihood of all the measurements they stand for."""
         self._fitted()
         desc = self.kern._desc(self.input_dim)
         ll, _, _, _, info = self._evaluate(desc[2], desc[3], self.noise_var)
@@ -358,7 +548,9 @@ class GPRegression(object):
         """Leave-one-out predictions ``(mean, var)``, ``(n, 1)`` each: every observation
         predicted from all the others at the current hyper-parameters, ``var`` the
         predictive variance of the noisy observation.  Closed form from the resident
-        factor, O(n^2) for all of them together (``sgp_gp_loo``)."""
+        factor, O(n^2) for all of them together (``sgp_gp_loo``).  A pooled row
+        (``pool_data``) is ONE observation here, of noise variance ``(noise_var + 1e-8)
+        r_i``: it is left out as a whole."""
         mean, var, _ = self._fitted().loo()
         return mean[:, None], var[:, None]
 
@@ -389,7 +581,9 @@ class GPRegression(object):
         and the model is fitted at them.  Returns an object with ``f_opt``, ``x_opt``,
         ``funct_eval``, ``status``.  ``objective='loo'`` maximises the leave-one-out log
         pseudo-likelihood instead (``f_opt = -L_LOO``): more robust than the marginal
-        likelihood when the kernel family does not fit the data."""
+        likelihood when the kernel family does not fit the data; it treats a pooled row
+        (``pool_data``) as one observation, where ``'lml'`` accounts for every measurement
+        of the row."""
         evaluate = self._evaluator(objective)
         if optimizer not in ('lbfgsb', 'lbfgs', None):
             raise NotImplementedError("optimizer %r (only 'lbfgsb')" % (optimizer,))
@@ -485,7 +679,8 @@ class GPRegression(object):
         dev = self._fitted()
         desc = self.kern._desc(self.input_dim)
         Om, b, W, E = _paths.draw_path_inputs((desc[1], desc[3]), self.noise_var, dev.n,
-                                              self.input_dim, size, features)
+                                              self.input_dim, size, features,
+                                              noise_scale=self._r)
         V = dev.path_weights(Om, b, W, E)
         return _paths.PosteriorPaths(Om, b, W, V,
                                      lambda X: dev.paths_eval(Om, b, W, V, X),

@@ -18,7 +18,8 @@ Order of the draws -- a seed pins a path:
    product of kernels is the convolution of the parts' measures;
 2. ``b = 2 pi random(m)``;
 3. ``W = standard_normal((m, size))``;
-4. ``E = sqrt(noise_var + 1e-8) standard_normal((n, size))``.
+4. ``E = sqrt(noise_var + 1e-8) standard_normal((n, size))``, row ``i`` times
+   ``sqrt(noise_scale[i])`` for a GP with per-observation noise scales.
 """
 from __future__ import annotations
 
@@ -29,7 +30,8 @@ RBF, MATERN32, MATERN52 = 0, 1, 2          # SGP_RBF / SGP_MATERN32 / SGP_MATERN
 SPECTRAL_DOF = {RBF: None, MATERN32: 3, MATERN52: 5}
 
 
-def draw_path_inputs(kern_parts, noise_var, n, d, size, features, rng=np.random, dof=None):
+def draw_path_inputs(kern_parts, noise_var, n, d, size, features, rng=np.random, dof=None,
+                     noise_scale=None):
     """``(Omega (m, d), b (m), W (m, size), E (n, size))`` for ``size`` paths of ``m =
     features`` random Fourier features each, in the order the module documents.
 
@@ -58,6 +60,8 @@ def draw_path_inputs(kern_parts, noise_var, n, d, size, features, rng=np.random,
     b = 2.0 * np.pi * rng.random(m)
     W = rng.standard_normal((m, size))
     E = np.sqrt(noise_var + 1e-8) * rng.standard_normal((n, size))
+    if noise_scale is not None:     # per-observation noise: variance (noise_var + 1e-8) r_i
+        E = E * np.sqrt(np.asarray(noise_scale, dtype=float).reshape(n, 1))
     return Omega, b, W, E
 
 
