@@ -11,7 +11,7 @@ __device__ __forceinline__ double swarm_penalty(double slack) {
   if (slack < 0.0 && slack > -0.001) pen *= 2.0;
   if (slack <= -0.001 && slack > -0.1) pen *= 5.0;
   if (slack <= -0.1 && slack > -1.0) pen *= 10.0;
-  if (slack < -1.0) pen = -300.0 * pen * pen;
+  if (slack < -1.0) pen = -300.0 * (pen * pen);   // -300 * pen ** 2: the square first
   return pen;
 }
 
