@@ -639,6 +639,53 @@ int sgp_grid_mes_comm(sgp_grid* grid, const double* ystar, int K, int rows, int 
                       double floor_value, double* alpha, double* value, int64_t* gidx,
                       double* floor_used);
 
+/* Expected improvement and probability of improvement as logarithms (LogEI: Ament, Daulton,
+ * Eriksson, Balandat, Bakshy 2023), optionally weighed by the probability that the constraints
+ * hold (EIC: Gelbart et al. 2014, Gardner et al. 2014).  With the objective GP 0, an incumbent
+ * tau, a margin xi >= 0 and sigma_g = sqrt(max(var_g, 1e-15)), per row
+ *   z = (mean_0 - tau - xi) / sigma_0,
+ *   SGP_EI_EI:  alpha = ln(max(var_0, 1e-15)) / 2 + ln(phi(z) + z Phi(z))   (= ln EI),
+ *   SGP_EI_PI:  alpha = ln Phi(z)                                           (= ln PI),
+ *   alpha += ln Phi((mean_g - fmin_g) / sigma_g) for every g with a finite fmin_g, in the
+ *   order of g (fmin NULL or fmin_g = -inf: GP g is not weighed; NaN and +inf are refused).
+ * Both logarithms through the scaled complementary error function (csrc/ei_term.h): finite
+ * and ordered where EI itself underflows to 0.  A row's alpha depends on its own (mean_g,
+ * var_g) and on (fmin, tau, xi, kind) alone: the same bits from sgp_ei_eval and from
+ * sgp_grid_ei, whatever N, the row's position or the rank.
+ *
+ * sgp_ei_eval: alpha at N arbitrary points from HOST arrays mean[G][N], var[G][N] -> out[N].
+ * 1 <= G <= SGP_MAX_GPS, a known kind, tau finite, xi finite and >= 0, or the call fails with
+ * nothing launched and nothing written.  N <= 0 returns 0 and writes nothing.              */
+enum { SGP_EI_EI = 0, SGP_EI_PI = 1 };                            /* kind                      */
+enum { SGP_EI_TAU_MEAN = 1, SGP_EI_TAU_VALUE = 2 };               /* the incumbent             */
+int sgp_ei_eval(sgp_ctx* ctx, const double* mean, const double* var, int64_t N, int G,
+                const double* fmin, int kind, double tau, double xi, double* out);
+/* alpha over the grid's RESIDENT posterior [G][N] (the rule of sgp_grid_mes: a pass that sweeps
+ * it must have run on the rows as they are, else the call fails) and its arg-max over the
+ * candidate rows in the same pass: every row (rows = SGP_MES_ALL), the rows of S (SGP_MES_S) or
+ * of M | G as they stand on the device (SGP_MES_MG); value and gidx = GLOBAL row, the lowest
+ * row among equal values, -inf / -1 when no row qualifies.  Rows outside the mask skip the
+ * evaluation unless alpha (N_local, may be NULL) is asked for.  The incumbent: tau_value, finite
+ * (SGP_EI_TAU_VALUE), or the maximum of the mean of GP 0 over the rows of S -- over all rows
+ * with SGP_MES_ALL, over S with SGP_MES_MG too -- (SGP_EI_TAU_MEAN): reduced on the device and
+ * read from device memory by the row pass, no host round trip in between.  With an empty S
+ * there is no incumbent and no pick: alpha is all -inf, tau_used = -inf.  fmin: G values, or
+ * NULL.  tau_used returns the incumbent applied.  One read-back of {value, gidx, tau}, one more
+ * of alpha when asked for.  Q, S, M, G, mean and var are only read.                         */
+int sgp_grid_ei(sgp_grid* grid, int kind, int rows, int tau_mode, double tau_value, double xi,
+                const double* fmin, double* alpha, double* value, int64_t* gidx,
+                double* tau_used);
+/* sgp_grid_ei over the shards of all ranks of the context's communicator (sgp_comm_init or
+ * sgp_comm_init_host): the incumbent of SGP_EI_TAU_MEAN is all-reduced (max), the ranks' records
+ * {value, GLOBAL row} are all-gathered and merged on the device -- the largest value, the
+ * lowest global row among equals, a shard without a candidate never wins -- all in the grid's
+ * stream (through the host transport otherwise), then ONE read-back.  Every rank returns the
+ * same value, gidx and tau_used; alpha stays the rank's N_local rows.  A collective: every
+ * rank calls it with the same arguments.  Without a communicator it equals sgp_grid_ei.     */
+int sgp_grid_ei_comm(sgp_grid* grid, int kind, int rows, int tau_mode, double tau_value,
+                     double xi, const double* fmin, double* alpha, double* value,
+                     int64_t* gidx, double* tau_used);
+
 /* Information-theoretic safe exploration (Bottero, Luis, Vinogradska, Berkenkamp, Peters 2022):
  * the approximate mutual information, in nats, between a noisy measurement at x and the safety
  * indicator [f(z) >= fmin] of a row z.  With mu = mean(z) - fmin, vz = max(var(z), 1e-15),

@@ -41,6 +41,8 @@ MAX_BLOCK = 16            # SGP_MAX_BLOCK: observations of one block append
 MAX_MES = 64              # SGP_MAX_MES: maxima of one max-value entropy search
 MES_ALL, MES_S, MES_MG = 0, 1, 2                        # candidate rows of sgp_grid_mes
 MES_FLOOR_NONE, MES_FLOOR_MEAN, MES_FLOOR_VALUE = 0, 1, 2
+EI_EI, EI_PI = 0, 1                                     # kind of sgp_ei_eval / sgp_grid_ei
+EI_TAU_MEAN, EI_TAU_VALUE = 1, 2                        # the incumbent of sgp_grid_ei
 MAX_ISE = 4096            # SGP_MAX_ISE: candidates of one information-theoretic safe exploration
 ISE_UNSAFE, ISE_ALL = 0, 1                              # the rows z of sgp_grid_ise
 
@@ -98,6 +100,12 @@ PROTOTYPES = {
                                c_double_p, c_double_p, c_i64_p, c_double_p]),
     "sgp_grid_mes_comm": (C.c_int, [vp, c_double_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                     c_double_p, c_double_p, c_i64_p, c_double_p]),
+    "sgp_ei_eval": (C.c_int, [vp, c_double_p, c_double_p, C.c_int64, C.c_int, c_double_p,
+                              C.c_int, C.c_double, C.c_double, c_double_p]),
+    "sgp_grid_ei": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                              c_double_p, c_double_p, c_double_p, c_i64_p, c_double_p]),
+    "sgp_grid_ei_comm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                   c_double_p, c_double_p, c_double_p, c_i64_p, c_double_p]),
     "sgp_ise_eval": (C.c_int, [vp, c_double_p, c_double_p, c_double_p, c_double_p, C.c_int64,
                                C.c_double, c_double_p]),
     "sgp_grid_ise": (C.c_int, [vp, vpp, C.c_int, c_double_p, c_i64_p, C.c_int, C.c_int,
@@ -590,6 +598,29 @@ class Context(object):
         out = np.empty(mean.shape)
         self.check(lib().sgp_mes_eval(self.h, dptr(mean), dptr(var), mean.size, dptr(ystar),
                                       int(ystar.size), float(floor), dptr(out)))
+        return out
+
+    def ei_eval(self, mean, var, tau, xi=0.0, kind=EI_EI, fmin=None):
+        """Log expected improvement (``kind=EI_EI``) or log probability of improvement
+        (``EI_PI``) at arbitrary points (``sgp_ei_eval``): the posterior ``mean`` / ``var`` there,
+        ``(G, N)`` with the objective in row 0 (or ``(N,)`` for the objective alone), the
+        incumbent ``tau`` and the margin ``xi`` -> alpha ``(N,)``, a natural logarithm.
+        ``fmin`` (G): every GP with a finite entry adds the log probability that it lies above
+        it; ``None``: no weights."""
+        mean, var = f64(mean), f64(var)
+        if mean.shape != var.shape:
+            raise ValueError("mean %r and var %r differ in shape" % (mean.shape, var.shape))
+        if mean.ndim > 2:
+            raise ValueError("mean must be (G, N) or (N,), got %r" % (mean.shape,))
+        G, N = (int(mean.shape[0]), int(mean.shape[1])) if mean.ndim == 2 else (1, int(mean.size))
+        if fmin is not None:
+            fmin = f64(fmin).reshape(-1)
+            if fmin.size != G:
+                raise ValueError("%d fmin for %d GPs" % (fmin.size, G))
+        out = np.empty(N)
+        self.check(lib().sgp_ei_eval(self.h, dptr(mean), dptr(var), N, G,
+                                     None if fmin is None else dptr(fmin), int(kind), float(tau),
+                                     float(xi), dptr(out)))
         return out
 
     def ise_eval(self, mu, vz, vx, c, s):
@@ -1552,6 +1583,35 @@ class DeviceGrid(object):
                             None if al is None else dptr(al), C.byref(v), C.byref(i),
                             C.byref(fu)))
         return al, v.value, i.value, fu.value
+
+    def ei(self, kind=EI_EI, rows=MES_S, tau='mean', xi=0.0, fmin=None, alpha=False,
+           comm=False):
+        """Log expected improvement / log probability of improvement over the resident posterior
+        (``sgp_grid_ei``): ``(alpha (N,) or None, value, global row, tau used)`` -- the arg-max
+        of alpha over the candidate ``rows`` (``MES_ALL`` / ``MES_S`` / ``MES_MG``), -inf / -1
+        when no row qualifies.  ``tau``: ``'mean'`` (the largest mean of GP 0 over ``S``) or a
+        finite float.  ``fmin`` (G) or ``None``: the feasibility weights.  ``comm``:
+        ``sgp_grid_ei_comm`` -- incumbent and arg-max over the rows of ALL ranks of the
+        context's communicator, the same on every rank (``alpha`` stays this rank's block); a
+        collective."""
+        if isinstance(tau, str):
+            if tau != 'mean':
+                raise ValueError("tau must be 'mean' or a float, got %r" % (tau,))
+            mode, tv = EI_TAU_MEAN, 0.0
+        else:
+            mode, tv = EI_TAU_VALUE, float(tau)
+        if fmin is not None:
+            fmin = f64(fmin).reshape(-1)
+            if fmin.size != self.G:
+                raise ValueError("%d fmin for %d GPs" % (fmin.size, self.G))
+        al = np.empty(self.N) if alpha else None
+        v, i, tu = C.c_double(0), C.c_int64(0), C.c_double(0)
+        call = lib().sgp_grid_ei_comm if comm else lib().sgp_grid_ei
+        self.ctx.check(call(self.h, int(kind), int(rows), mode, tv, float(xi),
+                            None if fmin is None else dptr(fmin),
+                            None if al is None else dptr(al), C.byref(v), C.byref(i),
+                            C.byref(tu)))
+        return al, v.value, i.value, tu.value
 
     def ise(self, gps, fmin, cand, about=ISE_UNSAFE, pairs=False, cov=False):
         """Information-theoretic safe exploration over the resident posterior

@@ -17,7 +17,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 OUT = os.path.join(PKG, "libsafeopt_hip.so")
-SOURCES = ["api.hip", "expander_api.hip", "batch.hip", "block.hip", "sweep.hip", "expander.hip", "sweep_pair.hip",
+SOURCES = ["api.hip", "expander_api.hip", "batch.hip", "block.hip", "ei.hip", "sweep.hip", "expander.hip", "sweep_pair.hip",
            "sweep_mid.hip", "sweep_tiny.hip", "step_small.hip",
            "factor.hip", "hyper.hip", "ise.hip", "joint.hip", "mes.hip", "paths.hip", "sets.hip", "swarm.hip",
            "swarm_api.hip", "swarm_batch.hip", "swarm_ise.hip"]
@@ -26,7 +26,7 @@ HEADERS = [os.path.join(CSRC, h) for h in ("common.h", "kern_eval.h", "fitness.h
                                             "sweep_slots.h", "set_order.h",
                                             "tiny_row.h", "sets_front.h",
                                             "expander_layout.h", "mes_term.h",
-                                            "ise_term.h")] + \
+                                            "ise_term.h", "ei_term.h")] + \
           [os.path.join(REPO, "include", "safeopt_hip.h")]
 BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
         "-I", os.path.join(REPO, "include"), "-I", CSRC, "-Wall",
@@ -40,6 +40,7 @@ BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 EXTRA = {"sets.hip": ["-ffp-contract=off"], "swarm.hip": ["-ffp-contract=off"],
          "swarm_batch.hip": ["-ffp-contract=off"], "mes.hip": ["-ffp-contract=off"],
          "ise.hip": ["-ffp-contract=off"], "swarm_ise.hip": ["-ffp-contract=off"],
+         "ei.hip": ["-ffp-contract=off"],
          "sweep.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-Wno-inline-asm"]}
 # e.g. SGP_HIPCC_FLAGS=-DSGP_INSTRUMENT for scripts/ablate.py (use --force)
 USER = os.environ.get("SGP_HIPCC_FLAGS", "").split()

@@ -215,6 +215,10 @@ enum ScratchSlot : int {
   kSlotSwarmIseIn = 31, // ... targets[Tp][d] | zmean[G][Tp] | zvar[G][Tp] | bestv[P] | bestt[P]
   kSlotSwarmIseOut = 32,// ... alpha[P] | target[P] | post[G][2][P] | pairs[P][T] | cov[G][P][T] of a
                         // fitness call that asks for them
+  kSlotEiIn = 33,       // ei.hip: mean[G] | var[G] | out of sgp_ei_eval's rows; the alpha array of a
+                        // grid call
+  kSlotEiPart = 34,     // ... per-workgroup (value, row) pairs and incumbent partials of a grid
+                        // call, its records and result (EiScratch)
   kScratchSlots
 };
 inline bool scratch_kept(ScratchSlot s) { return s >= kSlotOperands && s <= kSlotManyFlags; }

@@ -759,6 +759,16 @@ class _HipGridBackend(object):
             self.refresh_posterior()
         return self.grid.mes(ystar, rows=rows, floor=floor, alpha=alpha, comm=comm)
 
+    def ei(self, kind, rows, tau, xi, fmin, alpha=False, comm=False):
+        """Log expected improvement / log probability of improvement over the resident
+        posterior (``DeviceGrid.ei``); the posterior is swept first when it is not that of
+        the GPs as they are.  ``comm``: incumbent and arg-max merged over the ranks in the
+        grid's stream (``sgp_grid_ei_comm``)."""
+        if not self.posterior_is_current():
+            self.refresh_posterior()
+        return self.grid.ei(kind=kind, rows=rows, tau=tau, xi=xi, fmin=fmin, alpha=alpha,
+                            comm=comm)
+
     def ise_state(self):
         """What the host-side candidate selection of ``SafeOpt.ise_point`` reads, in one
         download each: the resident variances ``(G, N)``, the safe set ``(N,)`` and the
@@ -2017,6 +2027,118 @@ class SafeOpt(GaussianProcessOptimization):
             raise RuntimeError('There are no safe points to sample in.')
         x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
         return (x, alpha, values, ystar) if return_values else (x, alpha)
+
+    def ei_point(self, incumbent='mean', xi=0.0, within='safe', kind='ei', feasibility=False,
+                 return_values=False):
+        """The safe row with the largest expected improvement over the incumbent, evaluated
+        as a logarithm (LogEI: Ament et al. 2023).
+
+        With ``mu_g``, ``v_g`` the resident posterior of GP ``g`` (the objective is GP 0),
+        ``sigma_g = sqrt(max(v_g, 1e-15))``, the incumbent ``tau`` and
+        ``z = (mu_0 - tau - xi) / sigma_0``,
+
+            ``kind='ei'``: ``alpha(x) = ln sigma_0 + ln(phi(z) + z Phi(z))``  (= ln EI),
+            ``kind='pi'``: ``alpha(x) = ln Phi(z)``  (= ln of the probability of improvement),
+
+        and the pick is the row of ``S`` with the largest ``alpha`` (the lowest row among
+        equals).  One pass over the resident rows on the device.  On a converged run --
+        ``sigma`` tiny, the incumbent far above most safe rows -- EI itself underflows to 0 on
+        almost every row and its arg-max is "the lowest row among equals"; ``alpha`` stays
+        finite and ordered there.
+
+        ``incumbent='mean'`` (default): the largest posterior mean over ``S``; ``'data'``:
+        the largest measured objective value, ``max(opt.y[:, 0])``; a finite float: that
+        value.  ``xi >= 0``: the margin an improvement has to exceed.
+
+        ``feasibility=True``: every GP with a finite ``fmin`` adds ``ln Phi((mu_g - fmin_g) /
+        sigma_g)``, the log probability that its constraint holds (EIC: Gelbart et al. 2014,
+        Gardner et al. 2014).
+
+        ``within='safe'``: candidates ``S``.  ``'MG'``: candidates ``M | G`` as they stand --
+        call it after ``optimize()`` / ``compute_sets()``, which compute them; the incumbent
+        of ``'mean'`` is still that of ``S``.  ``'all'``: no mask for incumbent and candidates
+        -- NOT a safe pick; with ``feasibility=True`` it is the EIC baseline the safe-BO
+        papers compare against, for diagnostics and unconstrained problems only.
+
+        Returns ``(x, alpha)``: the row, context columns stripped as ``optimize()`` strips
+        them, and its ``alpha``; with ``return_values=True`` ``(x, alpha, values (N,),
+        tau)``: ``alpha`` of every row and the incumbent used.  Raises ``RuntimeError`` when
+        no row qualifies.  Changes no state of the optimiser or its GPs -- except that
+        pending in-place edits of ``opt.Q`` / ``opt.S`` are flushed first, as before a set
+        pass, and that the resident posterior is swept again if data came in since the last
+        interval update.  Draws no random numbers.
+
+        N ranks (SPMD: the same call on every rank): incumbent and pick are those of all
+        shards -- merged in the grid's stream with an in-stream communicator
+        (``sgp_grid_ei_comm``), else through ``allreduce_max`` of the shard's incumbent (one
+        extra pass over the shard finds it), one ``allgather`` of the ranks' records and
+        ``dist.merge_mes_records``; both give the bits of the one-rank run, on every rank.
+        ``values`` is gathered in global row order.  "No row qualifies" raises on every rank,
+        behind the collective."""
+        if within not in ('safe', 'MG', 'all'):
+            raise ValueError("within must be 'safe', 'MG' or 'all', got %r" % (within,))
+        if kind not in ('ei', 'pi'):
+            raise ValueError("kind must be 'ei' or 'pi', got %r" % (kind,))
+        xi = float(xi)
+        if not (np.isfinite(xi) and xi >= 0.0):
+            raise ValueError("xi must be finite and >= 0, got %r" % (xi,))
+        if isinstance(incumbent, str):
+            if incumbent not in ('mean', 'data'):
+                raise ValueError("incumbent must be 'mean', 'data' or a float, got %r"
+                                 % (incumbent,))
+            tau = 'mean'
+            if incumbent == 'data':
+                seen = self.y[:, 0][~np.isnan(self.y[:, 0])]
+                if seen.size == 0:
+                    raise ValueError("incumbent='data': the objective has no measurement")
+                tau = float(seen.max())
+        else:
+            tau = float(incumbent)
+        if tau != 'mean' and not np.isfinite(tau):
+            raise ValueError("the incumbent must be finite, got %r" % (tau,))
+        comm = self._comm
+        world = comm.world
+        if world > 1 and not all(callable(getattr(comm, f, None))
+                                 for f in ('allreduce_max', 'allgather')):
+            raise NotImplementedError(
+                "ei_point on more than one rank merges the ranks' picks through the "
+                "communicator's allreduce_max and allgather: this communicator of %d ranks "
+                "implements neither" % world)
+        if not hasattr(self._backend, 'ei'):
+            raise NotImplementedError("this grid backend runs no expected improvement")
+        self._flush_Q()
+        self._flush_masks()
+        safe = within != 'all'
+        rows = {'safe': _hip.MES_S, 'MG': _hip.MES_MG, 'all': _hip.MES_ALL}[within]
+        code = _hip.EI_EI if kind == 'ei' else _hip.EI_PI
+        fmin = np.asarray(self.fmin, dtype=float).reshape(-1) if feasibility else None
+        # (N ranks: raised behind the collective, where every rank is sure to arrive)
+        if world == 1 and safe and self._any_safe is not None and not self._any_safe:
+            raise RuntimeError('There are no safe points to sample in.')
+        be = self._backend
+        if world == 1 or getattr(comm, 'in_stream', False):
+            values, alpha, idx, tau = be.ei(code, rows, tau, xi, fmin, return_values,
+                                            comm=world > 1)
+        else:
+            if tau == 'mean':
+                # the shard's incumbent from a pass of its own, then the ranks' largest
+                tau = be.ei(code, rows, 'mean', xi, fmin)[3]
+                tau = float(comm.allreduce_max(np.array([tau]))[0])
+            if tau == -np.inf:                       # no rank has a safe row
+                lo, hi = shard_range(self.inputs.shape[0], comm.rank, world)
+                values = np.full(hi - lo, -np.inf) if return_values else None
+                v, i = -np.inf, -1
+            else:
+                values, v, i, _tau = be.ei(code, rows, tau, xi, fmin, return_values)
+            alpha, idx = merge_mes_records(comm.allgather(np.array([v, float(i)])))
+        if world > 1 and return_values:
+            N = self.inputs.shape[0]
+            values = allgather_rows(comm, values, [
+                hi - lo for lo, hi in (shard_range(N, r, world) for r in range(world))])
+        if idx < 0:
+            raise RuntimeError('There are no safe points to sample in.')
+        x = self.inputs[idx, :self.inputs.shape[1] - self.num_contexts]
+        return (x, alpha, values, tau) if return_values else (x, alpha)
 
     def _ise(self, candidates, about):
         """The body of ``ise_point``: ``(rows, values, targets, alpha, global row)``, the

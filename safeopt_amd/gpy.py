@@ -700,6 +700,18 @@ class GPRegression(object):
         dev = self._fitted()
         return dev.ctx.mes_eval(mean, var, ystar, -np.inf if floor is None else float(floor))
 
+    def log_expected_improvement(self, X, best, xi=0.0):
+        """The logarithm of the expected improvement over ``best`` at the rows of ``X``,
+        ``(N, 1)``: with ``mu, v = predict_noiseless(X)``, ``sigma = sqrt(max(v, 1e-15))`` and
+        ``z = (mu - best - xi) / sigma``, ``ln sigma + ln(phi(z) + z Phi(z))`` (LogEI, Ament et
+        al. 2023) -- finite and ordered where the expected improvement itself underflows to 0.
+        ``best`` finite, ``xi >= 0``.  One device call behind the prediction
+        (``sgp_ei_eval``)."""
+        mean, var = self.predict_noiseless(X)
+        dev = self._fitted()
+        return dev.ctx.ei_eval(mean.ravel(), var.ravel(), float(best),
+                               float(xi)).reshape(-1, 1)
+
     def posterior_samples(self, X, size=10):
         """``posterior_samples_f`` plus observation noise: ``sqrt(noise_var)`` times a
         second draw ``np.random.randn(N, 1, size)``."""
