@@ -1107,6 +1107,64 @@ int sgp_swarm_run_ise_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta
                             uint64_t seed, const double* targets, const double* zmean,
                             const double* zvar, int T, int64_t p0, int64_t P_total);
 
+/* The fitness of an EI swarm: log expected improvement / log probability of improvement (the
+ * rule of sgp_grid_ei) without a grid.  With mu_g, var_g the posterior of GP g at x (GP 0 the
+ * objective), sigma_g = sqrt(max(var_g, 1e-15)), the incumbent tau and the margin xi >= 0,
+ *   z = (mu_0 - tau - xi) / sigma_0
+ *   SGP_EI_EI:  alpha = ln(max(var_0, 1e-15)) / 2 + ln(phi(z) + z Phi(z)),
+ *   SGP_EI_PI:  alpha = ln Phi(z),
+ *   weigh = 1:  alpha += ln Phi((mu_g - fmin[g]) / sigma_g) for every g with a finite fmin[g],
+ *               in the order of g (weigh = 0: no weights);
+ *   free = 0:   values = alpha + total_pen, safe as for SGP_SWARM_MAXIMIZERS
+ *               (sgp_swarm_fitness_mes; fmin drives penalty and flag whatever weigh is);
+ *   free = 1:   values = alpha, safe = 1 -- penalty and safety rule switched off: with weigh
+ *               the EIC baseline over the bounds, NOT a safe pick.
+ * scaling does not scale alpha (a logarithm, not a function value).  A particle's alpha, value
+ * and flag depend on its coordinates, the GPs and (kind, tau, xi, fmin, weigh, free) alone --
+ * not on P, its row, the launch, the block or the rank -- and alpha has the bits of sgp_ei_eval
+ * on the posterior `post` the call returns.  The posterior is formed by the kernels
+ * sgp_swarm_fitness takes for that P and n (a block of a sharded run: P_total and n; a call of
+ * up to 4096 particles on GPs of 128 observations or more takes the few-points posterior, whose
+ * last bits may differ from the sweep's); alpha is one more launch behind the shaping pass
+ * (k_swarm_ei: one thread per particle on the fp64 VALU, no LDS, no atomics; its constants
+ * travel by value, nothing is staged).  alpha (P) and post (G,2,P: mean | var per GP) may be
+ * NULL.
+ * Checked in this order, a refused call launches and writes nothing: G >= 1 and gps[0]; a
+ * known kind; tau finite; xi finite and >= 0; weigh, then free, 0 or 1; with weigh no fmin[g]
+ * NaN or +inf; P <= 0 then returns 0; then the checks of sgp_swarm_fitness.            */
+int sgp_swarm_fitness_ei(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                         int64_t P, double beta, const double* fmin, const double* scaling,
+                         int kind, double tau, double xi, int weigh, int free_mode,
+                         double* values, uint8_t* safe, double* alpha, double* post);
+
+/* sgp_swarm_run for an EI swarm: the fitness is that of sgp_swarm_fitness_ei (no outputs),
+ * everything else as for sgp_swarm_run_mes, kind / tau / xi / weigh / free in place of ystar /
+ * K / floor.  The run ALWAYS takes the general launches -- move, fitness (posterior, shaping,
+ * alpha), personal bests, global best: with rand != NULL it is bit-identical to the host loop
+ * over sgp_swarm_fitness_ei.  The refusals of sgp_swarm_fitness_ei, in its order; P <= 0
+ * returns 0 and writes nothing.                                                      */
+int sgp_swarm_run_ei(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta, const double* fmin,
+                     const double* scaling, int64_t P, double* positions, double* velocities,
+                     double* best_positions, double* best_values, double* global_best,
+                     const double* velocity_scale, const double* bounds, int init, int iters,
+                     double inertia0, double step, const double* rand, uint64_t seed,
+                     int kind, double tau, double xi, int weigh, int free_mode);
+
+/* sgp_swarm_run_ei on a rank's block [p0, p0 + P) of an EI swarm of P_total: everything as
+ * sgp_swarm_run_mes_shard; every rank passes the same kind, tau, xi, weigh and free.  alpha is
+ * per particle, so a block computes the bits the whole swarm computes for its particles.
+ * P <= 0 and P_total <= 0 returns 0; an empty block of a sharded swarm is refused ("bad swarm
+ * size"), as is a block without a communicator on ctx.  p0 = 0, P = P_total is
+ * sgp_swarm_run_ei.                                                                  */
+int sgp_swarm_run_ei_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                           const double* fmin, const double* scaling, int64_t P,
+                           double* positions, double* velocities, double* best_positions,
+                           double* best_values, double* global_best,
+                           const double* velocity_scale, const double* bounds, int init,
+                           int iters, double inertia0, double step, const double* rand,
+                           uint64_t seed, int kind, double tau, double xi, int weigh,
+                           int free_mode, int64_t p0, int64_t P_total);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI -------------------------
  * The only cross-rank traffic of the path is a handful of scalars per
  * iteration (max / any / arg-max / top-k merge).                             */

@@ -238,6 +238,10 @@ PROTOTYPES = {
                                         c_double_p, c_double_p, c_double_p, C.c_int,
                                         c_double_p, c_u8_p, c_double_p, c_i64_p, c_double_p,
                                         c_double_p, c_double_p]),
+    "sgp_swarm_fitness_ei": (C.c_int, [vp, vpp, C.c_int, c_double_p, C.c_int64,
+                                       C.c_double, c_double_p, c_double_p,
+                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                       c_double_p, c_u8_p, c_double_p, c_double_p]),
     "sgp_swarm_grow": (C.c_int, [vp, vp, c_double_p, C.c_int64, c_double_p,
                                  C.c_int64, C.c_double, C.c_double, c_u8_p]),
     "sgp_swarm_run": (C.c_int, [vp, vpp, C.c_int, C.c_int, C.c_double,
@@ -284,6 +288,20 @@ PROTOTYPES = {
                                           C.c_int, C.c_double, C.c_double, c_double_p,
                                           C.c_uint64, c_double_p, c_double_p, c_double_p,
                                           C.c_int, C.c_int64, C.c_int64]),
+    "sgp_swarm_run_ei": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                   c_double_p, c_double_p, C.c_int64,
+                                   c_double_p, c_double_p, c_double_p, c_double_p,
+                                   c_double_p, c_double_p, c_double_p, C.c_int,
+                                   C.c_int, C.c_double, C.c_double, c_double_p,
+                                   C.c_uint64, C.c_int, C.c_double, C.c_double, C.c_int,
+                                   C.c_int]),
+    "sgp_swarm_run_ei_shard": (C.c_int, [vp, vpp, C.c_int, C.c_double,
+                                         c_double_p, c_double_p, C.c_int64,
+                                         c_double_p, c_double_p, c_double_p, c_double_p,
+                                         c_double_p, c_double_p, c_double_p, C.c_int,
+                                         C.c_int, C.c_double, C.c_double, c_double_p,
+                                         C.c_uint64, C.c_int, C.c_double, C.c_double, C.c_int,
+                                         C.c_int, C.c_int64, C.c_int64]),
     "sgp_swarm_run_path": (C.c_int, [vp, vpp, C.c_int, C.c_double,
                                      c_double_p, c_double_p, C.c_int64,
                                      c_double_p, c_double_p, c_double_p, c_double_p,
@@ -1762,14 +1780,28 @@ def _swarm_ise_args(gps, ise):
     return targets, zmean, zvar, T
 
 
-def _swarm_call(ctx, name, gps, swarm_type, path, clones, mes=None, ise=None):
-    """The C symbol ``sgp_swarm_<name>[_path|_hall|_mes|_ise]`` of a swarm variant, the head of its
+def _swarm_ei_args(ei):
+    """``ei = (kind, tau, xi, weigh, free)`` of an 'ei' swarm as the C side takes it: ``kind``
+    ``'ei'`` / ``'pi'`` or its code, ``weigh`` and ``free`` as 0 / 1 (an int is passed on as it
+    is, for the library to refuse)."""
+    kind, tau, xi, weigh, free = ei
+    kind = {"ei": EI_EI, "pi": EI_PI}.get(kind, kind) if isinstance(kind, str) else kind
+    return (int(kind), float(tau), float(xi), int(weigh), int(free))
+
+
+def _swarm_call(ctx, name, gps, swarm_type, path, clones, mes=None, ise=None, ei=None):
+    """The C symbol ``sgp_swarm_<name>[_path|_hall|_mes|_ise|_ei]`` of a swarm variant, the head of its
     argument list -- ``ctx, gps[, clones], G[, swarm type]`` -- and the staged-on-the-host
     path arguments that close it (``path = (Omega, phase, w, v)``, one sample path of
     ``gps[0]``; ``clones[g]``: ``gps[g].clone()`` with the pending picks appended; ``mes =
     (ystar, floor)``: the maxima of a max-value entropy search and the floor under them;
     ``ise = (targets, zmean, zvar)``: the targets of an information-theoretic safe exploration
-    and their posterior)."""
+    and their posterior; ``ei = (kind, tau, xi, weigh, free)``: the incumbent and the switches
+    of an expected-improvement swarm)."""
+    if ei is not None and (path is not None or clones is not None or mes is not None
+                           or ise is not None):
+        raise NotImplementedError("an 'ei' swarm takes neither a path, clones, maxima nor "
+                                  "targets")
     if ise is not None and (path is not None or clones is not None or mes is not None):
         raise NotImplementedError("an 'ise' swarm takes neither a path, clones nor maxima")
     if mes is not None and (path is not None or clones is not None):
@@ -1789,13 +1821,15 @@ def _swarm_call(ctx, name, gps, swarm_type, path, clones, mes=None, ise=None):
     elif ise is not None:
         targets, zmean, zvar, T = _swarm_ise_args(gps, ise)
         name, tail = name + "_ise", (dptr(targets), dptr(zmean), dptr(zvar), T)
+    elif ei is not None:
+        name, tail = name + "_ei", _swarm_ei_args(ei)
     else:
         head += (SWARM_TYPES[swarm_type],)
     return name, head, tail
 
 
 def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=None,
-               shard=None, mes=None, ise=None):
+               shard=None, mes=None, ise=None, ei=None):
     """Every whole PSO run on the device: ``fit = (beta, fmin, scaling, best_lower_bound)``,
     ``state = (positions, velocities, best_positions, best_values, global_best,
     velocity_scale, bounds)`` -- the first five updated in place -- and ``schedule = (init,
@@ -1803,8 +1837,9 @@ def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=Non
     swarm; ``swarm_type`` and the best lower bound are not used), ``clones`` (a hallucinated
     swarm), ``mes = (ystar, floor)`` (a max-value entropy search swarm; ``swarm_type`` and the
     best lower bound are not used), ``ise = (targets, zmean, zvar)`` (an information-theoretic
-    safe exploration swarm, likewise) and ``shard = (p0, P_total)`` pick the entry point
-    (``sgp_swarm_run[_hall|_path|_mes|_ise][_shard]``)."""
+    safe exploration swarm, likewise), ``ei = (kind, tau, xi, weigh, free)`` (an expected-
+    improvement swarm, likewise) and ``shard = (p0, P_total)`` pick the entry point
+    (``sgp_swarm_run[_hall|_path|_mes|_ise|_ei][_shard]``)."""
     beta, fmin, scaling, best_lower_bound = fit
     init, iters, inertia0, step, rand, seed = schedule
     P = state[0].shape[0]
@@ -1812,14 +1847,14 @@ def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=Non
         raise NotImplementedError("a hallucinated swarm is a maximizers or an expanders "
                                   "swarm, not a Thompson swarm")
     name, head, tail = _swarm_call(ctx, "sgp_swarm_run", gps, swarm_type, path, clones, mes,
-                                   ise)
+                                   ise, ei)
     for a in state[:5]:
         assert a.dtype == np.float64 and a.flags.c_contiguous
     vscale = f64(state[5])
     bnd = None if state[6] is None else f64(state[6])
     rnd = None if rand is None else f64(rand).ravel()
     args = head + (float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
-    if path is None and mes is None and ise is None:
+    if path is None and mes is None and ise is None and ei is None:
         args += (float(best_lower_bound),)
     args += (P,) + tuple(dptr(a) for a in state[:5]) + (
         dptr(vscale), None if bnd is None else dptr(bnd), int(bool(init)), int(iters),
@@ -1830,23 +1865,25 @@ def _swarm_run(ctx, gps, swarm_type, fit, state, schedule, path=None, clones=Non
 
 
 def _swarm_fitness(ctx, gps, swarm_type, particles, fit, path=None, clones=None,
-                   want_var=False, mes=None, want_post=False, ise=None, want=()):
+                   want_var=False, mes=None, want_post=False, ise=None, want=(), ei=None):
     """Every swarm fitness call: ``(values, safe)`` of ``particles``, with ``want_var`` (a
     hallucinated swarm's) also the hallucinated variances ``(G, P)``, with ``want_post`` (a
     'mes' swarm's) also the posterior ``(2, P)`` of GP 0 the term was formed from; ``fit``,
     ``path``, ``clones``, ``mes`` and ``ise`` as for :func:`_swarm_run`.  An 'ise' swarm
     returns ``(values, safe, out)``, ``out`` a dict of the arrays named in ``want``: 'alpha'
-    (P), 'target' (P, int64), 'post' (G, 2, P), 'pairs' (P, T), 'cov' (G, P, T)."""
+    (P), 'target' (P, int64), 'post' (G, 2, P), 'pairs' (P, T), 'cov' (G, P, T).  An 'ei'
+    swarm returns ``(values, safe)``, or with a non-empty ``want`` ``(values, safe, out)``:
+    'alpha' (P), 'post' (G, 2, P)."""
     beta, fmin, scaling, best_lower_bound = fit
     name, head, tail = _swarm_call(ctx, "sgp_swarm_fitness", gps, swarm_type, path, clones, mes,
-                                   ise)
+                                   ise, ei)
     particles = f64(particles).reshape(-1, gps[0].d)
     P = particles.shape[0]
     values = np.empty(P)
     safe = np.empty(P, dtype=np.uint8)
     var_h = np.empty((len(gps), P)) if want_var else None
     args = head + (dptr(particles), P, float(beta), dptr(f64(fmin)), dptr(f64(scaling)))
-    if path is None and mes is None and ise is None:
+    if path is None and mes is None and ise is None and ei is None:
         args += (float(best_lower_bound),)
     args += tail + (dptr(values), safe.ctypes.data_as(c_u8_p))
     if clones is not None:
@@ -1867,11 +1904,20 @@ def _swarm_fitness(ctx, gps, swarm_type, particles, fit, path=None, clones=None,
                 out[k] = np.empty(shapes[k], dtype=np.int64 if k == "target" else np.float64)
         args += tuple((out[k].ctypes.data_as(c_i64_p) if k == "target" else dptr(out[k]))
                       if k in out else None for k in ("alpha", "target", "post", "pairs", "cov"))
+    if ei is not None:
+        unknown = set(want) - {"alpha", "post"}
+        if unknown:
+            raise ValueError("unknown outputs %r of an 'ei' swarm" % sorted(unknown))
+        shapes = {"alpha": (P,), "post": (len(gps), 2, P)}
+        for k in ("alpha", "post"):
+            if k in want:
+                out[k] = np.empty(shapes[k])
+        args += tuple(dptr(out[k]) if k in out else None for k in ("alpha", "post"))
     # (an empty hallucinated call still checks its clones, an empty 'mes' call its maxima, an
-    # empty 'ise' call its targets)
-    if P or clones is not None or mes is not None or ise is not None:
+    # empty 'ise' call its targets, an empty 'ei' call its incumbent)
+    if P or clones is not None or mes is not None or ise is not None or ei is not None:
         ctx.check(getattr(lib(), name)(*args))
-    if ise is not None:
+    if ise is not None or (ei is not None and want):
         return values, safe.view(np.bool_), out
     if want_post:
         return values, safe.view(np.bool_), post
@@ -2001,3 +2047,36 @@ def swarm_run_ise(ctx, gps, beta, fmin, scaling, positions, velocities, best_pos
                (positions, velocities, best_positions, best_values, global_best,
                 velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
                ise=(targets, zmean, zvar), shard=shard)
+
+
+def swarm_fitness_ei(ctx, gps, particles, beta, fmin, scaling, kind, tau, xi, weigh, free,
+                     want_alpha=False, want_post=False):
+    """Fitness and safety of ``particles`` for an expected-improvement swarm
+    (``sgp_swarm_fitness_ei``): ``values = alpha + total_pen`` with ``alpha`` the logarithm of
+    :meth:`Context.ei_eval` on the posterior of ``gps`` -- ``kind`` ``'ei'`` / ``'pi'`` (or
+    ``EI_EI`` / ``EI_PI``), the incumbent ``tau``, the margin ``xi``, with ``weigh`` the log
+    probability of feasibility of every GP with a finite ``fmin`` -- the penalty and ``safe``
+    those of the maximizers swarm; ``free``: ``values = alpha`` and ``safe`` all true, penalty
+    and safety rule switched off.  Returns ``(values, safe)``, followed by ``alpha`` (P) with
+    ``want_alpha`` and by the posterior ``(G, 2, P)`` mean | var with ``want_post``."""
+    want = (("alpha",) if want_alpha else ()) + (("post",) if want_post else ())
+    res = _swarm_fitness(ctx, gps, None, particles, (beta, fmin, scaling, 0.0),
+                         ei=(kind, tau, xi, weigh, free), want=want)
+    if not want:
+        return res
+    return res[:2] + tuple(res[2][k] for k in want)
+
+
+def swarm_run_ei(ctx, gps, beta, fmin, scaling, positions, velocities, best_positions,
+                 best_values, global_best, velocity_scale, bounds, init, iters, inertia0,
+                 step, rand, kind, tau, xi, weigh, free, seed=0, shard=None):
+    """Whole PSO run of an expected-improvement swarm on the device (``sgp_swarm_run_ei``); the
+    state arrays are updated in place, ``kind`` .. ``free`` as for :func:`swarm_fitness_ei`.
+
+    ``shard=(p0, P_total)``: the arrays hold the rows ``[p0, p0 + P)`` of a swarm of
+    ``P_total`` sharded over the ranks of ``ctx``'s communicator
+    (``sgp_swarm_run_ei_shard``), as for :func:`swarm_run`."""
+    _swarm_run(ctx, gps, None, (beta, fmin, scaling, 0.0),
+               (positions, velocities, best_positions, best_values, global_best,
+                velocity_scale, bounds), (init, iters, inertia0, step, rand, seed),
+               ei=(kind, tau, xi, weigh, free), shard=shard)

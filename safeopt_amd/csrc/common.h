@@ -216,7 +216,8 @@ enum ScratchSlot : int {
   kSlotSwarmIseOut = 32,// ... alpha[P] | target[P] | post[G][2][P] | pairs[P][T] | cov[G][P][T] of a
                         // fitness call that asks for them
   kSlotEiIn = 33,       // ei.hip: mean[G] | var[G] | out of sgp_ei_eval's rows; the alpha array of a
-                        // grid call
+                        // grid call; swarm_api.hip: alpha and post of an 'ei' swarm fitness call
+                        // (SwarmEiLayout)
   kSlotEiPart = 34,     // ... per-workgroup (value, row) pairs and incumbent partials of a grid
                         // call, its records and result (EiScratch)
   kScratchSlots
@@ -537,6 +538,49 @@ int launch_swarm_mes(sgp_ctx* ctx, int64_t P, const double* mean, const double* 
 // The same branch of the shaping pass; the term on top is alpha = max_t pair(p, t) over the
 // staged targets (launch_swarm_ise behind the shaping launch)
 constexpr int kSwarmIse = 6;
+// ... and of sgp_swarm_fitness_ei / sgp_swarm_run_ei: log expected improvement.  The same
+// branch of the shaping pass; the term on top is ei_alpha (ei_term.h) of all G GPs' posterior
+// (launch_swarm_ei behind the shaping launch)
+constexpr int kSwarmEi = 7;
+// What an expected-improvement call fixes for all its rows (a kernel argument by value; the
+// arithmetic on it is ei_term.h's alone)
+struct EiTerm {
+  int kind;                  // SGP_EI_EI | SGP_EI_PI
+  int G;                     // GPs of the posterior; the feasibility weights walk all of them
+  double xi;
+  double fmin[SGP_MAX_GPS];  // -inf: GP g is not weighed
+};
+// The incumbent of an 'ei' swarm as the kernel takes it
+struct SwarmEi {
+  EiTerm term;
+  double tau;
+  int on;                // 0: not an 'ei' swarm
+  int free;              // 1: values = alpha, safe = 1 (no penalty, no safety rule)
+  double* alpha;         // [P] on the device: receives alpha, or null
+  double* post;          // [G][2][P] on the device: receives mean | var per GP, or null
+};
+// ei.hip: values[p] = ei_alpha(p) + values[p] (free: = ei_alpha(p), safe[p] = 1) over P
+// particles whose posterior is mean / var [G][P] (k_swarm_ei)
+int launch_swarm_ei(sgp_ctx* ctx, int G, int64_t P, const double* mean, const double* var,
+                    const SwarmEi& m, double* values, uint8_t* safe);
+// The block of an 'ei' swarm fitness call in kSlotEiIn (sgp_swarm_fitness_ei; neither
+// swarm_fitness nor swarm_run asks for this slot): alpha[P] | post[G][2][P], each only when
+// the call asks for it
+struct SwarmEiLayout {
+  size_t alpha, post, bytes;
+};
+constexpr SwarmEiLayout swarm_ei_layout(int64_t P, int G, bool alpha, bool post) {
+  SwarmEiLayout l{};
+  l.alpha = 0;
+  l.post = alpha && P > 0 ? size_t(P) * 8 : 0;
+  l.bytes = l.post + (post && P > 0 ? 2 * size_t(G) * size_t(P) * 8 : 0);
+  return l;
+}
+static_assert(swarm_ei_layout(3, 2, true, true).post == 24 &&
+                  swarm_ei_layout(3, 2, true, true).bytes == 24 + 96 &&
+                  swarm_ei_layout(3, 2, false, true).bytes == 96 &&
+                  swarm_ei_layout(3, 2, true, false).bytes == 24,
+              "SwarmEiLayout: post overlaps alpha or ends outside the block");
 // ise.hip: W = Ky^-1 k(X, x_j) of the K points xc [K][d] (device) in [n_pad][Kp], Kp a multiple
 // of 64, W zeroed by the caller, T an [n][Kp] workspace: the operand kernels of sgp_grid_ise
 int launch_ise_operands(sgp_ctx* ctx, sgp_gp* gp, const double* xc, int K, int Kp, double* W,
@@ -583,6 +627,9 @@ struct FitnessArgs {
   // a 'mes' swarm (swarm_type == kSwarmMes; K = 0 otherwise): read by launch_fitness_small on
   // the host, which launches the term behind the shaping kernel -- no kernel reads it
   SwarmMes mes;
+  // an 'ei' swarm (swarm_type == kSwarmEi; on = 0 otherwise): likewise read by
+  // launch_fitness_small on the host alone -- no kernel reads it
+  SwarmEi ei;
   // an 'ise' swarm (swarm_type == kSwarmIse; null otherwise): a HOST pointer, read by
   // launch_fitness_small alone, which launches the term behind the shaping kernel
   const SwarmIse* ise;
@@ -643,6 +690,7 @@ struct SwarmSpec {             // what the fitness is
   const SwarmMes* mes;         // a 'mes' swarm: the STAGED maxima; null otherwise
   const struct SwarmIseIn* ise = nullptr;   // an 'ise' swarm: the caller's targets (host); the two
                                // routines stage them behind their checks (swarm_ise_stage)
+  const SwarmEi* ei = nullptr; // an 'ei' swarm: incumbent, term and output buffers; null otherwise
 };
 struct SwarmIseIn {
   const double *targets, *zmean, *zvar;   // (T,d), (G,T), (G,T) on the host

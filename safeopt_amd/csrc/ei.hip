@@ -16,8 +16,9 @@
 // mask costs one byte unless the caller asked for the alpha array.  mean[g][i] / var[g][i] of
 // consecutive lanes are consecutive doubles.  A row's alpha is a function of its own (mean_g,
 // var_g) and of (fmin, tau, xi, kind) alone -- the same device function in the row kernel
-// (sgp_ei_eval) and in the grid kernel -- so it has the same bits whatever N, the launch shape,
-// the row's position or the rank.  The arg-max is an epilogue: per-workgroup (value, local row)
+// (sgp_ei_eval), in the grid kernel and in the particle kernel of an 'ei' swarm (k_swarm_ei,
+// behind the shaping pass of sgp_swarm_fitness_ei / sgp_swarm_run_ei) -- so it has the same
+// bits whatever N, the launch shape, the row's position or the rank.  The arg-max is an epilogue: per-workgroup (value, local row)
 // pairs, one small final kernel; the largest value, the lowest row among equals, rows outside
 // the mask never.  No atomics.  The incumbent of SGP_EI_TAU_MEAN is reduced on the device and
 // read from device memory by the grid kernel: nothing comes back to the host between the two.
@@ -164,6 +165,37 @@ inline unsigned ei_blocks(int64_t N) {
                                                          kEiMaxWg)));
 }
 
+// The fitness term of an 'ei' swarm (sgp_swarm_fitness_ei / sgp_swarm_run_ei), behind the
+// shaping pass of fitness.h (kSwarmEi): one thread per particle, grid-stride,
+//   a = ei_alpha of the particle's posterior, mean / var [G][P] as the shaping pass has just
+//       consumed them -- the bits of k_ei_rows on the same (mean_g, var_g);
+//   safe mode:  values[p] = a + values[p], values[p] the total_pen the shaping left;
+//   free mode:  values[p] = a, safe[p] = 1 -- penalty and safety rule switched off.
+// alpha: [P] receives a, or null.  post: [G][2][P] receives mean | var per GP, or null.
+__global__ __launch_bounds__(kEiThreads) void k_swarm_ei(const double* mean, const double* var,
+                                                         int64_t P, double tau, EiTerm term,
+                                                         int free, double* values,
+                                                         uint8_t* safe, double* alpha,
+                                                         double* post) {
+  for (int64_t p = int64_t(blockIdx.x) * kEiThreads + threadIdx.x; p < P;
+       p += int64_t(gridDim.x) * kEiThreads) {
+    const double a = ei_alpha(mean + p, var + p, P, tau, term);
+    if (alpha) alpha[p] = a;
+    if (post) {
+      for (int g = 0; g < term.G; ++g) {
+        post[(2 * g) * P + p] = mean[g * P + p];
+        post[(2 * g + 1) * P + p] = var[g * P + p];
+      }
+    }
+    if (free) {
+      values[p] = a;
+      safe[p] = 1;
+    } else {
+      values[p] = a + values[p];
+    }
+  }
+}
+
 // The checks the entry points share, and the call's constants as the kernels take them
 int ei_term(sgp_ctx* ctx, int G, const double* fmin, int kind, double xi, EiTerm* p) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
@@ -281,6 +313,22 @@ int grid_ei(sgp_grid* g, int kind, int rows, int tau_mode, double tau_value, dou
 }
 
 }  // namespace
+
+// The term of an 'ei' swarm over the P particles whose posterior is mean / var [G][P]
+// (common.h).  The events time the kernel for scripts/bench_swarm_ei.py, as grid_ei times its
+// row kernel; no flops are booked.
+int launch_swarm_ei(sgp_ctx* ctx, int G, int64_t P, const double* mean, const double* var,
+                    const SwarmEi& m, double* values, uint8_t* safe) {
+  if (P <= 0) return 0;
+  SGP_CHECK(ctx, m.on && m.term.G == G, "the term of an 'ei' swarm is set for %d GPs, not %d",
+            m.term.G, G);
+  SweepTimer tm;
+  SGP_TRY(tm.begin(ctx, 0.0));
+  hipLaunchKernelGGL(k_swarm_ei, dim3(ei_blocks(P)), dim3(kEiThreads), 0, ctx->stream, mean, var,
+                     P, m.tau, m.term, m.free, values, safe, m.alpha, m.post);
+  SGP_HIP(ctx, hipGetLastError());
+  return tm.end(ctx);
+}
 
 int sgp_ei_eval(sgp_ctx* ctx, const double* mean, const double* var, int64_t N, int G,
                 const double* fmin, int kind, double tau, double xi, double* out) {

@@ -1,11 +1,13 @@
 // The device functions every expected-improvement kernel shares (ei.hip: the row kernel of
-// sgp_ei_eval, the grid kernel of sgp_grid_ei): ln Phi, ln(phi + z Phi) and the alpha of one
+// sgp_ei_eval, the grid kernel of sgp_grid_ei, the particle kernel of an 'ei' swarm): ln Phi, ln(phi + z Phi) and the alpha of one
 // row -- LogEI (Ament, Daulton, Eriksson, Balandat, Bakshy 2023, "Unexpected improvements to
 // expected improvement for Bayesian optimization").  ONE definition, so that alpha has the
 // same bits wherever it is formed; the translation unit that includes it is compiled with
 // -ffp-contract=off (build.py).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "common.h"
 
 // Branch points of ei_log_h (tests/_ei_ref.py restates them)
 #define SGP_EI_Z_DIRECT (-1.0)     // z >= this: the direct form
@@ -44,13 +46,8 @@ __device__ __forceinline__ double ei_log_h(double z) {
   return log(1.0 - 1.77245385090551602730 * t * erfcx(t)) + tail;
 }
 
-// What a call fixes for all its rows (a kernel argument by value)
-struct EiTerm {
-  int kind;                  // SGP_EI_EI | SGP_EI_PI
-  int G;                     // GPs of the posterior; the feasibility weights walk all of them
-  double xi;
-  double fmin[SGP_MAX_GPS];  // -inf: GP g is not weighed
-};
+// (What a call fixes for all its rows, struct EiTerm, is declared in common.h: FitnessArgs
+// carries one for an 'ei' swarm.)
 
 // alpha of one row: mean / var point at the row's entry of GP 0, GP g `stride` doubles on
 //   z = (mean_0 - tau - xi) / sigma_0,  sigma_g = sqrt(max(var_g, 1e-15))

@@ -28,6 +28,9 @@ __device__ __forceinline__ double swarm_penalty(double slack) {
 // k_swarm_mes (mes.hip) adds alpha of GP 0's posterior: value = alpha + total_pen.
 // kSwarmIse (sgp_swarm_*_ise, internal): the same branch again -- k_swarm_ise (swarm_ise.hip)
 // adds alpha = max_t pair(p, t) over the staged targets: value = alpha + total_pen.
+// kSwarmEi (sgp_swarm_*_ei, internal): the same branch once more -- k_swarm_ei (ei.hip) adds the
+// log expected improvement of the G GPs' posterior: value = alpha + total_pen (or, in free
+// mode, replaces value and flag: value = alpha, safe = 1).
 // HALL (a hallucinated swarm, sgp_swarm_*_hall; maximizers and expanders): down(g) is what
 // the pending picks of the batch take off the variance of GP g here, and the `values` term
 // ALONE is formed from sd_h = sqrt(max(var - down, 1e-15)); lower, upper, both interests,
@@ -88,7 +91,7 @@ __device__ __forceinline__ void shape_particle(const FitnessArgs& f, int G, Post
   } else if (st == SGP_SWARM_SAFE_SET) {
     *value = lower;
     *is_safe = safe;
-  } else if (st == kSwarmThompson || st == kSwarmMes || st == kSwarmIse) {
+  } else if (st == kSwarmThompson || st == kSwarmMes || st == kSwarmIse || st == kSwarmEi) {
     *value = total_pen;
     *is_safe = safe;
   } else {

@@ -540,6 +540,10 @@ int launch_fitness_small(sgp_ctx* ctx, int G, int64_t P, const double* mean,
   // an 'ise' swarm: alpha over the staged targets, from every active GP's posterior
   if (fa.swarm_type == kSwarmIse)
     return launch_swarm_ise(ctx, G, P, mean, var, fa.fmin, *fa.ise, fa.values);
+  // an 'ei' swarm: log expected improvement from all G GPs' posterior, on top of the penalty
+  // (or, free, in its place)
+  if (fa.swarm_type == kSwarmEi)
+    return launch_swarm_ei(ctx, G, P, mean, var, fa.ei, fa.values, fa.safe);
   return 0;
 }
 

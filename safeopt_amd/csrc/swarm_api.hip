@@ -1,7 +1,7 @@
 // The swarm entry points of the C ABI (include/safeopt_hip.h): host-side launch sequences
-// around the kernels of swarm.hip, paths.hip, swarm_batch.hip, mes.hip, swarm_ise.hip and the
-// posterior sweeps.  Fifteen exported fitness / run functions (plain, hallucinated, Thompson,
-// 'mes' and 'ise': one fitness, one run and one sharded run each) fill SwarmSpec / SwarmState / PsoSchedule
+// around the kernels of swarm.hip, paths.hip, swarm_batch.hip, mes.hip, swarm_ise.hip, ei.hip and
+// the posterior sweeps.  Eighteen exported fitness / run functions (plain, hallucinated, Thompson,
+// 'mes', 'ise' and 'ei': one fitness, one run and one sharded run each) fill SwarmSpec / SwarmState / PsoSchedule
 // (common.h) and share ONE fitness routine and ONE run routine.
 #include <string.h>
 
@@ -78,13 +78,16 @@ static FitnessArgs make_fitness_args(const SwarmSpec& s) {
     fa.scaling[i] = (i < s.G) ? s.scaling[i] : 1.0;
   }
   if (s.mes) fa.mes = *s.mes;
+  if (s.ei) fa.ei = *s.ei;
   fa.ise = nullptr;            // (the routine points it at what it staged)
   return fa;
 }
 
-// a path comes with kSwarmThompson, maxima with kSwarmMes, targets with kSwarmIse, the public
-// types otherwise
+// a path comes with kSwarmThompson, maxima with kSwarmMes, targets with kSwarmIse, an incumbent
+// with kSwarmEi, the public types otherwise
 static bool swarm_type_ok(const SwarmSpec& s) {
+  if (s.ei)
+    return s.swarm_type == kSwarmEi && s.ei->on && !s.path && !s.clones && !s.mes && !s.ise;
   if (s.ise) return s.swarm_type == kSwarmIse && !s.path && !s.clones && !s.mes;
   if (s.path) return s.swarm_type == kSwarmThompson && !s.mes;
   if (s.mes) return s.swarm_type == kSwarmMes;
@@ -129,14 +132,22 @@ static int path_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, int m) {
 //   sgp_swarm_run_ise[_shard]  "no GP", "targets", "no GP is active", return 0 if P <= 0 and
 //                           P_total <= 0, then as sgp_swarm_run_shard (an empty block of a
 //                           sharded swarm: "bad swarm size", as for a path run); staged behind GPs
-// A Thompson, a 'mes' and an 'ise' call pass "type" and the second "no GP" by construction.
+//   sgp_swarm_fitness_ei    "no GP", "kind" (SGP_EI_EI / SGP_EI_PI), "tau" (finite), "xi" (finite,
+//                           >= 0), "weigh" then "free" (0 or 1), with weigh "fmin" (no fmin[g] NaN
+//                           or +inf), return 0 if P <= 0, GPs (which bounds G by SGP_MAX_GPS)
+//   sgp_swarm_run_ei[_shard]  "no GP", "kind", "tau", "xi", "weigh", "free", "fmin", return 0 if
+//                           P <= 0 and P_total <= 0, then as sgp_swarm_run_shard (an empty block
+//                           of a sharded swarm: "bad swarm size", as for a path run)
+// A Thompson, a 'mes', an 'ise' and an 'ei' call pass "type" and the second "no GP" by
+// construction.
 
 // All five fitness entry points: import the points, the real posterior and the shaping
 // pass (few-points path or sweep), with clones the downdate (launch_swarm_down) in front of
 // the shaping, with a path the path term (launch_swarm_path) behind it, with maxima alpha
 // (launch_swarm_mes, inside launch_fitness_small where mean and var are at hand), with targets
 // alpha of the 'ise' rule (launch_swarm_ise, likewise; the targets and operands are staged
-// here, ONCE, behind the last check).
+// here, ONCE, behind the last check), with an incumbent alpha of the 'ei' rule (launch_swarm_ei,
+// likewise; its constants travel by value, nothing is staged).
 static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particles, int64_t P,
                          double* values, uint8_t* safe, double* var_h) {
   SGP_HIP(ctx, hipSetDevice(ctx->device));
@@ -200,7 +211,8 @@ static int swarm_fitness(sgp_ctx* ctx, const SwarmSpec& s, const double* particl
 // s.path: a Thompson swarm, s.clones: a hallucinated swarm (the downdate in front of every
 // shaping pass), s.mes: a 'mes' swarm (alpha behind every shaping pass, launched by
 // launch_fitness_small), s.ise: an 'ise' swarm (likewise, the targets and operands staged once
-// behind the checks); all four always take the general launches below.
+// behind the checks), s.ei: an 'ei' swarm (likewise, nothing staged); all five always take the
+// general launches below.
 static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
                      const PsoSchedule& sch) {
   const int G = s.G, init = sch.init, iters = sch.iters;
@@ -269,7 +281,7 @@ static int swarm_run(sgp_ctx* ctx, const SwarmSpec& s, const SwarmState& st,
   const bool few_swept = Pt <= kSmallSwarm && !few;
   const double* r = drand;
   double inertia = sch.inertia0;
-  if ((few || few_swept) && !shard && !s.path && !s.clones && !s.mes && !s.ise) {
+  if ((few || few_swept) && !shard && !s.path && !s.clones && !s.mes && !s.ise && !s.ei) {
     // small swarm: three launches per iteration -- k(X, particles), the block
     // products on the matrix cores, and ONE workgroup for everything else
     // (fitness, bests, and the move that opens the next iteration)
@@ -407,6 +419,34 @@ static int swarm_mes_stage(sgp_ctx* ctx, const double* ystar, int K, double floo
   out->K = K;
   out->floor = floor;
   out->post = post ? reinterpret_cast<double*>(buf + l.post) : nullptr;
+  return 0;
+}
+
+// The checks an 'ei' entry point makes in front of its early return, and the call's constants
+// as the kernel takes them (by value: nothing is staged on the device).  The weights walk the
+// G GPs of the call; collect_gps, behind the early return, bounds G by SGP_MAX_GPS.
+static int swarm_ei_checks(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* fmin, int kind,
+                           double tau, double xi, int weigh, int free_mode, SwarmEi* out) {
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  SGP_CHECK(ctx, G >= 1 && gps[0], "no GP");
+  SGP_CHECK(ctx, kind == SGP_EI_EI || kind == SGP_EI_PI, "kind = %d is not SGP_EI_EI / SGP_EI_PI",
+            kind);
+  SGP_CHECK(ctx, std::isfinite(tau), "the incumbent tau = %g is not finite", tau);
+  SGP_CHECK(ctx, std::isfinite(xi) && xi >= 0.0, "xi = %g is negative or not finite", xi);
+  SGP_CHECK(ctx, weigh == 0 || weigh == 1, "weigh = %d is not 0 or 1", weigh);
+  SGP_CHECK(ctx, free_mode == 0 || free_mode == 1, "free = %d is not 0 or 1", free_mode);
+  SwarmEi e{};
+  e.term.kind = kind;
+  e.term.G = G;
+  e.term.xi = xi;
+  for (int g = 0; g < SGP_MAX_GPS; ++g) {
+    e.term.fmin[g] = weigh && g < G ? fmin[g] : -INFINITY;
+    SGP_CHECK(ctx, e.term.fmin[g] < INFINITY, "fmin[%d] is NaN or +inf", g);   // (NaN < inf is false)
+  }
+  e.tau = tau;
+  e.on = 1;
+  e.free = free_mode;
+  *out = e;
   return 0;
 }
 
@@ -615,6 +655,59 @@ int sgp_swarm_run_ise_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta
   SGP_TRY(swarm_ise_checks(ctx, gps, G, fmin, in));
   if (P <= 0 && P_total <= 0) return 0;
   const SwarmSpec s{gps, G, kSwarmIse, beta, fmin, scaling, 0.0, nullptr, nullptr, nullptr, &in};
+  const SwarmState st{positions, velocities, best_positions, best_values, global_best,
+                      velocity_scale, bounds, P, p0, P_total};
+  return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});
+}
+
+int sgp_swarm_fitness_ei(sgp_ctx* ctx, sgp_gp* const* gps, int G, const double* particles,
+                         int64_t P, double beta, const double* fmin, const double* scaling,
+                         int kind, double tau, double xi, int weigh, int free_mode,
+                         double* values, uint8_t* safe, double* alpha, double* post) {
+  SwarmEi ei;
+  SGP_TRY(swarm_ei_checks(ctx, gps, G, fmin, kind, tau, xi, weigh, free_mode, &ei));
+  if (P <= 0) return 0;
+  SGP_CHECK(ctx, G <= SGP_MAX_GPS, "%d GPs, supported 1..%d", G, SGP_MAX_GPS);
+  const SwarmEiLayout l = swarm_ei_layout(P, G, alpha != nullptr, post != nullptr);   // (common.h)
+  if (l.bytes) {
+    char* buf;
+    SGP_TRY(sgp_scratch(ctx, kSlotEiIn, l.bytes, &buf));
+    if (alpha) ei.alpha = reinterpret_cast<double*>(buf + l.alpha);
+    if (post) ei.post = reinterpret_cast<double*>(buf + l.post);
+  }
+  SwarmSpec s{gps, G, kSwarmEi, beta, fmin, scaling, 0.0, nullptr, nullptr, nullptr};
+  s.ei = &ei;
+  SGP_TRY(swarm_fitness(ctx, s, particles, P, values, safe, nullptr));
+  if (alpha) SGP_TRY(sgp_d2h(ctx, alpha, ei.alpha, size_t(P) * 8));
+  if (post) SGP_TRY(sgp_d2h(ctx, post, ei.post, 2 * size_t(G) * size_t(P) * 8));
+  return 0;
+}
+
+int sgp_swarm_run_ei(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta, const double* fmin,
+                     const double* scaling, int64_t P, double* positions, double* velocities,
+                     double* best_positions, double* best_values, double* global_best,
+                     const double* velocity_scale, const double* bounds, int init, int iters,
+                     double inertia0, double step_size, const double* rand, uint64_t seed,
+                     int kind, double tau, double xi, int weigh, int free_mode) {
+  return sgp_swarm_run_ei_shard(ctx, gps, G, beta, fmin, scaling, P, positions, velocities,
+                                best_positions, best_values, global_best, velocity_scale,
+                                bounds, init, iters, inertia0, step_size, rand, seed, kind, tau,
+                                xi, weigh, free_mode, 0, P);
+}
+
+int sgp_swarm_run_ei_shard(sgp_ctx* ctx, sgp_gp* const* gps, int G, double beta,
+                           const double* fmin, const double* scaling, int64_t P,
+                           double* positions, double* velocities, double* best_positions,
+                           double* best_values, double* global_best,
+                           const double* velocity_scale, const double* bounds, int init,
+                           int iters, double inertia0, double step_size, const double* rand,
+                           uint64_t seed, int kind, double tau, double xi, int weigh,
+                           int free_mode, int64_t p0, int64_t P_total) {
+  SwarmEi ei;
+  SGP_TRY(swarm_ei_checks(ctx, gps, G, fmin, kind, tau, xi, weigh, free_mode, &ei));
+  if (P <= 0 && P_total <= 0) return 0;
+  SwarmSpec s{gps, G, kSwarmEi, beta, fmin, scaling, 0.0, nullptr, nullptr, nullptr};
+  s.ei = &ei;
   const SwarmState st{positions, velocities, best_positions, best_values, global_best,
                       velocity_scale, bounds, P, p0, P_total};
   return swarm_run(ctx, s, st, PsoSchedule{init, iters, inertia0, step_size, rand, seed});

@@ -26,7 +26,7 @@ __all__ = ["shard_range", "allgather_rows", "LocalComm", "RcclComm", "SocketComm
            "merge_topk", "merge_argmax", "merge_path_records", "merge_batch_records",
            "merge_mes_records", "merge_ise_records", "pick_ise",
            "gather_shard_columns", "check_same_paths", "check_same_maxima",
-           "launch_check"]
+           "check_same_incumbent", "launch_check"]
 
 
 def shard_range(N, rank, world):
@@ -105,6 +105,24 @@ def check_same_maxima(comm, ystar, floor):
             "the ranks hold different maxima or floors (digest %012x on rank %d, the ranks' "
             "digests span %012x .. %012x): pass the same ystar and floor, and seed NumPy's "
             "global generator alike, on every rank before mes_point"
+            % (int(h), comm.rank, int(-red[1]), int(red[0])))
+
+
+def check_same_incumbent(comm, kind, tau, xi, feasibility, free):
+    """``ValueError`` -- on EVERY rank, as :func:`check_same_maxima` -- unless all ranks hold
+    the same incumbent and switches of an expected-improvement swarm: ``kind`` (``'ei'`` /
+    ``'pi'``), ``tau``, ``xi``, ``feasibility`` and ``free`` are arguments or functions of
+    replicated data.  One ``allreduce_max`` of ``[h, -h]``, ``h`` a 48-bit digest of their
+    bytes."""
+    h = _digest48((np.array([float(tau), float(xi)]),
+                   np.array([{'ei': 0.0, 'pi': 1.0}[kind], float(bool(feasibility)),
+                             float(bool(free))])))
+    red = comm.allreduce_max(np.array([h, -h]))
+    if red[0] != -red[1]:
+        raise ValueError(
+            "the ranks hold different incumbents (digest %012x on rank %d, the ranks' digests "
+            "span %012x .. %012x): pass the same incumbent, xi, kind, feasibility and within, "
+            "and the same data, on every rank before ei_point"
             % (int(h), comm.rank, int(-red[1]), int(red[0])))
 
 

@@ -32,8 +32,8 @@ import numpy as np
 
 from . import _hip
 from . import pooling as _pooling
-from .dist import (LocalComm, allgather_rows, check_same_maxima, check_same_paths,
-                   check_same_targets,
+from .dist import (LocalComm, allgather_rows, check_same_incumbent, check_same_maxima,
+                   check_same_paths, check_same_targets,
                    gather_shard_columns,
                    merge_argmax, merge_batch_records, merge_ise_records, merge_mes_records,
                    merge_path_records, merge_topk, pick_ise, shard_range)
@@ -2658,7 +2658,8 @@ class SafeOptSwarm(GaussianProcessOptimization):
     def _swarm_fitness(self, swarm_type, particles, **variant):
         """What the fitness callbacks share: the current ``beta``, the fitted device GPs and
         this optimiser's ``fmin`` / ``scaling`` / best lower bound; ``variant``: ``path=``,
-        ``clones=``, ``mes=`` or ``ise=`` (with ``want=``) of ``_hip._swarm_fitness``."""
+        ``clones=``, ``mes=``, ``ise=`` or ``ei=`` (the last two with ``want=``) of
+        ``_hip._swarm_fitness``."""
         beta = self.beta(self.t)
         devs = [g._fitted() for g in self.gps]
         return _hip._swarm_fitness(devs[0].ctx, devs, swarm_type, np.atleast_2d(particles),
@@ -2697,14 +2698,27 @@ class SafeOptSwarm(GaussianProcessOptimization):
         res = self._swarm_fitness(None, particles, ise=ise, want=want or ())
         return res if want else res[:2]
 
-    def _side_swarm_pick(self, swarm, configure, fitness, iters, empty_ok=False):
+    def _compute_ei_fitness(self, ei, particles, want=None):
+        """Fitness and safety of ``particles`` for an expected-improvement swarm with ``ei =
+        (kind, tau, xi, feasibility, free)``: ``values = alpha + `` the maximizers' penalty,
+        ``alpha`` the logarithm of ``Context.ei_eval`` on the posterior of the GPs, ``safe``
+        the maximizers' safety flag -- with ``free`` ``values = alpha`` and every particle
+        safe (``sgp_swarm_fitness_ei``).  The fitness callback of the host loop; ``want``:
+        ``(values, safe, out)`` with the arrays named in it, 'alpha' (P) and 'post' (G, 2, P)
+        (``_hip._swarm_fitness``)."""
+        return self._swarm_fitness(None, particles, ei=ei, want=want or ())
+
+    def _side_swarm_pick(self, swarm, configure, fitness, iters, empty_ok=False,
+                         unchecked=False):
         """One side swarm of ``optimize_batch`` / ``thompson_points`` and its pick ``(x,
         index)``: ``swarm_size`` draws of ``S`` as start positions (one ``randint``), then the
         device swarm ``swarm`` after ``configure(swarm)`` -- or, ``swarm is None``
         (``pso='host'``), a reference loop over the callback ``fitness`` -- runs ``iters``
         iterations; the pick is ``thompson_pick`` among the personal bests that are safe under
         one real ``'safe_set'`` fitness call.  None is safe: ``RuntimeError``, or ``None``
-        with ``empty_ok``."""
+        with ``empty_ok``.  ``unchecked`` (``ei_point(within='bounds')`` alone): no
+        ``'safe_set'`` call, the pick is ``thompson_pick`` among ALL personal bests -- not a
+        safe pick."""
         picks = np.random.randint(self.S.shape[0], size=self.swarm_size)
         if swarm is None:
             swarm = SwarmOptimization(self.swarm_size, self.optimal_velocities, fitness,
@@ -2713,6 +2727,9 @@ class SafeOptSwarm(GaussianProcessOptimization):
             configure(swarm)
         swarm.init_swarm(self.S[picks, :])
         swarm.run_swarm(iters)
+        if unchecked:
+            return thompson_pick(swarm.best_positions, swarm.best_values,
+                                 np.ones(len(swarm.best_values), dtype=bool))
         _, safe = self._compute_particle_fitness('safe_set', swarm.best_positions)
         if empty_ok and not np.any(safe):
             return None
@@ -3009,6 +3026,131 @@ class SafeOptSwarm(GaussianProcessOptimization):
         alpha = float(self.gp.max_value_entropy(x[None, :], ystar, floor)[0, 0])
         if return_state:
             return x, alpha, dict(ystar=ystar, floor=floor, thompson_x=thompson_x)
+        return x, alpha
+
+    def ei_point(self, incumbent='mean', xi=0.0, kind='ei', feasibility=False, within='safe',
+                 max_iters=None, return_state=False):
+        """The safe point with the largest expected improvement over the incumbent, evaluated
+        as a logarithm (LogEI: Ament et al. 2023), without a grid: ``SafeOpt.ei_point`` by a
+        swarm.  It needs no Lipschitz constant and no width rule.
+
+        1. The refusals below come before anything is drawn or run.
+        2. ``_recheck_safe_set()`` runs once.
+        3. The incumbent ``tau``.  ``incumbent='mean'`` (default): the largest posterior mean
+           of the objective GP over the rows of ``S`` (one ``predict_noiseless`` call; the
+           same for ``within='bounds'``, there is no other set); ``'data'``: the largest
+           measured objective value, ``max(opt.y[:, 0])`` over the entries that are not NaN; a
+           finite float: that value.  ``xi >= 0``: the margin an improvement has to exceed.
+        4. One swarm (``DeviceSwarmOptimization(..., 'ei')``; ``pso='host'``: the reference
+           loop over ``_compute_ei_fitness``) starts from ``swarm_size`` draws from ``S`` and
+           runs ``max_iters`` (default ``self.max_iters``) iterations.  With ``mu_g``, ``v_g``
+           the posterior of GP ``g`` (the objective is GP 0), ``sigma_g = sqrt(max(v_g,
+           1e-15))`` and ``z = (mu_0 - tau - xi) / sigma_0``,
+
+               ``kind='ei'``: ``alpha(x) = ln sigma_0 + ln(phi(z) + z Phi(z))``  (= ln EI),
+               ``kind='pi'``: ``alpha(x) = ln Phi(z)``  (= ln PI),
+
+           and with ``feasibility=True`` every GP with a finite ``fmin`` adds ``ln Phi((mu_g -
+           fmin_g) / sigma_g)`` (EIC: Gelbart et al. 2014, Gardner et al. 2014).  It is formed
+           on the device inside the swarm iteration (``k_swarm_ei``, ``csrc/ei.hip``).  On a
+           converged run EI itself underflows to 0 almost everywhere and a swarm on it has
+           nothing to climb; ``alpha`` stays finite and ordered.
+           ``within='safe'``: the fitness of a particle is ``alpha(x) + total_pen`` under the
+           penalty and safety rule of the maximizers swarm, and the pick is the personal best
+           with the largest value among those that are safe under the current posterior (one
+           ``safe_set`` fitness call), the lowest index among equals.
+           ``within='bounds'``: the fitness is ``alpha(x)`` alone, every particle counts as
+           safe, and the pick is the personal best with the largest value, the lowest index
+           among equals; no ``safe_set`` call.  This is NOT a safe pick: with
+           ``feasibility=True`` it is the EIC baseline the safe-BO papers compare against, for
+           diagnostics and unconstrained problems only.
+        5. Returns ``(x (d,), alpha)`` with ``alpha = ctx.ei_eval`` on ``predict_noiseless`` of
+           every GP at ``x`` -- the number the public per-point call gives; with
+           ``return_state=True`` ``(x, alpha, {'tau', 'kind', 'xi', 'safe'})``, ``safe`` the
+           ``safe_set`` flag of the pick (computed in that case for ``within='bounds'`` too).
+
+        Raises ``ValueError`` for a ``within`` other than ``'safe'`` / ``'bounds'``, a ``kind``
+        other than ``'ei'`` / ``'pi'``, an ``xi`` that is negative or not finite, an
+        ``incumbent`` that is neither ``'mean'``, ``'data'`` nor a finite float, or
+        ``'data'`` without a measurement of the objective; ``NotImplementedError`` for several
+        ranks whose communicator carries no device context; ``RuntimeError`` when the safe
+        set is empty or, ``within='safe'``, the swarm ends with no safe personal best.
+
+        Changes no state of the optimiser beyond what ``_recheck_safe_set`` does (it may drop
+        points that are no longer safe): ``S`` does not grow, ``greedy_point``,
+        ``best_lower_bound`` and the greedy / maximizers / expanders swarm objects are
+        untouched.  NumPy's global generator is consumed in the order of steps 2 - 3 of
+        ``mes_point``'s list; no path is drawn:
+
+        1. ``pso='device-rng'`` only: one ``randint`` for the key of the swarm's device
+           generator;
+        2. one swarm's worth: one ``randint(len(S), size=swarm_size)`` for the start
+           positions, then ``'host'``: ``rand(swarm_size, d)`` in ``init_swarm`` and ``rand(2
+           swarm_size, d)`` per iteration; ``'device'``: the same numbers as ``rand(swarm_size
+           d)`` and ``rand(2 swarm_size d max_iters)``; ``'device-rng'``: nothing.
+
+        N ranks (``comm=``; SPMD, the same seed and call on every rank): the incumbent is a
+        function of replicated data; one ``allreduce_max`` of a digest of ``(kind, tau, xi,
+        feasibility, free)`` verifies that the ranks hold the same, ``ValueError`` on every
+        rank otherwise.  The swarm is split over the ranks by particle
+        (``sgp_swarm_run_ei_shard``); the ``safe_set`` call and the pick run replicated on the
+        gathered personal bests: the bits of the one-rank run on every rank.
+
+        Out of scope: greedy batches of EI picks through the hallucination clones,
+        noisy-incumbent EI, an ``'ei'`` leg in ``info_point``."""
+        if within not in ('safe', 'bounds'):
+            raise ValueError("within must be 'safe' or 'bounds', got %r" % (within,))
+        if kind not in ('ei', 'pi'):
+            raise ValueError("kind must be 'ei' or 'pi', got %r" % (kind,))
+        xi = float(xi)
+        if not (np.isfinite(xi) and xi >= 0.0):
+            raise ValueError("xi must be finite and >= 0, got %r" % (xi,))
+        if isinstance(incumbent, str):
+            if incumbent not in ('mean', 'data'):
+                raise ValueError("incumbent must be 'mean', 'data' or a float, got %r"
+                                 % (incumbent,))
+            tau = 'mean'
+            if incumbent == 'data':
+                seen = self.y[:, 0][~np.isnan(self.y[:, 0])]
+                if seen.size == 0:
+                    raise ValueError("incumbent='data': the objective has no measurement")
+                tau = float(seen.max())
+        else:
+            tau = float(incumbent)
+        if tau != 'mean' and not np.isfinite(tau):
+            raise ValueError("the incumbent must be finite, got %r" % (tau,))
+        world = self._comm.world
+        if world > 1 and getattr(self._comm, 'ctx', None) is None:
+            raise NotImplementedError(
+                "the sharded 'ei' swarm merges the global best in the stream of the "
+                "communicator's device context: a merge over this host-only communicator of "
+                "%d ranks is not implemented" % world)
+        self._recheck_safe_set()
+        if tau == 'mean':
+            tau = float(np.max(self.gp.predict_noiseless(self.S)[0]))
+        free = within == 'bounds'
+        ei = (kind, tau, xi, bool(feasibility), free)
+        if world > 1:
+            check_same_incumbent(self._comm, *ei)
+        iters = int(max_iters or self.max_iters)
+        swarm = None                      # pso='host': a reference loop
+        if isinstance(self.swarms['maximizers'], DeviceSwarmOptimization):
+            swarm = DeviceSwarmOptimization(
+                self.swarm_size, self.optimal_velocities, self, 'ei',
+                bounds=self.bounds, rng=self.swarms['maximizers']._rng, comm=self._comm)
+        x, _ = self._side_swarm_pick(
+            swarm, lambda run: run.set_incumbent(*ei),
+            partial(self._compute_ei_fitness, ei), iters, unchecked=free)
+        post = [gp.predict_noiseless(x[None, :]) for gp in self.gps]
+        mean = np.stack([np.asarray(m, dtype=float).reshape(-1) for m, _ in post])
+        var = np.stack([np.asarray(v, dtype=float).reshape(-1) for _, v in post])
+        ctx = self.gp._fitted().ctx
+        alpha = float(ctx.ei_eval(
+            mean, var, tau, xi, _hip.EI_EI if kind == 'ei' else _hip.EI_PI,
+            np.asarray(self.fmin, dtype=float).reshape(-1) if feasibility else None)[0])
+        if return_state:
+            _, safe = self._compute_particle_fitness('safe_set', x[None, :])
+            return x, alpha, dict(tau=tau, kind=kind, xi=xi, safe=bool(safe[0]))
         return x, alpha
 
     def _ise_refusals(self, targets, about):

@@ -119,6 +119,8 @@ THOMPSON_CODE = 4
 MES_CODE = 5
 #: ... and of the information-theoretic safe exploration swarm (``kSwarmIse``)
 ISE_CODE = 6
+#: ... and of the expected-improvement swarm (``kSwarmEi``)
+EI_CODE = 7
 
 
 class DeviceSwarmOptimization(SwarmOptimization):
@@ -172,6 +174,14 @@ class DeviceSwarmOptimization(SwarmOptimization):
     ``set_targets(targets, zmean, zvar)`` comes before ``init_swarm``; with ``comm`` it is
     sharded like every other swarm (``sgp_swarm_run_ise_shard``), every rank holding the same
     targets.
+
+    ``swarm_type='ei'``: expected improvement -- the fitness is ``alpha + total_pen``, ``alpha``
+    the logarithm of ``Context.ei_eval`` (LogEI, log-PI, optionally weighed by the probability
+    of feasibility) on the posterior of the owner's GPs, under the maximizers' penalty and
+    safety rule -- or, ``free``, ``alpha`` alone with every particle counted safe
+    (``sgp_swarm_fitness_ei`` / ``sgp_swarm_run_ei``); ``set_incumbent(kind, tau, xi,
+    feasibility, free)`` comes before ``init_swarm``; with ``comm`` it is sharded like every
+    other swarm (``sgp_swarm_run_ei_shard``), every rank holding the same incumbent.
     """
 
     def __init__(self, swarm_size, velocity, owner, swarm_type, bounds=None,
@@ -197,7 +207,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
         # expanders swarms of one optimiser must not draw the same numbers
         if rng == 'device' and seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
-        code = {'thompson': THOMPSON_CODE, 'mes': MES_CODE, 'ise': ISE_CODE}.get(swarm_type)
+        code = {'thompson': THOMPSON_CODE, 'mes': MES_CODE, 'ise': ISE_CODE,
+                'ei': EI_CODE}.get(swarm_type)
         if code is None:
             code = _hip_swarm_types()[swarm_type]
         self._seed = (int(seed or 0) * 4 + code) & (2 ** 43 - 1)
@@ -206,6 +217,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
         self._clones = None
         self._maxima = None
         self._targets = None
+        self._incumbent = None
         self.global_best = np.zeros(self.ndim)
 
     def set_path(self, path):
@@ -274,6 +286,30 @@ class DeviceSwarmOptimization(SwarmOptimization):
         self._targets = (np.ascontiguousarray(targets), np.ascontiguousarray(zmean),
                          np.ascontiguousarray(zvar))
 
+    def set_incumbent(self, kind, tau, xi=0.0, feasibility=False, free=False):
+        """What an 'ei' swarm scores its particles with from the next ``init_swarm`` on:
+        ``kind`` ``'ei'`` (log expected improvement) or ``'pi'`` (log probability of
+        improvement), the finite incumbent ``tau``, the finite margin ``xi >= 0``,
+        ``feasibility`` (weigh by the probability that every constraint holds) and ``free``
+        (no penalty, no safety rule: every particle counts as safe).  A refused call leaves
+        the swarm as it was."""
+        if self._type != 'ei':
+            raise ValueError("only an 'ei' swarm takes an incumbent, this is %r" % (self._type,))
+        if kind not in ('ei', 'pi'):
+            raise ValueError("kind must be 'ei' or 'pi', got %r" % (kind,))
+        tau, xi = float(tau), float(xi)
+        if not np.isfinite(tau):
+            raise ValueError("the incumbent must be finite, got %r" % (tau,))
+        if not (np.isfinite(xi) and xi >= 0.0):
+            raise ValueError("xi must be finite and >= 0, got %r" % (xi,))
+        self._incumbent = (kind, tau, xi, bool(feasibility), bool(free))
+
+    def _need_incumbent(self):
+        if self._incumbent is None:
+            raise ValueError("an 'ei' swarm needs set_incumbent(kind, tau, xi, feasibility, free) "
+                             "before init_swarm")
+        return self._incumbent
+
     def _need_targets(self):
         if self._targets is None:
             raise ValueError("an 'ise' swarm needs set_targets(targets, zmean, zvar) before "
@@ -299,16 +335,21 @@ class DeviceSwarmOptimization(SwarmOptimization):
         if self._type == 'ise':
             targets = self._need_targets()
             return self._owner._compute_ise_fitness(targets, positions)
+        if self._type == 'ei':
+            incumbent = self._need_incumbent()
+            return self._owner._compute_ei_fitness(incumbent, positions)
         if self._clones is not None:
             return self._owner._compute_hall_fitness(self._type, self._clones, positions)
         return self._owner._compute_particle_fitness(self._type, positions)
 
     def _device_run(self, init, iters, inertia0, step):
         from . import _hip
-        # (a missing path or missing maxima are refused before anything is touched or drawn)
+        # (a missing path, missing maxima, targets or a missing incumbent are refused before
+        # anything is touched or drawn)
         path = self._need_path() if self._type == 'thompson' else None
         maxima = self._need_maxima() if self._type == 'mes' else None
         targets = self._need_targets() if self._type == 'ise' else None
+        incumbent = self._need_incumbent() if self._type == 'ei' else None
         o = self._owner
         devs = [g._fitted() for g in o.gps]
         sharded = self._comm.world > 1
@@ -330,7 +371,7 @@ class DeviceSwarmOptimization(SwarmOptimization):
             (self.positions, self.velocities, best_positions, best_values, self.global_best,
              np.broadcast_to(self.velocity_scale, (d,)), self.bounds),
             (init, iters, inertia0, step, rand, (self._seed << 20) + self._calls),
-            path=path, clones=self._clones, mes=maxima, ise=targets,
+            path=path, clones=self._clones, mes=maxima, ise=targets, ei=incumbent,
             shard=(self._rows[0], self.swarm_size) if sharded else None)
         if sharded:
             self.best_positions, self.best_values = self._gather(best_positions, best_values)
@@ -367,6 +408,8 @@ class DeviceSwarmOptimization(SwarmOptimization):
             self._need_maxima()
         if self._type == 'ise':
             self._need_targets()
+        if self._type == 'ei':
+            self._need_incumbent()
         positions = np.ascontiguousarray(positions, dtype=float)
         if self._comm.world > 1:
             lo, hi = self._rows
