@@ -526,6 +526,23 @@ int sgp_grid_step_small(sgp_grid* grid, sgp_gp* const* gps, int G, double beta,
                         double* mean_top, double* q_top, int32_t* flags, double* value,
                         int64_t* gidx, double* max_l_out);
 int sgp_grid_step_small_ok(sgp_grid* grid, sgp_gp* const* gps, int G);
+/* A FLEET of such problems in one call: sgp_grid_step_small for B grids of ONE context side
+ * by side, one workgroup per member, one launch per kernel instance present (input
+ * dimension, observation class 24 / 32 / 48, single-part kernels or not).  Member b computes
+ * the bits sgp_grid_step_small(grids[b], ...) computes and leaves the same arrays resident.
+ * Per member, packed at fixed strides: gps [B][SGP_MAX_GPS] handles (entries behind G[b]
+ * ignored, NULL by convention), G [B], beta [B], fmin / scaling / thr_beta [B][SGP_MAX_GPS]
+ * (the first G[b] read); out5 [B][6], x_top [B][SGP_MAX_D], mean_top [B][SGP_MAX_GPS],
+ * q_top [B][2 SGP_MAX_GPS], flags [B][SGP_MAX_GPS], value [B], gidx [B], max_l_out [B] --
+ * each row as the one-problem call fills its output of that name.
+ * Refused with an error that names the first offending member, before anything is launched
+ * or written: B < 1; a NULL grid; a member sgp_grid_step_small_ok refuses; members of
+ * different contexts; one grid twice; one GP under two members.                          */
+int sgp_grid_step_small_many(sgp_grid* const* grids, sgp_gp* const* gps, const int* G, int B,
+                             const double* beta, const double* fmin, const double* scaling,
+                             const double* thr_beta, double* out5, double* x_top,
+                             double* mean_top, double* q_top, int32_t* flags, double* value,
+                             int64_t* gidx, double* max_l_out);
 /* ... and when its first candidate is no expander: the expander test of gp_opt.py:579-606
  * for EVERY candidate of the list (global row indices, any order) in two launches and one
  * round trip; flags[c * G + i] != 0: candidate c lifts an unsafe row above fmin_i.  The

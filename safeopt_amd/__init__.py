@@ -18,11 +18,11 @@ in hand-written HIP kernels for gfx950 behind the C ABI of
 """
 from .utilities import linearly_spaced_combinations, sample_gp_function
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
-from .gp_opt import SafeOpt, SafeOptSwarm, GaussianProcessOptimization
+from .gp_opt import SafeOpt, SafeOptFleet, SafeOptSwarm, GaussianProcessOptimization
 from . import gpy
 from . import dist
 
-__all__ = ['SafeOpt', 'SafeOptSwarm', 'linearly_spaced_combinations',
+__all__ = ['SafeOpt', 'SafeOptFleet', 'SafeOptSwarm', 'linearly_spaced_combinations',
            'sample_gp_function', 'SwarmOptimization', 'DeviceSwarmOptimization',
            'gpy', 'dist']
 __version__ = "0.1.0"

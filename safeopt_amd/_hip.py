@@ -199,6 +199,10 @@ PROTOTYPES = {
                                       c_double_p, c_double_p, c_double_p, c_double_p,
                                       c_double_p, c_i32_p, c_double_p, c_i64_p, c_double_p]),
     "sgp_grid_step_small_ok": (C.c_int, [vp, vpp, C.c_int]),
+    "sgp_grid_step_small_many": (C.c_int, [vpp, vpp, c_int_p, C.c_int, c_double_p, c_double_p,
+                                           c_double_p, c_double_p, c_double_p, c_double_p,
+                                           c_double_p, c_double_p, c_i32_p, c_double_p,
+                                           c_i64_p, c_double_p]),
     "sgp_grid_expanders_small": (C.c_int, [vp, vpp, C.c_int, C.c_double, c_double_p, c_i64_p,
                                            C.c_int, c_i32_p]),
     "sgp_grid_sets_fused_comm": (C.c_int, [vp, vpp, C.c_int, C.c_double, c_double_p,
@@ -533,6 +537,14 @@ class Context(object):
         return (None, "classic", "pair", "tiny", "few-points",
                 "step-small", "mid")[int(lib().sgp_ctx_last_sweep(self.h)) & 255]
 
+    def step_small_many(self, plan):
+        """One ``sgp_grid_step_small_many`` call on the members of ``plan`` (a
+        :class:`FleetPlan` of this context, its inputs filled in): the B one-launch steps
+        side by side.  The results are in the plan's arrays."""
+        rc = plan.fn(*plan.args)
+        if rc != 0:
+            self.check(rc)
+
     def last_sweep_handed(self):
         """Did the last posterior sweep hand covariances from a GP to GPs with the same
         inputs and kernel (the paired kernel's hand-down, csrc/sweep_pair.hip)?"""
@@ -672,6 +684,55 @@ class Context(object):
 def _gp_array(gps):
     arr = (vp * len(gps))(*[g.h for g in gps])
     return C.cast(arr, vpp)
+
+
+class FleetPlan(object):
+    """The arguments of ``sgp_grid_step_small_many`` for a fixed list of grids, built once:
+    handle arrays, packed inputs and outputs, and their pointers.  Per step the caller
+    writes ``beta[b]`` and the rows ``fmin[b]`` / ``scaling[b]`` / ``thr_beta[b]``, calls
+    ``set_gps(b, gps)`` (a no-op while the handles stay) and ``Context.step_small_many``;
+    ``result(b, value, gidx, max_l)`` is then what ``DeviceGrid.step_small`` returns for
+    member ``b``, as views of the packed arrays."""
+
+    def __init__(self, ctx, grids):
+        B = len(grids)
+        self.ctx, self.grids, self.B = ctx, list(grids), B
+        self.grid_arr = (vp * B)(*[g.h for g in grids])
+        self.gp_arr = (vp * (B * MAX_GPS))()
+        self.G = (C.c_int * B)(*[g.G for g in grids])
+        self.beta = np.zeros(B)
+        self.fmin = np.full((B, MAX_GPS), -np.inf)
+        self.scaling = np.ones((B, MAX_GPS))
+        self.thr_beta = np.zeros((B, MAX_GPS))
+        self.out5 = np.zeros((B, 6))
+        self.x = np.zeros((B, MAX_D))
+        self.mean = np.zeros((B, MAX_GPS))
+        self.q = np.zeros((B, 2 * MAX_GPS))
+        self.flags = np.zeros((B, MAX_GPS), dtype=np.int32)
+        self.value = np.zeros(B)
+        self.gidx = np.zeros(B, dtype=np.int64)
+        self.max_l = np.zeros(B)
+        self._keys = [None] * B
+        self.rows = [(self.fmin[b, :g.G], self.scaling[b, :g.G], self.thr_beta[b, :g.G])
+                     for b, g in enumerate(grids)]
+        self._views = [(self.out5[b], self.x[b, :g.d], self.mean[b, :g.G], self.q[b, :2 * g.G],
+                        self.flags[b, :g.G]) for b, g in enumerate(grids)]
+        self.fn = lib().sgp_grid_step_small_many
+        self.args = (C.cast(self.grid_arr, vpp), C.cast(self.gp_arr, vpp), self.G, B,
+                     dptr(self.beta), dptr(self.fmin), dptr(self.scaling), dptr(self.thr_beta),
+                     dptr(self.out5), dptr(self.x), dptr(self.mean), dptr(self.q),
+                     self.flags.ctypes.data_as(c_i32_p), dptr(self.value),
+                     self.gidx.ctypes.data_as(c_i64_p), dptr(self.max_l))
+
+    def set_gps(self, b, gps):
+        key = tuple(g.h.value for g in gps)
+        if self._keys[b] != key:
+            self._keys[b] = key
+            for i in range(MAX_GPS):
+                self.gp_arr[b * MAX_GPS + i] = gps[i].h if i < len(gps) else None
+
+    def result(self, b, value, gidx, max_l):
+        return self._views[b] + (value, gidx, max_l)
 
 
 class DeviceGP(object):

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <new>
@@ -306,6 +307,9 @@ void sgp_destroy(sgp_ctx* ctx) {
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->step_host) (void)hipHostFree(ctx->step_host);
   if (ctx->sets_host) (void)hipHostFree(ctx->sets_host);
+  if (ctx->fleet_host) (void)hipHostFree(ctx->fleet_host);
+  if (ctx->fleet_stage) (void)hipHostFree(ctx->fleet_stage);
+  if (ctx->fleet_recs.p) (void)hipFree(ctx->fleet_recs.p);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -2020,6 +2024,171 @@ int sgp_grid_step_small_ok(sgp_grid* g, sgp_gp* const* gps, int G) {
     host[i] = gps[i]->dev;
   }
   return step_small_eligible(g->ctx, host, G, g->N) ? 1 : 0;
+}
+
+// A FLEET of small problems in one call: what sgp_grid_step_small does for one grid, for B
+// grids of one context side by side -- one workgroup per member (step_small.hip:
+// k_step_small_many), one launch per kernel instance present (input dimension, observation
+// class, single-part or not), back to back in the context's stream.  Every member gets its
+// own record, its own result block in mapped host memory and its own completion word; the
+// records and the GP descriptors they point to go up in ONE copy.  Nothing is launched or
+// written before every member has been checked.
+int sgp_grid_step_small_many(sgp_grid* const* grids, sgp_gp* const* gps, const int* G, int B,
+                             const double* beta, const double* fmin, const double* scaling,
+                             const double* thr_beta, double* out5, double* x_top,
+                             double* mean_top, double* q_top, int32_t* flags, double* value,
+                             int64_t* gidx, double* max_l_out) {
+  sgp_ctx* ctx = (grids && B >= 1 && grids[0]) ? grids[0]->ctx : nullptr;
+  SGP_CHECK(ctx, B >= 1, "sgp_grid_step_small_many: %d members, at least 1 expected", B);
+  SGP_CHECK(ctx, grids && grids[0], "sgp_grid_step_small_many: member 0 has no grid");
+  SGP_HIP(ctx, hipSetDevice(ctx->device));
+  // ---- every refusal, in member order
+  struct Seen {
+    const void* p;
+    int member;
+    bool operator<(const Seen& o) const { return p < o.p || (p == o.p && member < o.member); }
+  };
+  static thread_local std::vector<Seen> seen_grid, seen_gp;
+  static thread_local std::vector<GpDev> hosts;
+  static thread_local std::vector<int> first, key, order;
+  seen_grid.clear();
+  seen_gp.clear();
+  hosts.clear();
+  first.assign(size_t(B) + 1, 0);
+  key.assign(size_t(B), 0);
+  for (int b = 0; b < B; ++b) {
+    sgp_grid* g = grids[b];
+    SGP_CHECK(ctx, g, "sgp_grid_step_small_many: member %d has no grid", b);
+    SGP_CHECK(ctx, g->ctx == ctx,
+              "sgp_grid_step_small_many: member %d lives in another context than member 0", b);
+    sgp_gp* const* mg = gps + size_t(b) * SGP_MAX_GPS;
+    GpDev host[SGP_MAX_GPS];
+    bool ok = G[b] == g->G && G[b] >= 1 && G[b] <= SGP_MAX_GPS;
+    SGP_CHECK(ctx, ok, "sgp_grid_step_small_many: member %d: grid was created for %d GPs, got %d",
+              b, g->G, G[b]);
+    if (collect_gps(ctx, mg, G[b], g->d, host) != 0) {
+      const std::string why = ctx->err;
+      sgp_set_error(ctx, "sgp_grid_step_small_many: member %d: %s", b, why.c_str());
+      return -2;
+    }
+    SGP_CHECK(ctx, step_small_eligible(ctx, host, G[b], g->N),
+              "sgp_grid_step_small_many: member %d: %lld rows / a GP with more than 48 "
+              "observations (sgp_grid_step_small_ok)", b, (long long)g->N);
+    seen_grid.push_back({g, b});
+    for (int i = 0; i < G[b]; ++i) {
+      seen_gp.push_back({mg[i], b});
+      hosts.push_back(host[i]);
+    }
+    first[size_t(b) + 1] = first[size_t(b)] + G[b];
+    key[size_t(b)] = step_group_key(g->d, host, G[b]);
+  }
+  {
+    int bad_grid = B, bad_gp = B;
+    std::sort(seen_grid.begin(), seen_grid.end());
+    for (size_t i = 1; i < seen_grid.size(); ++i)
+      if (seen_grid[i].p == seen_grid[i - 1].p) bad_grid = std::min(bad_grid, seen_grid[i].member);
+    std::sort(seen_gp.begin(), seen_gp.end());
+    // (one member may name a GP twice, as sgp_grid_step_small allows; two members may not
+    // share one: the members of a fleet are independent problems)
+    for (size_t i = 1; i < seen_gp.size(); ++i)
+      if (seen_gp[i].p == seen_gp[i - 1].p && seen_gp[i].member != seen_gp[i - 1].member)
+        bad_gp = std::min(bad_gp, seen_gp[i].member);
+    SGP_CHECK(ctx, bad_grid == B || bad_gp < bad_grid,
+              "sgp_grid_step_small_many: member %d uses the grid of an earlier member", bad_grid);
+    SGP_CHECK(ctx, bad_gp == B,
+              "sgp_grid_step_small_many: member %d uses a GP of an earlier member", bad_gp);
+  }
+  // ---- room: result blocks, staging buffer, records on the device
+  if (ctx->fleet_cap < size_t(B)) {
+    if (ctx->fleet_host) {
+      SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      (void)hipHostFree(ctx->fleet_host);
+    }
+    ctx->fleet_host = nullptr;
+    ctx->fleet_cap = 0;
+    const size_t cap = std::max<size_t>(size_t(B) + size_t(B) / 2, 64);
+    SGP_TRY(mapped_block(ctx, cap * kStepResWords, &ctx->fleet_host, &ctx->fleet_dev));
+    ctx->fleet_cap = cap;
+  }
+  const size_t rb = step_record_bytes();
+  const size_t gp_at = (size_t(B) * rb + 15) & ~size_t(15);
+  const size_t bytes = gp_at + hosts.size() * sizeof(GpDev);
+  if (ctx->fleet_stage_cap < bytes) {
+    if (ctx->fleet_stage) {
+      SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      (void)hipHostFree(ctx->fleet_stage);
+    }
+    ctx->fleet_stage = nullptr;
+    ctx->fleet_stage_cap = 0;
+    const size_t cap = bytes + bytes / 2;
+    SGP_HIP(ctx, hipHostMalloc(&ctx->fleet_stage, cap, hipHostMallocDefault));
+    ctx->fleet_stage_cap = cap;
+  }
+  SGP_TRY(sgp_reserve(ctx, &ctx->fleet_recs, bytes));
+  // ---- records, grouped by kernel instance (a counting sort: members keep their order
+  // inside a group), each pointing at its member's slot of the result array
+  int gstart[kStepGroupKeys + 1] = {0};
+  for (int b = 0; b < B; ++b) ++gstart[key[size_t(b)] + 1];
+  for (int k = 0; k < kStepGroupKeys; ++k) gstart[k + 1] += gstart[k];
+  order.assign(size_t(B), 0);
+  {
+    int at[kStepGroupKeys];
+    for (int k = 0; k < kStepGroupKeys; ++k) at[k] = gstart[k];
+    for (int b = 0; b < B; ++b) order[size_t(at[key[size_t(b)]]++)] = b;
+  }
+  char* stage = static_cast<char*>(ctx->fleet_stage);
+  char* dev = static_cast<char*>(ctx->fleet_recs.p);
+  memcpy(stage + gp_at, hosts.data(), hosts.size() * sizeof(GpDev));
+  const uint64_t seq0 = ctx->step_seq;          // member b: seq0 + 1 + b
+  ctx->step_seq += uint64_t(B);
+  for (int r = 0; r < B; ++r) {
+    const int b = order[size_t(r)];
+    sgp_grid* g = grids[b];
+    g->l0_pending = 0;
+    const GpDev* gd = reinterpret_cast<const GpDev*>(dev + gp_at) + first[size_t(b)];
+    step_record_fill(stage + size_t(r) * rb, g, gd, G[b], beta[b],
+                     fmin + size_t(b) * SGP_MAX_GPS, scaling + size_t(b) * SGP_MAX_GPS,
+                     thr_beta + size_t(b) * SGP_MAX_GPS,
+                     ctx->fleet_dev + size_t(b) * kStepResWords, seq0 + 1 + uint64_t(b));
+  }
+  SGP_HIP(ctx, hipMemcpyAsync(dev, stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+  for (int k = 0; k < kStepGroupKeys; ++k)
+    if (gstart[k + 1] > gstart[k])
+      SGP_TRY(launch_step_small_group(ctx, k, dev + size_t(gstart[k]) * rb,
+                                      gstart[k + 1] - gstart[k]));
+  for (int b = 0; b < B; ++b) grids[b]->post_valid = true;
+  // ---- the B completion words: one deadline for all of them, then the stream
+  {
+    const auto t0 = std::chrono::steady_clock::now();
+    bool synced = false;
+    for (int b = 0; b < B; ++b) {
+      volatile uint64_t* done = reinterpret_cast<volatile uint64_t*>(
+          ctx->fleet_host + size_t(b) * kStepResWords) + (kStepResWords - 1);
+      const uint64_t seq = seq0 + 1 + uint64_t(b);
+      uint32_t spins = 0;
+      while (*done != seq) {
+        if (synced || ((++spins & 1023u) == 0 &&
+                       std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200))) {
+          if (!synced) SGP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+          synced = true;
+          SGP_CHECK(ctx, *done == seq,
+                    "sgp_grid_step_small_many: the kernel left no result for member %d", b);
+          break;
+        }
+      }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+  }
+  for (int b = 0; b < B; ++b) {
+    const size_t s = size_t(b);
+    double hostres[kStepResWords];
+    memcpy(hostres, ctx->fleet_host + s * kStepResWords, size_t(res_words(grids[b]->d, G[b])) * 8);
+    unpack_result(hostres, grids[b]->d, G[b],
+                  {out5 + s * 6, x_top + s * SGP_MAX_D, mean_top + s * SGP_MAX_GPS,
+                   q_top + s * 2 * SGP_MAX_GPS, flags + s * SGP_MAX_GPS, value + s, gidx + s,
+                   max_l_out + s});
+  }
+  return 0;
 }
 
 // N-rank certified step with ONE stream sync (the N-rank counterpart of

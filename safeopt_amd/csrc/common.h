@@ -296,6 +296,16 @@ struct sgp_ctx {
   double* sets_dev = nullptr;
   size_t sets_cap = 0;             // doubles
   uint64_t step_seq = 0;
+  // sgp_grid_step_small_many: one result block per member of the fleet, [B][kStepResWords]
+  // in host memory of the same kind (an array of its own: step_host stays the block of the
+  // one-problem call), the pinned staging buffer the records and GP descriptors of a call
+  // are built in, and their place on the device -- all three grown on demand
+  double* fleet_host = nullptr;
+  double* fleet_dev = nullptr;
+  size_t fleet_cap = 0;            // members
+  void* fleet_stage = nullptr;
+  size_t fleet_stage_cap = 0;      // bytes
+  DevBuf fleet_recs;
   // RCCL
   void* comm = nullptr;  // ncclComm_t
   int rank = 0, world = 1;
@@ -872,6 +882,16 @@ bool pair_sweep_wanted(const sgp_ctx* ctx, const GpDev* gh, int Geff);
 // step_small.hip: a whole SafeOpt.optimize() of a small grid in one launch
 constexpr int64_t kStepSmallRows = 16384;
 bool step_small_eligible(const sgp_ctx* ctx, const GpDev* gh, int G, int64_t N);
+// ... of many problems at once: opaque records of step_record_bytes() each, filled on the
+// host (step_record_fill), uploaded by the caller and launched one group -- a run of `count`
+// records of one kernel instance, step_group_key: 0 .. kStepGroupKeys - 1 -- at a time
+constexpr int kStepGroupKeys = SGP_MAX_D * 3 * 2;
+size_t step_record_bytes();
+int step_group_key(int d, const GpDev* gh, int G);
+void step_record_fill(void* rec, const sgp_grid* g, const GpDev* gps_dev, int G, double beta,
+                      const double* fmin, const double* scaling, const double* thr_beta,
+                      double* res, uint64_t seq);
+int launch_step_small_group(sgp_ctx* ctx, int key, const void* recs_dev, int count);
 int launch_step_small(sgp_grid* g, const GpDev* gps_dev, const GpDev* gh, int G, double beta,
                       const double* fmin, const double* scaling, const double* thr_beta,
                       double* res, uint64_t seq);

@@ -25,6 +25,7 @@
 // candidate mask and widths, max l0[S]) is resident exactly as the large-grid path
 // leaves it.
 #include <algorithm>
+#include <cstring>
 
 #include "set_order.h"
 #include "sets_front.h"
@@ -68,8 +69,12 @@ struct StepParams {
 #define STEP_STAMP(i) do {} while (0)
 #endif
 
+// Phases A-F of one problem by the calling workgroup: the body of the one-problem kernel
+// (k_step_small, `p` its by-value kernel argument) and of the many-problem kernel
+// (k_step_small_many, `p` the workgroup's record) -- one text, so a member of a fleet
+// computes the bits it computes alone.
 template <int D, int NP, bool SINGLE, int TH>
-__global__ __launch_bounds__(TH) void k_step_small(StepParams p) {
+__device__ __forceinline__ void step_small_body(const StepParams& p) {
   constexpr int kStepThreads = TH;
   constexpr int kStepWaves = TH / 64;
   __shared__ double tab[kExpTabSize];
@@ -479,19 +484,114 @@ __global__ __launch_bounds__(TH) void k_step_small(StepParams p) {
   }
 }
 
+template <int D, int NP, bool SINGLE, int TH>
+__global__ __launch_bounds__(TH) void k_step_small(StepParams p) {
+  step_small_body<D, NP, SINGLE, TH>(p);
+}
+
+// MANY problems in one launch, one workgroup each: workgroup b takes record b of `recs` and
+// runs the body above on it -- its own grid, its own GPs, its own slot of the host's result
+// array (p.res) and its own completion word.  No workgroup reads what another writes, none
+// waits for another (no grid barrier, no shared counter, no atomic across workgroups): the
+// launch makes progress however its workgroups are placed, and members beyond the compute
+// units queue behind the first.  The record is read as the by-value argument is: through
+// the constant address space (nothing writes the records while the launch runs), so its
+// fields arrive by wave-uniform loads.
+typedef const __attribute__((address_space(4))) StepParams* step_rec_c_t;
+
+template <int D, int NP, bool SINGLE, int TH>
+__global__ __launch_bounds__(TH) void k_step_small_many(const StepParams* recs) {
+  const step_rec_c_t rec = (step_rec_c_t)(recs + blockIdx.x);
+  step_small_body<D, NP, SINGLE, TH>(*(const StepParams*)(rec));
+}
+
+// The instance of a launch: input dimension, observation class (24 / 32 / 48 rows of the
+// staged L^-1) and whether every kernel is a single part.  `recs` null: the one-problem
+// kernel on `p`; else `count` records on the device, one workgroup each.
 template <int D, int NP, int TH>
-void launch_step_np(sgp_ctx* ctx, const StepParams& p, bool single) {
-  if (single)
+void launch_step_np(sgp_ctx* ctx, const StepParams& p, bool single, const StepParams* recs,
+                    int count) {
+  if (recs) {
+    if (single)
+      hipLaunchKernelGGL((k_step_small_many<D, NP, true, TH>), dim3(count), dim3(TH), 0,
+                         ctx->stream, recs);
+    else
+      hipLaunchKernelGGL((k_step_small_many<D, NP, false, TH>), dim3(count), dim3(TH), 0,
+                         ctx->stream, recs);
+  } else if (single) {
     hipLaunchKernelGGL((k_step_small<D, NP, true, TH>), dim3(1), dim3(TH), 0, ctx->stream, p);
-  else
+  } else {
     hipLaunchKernelGGL((k_step_small<D, NP, false, TH>), dim3(1), dim3(TH), 0, ctx->stream, p);
+  }
 }
 
 template <int D>
-void launch_step_d(sgp_ctx* ctx, const StepParams& p, int np, bool single) {
-  if (np <= 24) return launch_step_np<D, 24, 512>(ctx, p, single);
-  if (np <= 32) return launch_step_np<D, 32, 512>(ctx, p, single);
-  return launch_step_np<D, 48, 512>(ctx, p, single);
+void launch_step_d(sgp_ctx* ctx, const StepParams& p, int np, bool single,
+                   const StepParams* recs, int count) {
+  if (np <= 24) return launch_step_np<D, 24, 512>(ctx, p, single, recs, count);
+  if (np <= 32) return launch_step_np<D, 32, 512>(ctx, p, single, recs, count);
+  return launch_step_np<D, 48, 512>(ctx, p, single, recs, count);
+}
+
+int launch_step_instance(sgp_ctx* ctx, int d, int np, bool single, const StepParams& p,
+                         const StepParams* recs, int count) {
+  switch (d) {
+    case 1: launch_step_d<1>(ctx, p, np, single, recs, count); break;
+    case 2: launch_step_d<2>(ctx, p, np, single, recs, count); break;
+    case 3: launch_step_d<3>(ctx, p, np, single, recs, count); break;
+    case 4: launch_step_d<4>(ctx, p, np, single, recs, count); break;
+    case 5: launch_step_d<5>(ctx, p, np, single, recs, count); break;
+    case 6: launch_step_d<6>(ctx, p, np, single, recs, count); break;
+    case 7: launch_step_d<7>(ctx, p, np, single, recs, count); break;
+    case 8: launch_step_d<8>(ctx, p, np, single, recs, count); break;
+    default:
+      sgp_set_error(ctx, "input dimension %d not in 1..%d", d, SGP_MAX_D);
+      return -2;
+  }
+  SGP_HIP(ctx, hipGetLastError());
+  ctx->last_sweep = 5;
+  return 0;
+}
+
+StepParams step_params(const sgp_grid* g, const GpDev* gps_dev, int G, double beta,
+                       const double* fmin, const double* scaling, const double* thr_beta,
+                       double* res, uint64_t seq) {
+  StepParams p{};
+  p.gps = gps_dev;
+  p.G = G;
+  p.pts = SweepPoints{g->pts, g->N, 1, g->N};
+  p.conf.Q = g->Q;
+  p.conf.mean = g->mean;
+  p.conf.var = g->var;
+  p.conf.S = g->S;
+  p.conf.partial = g->partial;
+  p.conf.beta = beta;
+  for (int i = 0; i < SGP_MAX_GPS; ++i) {
+    p.conf.fmin[i] = i < G ? fmin[i] : -INFINITY;
+    p.scaling.v[i] = i < G ? scaling[i] : 1.0;
+    p.thr_beta.v[i] = i < G ? thr_beta[i] : 0.0;
+  }
+  p.M = g->M;
+  p.Gm = g->Gm;
+  p.cand = g->cand;
+  p.w = g->w;
+  p.goff = g->goff;
+  p.res = res;
+  p.scal = g->scal;
+  p.nfront = res_flags(g->d, G);
+  p.nfl = res_value(g->d, G) - res_flags(g->d, G);
+  p.seq = seq;
+  return p;
+}
+
+// what selects the instance: the largest n of the GPs and "every kernel has one part"
+void step_shape(const GpDev* gh, int G, int* np, bool* single) {
+  *np = 1;
+  *single = true;
+  for (int i = 0; i < G; ++i) {
+    *np = std::max(*np, gh[i].n);
+    *single = *single && gh[i].kern.n_parts == 1;
+  }
 }
 
 // ---- every candidate of a small grid at once ------------------------------------------
@@ -713,52 +813,39 @@ bool step_small_eligible(const sgp_ctx* ctx, const GpDev* gh, int G, int64_t N) 
 int launch_step_small(sgp_grid* g, const GpDev* gps_dev, const GpDev* gh, int G, double beta,
                       const double* fmin, const double* scaling, const double* thr_beta,
                       double* res, uint64_t seq) {
-  sgp_ctx* ctx = g->ctx;
-  StepParams p{};
-  p.gps = gps_dev;
-  p.G = G;
-  p.pts = SweepPoints{g->pts, g->N, 1, g->N};
-  p.conf.Q = g->Q;
-  p.conf.mean = g->mean;
-  p.conf.var = g->var;
-  p.conf.S = g->S;
-  p.conf.partial = g->partial;
-  p.conf.beta = beta;
-  for (int i = 0; i < SGP_MAX_GPS; ++i) {
-    p.conf.fmin[i] = i < G ? fmin[i] : -INFINITY;
-    p.scaling.v[i] = i < G ? scaling[i] : 1.0;
-    p.thr_beta.v[i] = i < G ? thr_beta[i] : 0.0;
-  }
-  p.M = g->M;
-  p.Gm = g->Gm;
-  p.cand = g->cand;
-  p.w = g->w;
-  p.goff = g->goff;
-  p.res = res;
-  p.scal = g->scal;
-  p.nfront = res_flags(g->d, G);
-  p.nfl = res_value(g->d, G) - res_flags(g->d, G);
-  p.seq = seq;
-  int np = 1;
-  bool single = true;
-  for (int i = 0; i < G; ++i) {
-    np = std::max(np, gh[i].n);
-    single = single && gh[i].kern.n_parts == 1;
-  }
-  switch (g->d) {
-    case 1: launch_step_d<1>(ctx, p, np, single); break;
-    case 2: launch_step_d<2>(ctx, p, np, single); break;
-    case 3: launch_step_d<3>(ctx, p, np, single); break;
-    case 4: launch_step_d<4>(ctx, p, np, single); break;
-    case 5: launch_step_d<5>(ctx, p, np, single); break;
-    case 6: launch_step_d<6>(ctx, p, np, single); break;
-    case 7: launch_step_d<7>(ctx, p, np, single); break;
-    case 8: launch_step_d<8>(ctx, p, np, single); break;
-    default:
-      sgp_set_error(ctx, "input dimension %d not in 1..%d", g->d, SGP_MAX_D);
-      return -2;
-  }
-  SGP_HIP(ctx, hipGetLastError());
-  ctx->last_sweep = 5;
-  return 0;
+  const StepParams p = step_params(g, gps_dev, G, beta, fmin, scaling, thr_beta, res, seq);
+  int np;
+  bool single;
+  step_shape(gh, G, &np, &single);
+  return launch_step_instance(g->ctx, g->d, np, single, p, nullptr, 0);
+}
+
+// ---- many problems in one launch (sgp_grid_step_small_many) ----------------------------
+// The host side works on opaque records: step_record_bytes() each, written by
+// step_record_fill into a pinned staging buffer, uploaded by the caller in one copy, and
+// launched group by group -- a group is a run of records of one instance
+// (step_group_key: D, observation class, single-part or not).
+size_t step_record_bytes() { return sizeof(StepParams); }
+
+int step_group_key(int d, const GpDev* gh, int G) {
+  int np;
+  bool single;
+  step_shape(gh, G, &np, &single);
+  const int cls = np <= 24 ? 0 : (np <= 32 ? 1 : 2);
+  return ((d - 1) * 3 + cls) * 2 + (single ? 1 : 0);
+}
+
+void step_record_fill(void* rec, const sgp_grid* g, const GpDev* gps_dev, int G, double beta,
+                      const double* fmin, const double* scaling, const double* thr_beta,
+                      double* res, uint64_t seq) {
+  const StepParams p = step_params(g, gps_dev, G, beta, fmin, scaling, thr_beta, res, seq);
+  memcpy(rec, &p, sizeof(p));
+}
+
+int launch_step_small_group(sgp_ctx* ctx, int key, const void* recs_dev, int count) {
+  static const int kClassNp[3] = {24, 32, 48};
+  const bool single = (key & 1) != 0;
+  const int cls = (key >> 1) % 3, d = (key >> 1) / 3 + 1;
+  return launch_step_instance(ctx, d, kClassNp[cls], single, StepParams{},
+                              static_cast<const StepParams*>(recs_dev), count);
 }

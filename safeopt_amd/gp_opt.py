@@ -39,7 +39,7 @@ from .dist import (LocalComm, allgather_rows, check_same_incumbent, check_same_m
                    merge_path_records, merge_topk, pick_ise, shard_range)
 from .swarm import SwarmOptimization, DeviceSwarmOptimization
 
-__all__ = ['SafeOpt', 'SafeOptSwarm']
+__all__ = ['SafeOpt', 'SafeOptFleet', 'SafeOptSwarm']
 
 _I64_MAX = np.iinfo(np.int64).max
 
@@ -1744,10 +1744,29 @@ class SafeOpt(GaussianProcessOptimization):
             self.compute_sets()
         return self.get_new_query_point(ucb=ucb)
 
+    def _small_step_devs(self):
+        """The fitted device GPs when ``optimize()`` (``ucb=False``) takes the one-launch
+        step of a small grid, else None: the condition at the top of ``optimize``, which
+        spells it out itself to keep a call off its 30-microsecond path (``SafeOptFleet``
+        asks here which members ride its launch)."""
+        if (not self.use_lipschitz and hasattr(self._backend, 'sets_fused')
+                and bool(np.any(self.fmin != -np.inf))
+                and self._comm.world == 1 and self.small_step
+                and hasattr(self._backend, 'step_small')):
+            return self._backend.small_step_devs()
+        return None
+
     def _small_step(self, context, devs):
         """``update_confidence_intervals`` + ``compute_sets`` of a small grid in one launch
         and one read-back (``sgp_grid_step_small``: grids of at most 16384 rows, GPs with at
         most 48 observations -- gp_opt.py:651-675 as the reference's examples run it)."""
+        beta = self._small_step_begin(context)
+        self._small_step_end(beta, self._backend.step_small(devs, beta, self.fmin, self.scaling,
+                                                            self._thr_beta))
+
+    def _small_step_begin(self, context):
+        """The host side of the one-launch step in front of the launch (shared with
+        ``SafeOptFleet``, which launches many members at once); returns ``beta``."""
         beta = self.beta(self.t)
         if self.num_contexts:
             self.context = context
@@ -1761,8 +1780,11 @@ class SafeOpt(GaussianProcessOptimization):
         # the launch recomputes all three sets (gp_opt.py:478-481, 505-615), exactly as
         # _flush_masks(for_sets=True) does in front of compute_sets on the large-grid path
         self._masks_written = set()
-        (out5, x_c, mu_c, q_c, flags, val, idx,
-         max_l) = self._backend.step_small(devs, beta, self.fmin, self.scaling, self._thr_beta)
+        return beta
+
+    def _small_step_end(self, beta, out):
+        """... and behind it: ``out`` is what the backend's ``step_small`` returns."""
+        out5, x_c, mu_c, q_c, flags, val, idx, max_l = out
         self._stale.update(Q=True, S=True)
         self._q_written = False          # (the sweep overwrites the intervals)
         self._s_user = False
@@ -2545,6 +2567,116 @@ def ise_targets(targets, bounds, about, fmin, beta, posterior):
                           "keeps every target)")
     return (np.ascontiguousarray(rows), np.ascontiguousarray(zmean),
             np.ascontiguousarray(zvar))
+
+
+class SafeOptFleet(object):
+    """Many small ``SafeOpt`` problems stepped together: the members whose ``optimize()``
+    would take the one-launch step of a small grid (``sgp_grid_step_small``) take it side by
+    side, one workgroup each, in one call (``sgp_grid_step_small_many``) instead of one
+    launch and one wait after another.
+
+    >>> fleet = SafeOptFleet(opts)                       # doctest: +SKIP
+    >>> X = fleet.optimize()                             # doctest: +SKIP
+    >>> for o, x in zip(opts, X):                        # doctest: +SKIP
+    ...     o.add_new_data_point(x, measure(x))
+
+    ``fleet.optimize(contexts)`` returns what ``[o.optimize(context=c) for o, c in zip(opts,
+    contexts)]`` returns and leaves every member in the state its own ``optimize()`` leaves
+    it, bit for bit: the members stay ordinary ``SafeOpt`` objects.  A member that does not
+    qualify for the one-launch step (``small_step = False``, Lipschitz certificates, more
+    than 48 observations, a grid over the step's budget, a backend without the step) runs its
+    own ``optimize()`` behind the launch; one whose first candidate the launch did not
+    certify continues alone, as it does behind its own launch.
+
+    The members are independent problems on one device context: an empty list, a member
+    that is no ``SafeOpt``, a member on several ranks, one member twice, a GP under two
+    members and members on different contexts are refused.  ``ucb`` steps never take the
+    one-launch step and are not offered.
+    """
+
+    def __init__(self, opts):
+        opts = list(opts)
+        if not opts:
+            raise ValueError("a fleet needs at least one SafeOpt member")
+        seen_gp = {}
+        for b, o in enumerate(opts):
+            if not isinstance(o, SafeOpt):
+                raise TypeError("member %d is a %s, not a SafeOpt" % (b, type(o).__name__))
+            if o._comm.world > 1:
+                raise ValueError("member %d runs on %d ranks: a fleet steps one-rank "
+                                 "optimisers" % (b, o._comm.world))
+            if any(o is e for e in opts[:b]):
+                raise ValueError("member %d is member %d again"
+                                 % (b, next(i for i, e in enumerate(opts) if e is o)))
+            for g in o.gps:
+                if seen_gp.setdefault(id(g), b) != b:
+                    raise ValueError("members %d and %d share a GP" % (seen_gp[id(g)], b))
+            if getattr(o._backend, 'ctx', None) is not getattr(opts[0]._backend, 'ctx', None):
+                raise ValueError("member %d lives in another device context than member 0" % b)
+        self.opts = opts
+        self._ctx = getattr(opts[0]._backend, 'ctx', None)
+        self._plan = self._plan_key = None
+
+    def __len__(self):
+        return len(self.opts)
+
+    def optimize(self, contexts=None, return_exceptions=False):
+        """One step of every member; the list of their query points.  ``contexts``: one
+        context per member (None: none).  A member may raise -- ``EnvironmentError`` when
+        none of its rows is safe, say: with ``return_exceptions`` the exception stands in
+        its place in the list, otherwise the first one in member order is raised -- in both
+        cases after ALL members have been stepped."""
+        opts = self.opts
+        B = len(opts)
+        if contexts is None:
+            contexts = [None] * B
+        elif len(contexts) != B:
+            raise ValueError("%d contexts for %d members" % (len(contexts), B))
+        out = [None] * B
+        ride, alone = [], []
+        for b, o in enumerate(opts):
+            try:
+                devs = o._small_step_devs() if self._ctx is not None else None
+                if devs is None:
+                    alone.append(b)
+                else:
+                    ride.append((b, o, devs, o._small_step_begin(contexts[b])))
+            except Exception as e:       # (the member's own step would have raised it)
+                out[b] = e
+        if ride:
+            key = tuple(r[0] for r in ride)
+            if self._plan_key != key:
+                self._plan = _hip.FleetPlan(self._ctx, [r[1]._backend.grid for r in ride])
+                self._plan_key = key
+            plan = self._plan
+            pbeta = plan.beta
+            for j, (b, o, devs, beta) in enumerate(ride):
+                o._backend._seen = [None] * len(devs)     # unknown until the call is through
+                plan.set_gps(j, devs)
+                pbeta[j] = beta
+                fm, sc, tb = plan.rows[j]
+                fm[:], sc[:], tb[:] = o.fmin, o.scaling, o._thr_beta
+            self._ctx.step_small_many(plan)
+            value, gidx, max_l = plan.value.tolist(), plan.gidx.tolist(), plan.max_l.tolist()
+            for j, (b, o, devs, beta) in enumerate(ride):
+                be = o._backend
+                be._seen = be._tags(devs)                # (a full sweep: the posterior is current)
+                be._rank1_streak = 0
+                try:
+                    o._small_step_end(beta, plan.result(j, value[j], gidx[j], max_l[j]))
+                    out[b] = o.get_new_query_point()
+                except Exception as e:
+                    out[b] = e
+        for b in alone:
+            try:
+                out[b] = opts[b].optimize(context=contexts[b])
+            except Exception as e:
+                out[b] = e
+        if not return_exceptions:
+            for x in out:
+                if isinstance(x, Exception):
+                    raise x
+        return out
 
 
 class SafeOptSwarm(GaussianProcessOptimization):
